@@ -19,6 +19,15 @@ Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (the scan)
 from HIP events recorded on its launch stream inside the timed region;
 `cpu_baseline` times the CPU oracle (numpy restatement of the reference path,
 float64 query exactly as the live path) on a bounded sample on the host cores.
+
+A plain run does only what the headline figure needs: set up, warm up, time the
+--steps steps, print the line.  Everything else - the batch and metric sweeps, the
+oracle check of the last step, the corpus variants, the C5 / encoder / C2 / hybrid
+/ BM25 legs, the CPU baselines, and the one-stream steps that price the kernel when
+several streams are in flight - runs only with --full (there, as governed by the
+options below).  --dump-outputs DIR writes the last timed step's answers (the
+arrays the caller of the search receives) as DIR/<name>.npy; inputs are seeded,
+so two builds can be compared output for output.
 """
 
 import argparse
@@ -77,6 +86,12 @@ def parse():
                     help="skip the clustered-corpus and near-duplicate-corpus legs of the headline search (single GPU only)")
     ap.add_argument("--no-cpu-legs", dest="cpu_legs", action="store_false",
                     help="skip the BM25 and encoder CPU baselines (the vector one is governed by --cpu-rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks after the timed steps (sweeps, oracle checks, corpus variants, "
+                         "the C5 / encoder / C2 / hybrid / BM25 legs, CPU baselines; the options above choose among them); "
+                         "without it only the headline steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's top-k distances, global row ids and counts as DIR/<name>.npy (float64)")
     return ap.parse_args()
 
 
@@ -903,7 +918,7 @@ def main():
                                         stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     t_build = time.time() - t0
-    sample_rows = min(args.cpu_rows, hi - lo) if rank == 0 and world == 1 else 0
+    sample_rows = min(args.cpu_rows, hi - lo) if rank == 0 and world == 1 and args.full else 0
     sample = shard[:sample_rows].cpu().numpy() if sample_rows else None
     del shard
     torch.cuda.empty_cache()
@@ -958,14 +973,19 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     flags_total = flags_all[n_warm:].sum(dtype=torch.int64).reshape(())
-    # the LAST timed step's own answers (not a separate index): compared with the CPU oracle over ALL rows further down
+    # the LAST timed step's own answers (not a separate index), copied before anything reuses the searchers' buffers:
+    # written by --dump-outputs, compared with the CPU oracle over ALL rows further down (--full)
+    last_dist, last_rows_all, last_cnt_all = (t.cpu().numpy() for t in out[:3])
     last_s = ((n_warm + args.steps - 1) * B) % (nq_pool - B + 1)
-    last_rows, last_cnt = out[1][:MAIN_LEG_CHECK_QUERIES].cpu().numpy(), out[2][:MAIN_LEG_CHECK_QUERIES].cpu().numpy()
+    last_rows, last_cnt = last_rows_all[:MAIN_LEG_CHECK_QUERIES], last_cnt_all[:MAIN_LEG_CHECK_QUERIES]
     last_q = queries[last_s : last_s + MAIN_LEG_CHECK_QUERIES].cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(np, args.dump_outputs, dist=last_dist, rows=last_rows_all, count=last_cnt_all)
     launches, scan_ms = index.profile_read(reset=True)
     sieve_stats = index.scan_stats(reset=True)
     bracket_over = "the timed region"
-    if n_streams > 1:
+    priced = n_streams == 1 or args.full  # several streams in flight: the kernel is priced by steps of its own (--full)
+    if n_streams > 1 and args.full:
         # with several steps in flight a launch's HIP-event bracket also holds the kernels other streams ran beside it: the
         # dominant kernel's duration is taken from min(K, 10) more steps of the same loop on ONE stream, right after the timed region
         extra = min(args.steps, 10)
@@ -1058,7 +1078,7 @@ def main():
             "rows_per_gpu": n_loc,
             "parallelism": f"row-shard x{world}, all-gather of partial top-k",
         },
-        "roofline": {
+        "roofline": None if not priced else {
             "bound": "mfma" if by_mfma else "hbm",
             # HIP events on the launch stream bracket the shard pass: both filter launches and what runs between them.  The
             # 32K-row sample launch before them and the scatter / select kernels after the second launch are outside the
@@ -1100,7 +1120,7 @@ def main():
     }
 
     # ---- the same index at other batch sizes: queries per pass trade QPS against roofline fraction ----
-    if args.sweep:
+    if args.full and args.sweep:
         sweep = []
         for Bs in (1, 32, 64, 128, 192, 256):
             if Bs == B:
@@ -1147,28 +1167,28 @@ def main():
             others.append({"metric": mt, "queries_per_step": B, "qps": round(B * 10 / el, 1), "ms_per_step": round(1e3 * el / 10, 4)})
         result["metric_sweep"] = others
     index.close()  # release the shard before the other legs allocate theirs
-    if world == 1 and rank == 0 and args.cpu_legs:
+    if args.full and world == 1 and rank == 0 and args.cpu_legs:
         # (after the timed region and the sweeps: the oracle is the checker, never the thing measured)
         result["timed_leg_check"] = timed_leg_check(np, torch, device, n, d, args, last_q, last_rows, last_cnt)
-    if args.variants and world == 1:
+    if args.full and args.variants and world == 1:
         for kind in ("clustered", "near_duplicate"):
             result[kind] = variant_leg(np, torch, args, local_rank, DeviceIndex, ShardedSearcher, kind)
-    if args.c5_rows > 0:
+    if args.full and args.c5_rows > 0:
         result["c5_float16_d1024"] = c5_leg(np, torch, dist, args, world, rank, local_rank, barrier, DeviceIndex, ShardedSearcher)
-    if args.encode_chunks > 0:
+    if args.full and args.encode_chunks > 0:
         result["index_build"] = encoder_leg(np, torch, dist, args, world, rank, local_rank, barrier)
         if rank == 0:
             import tempfile
 
             with tempfile.TemporaryDirectory() as td:
                 result["index_build"]["through_build_embeddings"] = build_embeddings_leg(np, torch, args, local_rank, td)
-    if args.c2_chunks > 0 and world == 1:
+    if args.full and args.c2_chunks > 0 and world == 1:
         result["c2_encode_index_search"] = c2_leg(np, torch, args, local_rank, DeviceIndex, ShardedSearcher)
-    if args.hybrid_docs > 0:
+    if args.full and args.hybrid_docs > 0:
         result["hybrid_c4"] = hybrid_leg(np, torch, dist, args, world, rank, local_rank, barrier, DeviceIndex, ShardedSearcher,
                                          check=(world == 1 and args.cpu_legs))
     bm25_state = None
-    if args.bm25_docs > 0 and world == 1:
+    if args.full and args.bm25_docs > 0 and world == 1:
         result["bm25_c3"], bm25_dev, bm25_corpus = bm25_leg(np, torch, args, local_rank)
         bm25_state = (bm25_dev, bm25_corpus)
     if rank == 0 and world == 1 and sample is not None and len(sample):
@@ -1184,6 +1204,13 @@ def main():
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(np, out_dir, **arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (row ids and counts are exact there)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def timed_leg_check(np, torch, device, n, d, args, qs, got_rows, got_cnt):

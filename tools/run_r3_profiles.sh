@@ -6,9 +6,9 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r3p
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 200 python3 $R/bench.py --rows 1250000 --no-variants --no-sweep --c5-rows 0 --encode-chunks 0 --bm25-docs 0 --hybrid-docs 0 --cpu-rows 0 --steps 200 --warmup 20 > $O/shard_1250k_b256.json 2> $O/shard_1250k_b256.err || exit 1
+timeout -k 10 200 python3 $R/bench.py --full --rows 1250000 --no-variants --no-sweep --c5-rows 0 --encode-chunks 0 --bm25-docs 0 --hybrid-docs 0 --cpu-rows 0 --steps 200 --warmup 20 > $O/shard_1250k_b256.json 2> $O/shard_1250k_b256.err || exit 1
 timeout -k 10 200 python3 $R/bench.py --rows 1250000 --no-variants --no-sweep --c5-rows 0 --encode-chunks 0 --bm25-docs 0 --hybrid-docs 0 --cpu-rows 0 --steps 200 --warmup 20 --streams 1 > $O/shard_1250k_b256_s1.json 2>> $O/shard_1250k_b256.err || exit 1
-timeout -k 10 200 python3 $R/bench.py --rows 1250000 --no-variants --no-sweep --c5-rows 0 --encode-chunks 0 --bm25-docs 0 --hybrid-docs 0 --cpu-rows 0 --steps 200 --warmup 20 --batch 128 > $O/shard_1250k_b128.json 2>> $O/shard_1250k_b256.err || exit 1
+timeout -k 10 200 python3 $R/bench.py --full --rows 1250000 --no-variants --no-sweep --c5-rows 0 --encode-chunks 0 --bm25-docs 0 --hybrid-docs 0 --cpu-rows 0 --steps 200 --warmup 20 --batch 128 > $O/shard_1250k_b128.json 2>> $O/shard_1250k_b256.err || exit 1
 echo shard done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python3 $R/bench.py --no-variants --no-sweep --c5-rows 0 --encode-chunks 0 --bm25-docs 0 --hybrid-docs 0 --cpu-rows 0 > $O/bench_traced.json 2> $O/bench_traced.err || exit 1
 echo trace done
