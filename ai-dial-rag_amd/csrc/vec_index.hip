@@ -417,7 +417,7 @@ static size_t carve(SearchBuffers &sb, char *base, int b, int k, int d, int kste
     sb.bound_row = c.take<uint32_t>(b);
     sb.part_exact = c.take<uint64_t>((size_t)b * pl.exact_grid * std::min(k, kExactRound) * 2);
     sb.qt = c.take<double>((size_t)((b + kXbQ - 1) / kXbQ) * xb_dpad(d) * kXbQ);
-    sb.part_sample = c.take<uint64_t>(std::max((size_t)kSampleWgs * 128 * klist, (size_t)kSampleWgs * std::max(128, qpw)));  // (the sieve's sample: two floats per workgroup and query)
+    sb.part_sample = c.take<uint64_t>(std::max((size_t)kSampleWgs * 128 * klist, (size_t)kSampleWgs * std::max(128, qpw) * 2));  // (the sieve's sample: two floats and their two rows per workgroup and query)
     const size_t sv_q = pl.sieve ? (size_t)b * kSieveQueryCap : 0;
     const size_t region = i8_rows ? (size_t)kI8Region : (size_t)kSieveRegion;  // (the int8 filter: eight wave-private parts per workgroup)
     sb.sv_cand = c.take<uint64_t>(pl.sieve ? (size_t)2 * nwg * region : 0);
@@ -908,8 +908,16 @@ static int32_t enqueue_search(mir_index *ix, const double *dq, int b, int k, int
             sa.out_flags = o_flags; sa.nflag = sb.nflag; sa.flagged = sb.flagged; sa.stats = ix->d_stats; sa.qt = sb.qt;
             rc = sieve(0, (uint32_t)kSampleWgs * pl.sample_tpw, kSampleWgs, nullptr, nullptr, nullptr, true);
             if (rc != MIR_OK) return rc;
-            sample_threshold_kernel<<<dim3(nq), dim3(256), 0, stream>>>(reinterpret_cast<const float *>(sb.part_sample), kSampleWgs, qpw,
-                                                                        k, nq, reinterpret_cast<unsigned long long *>(gt));
+            if (use_i8) {  // (the int8 filter's sample records its rows: T0 from their exact values)
+                SieveSampleArgs ta;
+                ta.part = reinterpret_cast<const float *>(sb.part_sample); ta.nwg = kSampleWgs; ta.qpw = qpw; ta.k = k; ta.nq = nq;
+                ta.q0 = q0; ta.d = d; ta.metric = metric; ta.docs = ix->d_orig; ta.doc_sq = ix->d_docsq;
+                ta.q = dq; ta.q_sq = sb.q_sq; ta.q_norm = sb.q_norm; ta.gthr = reinterpret_cast<unsigned long long *>(gt);
+                sieve_sample_threshold_kernel<<<dim3(nq), dim3(256), 0, stream>>>(ta);
+            } else {
+                sample_threshold_kernel<<<dim3(nq), dim3(256), 0, stream>>>(reinterpret_cast<const float *>(sb.part_sample), kSampleWgs, qpw,
+                                                                            k, nq, reinterpret_cast<unsigned long long *>(gt));
+            }
             MIR_HIP(hipGetLastError());
             rc = begin_profile();
             if (rc != MIR_OK) return rc;

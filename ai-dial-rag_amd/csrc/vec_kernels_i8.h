@@ -28,6 +28,28 @@
 // float32 rows.  The integer test is conservative by (|x|^2 - amin) / (2 s_t s_q) units, which is why the image is built only
 // for shards whose squared norms agree to 1e-3 (normalised embeddings: to 1e-7).
 //
+// Thresholds (round 5): exact values, not bounds.  The margin is paid in the listing test v + mg >= T; a threshold that is itself
+// a lower bound (the k-th largest v - mg) pays it a second time, and at the int8 margin (~0.37 sigma of x.q on unit rows) that
+// listed every row within ~0.73 sigma of the cut.  Now both thresholds are the k-th largest EXACT ranking value of k distinct rows,
+// less a slack, and never below the bound they replace:
+//   T0  the SAMPLE instance records the row of every per-lane maximum (lanes cover disjoint rows: 512 distinct rows per query);
+//       sieve_sample_threshold_kernel evaluates the k rows of the k largest lower bounds with the select kernel's float64 formula;
+//   T1  sieve_select_kernel, mode 0, evaluates class 1 of launch 1's list (certainly not NaN, lower bound >= kv: >= k rows).
+// Proof.  Let rk64 be the k-th largest of k numeric reference ranking values r_i (x.q; cosine: x^.q |q|, the filter's `tbc` units;
+// L2: 2 x.q - |x|^2) of distinct rows.  k rows of the shard then rank at or above rk64, none of them NaN, so every row of the true
+// first k (distance ascending, NaN last, then row) is numeric and has r >= rk64: the distance is a monotone function of r
+// (fl(|q|^2 - r), its square root) - ties of rounding aside, which, like the float64 formula's own error (~d 2^-53 |x||q|), lie
+// far inside the margin's 3e-5 |x|max |q| term.  T = fl32(rk64) - 4e-6 |fl32(rk64)| <= rk64 (rounding to nearest moves it by
+// <= 2^-24 |rk64|; index-wide margins also subtract the select's eps_m), and the filter lists every row with v + mg >= T, so
+// every row of the true first k is listed: the final select's argument is unchanged.  euclidean_dist: rows that may be NaN are
+// left out of the sample (`nan_guard`) and of class 1, an exact NaN distance counts for nothing; fewer than k numeric values,
+// or a class 1 beyond kSieveSelectCap, keep the lower bound (mode 0 never hands a query to the exact pass).
+// Measured (10M x 384, B = 256, k = 10; profiles/r05_exact_thresholds.md), bounds -> exact values:
+//   candidates per query, launch 1 + 2   1846 + 2365  ->  643 + 649
+//   filter launch 1 / 2                  110 / 870 us ->  97 / 803 us
+//   sample + threshold, select 0 / 1     17, 16 / 65  ->  27, 25 / 52 us
+//   step                                 1.137 ms     ->  1.043 ms (225k -> 245k QPS)
+//
 // Served: float32 shards the bf16 sieve serves (d padded to 128 / 256 / 384, >= 32K rows) whose rows are finite and of one
 // norm, all four metrics (cosine: see the kernel), k <= 16 (kI8MaxK: the lists grow with k).  Everything else - larger k,
 // other norms, the wide and the float16-native shards - stays on the bf16 / float16 filters.
@@ -54,6 +76,7 @@ typedef int __attribute__((ext_vector_type(4))) i32x4;
 constexpr int kI8StatWords = 8;
 // tile parameters (float4 per 32-row tile): x = s_t, y = e_t (largest |x - x^| of its rows, rounded up), z = 1 / (2 s_t), w = -
 constexpr int kI8MaxK = 16;           // results per query the int8 first stage serves (vec_index.hip, enqueue_search)
+static_assert(kI8MaxK <= kSieveSampleMaxK, "the exact sample threshold evaluates k rows in one round");
 constexpr int kI8Region = 32768;       // candidates per launch and CU: eight wave-private parts of 4096 (one eight-wave workgroup, or two of four waves)
 constexpr int kI8WavePart = kI8Region / 8;
 // The margin of a row of a tile with residual bound e_t and scale s_t, in inner-product units, as mg_t = e_t * A + B + 2 s_t s_q:
@@ -300,6 +323,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sieve_i8_kernel(const uint4 *__res
     // numbers the per-tile integer bound is made of: ib_t = floor((P1 - e_t A1) / s_t) - 4 (see the header)
     // (the float bound of the rare path is rebuilt from the same three numbers: bound_t = (P1 - e_t A1 - 2 s_t) L sq - amin)
     float sq[QT], mA[QT], mB[QT], P1[QT], A1[QT], guard[QT], best[QT];
+    uint32_t brow[QT];  // (SAMPLE) the row of `best`
     i32x4 qh[QT][KS64];
     const bool active = nq > wave8 * QT * 16;
 #pragma unroll
@@ -309,7 +333,7 @@ __global__ __launch_bounds__(NW * 64, 2) void sieve_i8_kernel(const uint4 *__res
         lane_live[u] = qloc[u] < nq;
         live_mask[u] = __builtin_amdgcn_ballot_w64(lane_live[u]);
         sq[u] = 1.0f; mA[u] = 0.f; mB[u] = 0.f; P1[u] = -__builtin_inff(); A1[u] = 0.f; tbc[u] = -__builtin_inff();
-        guard[u] = __builtin_inff(); best[u] = -__builtin_inff();
+        guard[u] = __builtin_inff(); best[u] = -__builtin_inff(); brow[u] = 0;
         if (lane_live[u]) {
             const float qn = (float)q_norm[qloc[u]] * (1.0f + 1e-6f);
             const float eq = (float)q_err[qloc[u]] * (1.0f + 1e-6f);
@@ -381,7 +405,8 @@ __global__ __launch_bounds__(NW * 64, 2) void sieve_i8_kernel(const uint4 *__res
                 for (int r = 0; r < 8; ++r) {
                     const float fi = (float)(r < 4 ? c0[r & 3] : c1[r & 3]);
                     const float w = KIND == SCAN_L2 ? fmaf(vs, fi, -ax[r]) : KIND == SCAN_COS ? vs * fi * ax[r] : vs * fi;
-                    if (w + mg < guard[u]) best[u] = fmaxf(best[u], w - mg);
+                    const uint32_t row = t * kTileRows + 4 * jg + 16 * (r >> 2) + (r & 3);
+                    if (w + mg < guard[u] && w - mg > best[u] && row < n_rows) { best[u] = w - mg; brow[u] = row; }
                 }
             }
             return;
@@ -514,12 +539,19 @@ __global__ __launch_bounds__(NW * 64, 2) void sieve_i8_kernel(const uint4 *__res
 #pragma unroll
         for (int u = 0; u < QT; ++u) filter(u, p0[u], p1[u], pax, pt, ptp);
     }
-    if (SAMPLE) {
+    if (SAMPLE) {  // two (lower bound, row) per workgroup and query: floats [grid][QPL][2], then their rows [grid][QPL][2]
+        uint32_t *part_row = reinterpret_cast<uint32_t *>(part_sample + (size_t)gridDim.x * QPL * 2);
 #pragma unroll
         for (int u = 0; u < QT; ++u) {
             const float o = __shfl_xor(best[u], 16, 64);
-            const float b2 = fmaxf(best[u], o);
-            if (lane_live[u] && (jg == 0 || jg == 2)) part_sample[((size_t)blockIdx.x * QPL + qloc[u]) * 2 + (jg >> 1)] = b2;
+            const uint32_t orow = (uint32_t)__shfl_xor((int)brow[u], 16, 64);
+            const bool other = o > best[u];
+            const float b2 = other ? o : best[u];
+            const size_t at = ((size_t)blockIdx.x * QPL + qloc[u]) * 2 + (jg >> 1);
+            if (lane_live[u] && (jg == 0 || jg == 2)) {
+                part_sample[at] = b2;
+                part_row[at] = other ? orow : brow[u];
+            }
         }
         return;
     }

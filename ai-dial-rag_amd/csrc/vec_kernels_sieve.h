@@ -26,7 +26,8 @@
 // Thresholds, progressively (as the q16 scan): a 32K-row sample gives T0 (the k-th largest of 512 per-lane lower
 // bounds v - mg over distinct rows); launch 1 sieves the first 1/16 of the tiles with T0; the k-th largest v of its
 // candidates gives T1 = kv - mg; launch 2 sieves the rest with T1.  The candidates of both launches are selected from
-// together at the end.
+// together at the end.  Round 5: T1 is the k-th largest EXACT value of the rows that bound it (select, mode 0), and behind the
+// int8 filter T0 too (sieve_sample_threshold_kernel) - never below the bound; the proof is in vec_kernels_i8.h's header.
 //
 // euclidean_dist quirk (embeddings_metrics.py:50): sqrt of a negative rounding residue is NaN and sorts LAST, so
 // a row (nearly) identical to the query has the LARGEST ranking value and the WORST rank.  Rows that could be NaN
@@ -960,18 +961,10 @@ __global__ __launch_bounds__(kSieveSelectThreads) void sieve_select_kernel(Sieve
     //         true value from below
     const bool have = ns >= a.k;
     const float kv = have ? kth_largest(s_v, n) : 0.f;
-    if (a.mode == 0) {
-        if (have && tid == 0) {
-            const float thr = kv - 4e-6f * fabsf(kv) - eps_m;
-            const unsigned long long key = (unsigned long long)orderable(thr) << 32;
-            if (thr == thr && key > a.gthr[blockIdx.x]) a.gthr[blockIdx.x] = key;
-        }
-        if (tid == 0) atomicAdd(a.stats + 4, (unsigned long long)n);  // entries listed after launch 1
-        return;
-    }
     // ---- 2. the rows that can be among the first k.  Class 1: lower bound >= kv (at least k of them), the ones that may be
     //         NaN, and everything when there is no kv - always evaluated.  Class 2: upper bound >= kv > lower bound - evaluated
     //         only if class 1's exact values leave them a chance (step 3).  s_fin = class 1, then class 2.
+    //         (mode 0: class 1 without the rows that may be NaN - the next launch's threshold is made of them alone)
     const float cut = have ? kv - 1e-5f * fabsf(kv) - eps_m : -__builtin_inff();
     auto compact = [&](int cls, int *counter) {
         for (int e0 = 0; e0 < n; e0 += NT) {
@@ -980,7 +973,8 @@ __global__ __launch_bounds__(kSieveSelectThreads) void sieve_select_kernel(Sieve
             if (e < n) {
                 const float lb = s_v[e];
                 const bool c1 = !have || !(lb > -__builtin_inff()) || !(lb < kv);
-                if (cls == 1) fin = c1;
+                if (a.mode == 0) fin = cls == 1 && lb > -__builtin_inff() && !(lb < kv);
+                else if (cls == 1) fin = c1;
                 else if (!c1) fin = !(lb + 2.0f * margin_of(lr[e]) * (1.0f + 1e-6f) < cut);
             }
             const unsigned long long bal = __ballot(fin);
@@ -992,15 +986,6 @@ __global__ __launch_bounds__(kSieveSelectThreads) void sieve_select_kernel(Sieve
         }
         __syncthreads();
     };
-    compact(1, &s_f);
-    const int f1 = s_f;
-    if (tid == 0) s_f1 = f1;
-    compact(2, &s_f);
-    int f = s_f;
-    if (f > kSieveSelectCap) {  // a mass of rows within the filter's resolution of the cut: the exact pass orders them
-        to_exact_pass();
-        return;
-    }
     // the reference's float64 formula for s_fin[lo..hi): four rows per wave at a time, 16 lanes each (a row is a chain of
     // dependent fetches - list -> row index -> row: with one row per wave a clustered corpus's ~1800 rows per query were 112
     // rounds of that latency).  s_d = the distance, s_x = its ranking value rounded to float
@@ -1029,6 +1014,52 @@ __global__ __launch_bounds__(kSieveSelectThreads) void sieve_select_kernel(Sieve
         }
         __syncthreads();
     };
+    // the number of numeric exact values among s_x[0..m) (a NaN distance is -inf there) -> s_nn
+    auto count_numeric = [&](int m) {
+        for (int i0 = 0; i0 < m; i0 += NT) {
+            const int i = i0 + tid;
+            const bool num = i < m && s_x[i] > -__builtin_inff();
+            const unsigned long long bal = __ballot(num);
+            if (bal && lane == __builtin_ctzll(bal)) atomicAdd(&s_nn, __popcll(bal));
+        }
+        __syncthreads();
+    };
+    if (a.mode == 0) {
+        // ---- mode 0: the next launch's threshold.  kv - mg bounds the k-th best true value from below; so do the EXACT values
+        //      of any k distinct rows - the reference formula on class 1 (the certainly-not-NaN rows with lower bound >= kv) -
+        //      and those lie up to 2 mg higher: every row within the filter's resolution of the bound would otherwise be listed
+        //      by the next launch (int8 filter, 10M x 384, k = 10: 2.4k -> ~0.6k rows per query).  A class too large for
+        //      the LDS, or fewer than k numeric values, keeps the lower bound.  Never the exact pass from here.
+        if (have) {
+            float thr = kv - 4e-6f * fabsf(kv) - eps_m;
+            compact(1, &s_f);
+            const int f1 = s_f;
+            if (f1 <= kSieveSelectCap) {
+                evaluate(0, f1);
+                count_numeric(f1);
+                if (s_nn >= a.k) {
+                    const float rk = kth_largest(s_x, f1);
+                    const float need = rk - 4e-6f * fabsf(rk) - eps_m;  // as step 3's: (float)rv rounds to nearest
+                    thr = need > thr ? need : thr;                       // (>= the lower bound by construction; a NaN keeps it)
+                }
+            }
+            if (tid == 0) {
+                const unsigned long long key = (unsigned long long)orderable(thr) << 32;
+                if (thr == thr && key > a.gthr[blockIdx.x]) a.gthr[blockIdx.x] = key;
+            }
+        }
+        if (tid == 0) atomicAdd(a.stats + 4, (unsigned long long)n);  // entries listed after launch 1
+        return;
+    }
+    compact(1, &s_f);
+    const int f1 = s_f;
+    if (tid == 0) s_f1 = f1;
+    compact(2, &s_f);
+    int f = s_f;
+    if (f > kSieveSelectCap) {  // a mass of rows within the filter's resolution of the cut: the exact pass orders them
+        to_exact_pass();
+        return;
+    }
 #if SIEVE_SELECT_ABL == 1
     return;
 #endif
@@ -1041,13 +1072,7 @@ __global__ __launch_bounds__(kSieveSelectThreads) void sieve_select_kernel(Sieve
     // ---- 3. class 2 against class 1's exact values: with rk = the k-th largest exact ranking value of class 1 (numeric
     //         distances only), a row whose v + mg stays below rk is beaten by k rows for certain and is dropped unevaluated
     if (two_rounds) {
-        for (int i0 = 0; i0 < f1; i0 += NT) {
-            const int i = i0 + tid;
-            const bool num = i < f1 && s_x[i] > -__builtin_inff();
-            const unsigned long long bal = __ballot(num);
-            if (bal && lane == __builtin_ctzll(bal)) atomicAdd(&s_nn, __popcll(bal));
-        }
-        __syncthreads();
+        count_numeric(f1);
         if (s_nn >= a.k) {
             const float rk = kth_largest(s_x, f1);
             const float need = rk - 4e-6f * fabsf(rk) - eps_m;  // (float)rv rounds to nearest: the slack covers it
@@ -1124,6 +1149,84 @@ __global__ __launch_bounds__(kSieveSelectThreads) void sieve_select_kernel(Sieve
         atomicAdd(a.stats + 2, 1ull);
         if (a.out_count) a.out_count[qi] = kout;
         if (a.out_flags) a.out_flags[qi] = 0;
+    }
+}
+
+// ---------------------------------------------------------------- the sample's threshold, exact
+// After the int8 filter's sample launch: per workgroup and query two (lower bound, row) pairs over disjoint rows.
+// sample_threshold_kernel's T0 is the k-th largest lower bound.  Here the k rows of the k largest lower bounds get the reference
+// formula (sieve_metric_g16, the select kernel's arithmetic); k distinct rows' exact values bound the k-th best true value from
+// below just as well, and lie up to 2 mg above their lower bounds: T0 = max(the k-th lower bound, the k-th exact ranking value
+// less the select's slack).  Rows that may be NaN are not in the sample (the filter's guard); a NaN distance counts for nothing,
+// and fewer than k numeric values keep the lower bound.  One block per query, k <= 16.
+constexpr int kSieveSampleMaxK = 16;
+struct SieveSampleArgs {
+    const float *part;      // [nwg][qpw][2] lower bounds, then (as uint32) [nwg][qpw][2] their rows
+    int nwg, qpw, k, nq, q0, d, metric;
+    const float *docs, *doc_sq;
+    const double *q, *q_sq, *q_norm;  // of the whole call: query q0 + blockIdx.x
+    unsigned long long *gthr;         // [nq] of this launch group
+};
+__global__ __launch_bounds__(256) void sieve_sample_threshold_kernel(SieveSampleArgs a) {
+    constexpr int kMaxVals = 2 * 256;  // two per workgroup, kSampleWgs <= 256
+    __shared__ unsigned long long keys[kMaxVals];
+    __shared__ float s_x[kSieveSampleMaxK];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q = blockIdx.x;
+    if (q >= a.nq || a.k > kSieveSampleMaxK) return;
+    const uint32_t *prow = reinterpret_cast<const uint32_t *>(a.part + (size_t)a.nwg * a.qpw * 2);
+    const int n = 2 * a.nwg;
+    for (int e = tid; e < kMaxVals; e += 256) {
+        unsigned long long key = 0;  // (nothing / NaN / -inf: 0, below every value)
+        if (e < n) {
+            const size_t at = ((size_t)(e >> 1) * a.qpw + q) * 2 + (e & 1);
+            const float v = a.part[at];
+            if (v > -__builtin_inff()) key = ((unsigned long long)orderable(v) << 32) | prow[at];
+        }
+        keys[e] = key;
+    }
+    // bitonic sort, descending (sample_threshold_kernel's)
+    for (int size = 2; size <= kMaxVals; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            const int lo = 2 * tid - (tid & (stride - 1)), hi = lo + stride;
+            const bool desc = (lo & size) == 0;
+            const unsigned long long x = keys[lo], y = keys[hi];
+            if ((x < y) == desc) {
+                keys[lo] = y;
+                keys[hi] = x;
+            }
+        }
+    __syncthreads();
+    if (keys[a.k - 1] == 0) return;  // fewer than k rows in the sample: no threshold (as sample_threshold_kernel)
+    // the reference formula for the k rows: four groups of 16 lanes per wave, one row each
+    const int qi = a.q0 + q;
+    const double *qv = a.q + (size_t)qi * a.d;
+    const double q_sq = a.q_sq[qi], q_norm = a.q_norm[qi];
+    const int sub = lane >> 4, lg = lane & 15;
+    for (int i0 = wave * 4; i0 < a.k; i0 += 16) {
+        const int i = i0 + sub;
+        const bool live = i < a.k;
+        const uint32_t row = (uint32_t)keys[live ? i : i0];
+        double rv, dist;
+        if ((a.d & 3) == 0)
+            dist = sieve_metric_g16<float>(a.docs + (size_t)row * a.d, qv, a.d, a.metric, a.doc_sq[row], q_sq, q_norm, lg, &rv);
+        else
+            dist = exact_metric_wave<float, 16, 8>(a.docs + (size_t)row * a.d, qv, a.d, a.metric, a.doc_sq[row], q_sq, q_norm, lg, &rv);
+        if (live && lg == 0) s_x[i] = dist == dist ? (float)rv : -__builtin_inff();  // (a NaN distance ranks last)
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float thr = key_value(keys[a.k - 1]);
+        int nn = 0;
+        for (int i = 0; i < a.k; ++i) nn += s_x[i] > -__builtin_inff() ? 1 : 0;
+        if (nn == a.k) {  // all k numeric: the smallest is the k-th largest
+            float rk = s_x[0];
+            for (int i = 1; i < a.k; ++i) rk = fminf(rk, s_x[i]);
+            const float need = rk - 4e-6f * fabsf(rk);  // (float)rv rounds to nearest: the select kernel's slack
+            thr = need > thr ? need : thr;
+        }
+        a.gthr[q] = (unsigned long long)orderable(thr) << 32;
     }
 }
 

@@ -7,7 +7,12 @@ protocol: T0 from a 32K-row sample, launch 1 over the first 1/16 of the rows, T1
 candidates, launch 2 over the rest, then the rows whose upper bound reaches the k-th largest lower bound are "evaluated"
 (the reference formula in float64).
 
-    python3 tools/i8_sieve_emulation.py [rows=10000000] [queries=16] [k=10]
+    python3 tools/i8_sieve_emulation.py [rows=10000000] [queries=16] [k=10] [first-launch rows=rows / 16]
+
+`exact` columns (round 5, the shipped protocol since): T0 and T1 are the k-th largest EXACT value of k distinct rows - the
+sample's k best lower bounds, and launch 1's candidates whose lower bound reaches the k-th largest - instead of the k-th
+largest lower bound (never below it).  The final select is the same either way.  (A 600K-row shard on 256 CUs: first launch
+149952 rows.)
 
 Variants: bf16 (the shipped filter: control - compare with bench.py's `sieve` counters), i8 with one scale per index,
 per 32-row tile, per row (a row / tile scale costs the filter a multiply per value or a bound per tile); `_rowm` = the same
@@ -89,6 +94,7 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
     nq = int(sys.argv[2]) if len(sys.argv) > 2 else 16
     k = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+    n1 = int(sys.argv[4]) if len(sys.argv) > 4 else n // 16
     d = 384
     torch.set_num_threads(8)
     names = ["bf16", "i8_index", "i8_tile", "i8_row"]
@@ -112,9 +118,11 @@ def main():
         v = {nm: torch.empty((n, nq)) for nm in names}
         ex = {nm: torch.empty(n) for nm in names}
         xn = torch.empty(n)
+        xt = torch.empty((n, nq))  # the exact values x.q (float64 products, stored rounded)
         for c0, x in corpus_chunks(kind, n, d):
             m = x.shape[0]
             xn[c0 : c0 + m] = x.norm(dim=1)
+            xt[c0 : c0 + m] = (x.double() @ q.double().T).float()
             img = {"bf16": bf16_round(x), "i8_index": quant_i8(x, gmax / 127.0)}
             rmax = x.abs().max(dim=1, keepdim=True).values
             img["i8_row"] = quant_i8(x, rmax / 127.0)
@@ -124,14 +132,15 @@ def main():
                 v[nm][c0 : c0 + m] = img[nm] @ qimg[nm].T
                 ex[nm][c0 : c0 + m] = (x - img[nm]).norm(dim=1)
         print(f"\n### {kind}: {n} x {d} unit rows, {nq} queries, k = {k}  (largest |x_i| {gmax:.3f}; {time.time() - t0:.0f} s)")
-        print("| filter | max residual norm of a row | mean | query residual | margin (ip units) | listed, launch 1 | launch 2 | evaluated in float64 |")
-        print("|---|---|---|---|---|---|---|---|")
-        n1 = n // 16
+        print("| filter | max residual norm of a row | mean | query residual | margin (ip units) | listed, launch 1 | launch 2 | evaluated in float64 "
+              "| exact: listed, launch 1 | launch 2 | evaluated |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|")
         for nm in names:
             for per_row in (False, True):
                 e_max = float(ex[nm].max())
                 xmax = float(xn.max())
                 l1 = l2 = ev = 0.0
+                x1 = x2 = xev = 0.0
                 mgs = []
                 for j in range(nq):
                     vj = v[nm][:, j]
@@ -150,10 +159,26 @@ def main():
                     ub = listed + 2 * torch.cat([mg[:n1][c1], mg[n1:][c2]])
                     kv = torch.topk(listed, k).values[-1]
                     l1 += float(c1.sum()); l2 += float(c2.sum()); ev += float((ub >= kv).sum())
+                    # exact thresholds: the k rows of the sample's k best lower bounds, then launch 1's class 1 (lower bound
+                    # >= its k-th largest), evaluated; the k-th largest exact value less the select's slack, never below the bound
+                    xj = xt[:, j]
+                    top0 = torch.topk(lb[:32768], k).indices
+                    e0 = torch.topk(xj[:32768][top0], k).values[-1]
+                    t0e = torch.maximum(t0_, e0 - 4e-6 * e0.abs())
+                    e1 = vj[:n1] + mg[:n1] >= t0e
+                    ids1 = torch.nonzero(e1).squeeze(1)
+                    kv1 = torch.topk(lb[ids1], k).values[-1]
+                    cls1 = ids1[lb[ids1] >= kv1]
+                    ek = torch.topk(xj[cls1], k).values[-1]
+                    t1e = torch.maximum(kv1, ek - 4e-6 * ek.abs())
+                    e2 = vj[n1:] + mg[n1:] >= t1e
+                    lst = torch.cat([lb[:n1][e1], lb[n1:][e2]])
+                    ubx = lst + 2 * torch.cat([mg[:n1][e1], mg[n1:][e2]])
+                    x1 += float(e1.sum()); x2 += float(e2.sum()); xev += float((ubx >= torch.topk(lst, k).values[-1]).sum())
                 tag = nm + ("_rowm" if per_row else "")
                 print(f"| {tag} | {e_max:.5f} | {float(ex[nm].mean()):.5f} | {float(eq[nm].mean()):.5f} | {np.mean(mgs):.5f} | "
-                      f"{l1 / nq:.0f} | {l2 / nq:.0f} | {ev / nq:.0f} |", flush=True)
-        del v, ex
+                      f"{l1 / nq:.0f} | {l2 / nq:.0f} | {ev / nq:.0f} | {x1 / nq:.0f} | {x2 / nq:.0f} | {xev / nq:.0f} |", flush=True)
+        del v, ex, xt
 
 
 if __name__ == "__main__":
