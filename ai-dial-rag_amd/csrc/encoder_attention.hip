@@ -78,7 +78,10 @@ __device__ __forceinline__ float attn_lane_max(const f32x16 &s) {  // this lane'
 }
 // move the reference by delta (0 leaves every value as it is, bit for bit: x - 0, x * exp2(-0))
 __device__ __forceinline__ void attn_rescale(AttnState &st, f32x16 &s, float delta) {
-    const float alpha = __builtin_amdgcn_exp2f(-delta);
+    // delta < 0 happens on a sequence's first key tile only (every score of the tile below 0), where o = lsum = 0: the factor
+    // does not matter there, but it must stay finite - below -128 exp2(-delta) is +inf and 0 x inf = NaN for the whole query
+    // (tests/test_gpu_encoder_attention.py, sharp, layer 2).  For delta >= 0 this is exp2(-delta) as before, bit for bit.
+    const float alpha = __builtin_amdgcn_exp2f(-fmaxf(delta, 0.f));
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         s[r] -= delta;

@@ -24,4 +24,7 @@ Pinning status ("Oracle"):
   ``EnsembleRetriever.weighted_reciprocal_rank`` restated.
 * encoder         - ``transformers.BertModel`` fp32 (third-party, present) is
   the arithmetic oracle; real bge-small-en weights are unavailable offline.
+  ``encoder.hidden_states_points`` restates the same arithmetic with a float16
+  rounding wherever the HIP kernels round (in float64 and float32), and the
+  case models there give the attention kernels peaked scores to work on.
 """

@@ -11,6 +11,11 @@ bge-small-en shape it is the oracle for the HIP kernels.  PARITY WITH THE REAL
 MODEL IS UNPINNED: no bge-small-en weights exist offline, and the reference's
 only pin (tests/test_retrievers.py:90-104, top-1 chunk for one query) needs
 them.
+
+Below `embed`: the rounding-point oracle (the same arithmetic with a float16
+rounding where the kernels round) and the case models whose attention is peaked
+the way a trained encoder's is (tests/test_oracle_encoder_points.py,
+tests/test_gpu_encoder_attention.py).
 """
 
 import numpy as np
@@ -24,7 +29,10 @@ def make_model(layers: int = 12, seed: int = 0, scale: float = 1.0):
                      vocab_size=30522, max_position_embeddings=512)
     torch.manual_seed(seed)
     m = BertModel(cfg, add_pooling_layer=False).eval()
-    if scale != 1.0:  # random init (std 0.02) gives near-linear layers; larger weights exercise softmax / GELU / LN
+    # random init (std 0.02) gives near-linear layers; larger weights move the GELU and the LayerNorms off their linear range.
+    # Attention stays NEAR-UNIFORM at scale 2.5 (largest softmax probability ~0.007 per query, no move of the kernels' lazy
+    # softmax reference after the first key tile): peaked attention needs the case models below (sharp_model, placed_model, ...).
+    if scale != 1.0:
         with torch.no_grad():
             for n, p in m.named_parameters():
                 if "LayerNorm" not in n and p.dim() == 2:
@@ -51,3 +59,300 @@ def embed(model, sequences, normalize=True) -> np.ndarray:
     if normalize:
         cls = cls / np.maximum(np.linalg.norm(cls, axis=1, keepdims=True), 1e-12)
     return cls.astype(np.float32)
+
+
+# ---------------------------------------------------------------- the rounding-point oracle
+# The same arithmetic as `hidden_states`, written out on the state dict, with a float16 rounding wherever the HIP kernels
+# store or feed float16 (read off ai-dial-rag_amd/csrc):
+#   weights            pack_block (encoder.hip): every Linear weight is an MFMA operand, float16; biases, LayerNorm
+#                      parameters and the three embedding tables stay float32
+#   embedding LN       embed_ln_kernel: pack2 of the LayerNorm output
+#   Q, K, V            qkv_kernel / qkv_small_kernel / the fused kernels: (acc + bias) [* kQScaleLog2e for Q] -> acc_to_frag
+#   P                  attn_pv: exp2(s - ref) -> pack2_cv; the row sum is taken FROM the rounded P (mfma_sum)
+#   context            attn_store: o / lsum -> acc_to_frag
+#   attention LN, FFN LN   ln_part_store: the LayerNorm output (it is also the next block's residual)
+#   GELU               gelu_pack2: x * Phi(x) -> float16 in one rounding
+# The kernels' P is exp2(s - ref) with a LAZY reference (ref >= the true row maximum - kAttnSlack, encoder_attention.hip);
+# the oracle uses the true maximum: the same relative rounding, other single flips.
+ATTN_TILE = 32     # queries per wave and keys per step
+ATTN_SLACK = 6.0   # kAttnSlack
+GELU_LUT_LIM = 5.5
+CASE_LENGTHS = (1, 31, 32, 33, 64, 95, 100, 255, 257, 512)  # 1, 1, 1, 2, 2, 3, 4, 8, 9, 16 key tiles; L mod 32 = 1, 31, 0 among them
+
+
+def _ln(x, g, b):
+    d = x - x.mean(-1, keepdim=True)
+    return d * torch.rsqrt((d * d).mean(-1, keepdim=True) + 1e-12) * g + b
+
+
+@torch.no_grad()
+def hidden_states_points(model, sequences, layers_to_run=None, dtype=torch.float64, points=True, pad_rows=False,
+                         extra_pad_keys=0, key_keep=None, trace=None, every_layer=False):
+    """Per-sequence hidden states (numpy float64) after `layers_to_run` layers, all arithmetic in `dtype` and - with
+    `points` - a float16 rounding at every point listed above.  points=False, float64 is `hidden_states` of model.double().
+
+    pad_rows: compute the rows the kernels compute - the sequence extended with token id 0 to a multiple of 32 rows, the
+      padding keys masked except the first `extra_pad_keys` of them (a seeded mask fault); only the real rows are returned.
+    key_keep(i, L) -> bool tensor over the keys of sequence i: a seeded fault that drops keys.
+    trace(dict): called per (sequence, layer) with the exp2-unit scores [heads, rows, rows], n_keys and the GELU inputs.
+    every_layer: per sequence the list of states after 0, 1, ..., `layers_to_run` layers instead of the last one."""
+    sd = {k: v.detach() for k, v in model.state_dict().items()}
+    rnd = (lambda x: x.to(torch.float32).to(torch.float16).to(dtype)) if points else (lambda x: x)
+    W = lambda k: rnd(sd[k].to(dtype))  # noqa: E731
+    F = lambda k: sd[k].to(dtype)  # noqa: E731
+    n_layers = 0
+    while f"encoder.layer.{n_layers}.attention.self.query.weight" in sd:
+        n_layers += 1
+    run = n_layers if layers_to_run is None else layers_to_run
+    # the kernels' constant is a float32 product (kQScaleLog2e); without rounding points the exact one, to equal the model
+    qs = float(np.float32(0.17677669529663688) * np.float32(1.4426950408889634)) if points else 1.4426950408889634 / 32 ** 0.5
+    outs = []
+    for si, ids in enumerate(sequences):
+        L = len(ids)
+        rows = (L + ATTN_TILE - 1) // ATTN_TILE * ATTN_TILE if pad_rows else L
+        t = torch.tensor(list(ids) + [0] * (rows - L), dtype=torch.long)
+        x = F("embeddings.word_embeddings.weight")[t] + F("embeddings.token_type_embeddings.weight")[0] \
+            + F("embeddings.position_embeddings.weight")[torch.arange(rows).clamp(max=511)]
+        x = rnd(_ln(x, F("embeddings.LayerNorm.weight"), F("embeddings.LayerNorm.bias")))
+        n_keys = min(L + extra_pad_keys, rows)
+        keep = torch.arange(rows) < n_keys
+        states = [x[:L].double().numpy()]
+        if key_keep is not None:
+            keep = keep & torch.cat([key_keep(si, L), torch.ones(rows - L, dtype=torch.bool)])
+        for li in range(run):
+            p = f"encoder.layer.{li}."
+            heads = lambda y: y.view(rows, 12, 32).transpose(0, 1)  # noqa: E731
+            q = heads(rnd((x @ W(p + "attention.self.query.weight").T + F(p + "attention.self.query.bias")) * qs))
+            k = heads(rnd(x @ W(p + "attention.self.key.weight").T + F(p + "attention.self.key.bias")))
+            v = heads(rnd(x @ W(p + "attention.self.value.weight").T + F(p + "attention.self.value.bias")))
+            s = (q @ k.transpose(1, 2)).masked_fill(~keep, float("-inf"))
+            pr = rnd(torch.exp2(s - s.max(-1, keepdim=True).values))
+            ctx = (pr @ v) / pr.sum(-1, keepdim=True)
+            ctx = rnd(ctx).transpose(0, 1).reshape(rows, 384)
+            a = ctx @ W(p + "attention.output.dense.weight").T + F(p + "attention.output.dense.bias") + x
+            x1 = rnd(_ln(a, F(p + "attention.output.LayerNorm.weight"), F(p + "attention.output.LayerNorm.bias")))
+            gin = x1 @ W(p + "intermediate.dense.weight").T + F(p + "intermediate.dense.bias")
+            if trace is not None:
+                trace({"seq": si, "layer": li, "scores": s.double(), "n_keys": n_keys, "len": L,
+                       "gelu_in": gin[:L].double()})
+            hdn = rnd(torch.nn.functional.gelu(gin))
+            y = hdn @ W(p + "output.dense.weight").T + F(p + "output.dense.bias") + x1
+            x = rnd(_ln(y, F(p + "output.LayerNorm.weight"), F(p + "output.LayerNorm.bias")))
+            states.append(x[:L].double().numpy())
+        outs.append(states if every_layer else states[-1])
+    return outs
+
+
+def lazy_reference_replay(scores, n_keys, length, slack=ATTN_SLACK):
+    """Float64 replay of the kernels' lazy softmax reference on one sequence's scores [heads, rows, rows] (exp2 units, rows a
+    multiple of 32: `pad_rows`, the padding queries vote like the kernels' do): one wave per (head, 32-query tile), 32 keys
+    per step, reference = the first tile's maximum, moved - for every query of the wave by max(own maximum, 0) - when any
+    query's maximum exceeds it by more than `slack`.  Returns per-step arrays over [heads, query tiles, key tiles - 1]:
+    voted; clamp (a voting step in which a real query's own maximum was <= 0); and moved [heads, rows, key tiles - 1]
+    (the query itself exceeded the slack); and first_ref [heads, rows], the reference after the first key tile."""
+    s = scores.double().numpy()
+    nh, rows, _ = s.shape
+    assert rows % ATTN_TILE == 0
+    n_qt, n_kt = rows // ATTN_TILE, (n_keys + ATTN_TILE - 1) // ATTN_TILE
+    real = np.arange(rows) < length
+    ref = s[:, :, : min(ATTN_TILE, n_keys)].max(-1)
+    first_ref = ref.copy()
+    voted = np.zeros((nh, n_qt, max(n_kt - 1, 0)), bool)
+    clamp = np.zeros_like(voted)
+    moved = np.zeros((nh, rows, max(n_kt - 1, 0)), bool)
+    for kt in range(1, n_kt):
+        mq = s[:, :, ATTN_TILE * kt : min(ATTN_TILE * (kt + 1), n_keys)].max(-1) - ref
+        moved[:, :, kt - 1] = mq > slack
+        vote = moved[:, :, kt - 1].reshape(nh, n_qt, ATTN_TILE).any(-1)
+        voted[:, :, kt - 1] = vote
+        clamp[:, :, kt - 1] = vote & ((mq <= 0) & real).reshape(nh, n_qt, ATTN_TILE).any(-1)
+        ref = ref + np.where(np.repeat(vote, ATTN_TILE, axis=1), np.maximum(mq, 0.0), 0.0)
+    return {"voted": voted, "clamp": clamp, "moved": moved, "last_tile_masked": n_kt > 1 and n_keys % ATTN_TILE != 0,
+            "first_ref": first_ref}
+
+
+# ---------------------------------------------------------------- case models: attention and magnitudes as trained encoders have them
+# All are 2-layer models of make_model's recipe with an edited state dict; run 1 or 2 of the layers.
+SHARP_GAINS = (1, 1, 2, 2, 3, 3, 4, 4, 6, 6, 8, 8)  # per head, on the rows of W_q, b_q, W_k, b_k: scores x gain^2
+LEVEL_IDS = tuple(range(1, 17))  # placed: token 1 + l is a key of score ~ 10 (l + 1) exp2 units for a seeker query of head 0
+PLAIN_ID = 20                    # placed: a token whose head-0 query is ~ -0.05 of a seeker's
+AVERSE_ID = 21                   # placed: a token whose head-0 query is ~ -1 of a seeker's: a level-l key scores -10 (l + 1)
+_PLACED_TOP = 210.0              # the score a key exactly along the level direction would have
+_BAIT_COS = 0.8                  # pad-bait: token 0 scores 168, above every level (160 at most)
+OUTLIER_CHANNELS = {7: 12.0, 77: 20.0, 150: 8.0, 229: 16.0, 300: 10.0, 381: 14.0}  # embedding LayerNorm: channel -> gamma gain
+OUTLIER_CHANNELS_ATTN = {33: 12.0, 120: 20.0, 199: 8.0, 260: 16.0, 333: 10.0, 370: 14.0}  # the attention blocks' LayerNorms
+
+
+def random_ids(rng, L):
+    ids = rng.integers(999, 30522, L).tolist()
+    ids[0] = 101
+    if L > 1:
+        ids[-1] = 102
+    return ids
+
+
+def random_sequences(seed):
+    rng = np.random.default_rng(seed)
+    return [(f"random_{L}", random_ids(rng, L)) for L in CASE_LENGTHS]
+
+
+@torch.no_grad()
+def sharp_model():
+    """Peaked heads with maxima at random positions: Q and K of head h scaled by SHARP_GAINS[h] (both layers)."""
+    m = make_model(layers=2, seed=3, scale=2.5)
+    sd = m.state_dict()
+    g = torch.tensor(SHARP_GAINS, dtype=torch.float32).repeat_interleave(32)
+    for li in range(2):
+        for nm in ("query", "key"):
+            sd[f"encoder.layer.{li}.attention.self.{nm}.weight"].mul_(g[:, None])
+            sd[f"encoder.layer.{li}.attention.self.{nm}.bias"].mul_(g)
+    return m
+
+
+def _directions(n, seed):
+    """n orthonormal zero-mean directions of the hidden space (zero mean: LayerNorm's centring leaves them alone)."""
+    gen = torch.Generator().manual_seed(seed)
+    a = torch.randn(384, n, generator=gen, dtype=torch.float64)
+    a -= a.mean(0, keepdim=True)
+    return torch.linalg.qr(a).Q.T.contiguous()
+
+
+@torch.no_grad()
+def placed_model(bait=False):
+    """Attention whose peaks the sequences choose (layer 1, head 0).  Directions d, dq, dv, da and one e_l per level are removed
+    from every embedding row; then head 0's key is kappa (d . x) u, its query (1 + rho (dq . x) + rho' (da . x)) u: a query that
+    is mostly its bias, so the score of key j is ~ _PLACED_TOP cos(word row j, d) whatever the query ("seekers"), except for
+    PLAIN_ID's queries, whose row along -dq brings the factor to -0.05, and AVERSE_ID's, whose row along -da brings it to -1.
+    LEVEL_IDS' rows lie at chosen angles to d.
+    bait: row 0 - the id the host pads tiles with - becomes the strongest key of all and, along dv, a value of norm ~60."""
+    m = make_model(layers=2, seed=4, scale=2.5)
+    sd = m.state_dict()
+    dirs = _directions(4 + len(LEVEL_IDS), 40)
+    d, dq, dv, da, D = dirs[0], dirs[1], dirs[2], dirs[3], dirs
+    for nm in ("word_embeddings", "position_embeddings", "token_type_embeddings"):
+        w = sd[f"embeddings.{nm}.weight"]
+        w.copy_((w.double() - (w.double() @ D.T) @ D).float())
+    word, amp, root = sd["embeddings.word_embeddings.weight"], 20.0, 384 ** 0.5
+    for l, tid in enumerate(LEVEL_IDS):
+        c = 10.0 * (l + 1) / _PLACED_TOP
+        word[tid] = (amp * (c * d + (1 - c * c) ** 0.5 * dirs[4 + l])).float()  # its own direction e_l: its own value vector
+    word[PLAIN_ID] = (-amp * dq).float()
+    word[AVERSE_ID] = (-amp * da).float()
+    u = torch.randn(32, generator=torch.Generator().manual_seed(41), dtype=torch.float64)
+    u /= u.norm()
+    p = "encoder.layer.0.attention.self."
+    sd[p + "query.weight"][:32] = (torch.outer(u, 1.05 / root * dq + 2.0 / root * da)).float()
+    sd[p + "query.bias"][:32] = u.float()
+    sd[p + "key.weight"][:32] = (_PLACED_TOP / root / (1.4426950408889634 / 32 ** 0.5) * torch.outer(u, d)).float()
+    sd[p + "key.bias"][:32] = 0
+    if bait:
+        word[0] = (amp * (_BAIT_COS * d + (1 - _BAIT_COS ** 2) ** 0.5 * dv)).float()
+        wv = torch.randn(32, generator=torch.Generator().manual_seed(42), dtype=torch.float64)
+        sd[p + "value.weight"][:32] += (100.0 / root * torch.outer(wv / wv.norm(), dv)).float()
+    return m
+
+
+def placed_sequences(seed=7):
+    """(name, ids): no token 0 anywhere.  Ordinary tokens score ~0 in head 0; level l scores 10 (l + 1)."""
+    rng = np.random.default_rng(seed)
+    top = LEVEL_IDS[-1]
+    out = []
+
+    def seq(name, L, marks):
+        ids = random_ids(rng, L)
+        for pos, tid in marks.items():
+            ids[pos] = tid
+        out.append((name, ids))
+
+    for L in (1, 31, 32, 33, 64, 95, 512):  # the spike at the last valid key: L mod 32 = 1, 31, 0, and L = 512
+        seq(f"spike_last_{L}", L, {L - 1: top})
+    seq("spike_first_tile_100", 100, {7: top})
+    seq("spike_middle_tile_257", 257, {130: top})
+    # staircases: one stronger key per tile (the last tile's at the last valid key); odd positions hold PLAIN_ID, so every
+    # 32-query wave mixes seekers (delta > 0 at every step) with plain queries (their scores fall: the clamp to 0)
+    for L in (100, 255, 257, 512):
+        n_kt = (L + 31) // 32
+        marks = {p: PLAIN_ID for p in range(1, L, 2)}
+        marks.update({32 * t + 6: LEVEL_IDS[t] for t in range(n_kt - 1)})
+        marks[L - 1] = LEVEL_IDS[n_kt - 1]
+        seq(f"rising_{L}", L, marks)
+    # real queries whose every score of the first key tile is below -128 exp2 units (the tile is all levels 14-16, the
+    # queries are averse): exp2(-delta) of the first tile's move overflows float32
+    marks = {p: LEVEL_IDS[13 + p % 3] for p in range(32)}
+    marks.update({p: AVERSE_ID for p in range(32, 39)})
+    seq("averse_first_tile_40", 40, marks)
+    seq("falling_512", 512, {32 * t + 6: LEVEL_IDS[15 - t] for t in range(16)})  # the reference never moves, late P underflows
+    return out
+
+
+@torch.no_grad()
+def outlier_model():
+    """Outlier channels: a handful of large gammas in the embedding and attention LayerNorms (hidden magnitudes in the
+    tens; different channels in the two, or the gains would compound to hundreds), and every fourth row of the FFN's W1
+    tripled: with the plain rows' GELU inputs of standard deviation ~1.3 and the tripled rows' ~4, a few per cent of the
+    inputs lie beyond the table's clamp at +-5.5 and about half within +-1."""
+    m = make_model(layers=2, seed=5, scale=2.5)
+    sd = m.state_dict()
+    for ch, gain in OUTLIER_CHANNELS.items():
+        sd["embeddings.LayerNorm.weight"][ch] *= gain
+    for li in range(2):
+        for ch, gain in OUTLIER_CHANNELS_ATTN.items():
+            sd[f"encoder.layer.{li}.attention.output.LayerNorm.weight"][ch] *= gain
+    for li in range(2):
+        sd[f"encoder.layer.{li}.intermediate.dense.weight"][::4] *= 3.0
+    return m
+
+
+def case(name):
+    """(model, [(sequence name, ids)]) of a case family."""
+    if name == "sharp":
+        return sharp_model(), random_sequences(99)
+    if name == "placed":
+        return placed_model(), placed_sequences()
+    if name == "pad_bait":
+        return placed_model(bait=True), placed_sequences()
+    if name == "outlier":
+        return outlier_model(), random_sequences(98)
+    raise KeyError(name)
+
+
+CASES = ("sharp", "placed", "pad_bait", "outlier")
+ATTENTION_CASES = ("sharp", "placed", "pad_bait")
+
+
+def truth(model, sequences, layers_to_run=None, **kw):
+    """T: plain float64, no rounding point (equal to model.double() - tests/test_oracle_encoder_points.py checks it)."""
+    return hidden_states_points(model, sequences, layers_to_run, torch.float64, points=False, **kw)
+
+
+def half_ulp16(top):
+    """Half a float16 ulp at magnitude `top`."""
+    return float(np.spacing(np.float16(top))) / 2
+
+
+def gates(t, p64, p32):
+    """The per-case gates from the three references (lists of per-sequence arrays): against P64, against T, and the floor
+    of the pooled embedding's cosine to T."""
+    mx = lambda a, b: float(np.max(np.concatenate([np.abs(x - y).ravel() for x, y in zip(a, b)])))  # noqa: E731 (NaN propagates)
+    h = half_ulp16(float(np.max(np.concatenate([np.abs(x).ravel() for x in t]))))
+    d32, d64 = mx(p32, p64), mx(p64, t)
+    cos = float(np.min([x[0] @ y[0] / np.linalg.norm(x[0]) / np.linalg.norm(y[0]) for x, y in zip(p64, t)]))
+    return {"h": h, "p32_p64": d32, "p64_t": d64, "gate_p64": 4 * d32 + h, "gate_t": 2 * d64 + h,
+            "cos_p64_t": cos, "gate_cos": min(1 - 2 * (1 - cos), 1 - 1e-6)}
+
+
+def references(model, sequences, layers):
+    """T, P64, P32 of a case after `layers` layers and the gates they give."""
+    return references_every_layer(model, sequences, layers)[layers]
+
+
+def references_every_layer(model, sequences, layers):
+    """{n: references after n layers} for n = 0 .. layers, from one pass per reference."""
+    t = truth(model, sequences, layers, every_layer=True)
+    p64 = hidden_states_points(model, sequences, layers, torch.float64, every_layer=True)
+    p32 = hidden_states_points(model, sequences, layers, torch.float32, every_layer=True)
+    out = {}
+    for n in range(layers + 1):
+        tn, an, bn = [x[n] for x in t], [x[n] for x in p64], [x[n] for x in p32]
+        out[n] = {"T": tn, "P64": an, "P32": bn, **gates(tn, an, bn)}
+    return out

@@ -1,0 +1,150 @@
+"""The encoder's attention on PEAKED scores, every route, against rounding-aware oracles.
+
+tests/test_gpu_encoder.py's model attends near-uniformly: the kernels' lazy softmax reference (encoder_attention.hip) never
+moves after a sequence's first key tile there.  The case models of oracle/encoder.py make it move - on most steps (sharp),
+on every step of a staircase, on a last key tile with masked rows, with seekers and clamped queries in one voting wave
+(placed), with the host's padding token as the strongest key and a huge value (pad_bait) - and put outlier channels and
+GELU inputs beyond the table's clamp through the rest of the layer (outlier).  tests/test_oracle_encoder_points.py proves
+those properties of the inputs on the CPU; here the kernels compute them.
+
+Three references per case (oracle/encoder.py): T = plain float64; P64 = float64 with a float16 rounding wherever the kernels
+store or feed float16; P32 = the same in float32.  The gates are computed from the references, none is a literal:
+  max |kernel - P64| <= 4 max |P32 - P64| + h     (h = half a float16 ulp at the case's largest |output|; P32 - P64 is what
+                                                   float32 accumulation and single flipped float16 roundings cost here; 4
+                                                   covers another summation order, 1-ulp v_exp_f32 / rsqrt, the GELU table)
+  max |kernel - T|   <= 2 max |P64 - T| + h       (what float16 operands must cost, with margin for the kernel's own flips)
+  pooled cosine to T >= 1 - 2 (1 - min cosine(P64, T)), never asked above 1 - 1e-6
+Routes: `single` = only single-tile sequences (qkv_attention_single / ln_qkv_attention_single); `small` = a mixed batch of at
+most 256 tiles (qkv_small + attention_kernel); `throughput` = more than 256 tiles, the case's own sequences repeated
+(qkv_kernel + attention_kernel + the persistent projection / FFN kernels); `fused` = the same batch with
+MIR_ENC_FUSED_QKV_ATTENTION=1 (fused_qkv_attention_kernel for the sequences of at most 8 tiles, the unfused kernels for the
+longer ones, one pass).  Every route is compared with the oracles, and all routes must agree bit for bit."""
+
+import os
+
+import numpy as np
+import pytest
+
+from oracle import encoder as oe
+
+pytestmark = pytest.mark.gpu
+
+ROUTES = ("single", "small", "throughput", "fused")
+SMALL_TILES = 256  # kSmallTiles (encoder_kernels.h)
+
+
+def _tiles(seqs):
+    return sum((len(s) + 31) // 32 for s in seqs)
+
+
+def _split(hidden, seqs):
+    out, off = [], 0
+    for s in seqs:
+        out.append(hidden[off : off + len(s)].astype(np.float64))
+        off += (len(s) + 31) // 32 * 32
+    return out
+
+
+@pytest.fixture(scope="module", params=oe.CASES)
+def case(request):
+    from aidial_rag_amd import _native
+    from aidial_rag_amd.embeddings.embeddings import BgeEncoder
+
+    assert _native.device_count() >= 1
+    model, named = oe.case(request.param)
+    seqs = [s for _, s in named]
+    var = "MIR_ENC_FUSED_QKV_ATTENTION"  # read when an encoder is created: unset for the default build's routes, 1 for `fused`
+    old = os.environ.pop(var, None)
+    try:
+        enc = BgeEncoder.from_state_dict(model.state_dict())
+        os.environ[var] = "1"
+        fused = BgeEncoder.from_state_dict(model.state_dict())
+    finally:
+        os.environ.pop(var, None)
+        if old is not None:
+            os.environ[var] = old
+    c = {"name": request.param, "named": named, "seqs": seqs, "enc": enc, "fused": fused,
+         "ref": oe.references_every_layer(model, seqs, 2), "got": {}}
+    yield c
+    enc.close()
+    fused.close()
+
+
+def _worst(got, want):
+    """max |got - want| over a route's sequences; NaN if any value is (np.max propagates it, the builtin max would not)."""
+    return float(np.max(np.concatenate([np.abs(v - want[i]).ravel() for i, v in got.items()])))
+
+
+def _run(c, route):
+    """{layers: per-sequence hidden states, "pooled": normalised embeddings} of the case's sequences through `route`; only the
+    sequences the route serves (index -> value)."""
+    if route in c["got"]:
+        return c["got"][route]
+    seqs = c["seqs"]
+    idx = [i for i, s in enumerate(seqs) if len(s) <= 32] if route == "single" else list(range(len(seqs)))
+    batch = [seqs[i] for i in idx]
+    copies = 1
+    if route in ("throughput", "fused"):
+        copies = SMALL_TILES // _tiles(batch) + 1  # filler = the case's own sequences again
+    if route == "single":
+        assert _tiles(batch) == len(batch) >= 3
+    elif route == "small":
+        assert len(batch) < _tiles(batch) <= SMALL_TILES
+    else:
+        assert _tiles(batch * copies) > SMALL_TILES
+    enc = c["fused"] if route == "fused" else c["enc"]
+    out = {}
+    for layers in (1, 2):
+        _, hidden = enc.debug_hidden(batch * copies, layers)
+        parts = _split(hidden, batch * copies)
+        for k in range(1, copies):  # a copy's rows do not depend on its place in the batch
+            for a, b in zip(parts[: len(batch)], parts[k * len(batch) : (k + 1) * len(batch)]):
+                np.testing.assert_array_equal(a, b)
+        out[layers] = dict(zip(idx, parts))
+    pooled = enc.encode_ids(batch * copies)
+    for k in range(1, copies):
+        np.testing.assert_array_equal(pooled[: len(batch)], pooled[k * len(batch) : (k + 1) * len(batch)])
+    out["pooled"] = dict(zip(idx, pooled[: len(batch)].astype(np.float64)))
+    c["got"][route] = out
+    return out
+
+
+@pytest.mark.parametrize("route", ROUTES)
+def test_route_against_the_oracles(case, route, note):
+    got = _run(case, route)
+    failures = []
+    for layers in (1, 2):
+        ref = case["ref"][layers]
+        for i, v in got[layers].items():  # the defect these cases found was a NaN: every row of every sequence, layer and route
+            assert np.isfinite(v).all(), f"{case['name']} / {route} / {layers} layer(s): non-finite hidden state in {case['named'][i][0]}"
+        e64, et = _worst(got[layers], ref["P64"]), _worst(got[layers], ref["T"])
+        note(f"[encoder attention] {case['name']} / {route} / {layers} layer(s): |kernel - P64| {e64:.3e} <= {ref['gate_p64']:.3e} "
+             f"(4 x |P32 - P64| {ref['p32_p64']:.3e} + h {ref['h']:.3e});  |kernel - T| {et:.3e} <= {ref['gate_t']:.3e} "
+             f"(2 x |P64 - T| {ref['p64_t']:.3e} + h)")
+        if not e64 <= ref["gate_p64"]:
+            failures.append(f"{layers} layer(s): |kernel - P64| {e64:.3e} > {ref['gate_p64']:.3e}")
+        if not et <= ref["gate_t"]:
+            failures.append(f"{layers} layer(s): |kernel - T| {et:.3e} > {ref['gate_t']:.3e}")
+    ref = case["ref"][2]
+    cos = []
+    for i, v in got["pooled"].items():
+        assert np.isfinite(v).all(), f"{case['name']} / {route}: non-finite embedding of {case['named'][i][0]}"
+        assert abs(np.linalg.norm(v) - 1.0) < 1e-5
+        t = ref["T"][i][0]
+        cos.append(float(v @ t / np.linalg.norm(t)))
+    cos = np.asarray(cos)
+    note(f"[encoder attention] {case['name']} / {route} / pooled: min cosine to T {cos.min():.7f} >= {ref['gate_cos']:.7f} "
+         f"(min cosine(P64, T) {ref['cos_p64_t']:.7f})")
+    if not cos.min() >= ref["gate_cos"]:
+        failures.append(f"pooled cosine {cos.min():.7f} < {ref['gate_cos']:.7f}")
+    assert not failures, failures
+
+
+def test_routes_agree_bit_for_bit(case):
+    """The hidden states and the embedding of a sequence do not depend on which kernels served it."""
+    runs = {r: _run(case, r) for r in ROUTES}
+    for key in (1, 2, "pooled"):
+        for r in ("single", "throughput", "fused"):
+            for i, v in runs[r][key].items():
+                assert np.isfinite(v).all()  # assert_array_equal takes NaN for equal to NaN
+                np.testing.assert_array_equal(v, runs["small"][key][i], err_msg=f"{case['name']} {r} vs small, {key}, sequence {case['named'][i][0]}")
