@@ -8,6 +8,7 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -96,8 +97,8 @@ struct mir_index {
     _Float16 *d_f16 = nullptr;   // float16-native index: the rows as given (re-scoring)
     bool native16 = false;       // float16 storage scanned as 2-byte fragments (vec_kernels_f16.h)
     bool layout16 = false;       // float32, d padded to 128 / 256 / 384: the 16x16x32 image of vec_kernels_q16.h
-    bool hi_only = false;        // layout16 shard that only the sieve ever scans (>= 32K rows): the image holds the bf16 hi blocks alone
-    bool wide16 = false;         // float32, 384 < d <= 1024, >= 32K rows: `d_hi16` = the bf16 hi parts in the float16-native image's layout,
+    bool hi_only = false;        // layout16 shard of sieve size (>= 32K rows: plan()): the image holds the bf16 hi blocks alone
+    bool wide16 = false;         // float32, 384 < d <= 1024, of sieve size: `d_hi16` = the bf16 hi parts in the float16-native image's layout,
     int ks16 = 0;                //   ks16 blocks of 1 KiB per tile (d padded to 512 / 1024); the sieve's BF filter scans it, nothing reads d_split
     uint4 *d_hi16 = nullptr;
     uint4 *d_split = nullptr;    // bf16 hi/lo fragments, or the float16 fragments of a native16 index
@@ -105,7 +106,7 @@ struct mir_index {
     float *d_invnorm = nullptr;  // padded to n_tiles*32
     float *d_dnorm = nullptr;    // max((float)|row|, 1e-8), exact_metric_wave's summation order: cosine_sim of the batched exact pass
     float *d_tilemax = nullptr;  // [n_tiles] a tile's largest row norm: the sieve's per-tile margin (layout16)
-    bool norms_spread = false;   // the largest row norm exceeds the smallest tile maximum by more than 1/16: the sieve takes its margins per tile /
+    bool norms_spread = false;   // the largest row norm exceeds the smallest tile maximum by more than 1/16 (or is not finite): the sieve takes its margins per tile /
                                  // per row (unit-norm embeddings - the headline - keep round 3's one margin per query: the per-tile form cost that step ~3 %)
     float *d_maxnorm = nullptr;
     // the sieve's int8 first stage (vec_kernels_i8.h): built after the float image where the shard qualifies (build_i8)
@@ -179,9 +180,30 @@ static void free_index(mir_index *ix) {
     delete ix;
 }
 
-// Threshold pre-pass of the wide scans: kSampleWgs workgroups x up to kSampleTilesPerWg tiles (32K rows)
+// The sieve's threshold sample: kSampleWgs workgroups x up to kSampleTilesPerWg tiles (32K rows)
 constexpr int kSampleWgs = 256;
 constexpr int kSampleTilesPerWg = 4;  // (8 / 16 / 32 tiles per workgroup measured within 0.5 % on 10M x 384, 1-4 % slower on 6.25M x 1024 float16)
+// The sieve's filter launches (plan()): 256 queries per launch - two query tiles per wave - when a layout16 batch has more than
+// 128 (the stream of a pass is the same, the matrix work doubles); shards of >= kSieveTwoLaunchTiles tiles per workgroup in two
+// launches, the first over 1/kSieveFirstDiv of the tiles, but not fewer than kSieveFirstMinTiles (~157K rows) nor more than 1/4
+constexpr int kSieveMaxQueriesPerLaunch = 256;
+constexpr int kSieveTwoLaunchTiles = 64;
+constexpr uint32_t kSieveFirstDiv = 16;
+constexpr uint32_t kSieveFirstMinTiles = 4896;
+constexpr int kI8FourWaveQueries = 65;  // the int8 filter runs four waves per workgroup from this many queries per launch (launch_sieve_i8)
+
+// float32 index with 384 < d <= 1024: scanned 64 queries per pass by the K-split kernel of vec_kernels_f16.h
+static bool wide64_split(const mir_index *ix) { return !ix->native16 && (ix->ksteps == 32 || ix->ksteps == 48 || ix->ksteps == 64); }
+// >= 32K rows: there is a sample to take the sieve's first threshold from
+static bool sieve_sized(const mir_index *ix) { return ix->n_tiles >= 4u * kSampleWgs; }
+
+// f(std::integral_constant<int, KIND>) for the scan kind `metric` ranks by (euclidean_dist ranks as squared L2)
+template <typename F>
+static int32_t with_kind(int metric, F f) {
+    if (metric == MIR_METRIC_INNER_PRODUCT) return f(std::integral_constant<int, SCAN_IP>{});
+    if (metric == MIR_METRIC_COSINE_SIM) return f(std::integral_constant<int, SCAN_COS>{});
+    return f(std::integral_constant<int, SCAN_L2>{});
+}
 
 // Build the derived device state from ix->d_orig (already filled) on `stream`.
 // doc_sq / inv_norm / max norm: rows staged through LDS when at least 32 of them fit (d <= 511), else one thread
@@ -207,13 +229,11 @@ static int32_t build_derived(mir_index *ix, hipStream_t stream) {
     ix->n_tiles = (uint32_t)((n + kTileRows - 1) / kTileRows);
     // A layout16 shard of >= 32K rows is scanned by the sieve alone (plan(): k <= 64 -> sieve, beyond -> the exact pass), and the
     // sieve reads only the hi blocks: no lo blocks are stored for it - 7.68 GB at 10M x 384 - and a tile's
-    // hi blocks follow the previous tile's directly, so the filter's stream is contiguous.  (MIR_NO_SIEVE - the A/B switch back to
-    // round 2's scan, which does read lo blocks - is read at build time too.)
-    ix->hi_only = ix->layout16 && ix->n_tiles >= 4u * kSampleWgs && getenv("MIR_NO_SIEVE") == nullptr;
+    // hi blocks follow the previous tile's directly, so the filter's stream is contiguous.  plan() routes on these same flags.
+    ix->hi_only = ix->layout16 && sieve_sized(ix);
     // wide float32 shards of >= 32K rows: the sieve's bf16 filter over a hi-only image of its own (round 4); the hi/lo split image
     // of the K-split list scan is then never read (k <= 64 -> sieve, beyond -> the exact pass) and is not built
-    ix->wide16 = !ix->native16 && !ix->layout16 && (ix->ksteps == 32 || ix->ksteps == 48 || ix->ksteps == 64) &&
-                 ix->n_tiles >= 4u * kSampleWgs && getenv("MIR_NO_SIEVE") == nullptr && getenv("MIR_NO_SIEVE_WIDE") == nullptr;
+    ix->wide16 = wide64_split(ix) && sieve_sized(ix);
     ix->ks16 = ix->wide16 ? (d + 511) / 512 * 32 : 0;
     const size_t split_bytes = ix->wide16 ? 16 : (size_t)ix->n_tiles * ix->ksteps * ((ix->native16 || ix->hi_only) ? 1024 : 2048);
     const size_t aux_bytes = (size_t)(ix->n_tiles + 1) * kTileRows * sizeof(float);  // (one tile more: the int8 filter reads 64-row stages)
@@ -355,7 +375,7 @@ struct SearchBuffers {
     float *q_amax;   // [b] the int8 filter: a query's largest |q_i| (-1: not finite); its scales go to `qscale`
     float *qscale;   // [b] 1 / (query scale) of the float16-native scan
     uint64_t *part;  // [ngroups][nwg][qpw][klist]
-    uint64_t *gthr;  // [ngroups][128] shared per-query thresholds of the 128-query scan; the control words below
+    uint64_t *gthr;  // [ngroups][max(128, qpw)] the sieve's per-query thresholds; the control words below
                      // follow it in ONE allocation, which the prep kernel zeroes (ctl_words)
     int32_t *nflag;  // [2] number of queries handed to the exact pass
     uint32_t *arrive;  // [b] arrival counters of the exact pass
@@ -365,7 +385,7 @@ struct SearchBuffers {
     uint32_t *bound_row; // [b]
     uint64_t *part_exact;  // [b][exact grid][64][2]
     double *qt;            // [ceil(b / 32)][d padded to 256][32]: the flagged queries, transposed, for the batched exact pass
-    uint64_t *part_sample;  // [kSampleWgs][128][klist], reused by every launch (stream-ordered)
+    uint64_t *part_sample;  // the sieve's threshold sample: [kSampleWgs][qpw] x (2 floats, then their 2 rows), reused by every launch group (stream-ordered)
     // the sieve (vec_kernels_sieve.h): candidate regions of its two launches, the queries' verified lists
     uint64_t *sv_cand;      // [2][nwg][kSieveRegion]
     float *sv_candv;        // [2][nwg][kSieveRegion]
@@ -386,9 +406,8 @@ struct SearchPlan {
     int ngroups = 0, nwg = 1, klist = 2, qpw = 32;
     int exact_grid = 1;       // workgroups of exact_topk_kernel
     bool exact_only = false;
-    int nwg_first = 0;        // layout16 progressive scan: workgroups (= candidate lists) and tiles of the first launch;
-    uint32_t tiles_first = 0; // nwg counts the lists of BOTH launches (0 = one launch)
-    bool sieve = false;       // large layout16 shard: hi-only filter + exhaustive verification (vec_kernels_sieve.h); nwg = workgroups per launch
+    bool sieve = false;       // shard of sieve size: hi-only filter + exhaustive verification (vec_kernels_sieve.h); nwg = workgroups per launch
+    uint32_t tiles_first = 0; // the sieve: tiles of the first of its two filter launches (0 = one launch)
     uint32_t sample_tpw = 0;  // the sieve's threshold sample: tiles per sample workgroup
 };
 
@@ -417,7 +436,7 @@ static size_t carve(SearchBuffers &sb, char *base, int b, int k, int d, int kste
     sb.bound_row = c.take<uint32_t>(b);
     sb.part_exact = c.take<uint64_t>((size_t)b * pl.exact_grid * std::min(k, kExactRound) * 2);
     sb.qt = c.take<double>((size_t)((b + kXbQ - 1) / kXbQ) * xb_dpad(d) * kXbQ);
-    sb.part_sample = c.take<uint64_t>(std::max((size_t)kSampleWgs * 128 * klist, (size_t)kSampleWgs * std::max(128, qpw) * 2));  // (the sieve's sample: two floats and their two rows per workgroup and query)
+    sb.part_sample = c.take<uint64_t>(pl.sieve ? (size_t)kSampleWgs * std::max(128, qpw) * 2 : 0);  // the sieve's sample: two floats and their two rows per workgroup and query
     const size_t sv_q = pl.sieve ? (size_t)b * kSieveQueryCap : 0;
     const size_t region = i8_rows ? (size_t)kI8Region : (size_t)kSieveRegion;  // (the int8 filter: eight wave-private parts per workgroup)
     sb.sv_cand = c.take<uint64_t>(pl.sieve ? (size_t)2 * nwg * region : 0);
@@ -498,9 +517,6 @@ static void release_ws(mir_index *ix, Workspace *w, hipStream_t used, bool pendi
     ix->pool.push_back(w);
 }
 
-// float32 index with 384 < d <= 1024: scanned 64 queries per pass by the K-split kernel of vec_kernels_f16.h (SPLIT form)
-static bool wide64_split(const mir_index *ix) { return !ix->native16 && (ix->ksteps == 32 || ix->ksteps == 48 || ix->ksteps == 64); }
-
 template <int KIND>
 static int32_t launch_scan(const mir_index *ix, const uint4 *qsplit_g, int nq, int klist, int nwg,
                            uint64_t *part_g, hipStream_t stream) {
@@ -537,7 +553,7 @@ static int32_t launch_scan(const mir_index *ix, const uint4 *qsplit_g, int nq, i
 // float32 layout16 scan: 128 queries per launch, 16 per wave (vec_kernels_q16.h)
 template <int KIND>
 static int32_t launch_scan_q16(const mir_index *ix, const uint4 *qsplit_g, const double *q_norm_g, int nq, int klist, int nwg,
-                               uint32_t tile0, uint32_t n_tiles, uint64_t *part_g, uint64_t *gthr_g, bool sample, hipStream_t stream) {
+                               uint64_t *part_g, hipStream_t stream) {
     const float *aux = KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
     const int ks32 = ix->ksteps / 2;
     const size_t lds = q16_lds_bytes(ks32, klist);
@@ -545,10 +561,10 @@ static int32_t launch_scan_q16(const mir_index *ix, const uint4 *qsplit_g, const
     const int ns = q16_ring_stages(klist);
 #define MIR_Q16_LAUNCH(KS, NSV)                                                                                        \
     do {                                                                                                               \
-        auto kern = sample ? scan_topk_q16_kernel<KS, KIND, true, NSV> : scan_topk_q16_kernel<KS, KIND, false, NSV>;   \
+        auto kern = scan_topk_q16_kernel<KS, KIND, NSV>;                                                               \
         MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        kern<<<dim3(nwg), dim3(512), lds, stream>>>(ix->d_split, aux, qsplit_g, q_norm_g, ix->d_maxnorm, n_rows, tile0, n_tiles, nq, \
-                                                    klist, part_g, gthr_g);                                            \
+        kern<<<dim3(nwg), dim3(512), lds, stream>>>(ix->d_split, aux, qsplit_g, q_norm_g, ix->d_maxnorm, n_rows, ix->n_tiles, nq, \
+                                                    klist, part_g);                                                    \
     } while (0)
 #define MIR_Q16_CASE(KS)                                                                                               \
     case KS:                                                                                                           \
@@ -588,7 +604,7 @@ static int32_t launch_sieve(const mir_index *ix, int qpw, const uint4 *qsplit_g,
         MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
         kern<<<dim3(nwg), dim3(512), lds, stream>>>(ix->d_split, aux, qsplit_g, q_norm_g, q_sq_g, q_err_g, ix->d_maxnorm, n_rows, tile0, n_tiles, \
                                                     nq, nan_guard, gthr_g, cand, candv, ccount, part_sample, stat,     \
-                                                    (uint32_t)(ks32 * 2 * 64 * (ix->hi_only ? 1 : 2)), ix->d_tilemax); \
+                                                    (uint32_t)(ks32 * 2 * 64), ix->d_tilemax); /* (a tile's hi blocks) */ \
         break;                                                                                                         \
     }
     switch (ks32) {
@@ -613,9 +629,8 @@ static int32_t launch_sieve_i8(const mir_index *ix, int qpw, const float *q_scal
                                bool sample, unsigned long long *stat, hipStream_t stream) {
     // from 65 queries per launch: four waves per workgroup (two or four query tiles each) and two workgroups per CU - 0.83 against
     // 0.92 ms per 128-query step at 10M x 384, 1.13-1.16 against 1.27-1.30 per 256; up to 64 queries half of four waves' query
-    // tiles would be empty: eight waves with one tile each.  MIR_SIEVE_I8_WAVES = 4 / 8 forces one geometry (A/B runs)
-    static const int nw_env = getenv("MIR_SIEVE_I8_WAVES") ? atoi(getenv("MIR_SIEVE_I8_WAVES")) : 0;
-    const bool four = nw_env ? nw_env == 4 : nq > 64;
+    // tiles would be empty: eight waves with one tile each
+    const bool four = nq >= kI8FourWaveQueries;
     const size_t lds = sieve_i8_lds_bytes(ix->ks64, four ? 4 : 8);
     const uint32_t n_rows = (uint32_t)ix->n;
     const int grid = (four && !sample) ? 2 * nwg : nwg;  // (the candidate parts are per wave: nwg x 8 of them either way)
@@ -679,17 +694,17 @@ static int32_t launch_sieve16(const mir_index *ix, const uint4 *qfrag_g, const f
 // float16-native scan: 128 queries per launch, 16 per wave, one float16 product per fragment (vec_kernels_h16.h)
 template <int KIND>
 static int32_t launch_scan_h16(const mir_index *ix, const uint4 *qfrag_g, const float *qscale_g, int nq, int klist, int nwg,
-                               uint32_t tile0, uint32_t n_tiles, uint64_t *part_g, uint64_t *gthr_g, bool sample, hipStream_t stream) {
+                               uint64_t *part_g, const uint64_t *gthr_g, hipStream_t stream) {
     const float *aux = KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
     const size_t lds = h16_lds_bytes(klist);
     const uint32_t n_rows = (uint32_t)ix->n;
     const int ns = h16_ring_stages(klist);
 #define MIR_H16_LAUNCH(KS, NSV)                                                                                        \
     do {                                                                                                               \
-        auto kern = sample ? scan_topk_h16_kernel<KS, KIND, true, NSV, H16_QT> : scan_topk_h16_kernel<KS, KIND, false, NSV, H16_QT>;   \
+        auto kern = scan_topk_h16_kernel<KS, KIND, NSV, H16_QT>;                                                       \
         MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        kern<<<dim3(nwg), dim3(512 / H16_QT), lds, stream>>>(ix->d_split, aux, qfrag_g, qscale_g, n_rows, tile0, n_tiles, nq, klist, part_g, \
-                                                    gthr_g);                                                           \
+        kern<<<dim3(nwg), dim3(512 / H16_QT), lds, stream>>>(ix->d_split, aux, qfrag_g, qscale_g, n_rows, 0, ix->n_tiles, nq, klist, part_g, \
+                                                    gthr_g);  /* (zeroed thresholds: see the kernel) */                \
     } while (0)
     // ksteps = 64: 512 < d <= 1024, 32 k-steps of 32 columns (128 VGPRs of query fragments per wave); 32: 256 < d <= 512
 #define MIR_H16_CASES(KS)                                                                                              \
@@ -714,18 +729,18 @@ static int32_t launch_scan_h16(const mir_index *ix, const uint4 *qfrag_g, const 
 
 // float32 rows with 384 < d <= 1024: the 64-query K-split scan over the bf16 hi/lo image
 template <int KIND>
-static int32_t launch_scan_f16(const mir_index *ix, const uint4 *qfrag_g, const float *qscale_g, int nq, int klist, int nwg,
-                               uint32_t n_tiles, uint64_t *part_g, uint64_t *gthr_g, bool sample, hipStream_t stream) {
+static int32_t launch_scan_f16(const mir_index *ix, const uint4 *qfrag_g, int nq, int klist, int nwg,
+                               uint64_t *part_g, hipStream_t stream) {
     const float *aux = KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
     const size_t lds = f16_lds_bytes(klist);
     const uint32_t n_rows = (uint32_t)ix->n;
 #define MIR_SCAN_CASE_SPLIT(KS)                                                                              \
     case KS: {                                                                                               \
-        auto kern = sample ? scan_topk_f16_kernel<KS, KIND, true, true> : scan_topk_f16_kernel<KS, KIND, false, true>; \
+        auto kern = scan_topk_f16_kernel<KS, KIND>;                                                          \
         MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                    \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
-        kern<<<dim3(nwg), dim3(512), lds, stream>>>(ix->d_split, aux, qfrag_g, qscale_g, n_rows, n_tiles,    \
-                                                    nq, klist, part_g, gthr_g);                              \
+        kern<<<dim3(nwg), dim3(512), lds, stream>>>(ix->d_split, aux, qfrag_g, n_rows, ix->n_tiles, nq,      \
+                                                    klist, part_g);                                          \
         break;                                                                                               \
     }
     switch (ix->ksteps) {
@@ -759,7 +774,7 @@ static int32_t enqueue_search(mir_index *ix, const double *dq, int b, int k, int
     const int ngroups = pl.ngroups, nwg = pl.nwg, klist = pl.klist, qpw = pl.qpw;
     const int d = ix->d;
     const int ntiles32 = ngroups * (qpw / 32);  // 32-query fragment tiles, padded to whole launches
-    // thresholds of the wide scans + the exact pass's control words: zeroed by the first blocks of the prep kernel
+    // the sieve's thresholds + the exact pass's control words: zeroed by the first blocks of the prep kernel
     unsigned long long *gz = reinterpret_cast<unsigned long long *>(sb.gthr);
     const int gwords = sb.ctl_words;
     // (blocks past the fragment and per-query blocks only zero their 64 words and return)
@@ -863,26 +878,23 @@ static int32_t enqueue_search(mir_index *ix, const double *dq, int b, int k, int
                 if (use_i8) {  // tiles -> 64-row stages: [t0 / 2, (t0 + nt + 1) / 2) (t0 is even or 0 wherever two launches meet: see below)
                     const uint32_t s0 = t0 / 2, s1 = std::min<uint32_t>((t0 + nt + 1) / 2, ix->n_stages);
                     const uint4 *qf = sb.qsplit + (size_t)g * (qpw / 16) * ix->ks64 * 64;
-                    if (metric == MIR_METRIC_INNER_PRODUCT)
-                        return launch_sieve_i8<SCAN_IP>(ix, qpw, sb.qscale + q0, qf, qn, qsq, qerr, nq, wgs, s0, s1 - s0, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                    if (metric == MIR_METRIC_COSINE_SIM)
-                        return launch_sieve_i8<SCAN_COS>(ix, qpw, sb.qscale + q0, qf, qn, qsq, qerr, nq, wgs, s0, s1 - s0, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                    return launch_sieve_i8<SCAN_L2>(ix, qpw, sb.qscale + q0, qf, qn, qsq, qerr, nq, wgs, s0, s1 - s0, guard, gt, cand, cv, cc, ps, smp, st, stream);
+                    return with_kind(metric, [&](auto kind) {
+                        return launch_sieve_i8<kind()>(ix, qpw, sb.qscale + q0, qf, qn, qsq, qerr, nq, wgs, s0, s1 - s0, guard, gt, cand, cv, cc, ps, smp, st, stream);
+                    });
                 }
-                if (ix->native16) {
-                    if (metric == MIR_METRIC_INNER_PRODUCT) return launch_sieve16<SCAN_IP>(ix, qs16, qsc, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                    if (metric == MIR_METRIC_COSINE_SIM) return launch_sieve16<SCAN_COS>(ix, qs16, qsc, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                    return launch_sieve16<SCAN_L2>(ix, qs16, qsc, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                }
+                if (ix->native16)
+                    return with_kind(metric, [&](auto kind) {
+                        return launch_sieve16<kind()>(ix, qs16, qsc, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
+                    });
                 if (ix->wide16) {  // (fragments of group g: 8 query tiles x ks16 / 2 k-steps x (hi, lo) blocks)
                     const uint4 *qw = sb.qsplit + (size_t)g * (kQ16Queries / 16) * (ix->ks16 / 2) * 128;
-                    if (metric == MIR_METRIC_INNER_PRODUCT) return launch_sieve16<SCAN_IP, true>(ix, qw, nullptr, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream, qerr);
-                    if (metric == MIR_METRIC_COSINE_SIM) return launch_sieve16<SCAN_COS, true>(ix, qw, nullptr, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream, qerr);
-                    return launch_sieve16<SCAN_L2, true>(ix, qw, nullptr, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream, qerr);
+                    return with_kind(metric, [&](auto kind) {
+                        return launch_sieve16<kind(), true>(ix, qw, nullptr, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream, qerr);
+                    });
                 }
-                if (metric == MIR_METRIC_INNER_PRODUCT) return launch_sieve<SCAN_IP>(ix, qpw, qs, qn, qsq, qerr, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                if (metric == MIR_METRIC_COSINE_SIM) return launch_sieve<SCAN_COS>(ix, qpw, qs, qn, qsq, qerr, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                return launch_sieve<SCAN_L2>(ix, qpw, qs, qn, qsq, qerr, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
+                return with_kind(metric, [&](auto kind) {
+                    return launch_sieve<kind()>(ix, qpw, qs, qn, qsq, qerr, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
+                });
             };
             SieveScatterArgs ca;
             ca.q0 = q0; ca.nq = nq; ca.l = sb.sv;
@@ -947,67 +959,20 @@ static int32_t enqueue_search(mir_index *ix, const double *dq, int b, int k, int
             if (rc != MIR_OK) return rc;
             continue;
         }
-        if (qpw != 32) {
-            uint64_t *gt = sb.gthr + (size_t)g * 128;
+        // the list scans: one launch over the whole shard (every shard with a sample to seed thresholds from is the sieve's)
+        rc = begin_profile();
+        if (rc != MIR_OK) return rc;
+        if (qpw == 32) {
+            rc = with_kind(metric, [&](auto kind) { return launch_scan<kind()>(ix, qs, nq, klist, nwg, pg, stream); });
+        } else if (ix->native16) {
+            const uint4 *qs16 = sb.qsplit + (size_t)g * (kQ16Queries / 16) * (ix->ksteps / 2) * 64;  // hi fragments only
             const float *qsc = sb.qscale + (size_t)g * qpw;
-            auto run = [&](int wgs, uint32_t tiles, uint64_t *out, bool sample) {
-                if (ix->layout16 || ix->native16) {
-                    const double *qn = sb.q_norm + (size_t)g * qpw;
-                    const uint4 *qs16 = sb.qsplit + (size_t)g * (kQ16Queries / 16) * (ix->ksteps / 2) * 64;  // native16: hi fragments only
-                    auto one = [&](int w, uint32_t t0, uint32_t nt, uint64_t *o, bool smp) {
-                        if (ix->native16) {
-                            if (metric == MIR_METRIC_INNER_PRODUCT) return launch_scan_h16<SCAN_IP>(ix, qs16, qsc, nq, klist, w, t0, nt, o, gt, smp, stream);
-                            if (metric == MIR_METRIC_COSINE_SIM) return launch_scan_h16<SCAN_COS>(ix, qs16, qsc, nq, klist, w, t0, nt, o, gt, smp, stream);
-                            return launch_scan_h16<SCAN_L2>(ix, qs16, qsc, nq, klist, w, t0, nt, o, gt, smp, stream);
-                        }
-                        if (metric == MIR_METRIC_INNER_PRODUCT) return launch_scan_q16<SCAN_IP>(ix, qs, qn, nq, klist, w, t0, nt, o, gt, smp, stream);
-                        if (metric == MIR_METRIC_COSINE_SIM) return launch_scan_q16<SCAN_COS>(ix, qs, qn, nq, klist, w, t0, nt, o, gt, smp, stream);
-                        return launch_scan_q16<SCAN_L2>(ix, qs, qn, nq, klist, w, t0, nt, o, gt, smp, stream);
-                    };
-                    if (sample || pl.nwg_first == 0) return one(wgs, 0, tiles, out, sample);
-                    // Progressive scan: the first 1/16 of the tiles with the sample's thresholds, then the klist-th best of
-                    // what that found as the threshold of the rest (list_threshold_kernel): the rest runs its correction
-                    // products for ~1 % of its blocks instead of ~25 %.  Lists of both launches go to finalize.
-                    int32_t r1 = one(pl.nwg_first, 0, pl.tiles_first, out, false);
-                    if (r1 != MIR_OK) return r1;
-                    list_threshold_kernel<<<dim3(nq), dim3(256), 0, stream>>>(out, pl.nwg_first, qpw, klist, nq,
-                                                                             reinterpret_cast<unsigned long long *>(gt));
-                    return one(wgs - pl.nwg_first, pl.tiles_first, tiles - pl.tiles_first, out + (size_t)pl.nwg_first * qpw * klist, false);
-                }
-                if (wide64_split(ix)) {
-                    if (metric == MIR_METRIC_INNER_PRODUCT) return launch_scan_f16<SCAN_IP>(ix, qs, qsc, nq, klist, wgs, tiles, out, gt, sample, stream);
-                    if (metric == MIR_METRIC_COSINE_SIM) return launch_scan_f16<SCAN_COS>(ix, qs, qsc, nq, klist, wgs, tiles, out, gt, sample, stream);
-                    return launch_scan_f16<SCAN_L2>(ix, qs, qsc, nq, klist, wgs, tiles, out, gt, sample, stream);
-                }
-                set_error("internal: no wide scan for this index");
-                return (int32_t)MIR_ERR_UNSUPPORTED;
-            };
-            // Scan a sample of the shard first and seed every query's threshold with a lower bound of its
-            // klist-th best value (sample_threshold_kernel), so the full pass starts with tight thresholds
-            // instead of accepting almost everything for its first ~50 tiles per workgroup.
-            // Measured: the pre-pass pays from ~32K rows up (500K rows: 0.48 -> 0.24 ms per step; 1M: 0.69 ->
-            // 0.39; 10M: see DESIGN.md), 4 tiles per workgroup being the best size from 100K to 10M rows; it
-            // must stay a small part of the shard, so smaller shards sample fewer tiles or skip it
-            const uint32_t tpw = std::min<uint32_t>(kSampleTilesPerWg, ix->n_tiles / (4u * kSampleWgs));
-            const uint32_t sample_tiles = (uint32_t)kSampleWgs * tpw;
-            rc = MIR_OK;
-            if (tpw >= 1) {
-                rc = run(kSampleWgs, sample_tiles, sb.part_sample, true);
-                if (rc == MIR_OK) {
-                    sample_threshold_kernel<<<dim3(nq), dim3(256), 0, stream>>>(reinterpret_cast<const float *>(sb.part_sample),
-                                                                                kSampleWgs, qpw, klist, nq,
-                                                                                reinterpret_cast<unsigned long long *>(gt));
-                    MIR_HIP(hipGetLastError());
-                }
-            }
-            if (rc == MIR_OK) rc = begin_profile();
-            if (rc == MIR_OK) rc = run(nwg, ix->n_tiles, pg, false);
-        } else {
-            rc = begin_profile();
-            if (rc != MIR_OK) return rc;
-            if (metric == MIR_METRIC_INNER_PRODUCT) rc = launch_scan<SCAN_IP>(ix, qs, nq, klist, nwg, pg, stream);
-            else if (metric == MIR_METRIC_COSINE_SIM) rc = launch_scan<SCAN_COS>(ix, qs, nq, klist, nwg, pg, stream);
-            else rc = launch_scan<SCAN_L2>(ix, qs, nq, klist, nwg, pg, stream);
+            rc = with_kind(metric, [&](auto kind) { return launch_scan_h16<kind()>(ix, qs16, qsc, nq, klist, nwg, pg, sb.gthr + (size_t)g * 128, stream); });
+        } else if (ix->layout16) {
+            const double *qn = sb.q_norm + (size_t)g * qpw;
+            rc = with_kind(metric, [&](auto kind) { return launch_scan_q16<kind()>(ix, qs, qn, nq, klist, nwg, pg, stream); });
+        } else {  // wide64_split(ix): plan() gives 64 queries per launch to no other index
+            rc = with_kind(metric, [&](auto kind) { return launch_scan_f16<kind()>(ix, qs, nq, klist, nwg, pg, stream); });
         }
         if (ev1) {
             (void)hipEventRecord(ev1, stream);
@@ -1038,6 +1003,16 @@ static int32_t enqueue_search(mir_index *ix, const double *dq, int b, int k, int
     return MIR_OK;
 }
 
+// How an index is searched.  Nothing but the index, b and k decides it:
+//
+//   index                                                   rows     k                path
+//   layout16 (float32, d padded to 128 / 256 / 384),        >= 32K   <= 64            sieve
+//   native16 (float16, 256 < d <= 1024),                    >= 32K   > 64             exact pass alone
+//   wide float32 (384 < d <= 1024)                          < 32K    fits the lists   q16 / h16 / K-split list scan, one launch
+//   everything else                                         any                       register-ring scans / exact pass
+//
+// 32K rows = 4 * kSampleWgs tiles (sieve_sized): from there the sieve has a sample to take its first threshold from, and the
+// index build stores only the image the sieve reads (hi_only, wide16) - which is why the same flags route here.
 static int32_t plan(const mir_index *ix, int b, int k, SearchPlan *pl) {
     // the exact pass: one workgroup of 16 waves per CU, one per 64-row block on small shards; its per-workgroup lists are
     // b x grid x min(k, 64) x 16 bytes of workspace - fewer workgroups for huge batches
@@ -1047,46 +1022,35 @@ static int32_t plan(const mir_index *ix, int b, int k, SearchPlan *pl) {
         pl->exact_grid = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ix->num_cus, by_mem), (ix->n + kXbRows - 1) / kXbRows));
     }
     pl->klist = std::min(k + (ix->native16 ? kH16ListMargin : kListMargin), kMaxList);
-    // The reference takes any `limit` (embeddings_index.py:58,81).  Beyond what the filter's per-lane candidate
-    // lists hold (LDS), an index that could actually return that many rows is searched by the exact pass alone.
-    static const bool sieve_off = getenv("MIR_NO_SIEVE") != nullptr;  // (A/B measurements against the round-2 scan)
-    static const bool sieve16_off = getenv("MIR_NO_SIEVE16") != nullptr;
-    if (((ix->layout16 && !sieve_off) || (ix->native16 && !sieve16_off && !sieve_off) || ix->wide16) && k <= kSieveMaxK) {
-        // large shards (the progressive scan's: >= 64 tiles per workgroup): filter on the hi blocks alone, verify every candidate
-        const int wgs = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(ix->num_cus, 1024), (int64_t)ix->n_tiles));
-        if (ix->n_tiles >= 4u * kSampleWgs) {  // from 32K rows: there is a sample to take the first threshold from
-            pl->sieve = true;
-            // 128 queries per filter launch, or 256 (two query tiles per wave) when the batch has more: the stream of a pass is
-            // the same, the matrix work doubles (MIR_SIEVE_QPL=128 keeps 128)
-            static const int qpl_max = getenv("MIR_SIEVE_QPL") ? atoi(getenv("MIR_SIEVE_QPL")) : 256;
-            pl->qpw = (ix->layout16 && b > kQ16Queries && qpl_max >= 256) ? 2 * kQ16Queries : kQ16Queries;
-            pl->ngroups = (b + pl->qpw - 1) / pl->qpw;
-            pl->nwg = wgs;
-            pl->klist = std::min(k, kMaxList);
-            // shards of >= 64 tiles per workgroup in two filter launches (1/16 of the tiles, but not fewer than ~157K rows
-            // nor more than 1/4, then the rest with the exact k-th best so far as the threshold); smaller ones in one
-            // (experiments: MIR_SIEVE_TWO_PHASE_TILES = shards with at least this many tiles per workgroup take two launches;
-            //  MIR_SIEVE_SAMPLE_TPW = tiles per sample workgroup on one-launch shards)
-            static const int two_phase_tiles = getenv("MIR_SIEVE_TWO_PHASE_TILES") ? atoi(getenv("MIR_SIEVE_TWO_PHASE_TILES")) : 64;
-            static const int single_tpw = getenv("MIR_SIEVE_SAMPLE_TPW") ? atoi(getenv("MIR_SIEVE_SAMPLE_TPW")) : kSampleTilesPerWg;
-            const bool two = (int64_t)ix->n_tiles >= (int64_t)two_phase_tiles * wgs;
-            static const uint32_t first_div = getenv("MIR_SIEVE_FIRST_DIV") ? (uint32_t)atoi(getenv("MIR_SIEVE_FIRST_DIV")) : 16u;  // (experiments)
-            pl->tiles_first = two ? std::max<uint32_t>(ix->n_tiles / first_div, std::min<uint32_t>(ix->n_tiles / 4, 4896u)) : 0;
-            pl->tiles_first &= ~1u;  // (the int8 filter walks 64-row stages: the two launches meet at a stage boundary)
-            static const int two_tpw = getenv("MIR_SIEVE_SAMPLE_TPW2") ? atoi(getenv("MIR_SIEVE_SAMPLE_TPW2")) : kSampleTilesPerWg;  // (experiments)
-            pl->sample_tpw = std::max<uint32_t>(1, std::min<uint32_t>(two ? two_tpw : single_tpw, ix->n_tiles / (4u * kSampleWgs)));
-            return MIR_OK;
-        }
-    }
-    const bool wide64 = wide64_split(ix);
-    const bool lists_fit = k + (ix->native16 ? kH16ListMargin : kListMargin) <= kMaxList;
-    if (!lists_fit && ix->n > (int64_t)kMaxList) {  // (n <= 64: every row fits the lists)
+    auto exact_only = [&]() {
         pl->exact_only = true;
         pl->ngroups = 0;
         pl->qpw = 32;
         pl->nwg = 1;
         return MIR_OK;
+    };
+    if (ix->hi_only || ix->wide16 || (ix->native16 && sieve_sized(ix))) {
+        // filter on the hi blocks alone, verify every candidate; beyond the sieve's lists (k > 64, which no list scan holds
+        // either) the exact pass alone
+        if (k > kSieveMaxK) return exact_only();
+        pl->sieve = true;
+        pl->qpw = (ix->layout16 && b > kQ16Queries) ? kSieveMaxQueriesPerLaunch : kQ16Queries;
+        pl->ngroups = (b + pl->qpw - 1) / pl->qpw;
+        pl->nwg = (int)std::min<int64_t>(std::min(ix->num_cus, 1024), (int64_t)ix->n_tiles);
+        pl->klist = std::min(k, kMaxList);
+        // two filter launches on shards of >= kSieveTwoLaunchTiles tiles per workgroup: the second takes the exact k-th best
+        // of the first as its threshold
+        const bool two = (int64_t)ix->n_tiles >= (int64_t)kSieveTwoLaunchTiles * pl->nwg;
+        pl->tiles_first = two ? std::max<uint32_t>(ix->n_tiles / kSieveFirstDiv, std::min<uint32_t>(ix->n_tiles / 4, kSieveFirstMinTiles)) : 0;
+        pl->tiles_first &= ~1u;  // (the int8 filter walks 64-row stages: the two launches meet at a stage boundary)
+        pl->sample_tpw = std::max<uint32_t>(1, std::min<uint32_t>(kSampleTilesPerWg, ix->n_tiles / (4u * kSampleWgs)));
+        return MIR_OK;
     }
+    // The reference takes any `limit` (embeddings_index.py:58,81).  Beyond what the filter's per-lane candidate
+    // lists hold (LDS), an index that could actually return that many rows is searched by the exact pass alone.
+    const bool wide64 = wide64_split(ix);
+    const bool lists_fit = k + (ix->native16 ? kH16ListMargin : kListMargin) <= kMaxList;
+    if (!lists_fit && ix->n > (int64_t)kMaxList) return exact_only();  // (n <= 64: every row fits the lists)
     if (wide64 && f16_lds_bytes(pl->klist) <= 160 * 1024) {  // 64 queries per pass; its LDS holds lists up to k = 28 (a float32
         pl->qpw = kF16Queries;                                  // index with a larger k falls through to the 32-query kernels)
         pl->ngroups = (b + pl->qpw - 1) / pl->qpw;
@@ -1094,27 +1058,11 @@ static int32_t plan(const mir_index *ix, int b, int k, SearchPlan *pl) {
         pl->nwg = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(ix->num_cus, 1024), want16));
         return MIR_OK;
     }
-    if ((ix->layout16 || ix->native16) && pl->klist > kQ16MaxList) {  // k > 52 (48 on a float16-native index) on a 16-queries-per-wave index: the exact pass alone (any n)
-        pl->exact_only = true;
-        pl->ngroups = 0;
-        pl->qpw = 32;
-        pl->nwg = 1;
-        return MIR_OK;
-    }
+    if ((ix->layout16 || ix->native16) && pl->klist > kQ16MaxList) return exact_only();  // k > 52 (48 on a float16-native index) on a 16-queries-per-wave index (any n)
     if (ix->layout16 || ix->native16) {  // the images only the 16-queries-per-wave kernels read: they take every k their buffers hold (k <= 52; 48 on a float16-native index)
         pl->qpw = kQ16Queries;
         pl->ngroups = (b + pl->qpw - 1) / pl->qpw;
         pl->nwg = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(ix->num_cus, 1024), (int64_t)ix->n_tiles));
-        // Shards of >= 64 tiles per workgroup are scanned in two launches (1/16 first, re-seed, the rest).  Measured per
-        // 128-query step (1.25M / 2.5M / 5M rows): two launches 0.427 / 0.689 / 1.240 ms, one launch 0.441 / 0.773 / 1.496;
-        // first-launch fractions 1/8, 1/32, 1/64 on 10M rows: 2.351 / 2.346 / 2.445 ms against 2.324 at 1/16.
-        if ((int64_t)ix->n_tiles >= 64 * (int64_t)pl->nwg) {
-            // 1/16 of the tiles, but not fewer than ~157K rows (their klist-th best is what makes the second launch's
-            // thresholds tight: 1.25M rows measured 0.429 ms per step with 78K rows first, 0.411 with 156K) nor more than 1/4
-            pl->tiles_first = std::max<uint32_t>(ix->n_tiles / 16, std::min<uint32_t>(ix->n_tiles / 4, 4896u));
-            pl->nwg_first = pl->nwg;
-            pl->nwg = 2 * pl->nwg;  // lists for finalize
-        }
         return MIR_OK;
     }
     pl->qpw = 32;  // the register-ring kernels: d <= 64, d > 1024, or a float32 wide index with k > 28
@@ -1319,9 +1267,10 @@ static int32_t create_common(const RowSource &src, int64_t n, int32_t d, int32_t
             set_error("index build failed: %s", hipGetErrorString(e));
             return fail(MIR_ERR_HIP);
         }
-        ix->norms_spread = !(st[0] <= 1.0625f * st[4]) || getenv("MIR_SIEVE_PER_TILE") != nullptr;  // (NaN / infinite norms: spread)
+        ix->norms_spread = !(st[0] <= 1.0625f * st[4]);  // (NaN / infinite norms: spread)
         // the int8 first stage (vec_kernels_i8.h) serves the squared-L2 / euclidean / inner-product searches of a shard of finite rows
-        // of one norm; MIR_SIEVE_I8=0 keeps the bf16 filter for everything (read per build: tests and A/B runs switch it)
+        // of one norm; MIR_SIEVE_I8=0 keeps the bf16 filter for everything (read per build, the library's one switch: the tests build
+        // the same index with and without the image; it decides whether the image is BUILT - a search routes on ix->i8)
         const bool i8_on = !(getenv("MIR_SIEVE_I8") != nullptr && atoi(getenv("MIR_SIEVE_I8")) == 0);
         unsigned int nonfinite = 0;
         memcpy(&nonfinite, &st[1], 4);

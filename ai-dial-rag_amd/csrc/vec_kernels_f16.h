@@ -1,15 +1,11 @@
-// The 64-query K-split scan (round 1's float16-native kernel).  Since round 2 the float16-NATIVE index (BASELINE config
-// C5) is scanned by vec_kernels_h16.h; what still runs here is the SPLIT = true instantiation: float32 rows with
-// 384 < d <= 1024 (the multimodal / description retrievers' page embeddings) over their bf16 hi/lo image, three bf16
-// MFMAs per k-step, K split over four waves per 32-query tile.  The SPLIT = false form (one 2-byte fragment stream, two
-// f16 MFMAs per k-step for the query's hi and lo parts) is kept as the description of that layout:
-// [tile of 32 rows][k-step][64 lanes][8 f16], lane l = row (l & 31), columns 16 ks + 8 (l >> 5) .. +7.
+// The 64-query K-split list scan of a float32 index with 384 < d <= 1024 (the multimodal / description retrievers' page
+// embeddings; embeddings_index.py:139-153 stores them as float32) of fewer than 32K rows - larger ones are the sieve's
+// (vec_index.hip, plan()).  It reads the index's bf16 hi/lo image (vec_kernels.h): a k-step is a (hi, lo) pair of 1-KiB blocks,
+// three bf16 MFMAs per k-step (hi*hi, hi*lo, lo*hi), K split over four waves per 32-query tile.
 #pragma once
 #include "vec_kernels.h"
 
 namespace mir {
-
-typedef _Float16 __attribute__((ext_vector_type(8))) f16x8;
 
 // 64-query scan geometry
 constexpr int kF16Queries = 64;
@@ -29,23 +25,16 @@ __host__ __device__ constexpr size_t f16_lds_bytes(int klist) {
 // stage.  A tile's four partial 32x32 accumulators meet once per tile: three waves write theirs to
 // LDS, the fourth (the query tile's reducer, j = 2 qt: on different SIMDs for the two query tiles)
 // adds them, un-scales, applies the norm column and runs the candidate filter of
-// lane-list filter one tile behind.
-//
-// SPLIT = true is the same kernel over the float32 index's bf16 hi/lo image (vec_kernels.h) for 384 < d <= 1024 -
-// float32 page embeddings of the multimodal / description retrievers (embeddings_index.py:139-153 stores them as
-// float32): a k-step is a (hi, lo) pair of 1-KiB blocks, three bf16 MFMAs per k-step (hi*hi, hi*lo, lo*hi), a
-// stage is 16 k-steps (the same 32 KiB), the query is not scaled.  Before, such an index ran scan_topk_generic_kernel
-// (32 queries per pass, fragments re-read from L2 per k-step, nothing in flight across tiles).
-template <int KSTEPS, int KIND, bool SAMPLE, bool SPLIT = false>
+// lane-list filter one tile behind.  A stage is 16 k-steps (32 KiB); the query is not scaled.  Before, such an index ran
+// scan_topk_generic_kernel (32 queries per pass, fragments re-read from L2 per k-step, nothing in flight across tiles).
+template <int KSTEPS, int KIND>
 __global__ __launch_bounds__(512, 2) void scan_topk_f16_kernel(const uint4 *__restrict__ docs,
                                                                const float *__restrict__ aux,
-                                                               const uint4 *__restrict__ qfrag,
-                                                               const float *__restrict__ qscale_inv, uint32_t n_rows,
+                                                               const uint4 *__restrict__ qfrag, uint32_t n_rows,
                                                                uint32_t n_tiles, int nq, int klist,
-                                                               uint64_t *__restrict__ part,
-                                                               const uint64_t *__restrict__ gthr) {
-    constexpr int BPK = SPLIT ? 2 : 1;        // 1-KiB blocks per k-step
-    constexpr int SK = kF16StageKsteps / BPK; // k-steps per stage (32 KiB either way)
+                                                               uint64_t *__restrict__ part) {
+    constexpr int BPK = 2;                    // 1-KiB blocks per k-step: hi, lo
+    constexpr int SK = kF16StageKsteps / BPK; // k-steps per stage (32 KiB)
     static_assert(KSTEPS % SK == 0 && KSTEPS / SK >= 2, "wide scan: whole stages, at least two per tile");
     constexpr int SPT = KSTEPS / SK;          // stages per tile (>= 2: the exchange buffer is single)
     constexpr int WK = SK / 4;                // k-steps per wave per stage
@@ -74,23 +63,20 @@ __global__ __launch_bounds__(512, 2) void scan_topk_f16_kernel(const uint4 *__re
     const bool lane_live = qj + 32 * qt < nq;
     const uint32_t G = gridDim.x;
 
-    if (is_red && !SAMPLE) {
+    if (is_red) {
         for (int p = 0; p < klist + kF16Pending; ++p) list[p * LS + ltid] = 0;
     }
-    float best = -__builtin_inff();
     uint64_t minkey = 0;
     int minpos = 0, pending = 0;
-    const uint64_t seed_thr = (!is_red || SAMPLE) ? 0 : gthr[qt * 32 + qj];
-    const float qinv = SPLIT ? 1.0f : (is_red && lane_live) ? qscale_inv[32 * qt + qj] : 0.f;
 
     // this wave's quarter of its query tile's fragments: slot s <-> k-step (s / WK) * SK + j * WK + s % WK
-    f16x8 qh[QK], ql[QK];
+    bf16x8 qh[QK], ql[QK];
 #pragma unroll
     for (int s = 0; s < QK; ++s) {
         const int kg = (s / WK) * SK + j * WK + (s % WK);
         const uint4 *qs = qfrag + ((size_t)qt * KSTEPS + kg) * 128 + lane;
-        qh[s] = __builtin_bit_cast(f16x8, qs[0]);
-        ql[s] = __builtin_bit_cast(f16x8, qs[64]);
+        qh[s] = __builtin_bit_cast(bf16x8, qs[0]);
+        ql[s] = __builtin_bit_cast(bf16x8, qs[64]);
     }
     const uint32_t my_tiles = blockIdx.x < n_tiles ? (n_tiles - blockIdx.x + G - 1) / G : 0;
     const uint32_t NG = my_tiles * SPT;
@@ -134,7 +120,7 @@ __global__ __launch_bounds__(512, 2) void scan_topk_f16_kernel(const uint4 *__re
         }
     };
 
-    // reducer: scores of the previous tile = (own partial + the three others') / s, then the metric's form
+    // reducer: scores of the previous tile = own partial + the three others', then the metric's form
     auto epilogue = [&](const float4 (&w4)[4]) {
         float pv[16];
 #pragma unroll
@@ -143,7 +129,7 @@ __global__ __launch_bounds__(512, 2) void scan_topk_f16_kernel(const uint4 *__re
             const float av[4] = {pax[c].x, pax[c].y, pax[c].z, pax[c].w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float dot = (pacc[4 * c + i] + wv[i]) * qinv;
+                const float dot = pacc[4 * c + i] + wv[i];
                 pv[4 * c + i] = KIND == SCAN_L2 ? fmaf(2.0f, dot, -av[i]) : KIND == SCAN_COS ? dot * av[i] : dot;
             }
         }
@@ -151,14 +137,9 @@ __global__ __launch_bounds__(512, 2) void scan_topk_f16_kernel(const uint4 *__re
         const float m03 = fmaxf(fmaxf(pv[6], pv[7]), pv[8]), m04 = fmaxf(fmaxf(pv[9], pv[10]), pv[11]);
         const float m05 = fmaxf(fmaxf(pv[12], pv[13]), pv[14]);
         const float mx = fmaxf(fmaxf(fmaxf(m01, m02), fmaxf(m03, m04)), fmaxf(m05, pv[15]));
-        if (SAMPLE) {
-            if (prow0 != n_rows) best = fmaxf(best, mx);
-            return;
-        }
         const uint64_t other = ((uint64_t)__shfl_xor((uint32_t)(minkey >> 32), 32, 64) << 32) |
                                (uint64_t)__shfl_xor((uint32_t)minkey, 32, 64);
-        uint64_t thr = other > minkey ? other : minkey;
-        thr = seed_thr > thr ? seed_thr : thr;
+        const uint64_t thr = other > minkey ? other : minkey;
         const float vmin = thr == 0 ? -__builtin_inff() : key_value(thr);
         if (!__any(!(mx < vmin) && prow0 != n_rows)) return;
         uint32_t pmask = 0;
@@ -196,37 +177,23 @@ __global__ __launch_bounds__(512, 2) void scan_topk_f16_kernel(const uint4 *__re
             }
             if (active) {
                 const uint4 *st = ring + (size_t)(g % NS) * STAGE_U4 + (j * WK * BPK) * 64 + lane;
-                if constexpr (!SPLIT) {
-                    uint4 fr[3];
-                    fr[0] = st[0 * 64];
-                    fr[1] = st[1 * 64];
+                uint4 fh[3], fl[3];
+                fh[0] = st[0 * 64];
+                fl[0] = st[1 * 64];
+                fh[1] = st[2 * 64];
+                fl[1] = st[3 * 64];
 #pragma unroll
-                    for (int i = 0; i < WK; ++i) {
-                        if (i + 2 < WK) fr[(i + 2) % 3] = st[(i + 2) * 64];
-                        __builtin_amdgcn_sched_barrier(0);
-                        const f16x8 a = __builtin_bit_cast(f16x8, fr[i % 3]);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qh[part_i * WK + i], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, ql[part_i * WK + i], acc, 0, 0, 0);
+                for (int i = 0; i < WK; ++i) {
+                    if (i + 2 < WK) {
+                        fh[(i + 2) % 3] = st[(2 * (i + 2) + 0) * 64];
+                        fl[(i + 2) % 3] = st[(2 * (i + 2) + 1) * 64];
                     }
-                } else {
-                    uint4 fh[3], fl[3];
-                    fh[0] = st[0 * 64];
-                    fl[0] = st[1 * 64];
-                    fh[1] = st[2 * 64];
-                    fl[1] = st[3 * 64];
-#pragma unroll
-                    for (int i = 0; i < WK; ++i) {
-                        if (i + 2 < WK) {
-                            fh[(i + 2) % 3] = st[(2 * (i + 2) + 0) * 64];
-                            fl[(i + 2) % 3] = st[(2 * (i + 2) + 1) * 64];
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                        const bf16x8 ah = __builtin_bit_cast(bf16x8, fh[i % 3]), al = __builtin_bit_cast(bf16x8, fl[i % 3]);
-                        const bf16x8 bh = __builtin_bit_cast(bf16x8, qh[part_i * WK + i]), bl = __builtin_bit_cast(bf16x8, ql[part_i * WK + i]);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    const bf16x8 ah = __builtin_bit_cast(bf16x8, fh[i % 3]), al = __builtin_bit_cast(bf16x8, fl[i % 3]);
+                    const bf16x8 bh = qh[part_i * WK + i], bl = ql[part_i * WK + i];
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
                 }
                 if (part_i == SPT - 1 && is_red) epilogue(w4);
             }
@@ -257,11 +224,6 @@ __global__ __launch_bounds__(512, 2) void scan_topk_f16_kernel(const uint4 *__re
             if (key > minkey) list_insert<LS>(list, klist, ltid, key, minkey, minpos);
         }
     }
-    if (SAMPLE) {
-        if (is_red) reinterpret_cast<float *>(part)[((size_t)blockIdx.x * kF16Queries + 32 * qt + qj) * 2 + h] = best;
-        return;
-    }
-
     // ---- merge the two half-lists of each query, write [64][klist] per workgroup ----
     __syncthreads();
     for (int i = tid; i < kF16Queries * klist; i += 512) stage_out[i] = 0;

@@ -1,7 +1,7 @@
 // The 128-query scan of the float16-NATIVE index (BASELINE config C5: d = 1024 float16, multimodal_retriever.py:96-153),
 // round 2: 16 queries per wave over the full dimension on v_mfma_f32_16x16x32_f16, ONE product per fragment.
 //
-// Why: the earlier kernel (scan_topk_f16_kernel, 64 queries per pass, K-split over four waves, two MFMAs per k-step for
+// Why: round 1's kernel (64 queries per pass, K-split over four waves as vec_kernels_f16.h still is, two MFMAs per k-step for
 // the query's float16 hi and lo parts) ran at 68-69 % of the HBM roofline - power-limited like the float32 kernel it
 // was modelled on.  The documents of this index are EXACT in float16, so the only rounding in a
 // one-product scan is the query's: q_hi = f16(s q) with s a per-query power of two, |x.q - x.q_hi / s| <=
@@ -16,13 +16,14 @@
 // Index image: per 32-row tile, block (s, rh) = k-step of 32 columns s, row half rh at [2 s + rh]: 64 lanes x 8 f16,
 // lane l = (row 16 rh + (l & 15), columns 32 s + 8 (l >> 4) .. + 7) - the A operand of v_mfma_f32_16x16x32_f16.
 // A stage of the LDS-DMA ring is 16 k-steps = 32 blocks = 32 KiB (half of a d = 1024 tile).
-// Candidate buffers (Q16Lists), thresholds, the sample pre-pass and the progressive two-launch scheme are those of
-// vec_kernels_q16.h.
+// Candidate buffers (Q16Lists) and thresholds are those of vec_kernels_q16.h; like that scan, this one runs in one launch over
+// a shard of fewer than 32K rows (larger ones: sieve_h16_kernel, vec_kernels_sieve.h).
 #pragma once
-#include "vec_kernels_f16.h"
 #include "vec_kernels_q16.h"
 
 namespace mir {
+
+typedef _Float16 __attribute__((ext_vector_type(8))) f16x8;
 
 // |x . q - (x . f16(s q)) / s| <= 2^-11 |x||q| for the rounding of the query (4.88e-4; components that round into
 // float16's subnormal range add < 1e-8) plus the float32 accumulation of up to 1024 products (<= 1024 * 2^-24 = 6.1e-5 of
@@ -162,11 +163,12 @@ __global__ __launch_bounds__(64) void prep_queries_h16_kernel(const double *__re
 // QT = query tiles (16 queries each) per wave: 1 -> 8 waves, two per SIMD; 2 -> 4 waves, one per SIMD, each 1-KiB document
 // fragment read from LDS once per wave feeds BOTH query tiles' MFMAs (half the LDS reads per byte streamed; the wave then
 // holds 256 VGPRs of query fragments at d = 1024).
-template <int KS32, int KIND, bool SAMPLE, int NS, int QT>
+template <int KS32, int KIND, int NS, int QT>
 __global__ __launch_bounds__(512 / QT, QT == 1 ? 2 : 1) void scan_topk_h16_kernel(
     const uint4 *__restrict__ docs, const float *__restrict__ aux, const uint4 *__restrict__ qfrag, const float *__restrict__ qscale_inv,
     uint32_t n_rows, uint32_t tile0, uint32_t n_tiles, int nq, int klist, uint64_t *__restrict__ part, const uint64_t *__restrict__ gthr) {
-    // this launch walks tiles [tile0, tile0 + n_tiles) of the shard
+    // tile0 (always 0) and gthr (the zeroed control block: every list starts open) are what is left of the two-launch scan;
+    // without them the d = 1024 instance measured 1.2 % slower, so they stay
     static_assert(KS32 % kH16StageKs == 0, "h16 scan: d padded to a multiple of 512");
     static_assert(QT == 1 || QT == 2, "query tiles per wave");
     constexpr int WAVES = 8 / QT;
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(512 / QT, QT == 1 ? 2 : 1) void scan_topk_h16_kerne
     int qloc[QT], cnt[QT];
     bool lane_live[QT], active[QT];
     uint64_t thr[QT];   // admission threshold: max(seed, list minimum once the list is full)
-    float best[QT], inv_s[QT];
+    float inv_s[QT];
     f16x8 qh[QT][KS32];
     bool any_active = false;
 #pragma unroll
@@ -200,9 +202,8 @@ __global__ __launch_bounds__(512 / QT, QT == 1 ? 2 : 1) void scan_topk_h16_kerne
         lane_live[u] = qloc[u] < nq;
         active[u] = nq > t16 * 16;
         any_active |= active[u];
-        thr[u] = (SAMPLE || !lane_live[u]) ? 0 : gthr[qloc[u]];
+        thr[u] = !lane_live[u] ? 0 : gthr[qloc[u]];
         cnt[u] = 0;
-        best[u] = -__builtin_inff();
         inv_s[u] = lane_live[u] ? qscale_inv[qloc[u]] : 0.f;
         const uint4 *qs = qfrag + (size_t)t16 * KS32 * 64 + lane;
 #pragma unroll
@@ -282,11 +283,6 @@ __global__ __launch_bounds__(512 / QT, QT == 1 ? 2 : 1) void scan_topk_h16_kerne
             float v[8];
             to_values(u, c0[u], c1[u], ax, v);
             const float mx = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
-            if (SAMPLE) {
-                // thresholds and list values are in the same (hi-only) units: the maximum itself is the bound (sample tiles are whole tiles)
-                if (lane_live[u]) best[u] = fmaxf(best[u], mx);
-                continue;
-            }
             // can any row reach this lane's threshold?  (NaN passes: `!(x < y)`; an open list takes everything)
             const float vmin0 = thr[u] == 0 ? -__builtin_inff() : key_value(thr[u]);
             if (!__any(lane_live[u] && !(mx < vmin0))) continue;
@@ -302,17 +298,9 @@ __global__ __launch_bounds__(512 / QT, QT == 1 ? 2 : 1) void scan_topk_h16_kerne
     }
 #pragma unroll
     for (int u = 0; u < QT; ++u) {
-        if (SAMPLE) {
-            // four lanes hold a query's column: two values per query, each the maximum over distinct rows
-            const float o = __shfl_xor(best[u], 16, 64);
-            const float b2 = fmaxf(best[u], o);
-            if (lane_live[u] && (jg == 0 || jg == 2))
-                reinterpret_cast<float *>(part)[((size_t)blockIdx.x * kQ16Queries + qloc[u]) * 2 + (jg >> 1)] = b2;
-        } else {
-            // every buffer compacted once more (sorted, best first) and written out, empty entries as 0: [128][klist] per workgroup
-            const Q16Lists L{lists + (size_t)(wv * QT + u) * 16 * cap, cap, klist, lane, qc, jg, colmask};
-            L.write_out(part + (size_t)blockIdx.x * kQ16Queries * klist + (size_t)(wv * QT + u) * 16 * klist, cnt[u], thr[u]);
-        }
+        // every buffer compacted once more (sorted, best first) and written out, empty entries as 0: [128][klist] per workgroup
+        const Q16Lists L{lists + (size_t)(wv * QT + u) * 16 * cap, cap, klist, lane, qc, jg, colmask};
+        L.write_out(part + (size_t)blockIdx.x * kQ16Queries * klist + (size_t)(wv * QT + u) * 16 * klist, cnt[u], thr[u]);
     }
 }
 

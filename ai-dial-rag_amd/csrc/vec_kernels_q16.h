@@ -1,5 +1,6 @@
 // The 128-query scan of the float32 index, round 2: 16 queries per wave over the FULL dimension, 16x16x32 MFMA tiles,
-// the bf16 correction products only where a block can reach a threshold.
+// the bf16 correction products only where a block can reach a threshold.  One launch over a shard of fewer than 32K rows, the
+// lists starting empty: larger shards are the sieve's (vec_index.hip, plan()).
 //
 // Why (profiles/r01_scan_clock_pmc.md): round 1's K-split kernel (scan_topk_b128_kernel, two waves per
 // 32-query tile, each half of K) streamed 10M x 384 rows in an almost
@@ -297,13 +298,11 @@ __device__ __forceinline__ void q16_load_aux(const float *__restrict__ aux, uint
     }
 }
 
-template <int KS32, int KIND, bool SAMPLE, int NS>
+template <int KS32, int KIND, int NS>
 __global__ __launch_bounds__(512, 2) void scan_topk_q16_kernel(const uint4 *__restrict__ docs, const float *__restrict__ aux,
                                                                const uint4 *__restrict__ qsplit, const double *__restrict__ q_norm,
                                                                const float *__restrict__ max_norm, uint32_t n_rows,
-                                                               uint32_t tile0, uint32_t n_tiles, int nq, int klist,
-                                                               uint64_t *__restrict__ part, const uint64_t *__restrict__ gthr) {
-    // this launch walks tiles [tile0, tile0 + n_tiles) of the shard
+                                                               uint32_t n_tiles, int nq, int klist, uint64_t *__restrict__ part) {
     constexpr int SB = KS32 * 2;          // 1-KiB blocks per stage
     constexpr int STAGE_U4 = SB * 64;
     constexpr int TILE_U4 = 2 * STAGE_U4;
@@ -324,10 +323,8 @@ __global__ __launch_bounds__(512, 2) void scan_topk_q16_kernel(const uint4 *__re
     uint64_t *mylist = lists + (size_t)wave8 * 16 * cap;  // this wave's 16 buffers, query-major
     const unsigned long long colmask = 0x0001000100010001ull << qc;  // the four lanes of this lane's column
     // per-query state, replicated in the four lanes of a column
-    const uint64_t seed_thr = (SAMPLE || !lane_live) ? 0 : gthr[qloc];
-    uint64_t thr = seed_thr;   // admission threshold: max(seed, list minimum once the list is full)
+    uint64_t thr = 0;          // admission threshold: the list minimum once the list is full
     int cnt = 0;               // entries in the query's list
-    float best = -__builtin_inff();
     // margin of the hi*hi-only value, in the units the lists rank by
     float mg = 0.f;
     if (lane_live) {
@@ -348,7 +345,7 @@ __global__ __launch_bounds__(512, 2) void scan_topk_q16_kernel(const uint4 *__re
     const uint32_t NG = my_tiles * 2;
 
     auto issue = [&](uint32_t g) {
-        const uint32_t tile = tile0 + blockIdx.x + (g >> 1) * G;
+        const uint32_t tile = blockIdx.x + (g >> 1) * G;
         const uint4 *src = docs + (size_t)tile * TILE_U4 + (size_t)(g & 1) * STAGE_U4 + (wave8 * PPW) * 64 + lane;
         const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_addr_of(ring) + ((g % NS) * STAGE_U4 + (wave8 * PPW) * 64) * 16);
 #pragma unroll
@@ -378,7 +375,7 @@ __global__ __launch_bounds__(512, 2) void scan_topk_q16_kernel(const uint4 *__re
     const Q16Lists L{mylist, cap, klist, lane, qc, jg, colmask};
 
     for (uint32_t ts = 0; ts < my_tiles; ++ts) {
-        const uint32_t t = tile0 + blockIdx.x + ts * G;
+        const uint32_t t = blockIdx.x + ts * G;
         const uint32_t g = 2 * ts;
         const uint32_t row0 = t * kTileRows + 4 * jg;  // this lane's rows: row0 + 16 rh + i
         // ------------------------------------------------ stage 2t: the hi blocks, hi*hi for all of K
@@ -407,21 +404,16 @@ __global__ __launch_bounds__(512, 2) void scan_topk_q16_kernel(const uint4 *__re
             float v[8];
             to_values(c0, c1, ax, v);
             const float mx0 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), mx1 = fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7]));
-            if (SAMPLE) {
-                // a LOWER bound of this lane's best value: hi*hi minus the margin (sample tiles are whole tiles)
-                if (lane_live) best = fmaxf(best, fmaxf(mx0, mx1) - mg);
-            } else {
-                // can any row of a half reach this lane's threshold?  (NaN passes: `!(x < y)`; an open list takes everything)
-                const float vmin = thr == 0 ? -__builtin_inff() : key_value(thr);
-                need0 = __any(lane_live && !(mx0 + mg < vmin));
-                need1 = __any(lane_live && !(mx1 + mg < vmin));
-            }
+            // can any row of a half reach this lane's threshold?  (NaN passes: `!(x < y)`; an open list takes everything)
+            const float vmin = thr == 0 ? -__builtin_inff() : key_value(thr);
+            need0 = __any(lane_live && !(mx0 + mg < vmin));
+            need1 = __any(lane_live && !(mx1 + mg < vmin));
         }
         // ------------------------------------------------ stage 2t + 1: the lo blocks; corrections where needed
         wait_stage(g + 1);
         __builtin_amdgcn_s_barrier();
         if (g + 1 + D < NG) issue(g + 1 + D);
-        if (!SAMPLE && (need0 || need1)) {
+        if (need0 || need1) {
             // hi*lo and lo*hi for one 16-row half: two independent chains, both fragment streams three reads ahead
             auto correct = [&](int rh, f32x4 &c) {
                 const uint4 *sh = ring + (size_t)(g % NS) * STAGE_U4 + rh * 64 + lane;
@@ -455,32 +447,8 @@ __global__ __launch_bounds__(512, 2) void scan_topk_q16_kernel(const uint4 *__re
             L.append(pm, v, row0, cnt, thr);
         }
     }
-    if (SAMPLE) {
-        // four lanes hold a query's column: two values per query, each the maximum over distinct rows
-        const float o = __shfl_xor(best, 16, 64);
-        const float b2 = fmaxf(best, o);
-        if (lane_live && (jg == 0 || jg == 2))
-            reinterpret_cast<float *>(part)[((size_t)blockIdx.x * kQ16Queries + qloc) * 2 + (jg >> 1)] = b2;
-        return;
-    }
     // ---- every buffer compacted once more (sorted, best first) and written out, empty entries as 0: [128][klist] per workgroup ----
     L.write_out(part + (size_t)blockIdx.x * kQ16Queries * klist + (size_t)wave8 * 16 * klist, cnt, thr);
-}
-
-// Between the two launches of a progressive scan: a query's klist-th best key over the per-workgroup lists of the first
-// launch is the klist-th best of the rows scanned so far - a subset of the shard, hence a valid (and, after 1/16 of the
-// rows, tight: ~4.0 sigma at 10M rows against the sample pre-pass's 3.2) starting threshold for the rest.  One block per query.
-__global__ __launch_bounds__(256) void list_threshold_kernel(const uint64_t *__restrict__ part, int nwg, int qpw, int klist, int nq,
-                                                             unsigned long long *__restrict__ gthr) {
-    __shared__ uint64_t keys[kMaxList];
-    __shared__ uint64_t red[4];
-    const int q = blockIdx.x, tid = threadIdx.x;
-    if (q >= nq) return;
-    merge_sorted_lists(part + (size_t)q * klist, (size_t)qpw * klist, nwg, klist, keys, red, tid);
-    if (tid == 0) {
-        const uint64_t kth = keys[klist - 1];
-        if (kth != 0 && kth > gthr[q]) gthr[q] = kth;
-    }
 }
 
 }  // namespace mir

@@ -222,11 +222,12 @@ def test_batches_larger_than_a_query_group(amd):
 
 
 @pytest.mark.parametrize("metric", ["sqeuclidean_dist", "cosine_sim", "inner_product"])
-def test_large_shard_wide_scan_with_sample_thresholds(amd, metric):
-    """1.2M rows x 128 queries: the 128-query scan (16 queries per wave) with its sample pre-pass and the two-launch
-    progressive thresholds (shards of >= 64 tiles per workgroup).  Oracle on 6 queries (the CPU path costs ~1 s per query here); planted
-    duplicates must resolve to the lower row; every flag must be clear; repeated runs must agree bit for bit
-    (the scan has inter-wave hand-offs: a race would show up as run-to-run differences)."""
+def test_large_shard_sieve_float32(amd, metric):
+    """1.2M x 384 float32 rows x 128 queries: the sieve (csrc/vec_kernels_sieve.h) - threshold sample, two filter launches
+    (a shard of >= 64 tiles per workgroup) - over the int8 image here (csrc/vec_kernels_i8.h: rows of one norm, k <= 16) - and
+    the exhaustive verification of every candidate.  Oracle on 6 queries (the CPU path costs ~1 s per query here); planted
+    duplicates must resolve to the lower row; every flag must be clear; repeated runs must agree bit for bit (the filter
+    has inter-wave hand-offs: a race would show up as run-to-run differences)."""
     from oracle import embeddings_index as oi
 
     rng = np.random.default_rng(77)
@@ -392,8 +393,9 @@ def test_float16_native_padded_dimension(amd):
             np.testing.assert_allclose(dist[i], wdist, rtol=1e-12, atol=1e-6)
 
 
-def test_float16_native_large_shard_sample_prepass(amd):
-    """More than 32768 tiles: the threshold pre-pass runs on the float16 scan too."""
+def test_float16_native_large_shard_sieve(amd):
+    """1.06M x 1024 float16 rows (more than 32768 tiles): the float16 sieve (sieve_h16_kernel) - threshold sample, two filter
+    launches over the float16 image, every candidate verified."""
     from oracle import embeddings_index as oi
 
     rng = np.random.default_rng(616)
