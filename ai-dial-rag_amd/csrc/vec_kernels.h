@@ -210,6 +210,14 @@ __device__ __forceinline__ float bf16_residual_norm(const T *a, int d) {
     return (float)sqrt(s) * (1.0f + 1e-6f);
 }
 
+// The reference's row norm under cosine_sim, max(|x|, 1e-8) in the rows' float32: `s` is the float64 square sum, `doc_sq32` the
+// float32 pairwise sum the reference's own norm is the root of.  Where that sum overflows (finite components near 2^64) the
+// reference's norm is +inf and its unit row all zeros, whatever the float64 sum says.  Every evaluator of the formula
+// (exact_metric_wave, sieve_metric_g16, the batched exact pass) and the filters' inverse norms (then 0) go through this.
+__device__ __forceinline__ float ref_row_norm(double s, float doc_sq32) {
+    return doc_sq32 == __builtin_inff() ? __builtin_inff() : fmaxf((float)sqrt(s), 1e-8f);
+}
+
 // One thread per row: doc_sq (f32, numpy order), inv_norm = 1/max(|d|, 1e-8),
 // and the running maximum row norm (for the scan's error bound).
 // T = float, or _Float16 (a float16 index: the reference up-casts to float32 first, so the values
@@ -223,11 +231,12 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const T *__restrict__ sr
     float nrm = 0.f, res = 0.f, rel = 0.f;
     if (row < n) {
         const T *a = src + row * (int64_t)d;
-        doc_sq[row] = np_pairwise_sq<12>(a, d);
+        const float dsq = np_pairwise_sq<12>(a, d);
+        doc_sq[row] = dsq;
         const double s = seq_sum_sq_f64(a, d);
         nrm = (float)sqrt(s);
         nrm = nrm * (1.0f + 1e-6f);  // round up: used as an upper bound
-        inv_norm[row] = 1.0f / fmaxf((float)sqrt(s), 1e-8f);
+        inv_norm[row] = 1.0f / ref_row_norm(s, dsq);  // (0 where the reference's float32 norm is +inf: the filter's cosine is the reference's 0)
         if (sizeof(T) == 4) {
             res = bf16_residual_norm(a, d);
             rel = res * inv_norm[row] * (1.0f + 1e-6f);
@@ -279,22 +288,28 @@ __global__ __launch_bounds__(256) void row_norms_lds_kernel(const T *__restrict_
     __syncthreads();
     // the two sums of a row are independent: threads [0, rows) of the first half of the workgroup take the float32
     // pairwise sum, threads [128, 128 + rows) the float64 one (rows <= 128 by construction of rows_per_wg)
+    // (the inverse norm needs the float32 sum too - ref_row_norm: the second half reads what the first half stored to doc_sq,
+    // behind the workgroup's barrier; the dynamic LDS is full at some d, so it does not travel through LDS)
     float nrm = 0.f, res = 0.f, rel = 0.f;
     const int rt = threadIdx.x & 127;
+    const float *a = norms_lds + rt * stride;
+    const int64_t row = row0 + rt;
+    double s = 0.0;
     if (rt < rows) {
-        const float *a = norms_lds + rt * stride;
-        const int64_t row = row0 + rt;
         if (threadIdx.x < 128) {
             doc_sq[row] = np_pairwise_sq<12>(a, d);
         } else {
-            const double s = seq_sum_sq_f64(a, d);
-            nrm = (float)sqrt(s);
-            nrm = nrm * (1.0f + 1e-6f);
-            inv_norm[row] = 1.0f / fmaxf((float)sqrt(s), 1e-8f);
-            if (sizeof(T) == 4) {
-                res = bf16_residual_norm(a, d);
-                rel = res * inv_norm[row] * (1.0f + 1e-6f);
-            }
+            s = seq_sum_sq_f64(a, d);
+        }
+    }
+    __syncthreads();
+    if (rt < rows && threadIdx.x >= 128) {
+        nrm = (float)sqrt(s);
+        nrm = nrm * (1.0f + 1e-6f);
+        inv_norm[row] = 1.0f / ref_row_norm(s, const_cast<const volatile float *>(doc_sq)[row]);
+        if (sizeof(T) == 4) {
+            res = bf16_residual_norm(a, d);
+            rel = res * inv_norm[row] * (1.0f + 1e-6f);
         }
     }
     for (int off = 32; off >= 1; off >>= 1) { res = fmaxf(res, __shfl_xor(res, off, 64)); rel = fmaxf(rel, __shfl_xor(rel, off, 64)); }
@@ -717,7 +732,7 @@ __device__ __forceinline__ double exact_metric_wave(const T *__restrict__ row, c
                 }
         }
         s = group_sum<W>(s);
-        const float dn = fmaxf((float)sqrt(s), 1e-8f);
+        const float dn = ref_row_norm(s, doc_sq32);
         const double qn = fmax(q_norm, 1e-8);
         double c = 0.0;
         for (int j0 = lane; j0 < d; j0 += W * U) {
@@ -880,6 +895,22 @@ __device__ __forceinline__ void exact_publish_query(double *__restrict__ qt, int
     }
 }
 
+// What a query must satisfy to be served by a filter scan.  The filters see a float32 image of the query (bf16
+// pairs, a scaled float16, a scaled int8) and bound its error RELATIVE to |q| |x|max; that holds only while the image and the
+// float32 arithmetic on it neither overflow nor underflow:
+//   2^-100 <= |q| <= 2^100 (finite, no NaN; components below 2^-126 cost at most 2^-26 |q| each), or q = 0 (an exact image);
+//   squared L2 / L2: |q| <= 2^24 |x|max.  The filters rank 2 x.q - |x|^2 and leave |q|^2 out; the reference adds it in float64,
+//     and beyond this ratio its rounding (2^-53 |q|^2) ties rows the ranking value separates by more than the margin's slop
+//     (3e-5 |x|max |q|): the reference then orders them by row, and rows the filter dropped belong to the answer.
+// Any other query is answered by the exact pass alone: the flagging kernels (finalize_kernel, sieve_select_kernel) hand it
+// over whatever its lists hold, and the sieve's filters emit nothing for it, so it does not fill the candidate region it
+// shares with its neighbours.
+__device__ __forceinline__ bool query_filterable(bool l2, double qn, float max_norm) {
+    if (qn == 0.0) return true;
+    if (!(qn >= 0x1p-100 && qn <= 0x1p100)) return false;  // (false for a NaN)
+    return !(l2 && qn > 0x1p24 * (double)max_norm);         // (a NaN largest norm - NaN rows - excludes nothing)
+}
+
 struct FinalizeArgs {
     const uint64_t *part;   // [launch][nwg][qpw][klist]
     int nwg;                // workgroups of the scan
@@ -987,6 +1018,8 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
             const double vk = s_vk;
             if (!(tau + eps < vk)) flag = MIR_FLAG_UNCERTAIN;
         }
+        if (!query_filterable(a.metric == MIR_METRIC_SQEUCLIDEAN_DIST || a.metric == MIR_METRIC_EUCLIDEAN_DIST, a.q_norm[qi], a.max_norm[0]))
+            flag = MIR_FLAG_UNCERTAIN;  // the scan's bound does not hold for this query's float32 image
         // An unproven query is handed to exact_topk_kernel (enqueued right behind this kernel), which
         // overwrites its outputs and flag; the reference is always exact (embeddings_index.py:51-60).
         s_f = -1;

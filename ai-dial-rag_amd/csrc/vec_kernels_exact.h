@@ -196,7 +196,8 @@ __device__ __forceinline__ void exact_topk_batch(const ExactBatchArgs &a, const 
             double acc[kXbQW];
 #pragma unroll
             for (int i = 0; i < kXbQW; ++i) acc[i] = 0.0;
-            const float dn = (COS && row_ok) ? a.dnorm[row] : 1.0f;
+            // (a float32 square sum that overflowed: the reference's row norm is +inf, ref_row_norm)
+            const float dn = (COS && row_ok) ? (a.doc_sq[row] == __builtin_inff() ? __builtin_inff() : a.dnorm[row]) : 1.0f;
             for (int s = 0; s < nslices; ++s) {
                 __syncthreads();  // the previous slice has been consumed
                 stash();

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(64) void prep_queries_i8_stats_kernel(const double 
     if (lane == 0) {
         q_sq[qi] = s;
         q_norm[qi] = sqrt(s);
-        q_amax[qi] = bad ? -1.0f : m;  // (a query with a NaN / an infinity takes no part in the scale; the filter passes everything for it)
+        q_amax[qi] = bad ? -1.0f : m;  // (a query with a NaN / an infinity takes no part in the scale; the exact pass answers it: query_filterable)
     }
 }
 // Kernel 2.  Blocks [0, ntiles16 * ks64): B-operand fragments of query tile w, k-step s: lane l = (query 16 w + (l & 15), columns
@@ -330,14 +330,14 @@ __global__ __launch_bounds__(NW * 64, 2) void sieve_i8_kernel(const uint4 *__res
     for (int u = 0; u < QT; ++u) {
         const int t16 = wave8 * QT + u;
         qloc[u] = t16 * 16 + qc;
-        lane_live[u] = qloc[u] < nq;
+        lane_live[u] = qloc[u] < nq && (SAMPLE || query_filterable(KIND == SCAN_L2, q_norm[qloc[u]], stats[0]));  // (as sieve_q16_kernel)
         live_mask[u] = __builtin_amdgcn_ballot_w64(lane_live[u]);
         sq[u] = 1.0f; mA[u] = 0.f; mB[u] = 0.f; P1[u] = -__builtin_inff(); A1[u] = 0.f; tbc[u] = -__builtin_inff();
         guard[u] = __builtin_inff(); best[u] = -__builtin_inff(); brow[u] = 0;
         if (lane_live[u]) {
             const float qn = (float)q_norm[qloc[u]] * (1.0f + 1e-6f);
             const float eq = (float)q_err[qloc[u]] * (1.0f + 1e-6f);
-            const bool good = qn < __builtin_inff() && eq < __builtin_inff();  // (false for a NaN too: such a query passes everything, as in the bf16 filter)
+            const bool good = qn < __builtin_inff() && eq < __builtin_inff();  // (false for a NaN too; the filter launches never get here with one: query_filterable, only the sample does)
             sq[u] = q_scale[qloc[u]];
             if (good) i8_margin_ab(qn, eq, stats, mA[u], mB[u]);
             if (!SAMPLE) {

@@ -124,7 +124,8 @@ __global__ __launch_bounds__(512, 2) void sieve_q16_kernel(const uint4 *__restri
     for (int u = 0; u < QT; ++u) {
         const int t16 = wave8 * QT + u;
         qloc[u] = t16 * 16 + qc;
-        lane_live[u] = qloc[u] < nq;
+        // (the filter instances emit nothing for a query the exact pass answers: query_filterable; the sample keeps its slots written)
+        lane_live[u] = qloc[u] < nq && (SAMPLE || query_filterable(KIND == SCAN_L2, q_norm[qloc[u]], max_norm[0]));
         live_mask[u] = __builtin_amdgcn_ballot_w64(lane_live[u]);
         mg[u] = 0.f; bound[u] = -__builtin_inff(); guard[u] = __builtin_inff(); best[u] = -__builtin_inff();
         cq[u] = 0.f; tb[u] = -__builtin_inff();
@@ -436,7 +437,7 @@ __global__ __launch_bounds__(512, 2) void sieve_h16_kernel(const uint4 *__restri
     const int tid = threadIdx.x, lane = tid & 63, qc = lane & 15, jg = lane >> 4;
     const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int qloc = wave8 * 16 + qc;
-    const bool lane_live = qloc < nq;
+    const bool lane_live = qloc < nq && (SAMPLE || query_filterable(KIND == SCAN_L2, q_norm[qloc], max_norm[0]));  // (as sieve_q16_kernel)
     const bool active = nq > wave8 * 16;
     const uint32_t G = gridDim.x;
     if (tid == 0) *s_count = 0;
@@ -756,7 +757,7 @@ __device__ __forceinline__ double sieve_metric_g16(const T *__restrict__ row, co
                 }
         }
         s = group_sum<16>(s);
-        dn = fmaxf((float)sqrt(s), 1e-8f);
+        dn = ref_row_norm(s, doc_sq32);
         qn = fmax(q_norm, 1e-8);
     }
     double dot = 0.0;
@@ -881,7 +882,9 @@ __global__ __launch_bounds__(kSieveSelectThreads) void sieve_select_kernel(Sieve
         __syncthreads();
         exact_publish_query(a.qt, s_slot, a.q + (size_t)qi * a.d, a.d, a.metric, a.q_norm[qi], tid, NT);
     };
-    if (over) {  // a candidate of this query was dropped somewhere (mode 0: the sample's threshold stays)
+    const bool served = query_filterable(!(a.metric == MIR_METRIC_INNER_PRODUCT || a.metric == MIR_METRIC_COSINE_SIM), a.q_norm[qi],
+                                         a.max_norm[0]);  // (word 0 of the int8 statistics is the largest row norm too)
+    if (over || !served) {  // a candidate of this query was dropped somewhere, or the filters did not serve it (mode 0: the sample's threshold stays)
         to_exact_pass();
         return;
     }

@@ -18,6 +18,10 @@ Pinning status ("Oracle"):
   (``tests/golden/make_golden.py`` -> ``tests/golden/metrics_*.npz``).
 * index / top-k   - PINNED by the cases of ``tests/test_embeddings_index.py``
   (tie-break, limits, empties) restated in ``tests/golden/index_cases.json``.
+* query range     - ``query_range`` adds no formula: it names queries at the edges
+  of float range, builds the smallest corpus per search route and derives the
+  float64 error bound of the metrics above; ``tests/test_oracle_query_range.py``
+  proves that those inputs can be judged with identical ids.
 * BM25            - parity unpinned upstream: arithmetic lives in third-party
   ``rank-bm25==0.2.2`` which is absent; restated from its published algorithm.
 * RRF fusion      - parity unpinned upstream: langchain 0.3.21
