@@ -18,7 +18,7 @@ METRIC_CODES = {"cosine_sim": 0, "euclidean_dist": 1, "sqeuclidean_dist": 2, "in
 DTYPE_F32, DTYPE_F16 = 0, 1
 FLAG_UNCERTAIN = 1  # never returned since ABI 2
 FLAG_EXACT_PASS = 2  # the query was answered by the exact pass (exact_topk_kernel)
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class NativeLibraryMissing(ImportError):
@@ -67,6 +67,8 @@ def _load():
         "mir_index_info": ([vp, vp, vp, vp, vp, vp], i32),
         "mir_index_search": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp], i32),
         "mir_index_search_device": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp], i32),
+        "mir_index_search_scoped": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "mir_index_search_scoped_device": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_index_profile": ([vp, i32], i32),
         "mir_index_profile_read": ([vp, i32, vp, vp], i32),
         "mir_index_scan_stats": ([vp, i32, vp], i32),

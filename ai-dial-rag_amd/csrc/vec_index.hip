@@ -19,6 +19,7 @@
 #include "vec_kernels_sieve.h"
 #include "vec_kernels_i8.h"
 #include "vec_kernels_exact.h"
+#include "vec_kernels_scoped.h"
 
 namespace mir {
 
@@ -1558,6 +1559,229 @@ int32_t mir_index_search(mir_index *idx, const double *queries_host, int32_t b, 
     release_ws(idx, w, s, false);
     return MIR_OK;
 }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- scoped search (vec_kernels_scoped.h)
+
+namespace mir {
+
+struct ScopedBuffers {
+    double *q;            // host API: [b][d]
+    int32_t *scope_ptr;   // host API: [b + 1]
+    int64_t *seg_begin;   // host API: [nseg]
+    int64_t *seg_end;     // host API: [nseg]
+    size_t in_span;       // host API: bytes from q to the end of seg_end (one copy in)
+    double *q_sq, *q_norm;
+    unsigned long long *arrive;  // [ceil(b / 2)] words = b counters, zeroed by the prep kernel
+    double *bound_dist;
+    uint32_t *bound_pos;
+    uint64_t *part;       // [b][P][min(k, 64)][2]
+    int32_t *o_doc;       // host API staging of outputs, [b][k]
+    int64_t *o_chunk;
+    int64_t *o_row;
+    double *o_dist;
+    int32_t *o_count;
+    int32_t *o_flags;
+};
+
+static size_t carve_scoped(ScopedBuffers &sb, char *base, int b, int k, int d, int P, size_t nseg, bool host_api) {
+    Carver c{base};
+    sb.q = host_api ? c.take<double>((size_t)b * d) : nullptr;
+    sb.scope_ptr = host_api ? c.take<int32_t>((size_t)b + 1) : nullptr;
+    sb.seg_begin = host_api ? c.take<int64_t>(nseg) : nullptr;
+    sb.seg_end = host_api ? c.take<int64_t>(nseg) : nullptr;
+    sb.in_span = c.off;
+    sb.q_sq = c.take<double>(b);
+    sb.q_norm = c.take<double>(b);
+    sb.arrive = c.take<unsigned long long>(((size_t)b + 1) / 2);
+    sb.bound_dist = c.take<double>(b);
+    sb.bound_pos = c.take<uint32_t>(b);
+    sb.part = c.take<uint64_t>(P > 1 ? (size_t)b * P * std::min(k, kExactRound) * 2 : 0);
+    if (host_api) {
+        sb.o_doc = c.take<int32_t>((size_t)b * k);
+        sb.o_chunk = c.take<int64_t>((size_t)b * k);
+        sb.o_row = c.take<int64_t>((size_t)b * k);
+        sb.o_dist = c.take<double>((size_t)b * k);
+        sb.o_count = c.take<int32_t>(b);
+        sb.o_flags = c.take<int32_t>(b);
+    } else {
+        sb.o_doc = nullptr; sb.o_chunk = nullptr; sb.o_row = nullptr; sb.o_dist = nullptr;
+        sb.o_count = nullptr; sb.o_flags = nullptr;
+    }
+    return c.off + 256;
+}
+
+// Workgroups per query: about four per CU in all, the kernel's merge takes up to kScopedMaxP lists.  One query over a
+// million rows gets 64 workgroups, 256 queries over a thousand rows each get four.
+// `max_rows`: the longest scope where the caller can see the scopes (the host form; 0 = unknown): a workgroup's share is 64
+// positions at the least, a document of a few hundred rows is not spread over 64 lists.
+static int scoped_split(const mir_index *ix, int b, uint64_t max_rows) {
+    int want = (4 * std::max(ix->num_cus, 1) + b - 1) / b;
+    if (max_rows) want = (int)std::min<uint64_t>((uint64_t)want, (max_rows + 63) / 64);
+    return std::min(std::max(want, 1), kScopedMaxP);
+}
+
+static int32_t check_scoped_args(const mir_index *ix, const void *queries, int32_t b, int32_t k, int32_t metric,
+                                 const int32_t *scope_ptr, const int32_t *out_count) {
+    int32_t rc = check_search_args(ix, queries, b, k, metric, out_count);
+    if (rc != MIR_OK) return rc;
+    MIR_REQUIRE(b == 0 || scope_ptr != nullptr, "scope_ptr is NULL");
+    return MIR_OK;
+}
+
+static int32_t enqueue_scoped(mir_index *ix, const double *dq, int b, int k, int metric, int P, const ScopedBuffers &sb,
+                              const int32_t *scope_ptr, const int64_t *seg_begin, const int64_t *seg_end, int32_t *o_doc,
+                              int64_t *o_chunk, int64_t *o_row, double *o_dist, int32_t *o_count, int32_t *o_flags,
+                              hipStream_t stream) {
+    const int d = ix->d;
+    // per-query norms (ngroups = 0: no fragments) + the arrival counters zeroed
+    const int arrive_words = (b + 1) / 2;
+    prep_queries_kernel<<<dim3(std::max(b, (arrive_words + 63) / 64)), dim3(64), 0, stream>>>(dq, b, d, ix->ksteps, 0, nullptr, sb.q_sq,
+                                                                                                sb.q_norm, sb.arrive, arrive_words);
+    ScopedArgs a;
+    a.docs = ix->d_orig; a.docs16 = ix->d_f16; a.doc_sq = ix->d_docsq; a.n_rows = (uint32_t)ix->n; a.d = d; a.metric = metric;
+    a.q = dq; a.q_sq = sb.q_sq; a.q_norm = sb.q_norm; a.scope_ptr = scope_ptr; a.seg_begin = seg_begin; a.seg_end = seg_end;
+    a.k = k; a.list_stride = std::min(k, kExactRound); a.part = sb.part; a.arrive = reinterpret_cast<uint32_t *>(sb.arrive);
+    a.bound_dist = sb.bound_dist; a.bound_pos = sb.bound_pos; a.chunk_ids = ix->d_chunk; a.row_offset = ix->row_offset;
+    a.out_doc = o_doc; a.out_chunk = o_chunk; a.out_row = o_row; a.out_dist = o_dist; a.out_count = o_count; a.out_flags = o_flags;
+    const bool qlds = d <= kScopedLdsDim;
+    const size_t lds = qlds ? (size_t)d * sizeof(double) : 0;
+    constexpr int kSlice = 32768;  // queries per launch (grid.y)
+    for (int round = 0; round * kExactRound < k; ++round) {
+        a.round = round;
+        for (int q0 = 0; q0 < b; q0 += kSlice) {
+            a.q0 = q0;
+            const dim3 grid((unsigned)P, (unsigned)std::min(kSlice, b - q0));
+            if (ix->d_f16 && qlds) scoped_topk_kernel<_Float16, true><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
+            else if (ix->d_f16) scoped_topk_kernel<_Float16, false><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
+            else if (qlds) scoped_topk_kernel<float, true><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
+            else scoped_topk_kernel<float, false><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
+        }
+    }
+    MIR_HIP(hipGetLastError());
+    return MIR_OK;
+}
+
+}  // namespace mir
+
+extern "C" {
+
+int32_t mir_index_search_scoped_device(mir_index *idx, const double *queries_device, int32_t b, int32_t k, int32_t metric,
+                                       const int32_t *scope_ptr_device, const int64_t *seg_begin_device,
+                                       const int64_t *seg_end_device, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row,
+                                       double *out_dist, int32_t *out_count, int32_t *out_flags, void *stream_) {
+    int32_t rc = check_scoped_args(idx, queries_device, b, k, metric, scope_ptr_device, out_count);
+    if (rc != MIR_OK) return rc;
+    if (b == 0) return MIR_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    rc = use_device(idx->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    const int P = scoped_split(idx, b, 0);
+    ScopedBuffers sb;
+    const size_t need = carve_scoped(sb, nullptr, b, k, idx->d, P, 0, false);
+    Workspace *w = nullptr;
+    rc = acquire_ws(idx, stream, need, &w);
+    if (rc != MIR_OK) return rc;
+    carve_scoped(sb, static_cast<char *>(w->buf), b, k, idx->d, P, 0, false);
+    rc = enqueue_scoped(idx, queries_device, b, k, metric, P, sb, scope_ptr_device, seg_begin_device, seg_end_device, out_doc,
+                        out_chunk, out_row, out_dist, out_count, out_flags, stream);
+    release_ws(idx, w, stream, true);
+    return rc;
+}
+
+int32_t mir_index_search_scoped(mir_index *idx, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                                const int32_t *scope_ptr_host, const int64_t *seg_begin_host, const int64_t *seg_end_host,
+                                int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
+                                int32_t *out_flags) {
+    int32_t rc = check_scoped_args(idx, queries_host, b, k, metric, scope_ptr_host, out_count);
+    if (rc != MIR_OK) return rc;
+    if (b == 0) return MIR_OK;
+    // everything the device form leaves to the kernel's clamping is refused here, before anything is launched
+    MIR_REQUIRE(scope_ptr_host[0] == 0, "scope_ptr[0]=%d must be 0", scope_ptr_host[0]);
+    for (int q = 0; q < b; ++q)
+        MIR_REQUIRE(scope_ptr_host[q + 1] >= scope_ptr_host[q], "scope_ptr decreases at query %d", q);
+    const size_t nseg = (size_t)scope_ptr_host[b];
+    MIR_REQUIRE(nseg == 0 || (seg_begin_host != nullptr && seg_end_host != nullptr), "segment arrays are NULL");
+    uint64_t max_rows = 1;
+    for (int q = 0; q < b; ++q) {
+        uint64_t rows = 0;
+        for (int s = scope_ptr_host[q]; s < scope_ptr_host[q + 1]; ++s) {
+            MIR_REQUIRE(seg_begin_host[s] >= 0 && seg_begin_host[s] <= seg_end_host[s] && seg_end_host[s] <= idx->n,
+                        "segment %d of query %d is [%lld, %lld): not inside 0 <= begin <= end <= n=%lld", s - scope_ptr_host[q], q,
+                        (long long)seg_begin_host[s], (long long)seg_end_host[s], (long long)idx->n);
+            rows += (uint64_t)(seg_end_host[s] - seg_begin_host[s]);
+            MIR_REQUIRE(rows < (1ull << 32), "the scope of query %d holds 2^32 rows or more", q);
+        }
+        max_rows = std::max(max_rows, rows);
+    }
+    rc = use_device(idx->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    const int P = scoped_split(idx, b, max_rows);
+    ScopedBuffers sb;
+    const size_t need = carve_scoped(sb, nullptr, b, k, idx->d, P, nseg, true);
+    Workspace *w = nullptr;
+    rc = acquire_ws(idx, nullptr, need, &w);
+    if (rc != MIR_OK) return rc;
+    carve_scoped(sb, static_cast<char *>(w->buf), b, k, idx->d, P, nseg, true);
+    hipStream_t s = w->stream;
+    auto bail = [&](int32_t code) {
+        (void)hipStreamSynchronize(s);
+        release_ws(idx, w, s, false);
+        return code;
+    };
+#define MIR_TRY(call)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            set_error("%s failed: %s", #call, hipGetErrorString(e_));                              \
+            return bail(MIR_ERR_HIP);                                                              \
+        }                                                                                          \
+    } while (0)
+    // the pinned staging buffer of mir_index_search: [q | scope_ptr | seg_begin | seg_end] goes in as ONE copy of the span
+    // carved in that order, [o_doc .. o_flags] comes back as one
+    const char *in0 = reinterpret_cast<const char *>(sb.q);
+    const size_t in_pad = (sb.in_span + 255) & ~(size_t)255;
+    const char *span0 = reinterpret_cast<const char *>(sb.o_doc);
+    const size_t span = (size_t)(reinterpret_cast<const char *>(sb.o_flags) + (size_t)b * 4 - span0);
+    if (w->pin_cap < in_pad + span) {
+        if (w->pin) (void)hipHostFree(w->pin);
+        w->pin = nullptr;
+        w->pin_cap = 0;
+        MIR_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->pin), in_pad + span, hipHostMallocDefault));
+        w->pin_cap = in_pad + span;
+    }
+    auto in_at = [&](const void *dev_ptr) { return w->pin + (reinterpret_cast<const char *>(dev_ptr) - in0); };
+    std::memcpy(in_at(sb.q), queries_host, (size_t)b * idx->d * sizeof(double));
+    std::memcpy(in_at(sb.scope_ptr), scope_ptr_host, ((size_t)b + 1) * 4);
+    if (nseg) {
+        std::memcpy(in_at(sb.seg_begin), seg_begin_host, nseg * 8);
+        std::memcpy(in_at(sb.seg_end), seg_end_host, nseg * 8);
+    }
+    MIR_TRY(hipMemcpyAsync(sb.q, w->pin, sb.in_span, hipMemcpyHostToDevice, s));
+    rc = enqueue_scoped(idx, sb.q, b, k, metric, P, sb, sb.scope_ptr, sb.seg_begin, sb.seg_end, out_doc ? sb.o_doc : nullptr,
+                        out_chunk ? sb.o_chunk : nullptr, out_row ? sb.o_row : nullptr, out_dist ? sb.o_dist : nullptr,
+                        sb.o_count, sb.o_flags, s);
+    if (rc != MIR_OK) return bail(rc);
+    const size_t bk = (size_t)b * k;
+    char *res = w->pin + in_pad;
+    MIR_TRY(hipMemcpyAsync(res, span0, span, hipMemcpyDeviceToHost, s));
+    MIR_TRY(hipStreamSynchronize(s));
+    auto at = [&](const void *dev_ptr) { return res + (reinterpret_cast<const char *>(dev_ptr) - span0); };
+    if (out_doc) std::memcpy(out_doc, at(sb.o_doc), bk * 4);
+    if (out_chunk) std::memcpy(out_chunk, at(sb.o_chunk), bk * 8);
+    if (out_row) std::memcpy(out_row, at(sb.o_row), bk * 8);
+    if (out_dist) std::memcpy(out_dist, at(sb.o_dist), bk * 8);
+    std::memcpy(out_count, at(sb.o_count), (size_t)b * 4);
+    if (out_flags) std::memcpy(out_flags, at(sb.o_flags), (size_t)b * 4);
+#undef MIR_TRY
+    release_ws(idx, w, s, false);
+    return MIR_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int32_t mir_index_metric_eval(mir_index *idx, const double *query_host, int32_t metric, double *out_host) {
     MIR_REQUIRE(idx != nullptr, "index is NULL");

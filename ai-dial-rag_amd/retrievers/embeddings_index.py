@@ -38,6 +38,22 @@ class DocIndex:
         self.embeddings = embeddings if embeddings is not None else np.array([], dtype=np.float32)
 
 
+def scope_segments(doc_lengths: Sequence[int], doc_positions: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:
+    """Row ranges of the listed documents inside an index that holds the documents' rows flattened in order:
+    (begin int64[m], end int64[m]), one segment per listed position, in the order listed.  An empty document gives
+    an empty segment (it keeps its ordinal, as it keeps its doc id in embeddings_index.py:67-69); a position may be
+    listed more than once.  Pure host arithmetic."""
+    lengths = np.asarray(doc_lengths, dtype=np.int64).reshape(-1)
+    if np.any(lengths < 0):
+        raise ValueError("negative document length")
+    pos = np.asarray(doc_positions, dtype=np.int64).reshape(-1)
+    if np.any((pos < 0) | (pos >= len(lengths))):
+        raise ValueError(f"document position outside [0, {len(lengths)})")
+    ends = np.cumsum(lengths)
+    begin = (ends - lengths)[pos]
+    return begin.astype(np.int64), ends[pos].astype(np.int64)
+
+
 class DeviceRows:
     """Owner of one ``mir_rows`` handle: ONE document's rows (and chunk ids) resident in HBM.  Indexes over any
     set of documents are composed from these device-to-device (``DeviceIndex.from_rows``)."""
@@ -156,6 +172,43 @@ class DeviceIndex:
         nat.check(nat.lib.mir_index_search_device(self._h, q_ptr, b, k, code, out_doc_ptr or None, out_chunk_ptr or None,
                                                   out_row_ptr or None, out_dist_ptr or None, out_count_ptr,
                                                   out_flags_ptr or None, stream or None))
+
+    def search_scoped(self, queries: np.ndarray, k: int, metric, scope_ptr, seg_begin, seg_end) -> Tuple[np.ndarray, ...]:
+        """Every query searches its own rows: query q's scope is the concatenation of the LOCAL row ranges
+        [seg_begin[s], seg_end[s]), s in [scope_ptr[q], scope_ptr[q + 1]).  Returns the tuple of `search`; doc_ids are
+        the ordinals of the segments inside each query's scope, count[q] = min(k, rows of the scope)."""
+        q = nat.as_f64_queries(queries, self.d)
+        b = q.shape[0]
+        code = nat.METRIC_CODES[Metric(metric).value]
+        sp = np.ascontiguousarray(scope_ptr, dtype=np.int32).reshape(-1)
+        sb = np.ascontiguousarray(seg_begin, dtype=np.int64).reshape(-1)
+        se = np.ascontiguousarray(seg_end, dtype=np.int64).reshape(-1)
+        if len(sp) != b + 1:
+            raise ValueError(f"scope_ptr has {len(sp)} entries for {b} queries (want b + 1)")
+        if len(sb) != len(se) or int(sp.max()) > len(sb):
+            raise ValueError(f"{len(sb)} segment begins, {len(se)} ends, scope_ptr up to {int(sp.max())}")
+        doc = np.zeros((b, k), np.int32)
+        chunk = np.zeros((b, k), np.int64)
+        row = np.zeros((b, k), np.int64)
+        dist = np.zeros((b, k), np.float64)
+        cnt = np.zeros(b, np.int32)
+        flg = np.zeros(b, np.int32)
+        nat.check(nat.lib.mir_index_search_scoped(self._h, nat.ptr(q), b, k, code, nat.ptr(sp), nat.ptr(sb), nat.ptr(se), nat.ptr(doc),
+                                                  nat.ptr(chunk), nat.ptr(row), nat.ptr(dist), nat.ptr(cnt), nat.ptr(flg)))
+        return doc, chunk, row, dist, cnt, flg
+
+    def search_scoped_device(self, q_ptr: int, b: int, k: int, metric, scope_ptr_ptr: int, seg_begin_ptr: int, seg_end_ptr: int,
+                             out_row_ptr: int, out_dist_ptr: int, out_count_ptr: int, out_flags_ptr: int = 0, out_doc_ptr: int = 0,
+                             out_chunk_ptr: int = 0, stream: int = 0) -> None:
+        """Asynchronous scoped search with every buffer in HBM (pointers as ints).  Nothing in the arrays is validated:
+        the kernel clamps segment begins and ends into the index, so a malformed segment gives unspecified results
+        but reads no row outside it.  scope_ptr itself is trusted: it must be monotone from 0 and index inside the
+        segment arrays, or the kernel reads those arrays out of bounds."""
+        code = nat.METRIC_CODES[Metric(metric).value]
+        nat.check(nat.lib.mir_index_search_scoped_device(self._h, q_ptr, b, k, code, scope_ptr_ptr or None, seg_begin_ptr or None,
+                                                         seg_end_ptr or None, out_doc_ptr or None, out_chunk_ptr or None,
+                                                         out_row_ptr or None, out_dist_ptr or None, out_count_ptr,
+                                                         out_flags_ptr or None, stream or None))
 
     def profile(self, enable: bool) -> None:
         nat.check(nat.lib.mir_index_profile(self._h, 1 if enable else 0))
@@ -295,6 +348,34 @@ class EmbeddingsIndex:
             return z.astype(np.int32), z.astype(np.int64), z, np.zeros(b, np.int32), np.zeros(b, np.int32)
         doc, chunk, _row, dist, cnt, flg = dev.search(queries, self.limit, self.metric)
         return doc, chunk, dist, cnt, flg
+
+    def find_in_doc(self, query: np.ndarray, doc_index: DocIndex) -> Tuple[npt.NDArray[np.int64], npt.NDArray[np.float64]]:
+        """embeddings_index.py:51-60: the first `limit` rows of ONE document under (distance, row) -> (chunk ids,
+        distances).  A document of this index (by identity) is one segment of the index already in HBM; any other
+        DocIndex is searched through a one-document index of its own, which costs an upload and an index build on
+        EVERY call (nothing foreign is cached): a document that is asked often belongs in the index."""
+        Metric(self.metric)
+        n = len(doc_index.embeddings)
+        if n == 0:
+            return np.zeros(0, np.int64), np.zeros(0, np.float64)
+        begin, member = 0, False
+        for doc in self.doc_indexes:
+            if doc is doc_index:
+                member = True
+                break
+            begin += len(doc.embeddings)  # (empty documents hold no rows of the flattened index)
+        dev = self._device_index() if member else None
+        if dev is not None:
+            q = nat.as_f64_queries(query, dev.d)
+            _doc, chunk, _row, dist, cnt, _ = dev.search_scoped(q, self.limit, self.metric, [0, 1], [begin], [begin + n])
+        else:
+            one = DeviceIndex.from_host(np.asarray(doc_index.embeddings), np.asarray(doc_index.chunk_ids, dtype=np.int64), None, self.device)
+            try:
+                _doc, chunk, _row, dist, cnt, _ = one.search(nat.as_f64_queries(query, one.d), self.limit, self.metric)
+            finally:
+                one.close()
+        m = int(cnt[0])
+        return chunk[0, :m].copy(), dist[0, :m].copy()
 
     def find_batch(self, queries: np.ndarray) -> List[List[Document]]:
         doc, chunk, _dist, cnt, _ = self.search_arrays(queries)

@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 4 /* 4: mir_keywords_preprocess / mir_kwp_result_*;
+#define MIR_ABI_VERSION 5 /* 5: mir_index_search_scoped[_device];
+                            4: mir_keywords_preprocess / mir_kwp_result_*;
                             3: 2: results always exact (exact pass), any k; mir_bm25_tune / _corpus_stats / _idf_from_stats /
                              _set_global_stats, mir_rrf_fuse_batch, mir_wordpiece_* added
                              3: mir_index_scan_stats added; mir_bm25_search[_device] take any k (no MIR_ERR_UNSUPPORTED past 64);
@@ -151,6 +152,36 @@ int32_t mir_index_search(mir_index *idx, const double *queries_host, int32_t b, 
 int32_t mir_index_search_device(mir_index *idx, const double *queries_device, int32_t b, int32_t k,
                                 int32_t metric, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row,
                                 double *out_dist, int32_t *out_count, int32_t *out_flags, void *stream);
+
+/* Scoped search: every query of the batch searches its OWN rows of the index (csrc/vec_kernels_scoped.h).
+ * Query q's scope is the concatenation of the segments [seg_begin[s], seg_end[s]),
+ * s in [scope_ptr[q], scope_ptr[q + 1]), in the order given; segments are LOCAL row ranges of this index
+ * (row_offset is not part of them), may be empty, may repeat and may overlap.  A row's index in that
+ * concatenation is its scope position.  The answer is the first out_count[q] = min(k, L_q) scope positions
+ * (L_q = the scope's row count; 0 for an empty scope) under (distance ascending, NaN last, scope position
+ * ascending), every distance being the reference's float64 formula: with one segment per document of a request,
+ * empties included, EmbeddingsIndex.find over that request's document list (embeddings_index.py:62-89).
+ *   out_doc   : the ORDINAL of the row's segment inside the query's scope (that request's doc_id)
+ *   out_chunk : chunk_ids[row];  out_row : row_offset + row;  out_dist : as mir_index_search
+ *   out_flags : 0
+ * Any k >= 1; any of out_doc / out_chunk / out_row / out_dist / out_flags may be NULL.  scope_ptr: int32[b + 1],
+ * scope_ptr[0] = 0, non-decreasing; seg_begin / seg_end: int64[scope_ptr[b]].
+ * The host form returns MIR_ERR_INVALID, before anything is launched, for scope_ptr[0] != 0, a decreasing
+ * scope_ptr, a segment outside 0 <= begin <= end <= n and a scope of 2^32 rows or more. */
+int32_t mir_index_search_scoped(mir_index *idx, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                                const int32_t *scope_ptr_host, const int64_t *seg_begin_host,
+                                const int64_t *seg_end_host, int32_t *out_doc, int64_t *out_chunk,
+                                int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags);
+
+/* The same with every buffer in HBM, asynchronous on `stream` (no synchronisation).  This form cannot see the
+ * arrays and validates nothing in them: the kernel clamps begin / end into [0, n], treats end < begin as empty
+ * and cuts a scope off at 2^32 - 1 rows, so it never reads a row outside the index; what a malformed scope
+ * returns is unspecified.  scope_ptr must still index inside the segment arrays. */
+int32_t mir_index_search_scoped_device(mir_index *idx, const double *queries_device, int32_t b, int32_t k,
+                                       int32_t metric, const int32_t *scope_ptr_device,
+                                       const int64_t *seg_begin_device, const int64_t *seg_end_device,
+                                       int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist,
+                                       int32_t *out_count, int32_t *out_flags, void *stream);
 
 /* Benchmark instrumentation: when enabled, every launch of the scan kernel (the
  * dominant, HBM-streaming kernel) is bracketed by HIP events on the stream it

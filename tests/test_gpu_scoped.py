@@ -1,0 +1,420 @@
+"""GPU parity of the scoped search (csrc/vec_kernels_scoped.h): every query of a batch searches its own row ranges of one
+shared index.  Expected answers: the oracle's `find` over just the documents of the scope, in the order of the scope -
+(segment ordinal, chunk id) pairs identical (cosine: up to ties within COS_NOISE, as test_gpu_vector.py), distances
+within 1e-9 (cosine 5e-7), the exact pass's tolerances."""
+
+import threading
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+METRICS = ["cosine_sim", "euclidean_dist", "sqeuclidean_dist", "inner_product"]
+COS_NOISE = 2e-7
+
+
+def dist_tol(metric):
+    return 5e-7 if metric == "cosine_sim" else 1e-9
+
+
+@pytest.fixture(scope="module")
+def amd():
+    from aidial_rag_amd import _native
+    from aidial_rag_amd.index_record import RetrievalType
+    from aidial_rag_amd.retrievers import corpus_index as ci
+    from aidial_rag_amd.retrievers import embeddings_index as ei
+    from oracle import embeddings_index as oi
+
+    assert _native.device_count() >= 1, "no GPU visible: the product path has no CPU fallback"
+
+    class NS:
+        pass
+
+    ns = NS()
+    ns.nat, ns.ei, ns.ci, ns.oi, ns.RetrievalType = _native, ei, ci, oi, RetrievalType
+    return ns
+
+
+def unit(x):
+    return (x / np.linalg.norm(x, axis=-1, keepdims=True)).astype(np.float32)
+
+
+def flatten(parts, chunks):
+    live = [i for i, p in enumerate(parts) if len(p)]
+    return np.concatenate([parts[i] for i in live]), np.concatenate([chunks[i] for i in live])
+
+
+def csr(segment_lists):
+    """[(begin[], end[]) per query] -> scope_ptr, seg_begin, seg_end"""
+    ptr = np.zeros(len(segment_lists) + 1, np.int32)
+    np.cumsum([len(b) for b, _ in segment_lists], out=ptr[1:])
+    begin = np.concatenate([np.asarray(b, np.int64) for b, _ in segment_lists] + [np.zeros(0, np.int64)])
+    end = np.concatenate([np.asarray(e, np.int64) for _, e in segment_lists] + [np.zeros(0, np.int64)])
+    return ptr, begin, end
+
+
+def check_against_oracle(oi, metric, q, scope_docs, k, got_doc, got_chunk, got_dist, got_cnt, msg):
+    """scope_docs: the oracle DocIndex objects of the scope, in its order"""
+    with np.errstate(invalid="ignore"):
+        want, wdist = oi.find(q, scope_docs, metric, k)
+    m = int(got_cnt)
+    assert m == len(want), msg
+    got = [(int(a), int(b)) for a, b in zip(got_doc[:m], got_chunk[:m])]
+    if metric != "cosine_sim":
+        assert got == want, msg
+    else:
+        def dist_of(pair):
+            doc = scope_docs[pair[0]]
+            row = int(np.nonzero(doc.chunk_ids == pair[1])[0][0])
+            return float(oi.ENUM_TO_METRIC[oi.Metric(metric)](q, doc.embeddings[row : row + 1])[0])
+
+        for g, w in zip(got, want):
+            if g != w:
+                assert abs(dist_of(g) - dist_of(w)) <= COS_NOISE, f"{msg}: {g} vs {w}"
+    np.testing.assert_allclose(got_dist[:m], wdist, rtol=0, atol=dist_tol(metric), equal_nan=True, err_msg=msg)
+
+
+# ---------------------------------------------------------------- 1. parity
+
+@pytest.fixture(scope="module")
+def ragged(amd):
+    rng = np.random.default_rng(2024)
+    sizes = rng.integers(2, 200, 60)
+    sizes[[3, 10, 44]] = 0   # empty documents
+    sizes[7] = 1             # a one-row document
+    sizes[8] = 5
+    parts = [unit(rng.standard_normal((m, 384))) if m else np.zeros((0, 384), np.float32) for m in sizes]
+    chunks = [3 * np.arange(m, dtype=np.int64) + 1 for m in sizes]  # chunk ids that are not rows
+    docs = [amd.oi.DocIndex(c, p) if len(p) else amd.oi.DocIndex() for c, p in zip(chunks, parts)]
+    emb, chunk = flatten(parts, chunks)
+    dev = amd.ei.DeviceIndex.from_host(emb, chunk)
+    scopes = [[12], [3], [], list(range(60)), [50, 40, 30, 20, 11], [9, 9], [7, 8], [0, 59]]
+    queries = rng.standard_normal((len(scopes), 384))
+    # the all-documents query is a copy of a stored row whose squared distance to itself is NEGATIVE in the reference's
+    # arithmetic (float32 doc_sq against float64 dot): euclidean_dist's NaN, sorted last
+    with np.errstate(invalid="ignore"):
+        self_sq = np.array([amd.oi.ENUM_TO_METRIC[amd.oi.Metric("sqeuclidean_dist")](r.astype(np.float64), r[None])[0] for r in emb[:400]])
+    twin = int(np.argmin(self_sq))
+    assert self_sq[twin] < -1e-9
+    queries[3] = emb[twin].astype(np.float64)
+    twin_doc = int(np.searchsorted(np.cumsum(sizes), twin, side="right"))
+    return sizes, docs, dev, scopes, queries, emb, twin_doc
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_parity_over_ragged_documents(amd, ragged, metric):
+    sizes, docs, dev, scopes, queries, emb, twin_doc = ragged
+    segs = [amd.ei.scope_segments(sizes, s) for s in scopes]
+    ptr, begin, end = csr(segs)
+    for k in (1, 7, 64):
+        doc, chunk, row, dist, cnt, flags = dev.search_scoped(queries, k, metric, ptr, begin, end)
+        assert (flags == 0).all()
+        assert cnt[1] == 0 and cnt[2] == 0  # only an empty document; no segment at all
+        assert cnt[6] == min(k, 6)          # a scope of 6 rows
+        for i, s in enumerate(scopes):
+            check_against_oracle(amd.oi, metric, queries[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{metric} k={k} scope {i}")
+            # the B = 1 call is the same computation
+            p1, b1, e1 = csr([segs[i]])
+            one = dev.search_scoped(queries[i : i + 1], k, metric, p1, b1, e1)
+            m = int(cnt[i])
+            assert int(one[4][0]) == m
+            for got, batched in zip(one[:4], (doc, chunk, row, dist)):
+                np.testing.assert_array_equal(got[0, :m], batched[i, :m])
+        # all documents in order = the unscoped search of the index
+        _, uchunk, urow, udist, ucnt, _ = dev.search(queries[3:4], k, metric)
+        assert ucnt[0] == cnt[3] == k
+        if metric != "cosine_sim":
+            np.testing.assert_array_equal(row[3], urow[0])
+        else:
+            with np.errstate(invalid="ignore"):
+                alld = amd.oi.ENUM_TO_METRIC[amd.oi.Metric(metric)](queries[3], emb)
+            for g, w in zip(row[3], urow[0]):
+                assert g == w or abs(alld[g] - alld[w]) <= COS_NOISE
+        np.testing.assert_allclose(dist[3], udist[0], rtol=0, atol=dist_tol(metric), equal_nan=True)
+        if metric == "euclidean_dist":
+            assert not np.isnan(dist[3]).any()  # NaN sorts last: never among the first k of some 5000 rows
+    if metric == "euclidean_dist":
+        # ... and it IS last where the scope is the twin's own document, searched to its last row
+        b, e = amd.ei.scope_segments(sizes, [twin_doc])
+        n = int(sizes[twin_doc])
+        p1, b1, e1 = csr([(b, e)])
+        doc, chunk, _, dist, cnt, _ = dev.search_scoped(queries[3:4], n, metric, p1, b1, e1)
+        assert cnt[0] == n and np.isnan(dist[0, n - 1]) and not np.isnan(dist[0, : n - 1]).any()
+        check_against_oracle(amd.oi, metric, queries[3], [docs[twin_doc]], n, doc[0], chunk[0], dist[0], cnt[0], "NaN last")
+
+
+# ---------------------------------------------------------------- 2. order
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_ties_follow_the_scope_order_and_row_offset_shifts_rows(amd, metric):
+    rng = np.random.default_rng(5)
+    parts = [unit(rng.standard_normal((m, 384))) for m in (10, 12, 9)]
+    x = unit(rng.standard_normal(384))
+    parts[0][3] = x          # document A
+    parts[1][5] = x          # document B
+    parts[0][7] = parts[0][2]  # duplicates inside one document
+    chunks = [np.arange(len(p), dtype=np.int64) for p in parts]
+    docs = [amd.oi.DocIndex(c, p) for c, p in zip(chunks, parts)]
+    emb, chunk = flatten(parts, chunks)
+    sizes = [len(p) for p in parts]
+    dev = amd.ei.DeviceIndex.from_host(emb, chunk, row_offset=1000)
+    scopes = [[1, 0], [0, 1], [0]]
+    queries = np.stack([x.astype(np.float64), x.astype(np.float64), parts[0][2].astype(np.float64)])
+    ptr, begin, end = csr([amd.ei.scope_segments(sizes, s) for s in scopes])
+    doc, chunk_o, row, dist, cnt, _ = dev.search_scoped(queries, 3, metric, ptr, begin, end)
+    for i, s in enumerate(scopes):
+        check_against_oracle(amd.oi, metric, queries[i], [docs[j] for j in s], 3, doc[i], chunk_o[i], dist[i], cnt[i], f"{metric} scope {s}")
+    if metric != "euclidean_dist":  # (there the copies are the NaN-last rows or near-zero values; the oracle check above covers it)
+        assert [(doc[0, j], chunk_o[0, j]) for j in range(2)] == [(0, 5), (1, 3)]  # scope [B, A]: B's copy first
+        assert [(doc[1, j], chunk_o[1, j]) for j in range(2)] == [(0, 3), (1, 5)]  # scope [A, B]: A's
+        assert dist[0, 0] == dist[0, 1] and dist[1, 0] == dist[1, 1]
+        assert list(chunk_o[2, :2]) == [2, 7] and dist[2, 0] == dist[2, 1]       # lower row first
+        # segments are local rows; reported rows carry the index's offset
+        assert list(row[0, :2]) == [1000 + 10 + 5, 1000 + 3] and list(row[2, :2]) == [1002, 1007]
+    assert row.min() >= 1000 and row.max() < 1000 + sum(sizes)
+
+
+# ---------------------------------------------------------------- 3. k beyond one round
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_k_beyond_one_round_with_ties_across_position_64(amd, metric):
+    rng = np.random.default_rng(77)
+    q = rng.standard_normal(64)
+    parts = []
+    for m in (150, 90, 20):
+        p = rng.standard_normal((m, 64))
+        p[:, 0] = 0.0
+        parts.append(unit(p))
+    # Ten rows of each searched document become the basis vector e_0: their dot product with q is q[0] in EVERY summation
+    # order (the reference's BLAS does not give bit-identical rows in different positions the same last bit otherwise), and
+    # no other row has a component there.  q[0] is put between the 60th and the 61st best of the document's other rows
+    # (one query per document): ten exact ties on ranks 60 .. 69, across the end of the first round of 64.
+    tied = [np.sort(rng.choice(m, 10, replace=False)) for m in (150, 90)]
+    q[0] = 0.0
+    qs = np.stack([q, q])  # one query per document, equal but for component 0
+    for i in range(2):
+        best_first = np.sort(np.delete(parts[i], tied[i], axis=0).astype(np.float64) @ q)[::-1]
+        qs[i, 0] = 0.5 * (best_first[59] + best_first[60])
+        parts[i][tied[i]] = 0.0
+        parts[i][tied[i], 0] = 1.0
+    chunks = [np.arange(len(p), dtype=np.int64) for p in parts]
+    docs = [amd.oi.DocIndex(c, p) for c, p in zip(chunks, parts)]
+    emb, chunk = flatten(parts, chunks)
+    dev = amd.ei.DeviceIndex.from_host(emb, chunk)
+    sizes = [len(p) for p in parts]
+    scopes = [[0], [1]]
+    ptr, begin, end = csr([amd.ei.scope_segments(sizes, s) for s in scopes])
+    for k in (100, 130):
+        doc, chunk_o, _, dist, cnt, _ = dev.search_scoped(qs, k, metric, ptr, begin, end)
+        assert list(cnt) == [k, 90]
+        for i, s in enumerate(scopes):
+            check_against_oracle(amd.oi, metric, qs[i], [docs[j] for j in s], k, doc[i], chunk_o[i], dist[i], cnt[i], f"{metric} k={k} scope {s}")
+            assert (dist[i, 60:70] == dist[i, 60]).all()  # one value ...
+            np.testing.assert_array_equal(chunk_o[i, 60:70], tied[i])  # ... rows ascending
+
+
+# ---------------------------------------------------------------- 4. split and merge on a sieve-image shard
+
+@pytest.fixture(scope="module")
+def big(amd):
+    rng = np.random.default_rng(9)
+    emb = unit(rng.standard_normal((70_000, 64)))
+    return emb, amd.ei.DeviceIndex.from_host(emb), rng.standard_normal((3, 64))
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_whole_index_scope_and_long_segment_list(amd, big, metric):
+    emb, dev, qs = big
+    n = len(emb)
+    k = 10
+    # B = 1, the whole index as one segment: many workgroups for the query, their lists merged
+    p1, b1, e1 = csr([([0], [n])])
+    doc, chunk, row, dist, cnt, _ = dev.search_scoped(qs[:1], k, metric, p1, b1, e1)
+    wrows, wdist = amd.oi.find_flat(qs[0], emb, metric, k)
+    alld = amd.oi.ENUM_TO_METRIC[amd.oi.Metric(metric)](qs[0], emb)
+
+    def same_rows(got, want, all_dist):
+        for g, w in zip(got, want):
+            assert g == w or (metric == "cosine_sim" and abs(all_dist[g] - all_dist[w]) <= COS_NOISE), (metric, got, want)
+
+    assert cnt[0] == k and (doc[0] == 0).all()
+    same_rows(row[0], wrows, alld)
+    np.testing.assert_array_equal(chunk[0], row[0])
+    np.testing.assert_allclose(dist[0], wdist, rtol=0, atol=dist_tol(metric))
+    # B = 3: that scope, a 10-row scope and 3000 one-row segments one row apart
+    even = 2 * np.arange(3000, dtype=np.int64)
+    ptr, begin, end = csr([([0], [n]), ([500], [510]), (even, even + 1)])
+    doc3, chunk3, row3, dist3, cnt3, _ = dev.search_scoped(qs, k, metric, ptr, begin, end)
+    assert list(cnt3) == [k, k, k]
+    np.testing.assert_array_equal(row3[0], row[0])
+    np.testing.assert_array_equal(dist3[0], dist[0])
+    w1, d1 = amd.oi.find_flat(qs[1], emb[500:510], metric, k)
+    same_rows(row3[1] - 500, w1, amd.oi.ENUM_TO_METRIC[amd.oi.Metric(metric)](qs[1], emb[500:510]))
+    assert (doc3[1] == 0).all()
+    np.testing.assert_allclose(dist3[1], d1, rtol=0, atol=dist_tol(metric))
+    w2, d2 = amd.oi.find_flat(qs[2], emb[0:6000:2], metric, k)
+    same_rows(doc3[2], w2, amd.oi.ENUM_TO_METRIC[amd.oi.Metric(metric)](qs[2], emb[0:6000:2]))  # the ordinal IS the position
+    np.testing.assert_array_equal(row3[2], 2 * doc3[2].astype(np.int64))
+    np.testing.assert_allclose(dist3[2], d2, rtol=0, atol=dist_tol(metric))
+
+
+# ---------------------------------------------------------------- 5. other storage
+
+@pytest.mark.parametrize("metric", METRICS)
+@pytest.mark.parametrize("shape", ["f16_d1024", "f32_d100", "f32_d1"])
+def test_other_storage(amd, metric, shape):
+    rng = np.random.default_rng(len(shape) + 31)
+    if shape == "f16_d1024":
+        emb = (rng.standard_normal((2000, 1024)) / 32).astype(np.float16)  # float16-native: the rows stay two bytes wide
+    elif shape == "f32_d100":
+        emb = rng.standard_normal((777, 100)).astype(np.float32)    # d % 4 != 0: no 16-byte loads
+    else:
+        emb = rng.standard_normal((300, 1)).astype(np.float32)
+    n, d = emb.shape
+    dev = amd.ei.DeviceIndex.from_host(emb)
+    ref = emb.astype(np.float32)  # the reference up-casts float16 storage
+    cuts = [0, n // 7, n // 7, n // 2, n - 1, n]
+    docs = [amd.oi.DocIndex(np.arange(a, b, dtype=np.int64), ref[a:b]) if b > a else amd.oi.DocIndex() for a, b in zip(cuts[:-1], cuts[1:])]
+    sizes = [b - a for a, b in zip(cuts[:-1], cuts[1:])]
+    scopes = [[0, 1, 2, 3, 4], [4, 2], [3, 0]]
+    qs = rng.standard_normal((len(scopes), d))
+    ptr, begin, end = csr([amd.ei.scope_segments(sizes, s) for s in scopes])
+    for k in (5, 70):
+        doc, chunk, row, dist, cnt, _ = dev.search_scoped(qs, k, metric, ptr, begin, end)
+        np.testing.assert_array_equal(chunk, row)
+        for i, s in enumerate(scopes):
+            check_against_oracle(amd.oi, metric, qs[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{shape} {metric} k={k} scope {s}")
+
+
+# ---------------------------------------------------------------- 6. device entry, and what the host entry refuses
+
+def test_device_entry_matches_host_entry_on_a_side_stream(amd):
+    import torch
+
+    rng = np.random.default_rng(12)
+    emb = unit(rng.standard_normal((5000, 384)))
+    chunk = np.arange(5000, dtype=np.int64)[::-1].copy()
+    dev = amd.ei.DeviceIndex.from_host(emb, chunk)
+    b, k = 5, 70
+    qs = rng.standard_normal((b, 384))
+    ptr, begin, end = csr([([0], [5000]), ([10, 4000], [20, 4100]), ([], []), ([77], [77]), ([4999, 0], [5000, 1])])
+    want = dev.search_scoped(qs, k, "sqeuclidean_dist", ptr, begin, end)
+    cuda = torch.device("cuda:0")
+    stream = torch.cuda.Stream(device=cuda)
+    with torch.cuda.stream(stream):
+        tq = torch.from_numpy(qs).to(cuda)
+        tptr, tb, te = (torch.from_numpy(a).to(cuda) for a in (ptr, begin, end))
+        o_doc = torch.zeros((b, k), dtype=torch.int32, device=cuda)
+        o_chunk = torch.zeros((b, k), dtype=torch.int64, device=cuda)
+        o_row = torch.zeros((b, k), dtype=torch.int64, device=cuda)
+        o_dist = torch.zeros((b, k), dtype=torch.float64, device=cuda)
+        o_cnt = torch.full((b,), -1, dtype=torch.int32, device=cuda)
+        o_flg = torch.full((b,), -1, dtype=torch.int32, device=cuda)
+        dev.search_scoped_device(tq.data_ptr(), b, k, "sqeuclidean_dist", tptr.data_ptr(), tb.data_ptr(), te.data_ptr(), o_row.data_ptr(),
+                                 o_dist.data_ptr(), o_cnt.data_ptr(), o_flg.data_ptr(), o_doc.data_ptr(), o_chunk.data_ptr(),
+                                 stream=stream.cuda_stream)
+    stream.synchronize()
+    cnt = o_cnt.cpu().numpy()
+    np.testing.assert_array_equal(cnt, want[4])
+    assert list(cnt) == [70, 70, 0, 0, 2] and (o_flg.cpu().numpy() == 0).all()
+    for got, host in zip((o_doc, o_chunk, o_row, o_dist), want[:4]):
+        g = got.cpu().numpy()
+        for i in range(b):
+            np.testing.assert_array_equal(g[i, : cnt[i]], host[i, : cnt[i]])
+
+
+def test_host_entry_refuses_malformed_scopes(amd):
+    emb = unit(np.random.default_rng(1).standard_normal((100, 8)))
+    dev = amd.ei.DeviceIndex.from_host(emb)
+    q = np.zeros((2, 8))
+    ok = dev.search_scoped(q, 3, "inner_product", [0, 1, 2], [0, 50], [50, 100])
+    assert list(ok[4]) == [3, 3]
+    bad = [
+        ([1, 1, 2], [0, 50], [50, 100]),      # scope_ptr[0] != 0
+        ([0, 2, 1], [0, 50], [50, 100]),      # decreasing scope_ptr
+        ([0, 1, 2], [-1, 50], [50, 100]),     # begin < 0
+        ([0, 1, 2], [60, 50], [50, 100]),     # end < begin
+        ([0, 1, 2], [0, 50], [50, 101]),      # end > n
+        ([0, 1, 3], [0, 50], [50, 100]),      # scope_ptr past the segment arrays
+        ([0, 1], [0], [50]),                  # not b + 1 entries
+    ]
+    for ptr, begin, end in bad:
+        with pytest.raises(ValueError):
+            dev.search_scoped(q, 3, "inner_product", ptr, begin, end)
+    # a scope of 2^32 rows or more (a segment may repeat): refused on the host, nothing is launched
+    big = amd.ei.DeviceIndex.from_host(np.zeros((70_000, 1), np.float32))
+    reps = (1 << 32) // 70_000 + 1
+    with pytest.raises(ValueError, match="2\\^32"):
+        big.search_scoped(np.zeros((1, 1)), 1, "inner_product", [0, reps], np.zeros(reps, np.int64), np.full(reps, 70_000, np.int64))
+
+
+# ---------------------------------------------------------------- 7. product surface
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_find_in_doc_member_and_foreign_document(amd, metric):
+    rng = np.random.default_rng(21)
+    sizes = [30, 0, 120, 45]
+    parts = [unit(rng.standard_normal((m, 384))) if m else np.zeros((0, 384), np.float32) for m in sizes]
+    chunks = [3 * np.arange(m, dtype=np.int64) + 1 for m in sizes]
+    mine = [amd.ei.DocIndex(c, p) if len(p) else amd.ei.DocIndex() for c, p in zip(chunks, parts)]
+    foreign = unit(rng.standard_normal((33, 384)))
+    q = rng.standard_normal(384)
+    ix = amd.ei.EmbeddingsIndex(amd.RetrievalType.TEXT, mine, metric=metric, limit=40)
+    cases = [(mine[j], amd.oi.DocIndex(chunks[j], parts[j])) for j in (0, 2, 3)]
+    cases.append((amd.ei.DocIndex(np.arange(33, dtype=np.int64), foreign), amd.oi.DocIndex(np.arange(33, dtype=np.int64), foreign)))
+    for doc, theirs in cases:
+        got_c, got_d = ix.find_in_doc(q, doc)
+        want_c, want_d = amd.oi.find_in_doc(q, theirs, metric, 40)
+        assert got_c.dtype == np.int64 and got_d.dtype == np.float64 and len(got_c) == len(want_c) == min(40, len(theirs.embeddings))
+        np.testing.assert_allclose(got_d, want_d, rtol=0, atol=dist_tol(metric))
+        if metric != "cosine_sim":
+            np.testing.assert_array_equal(got_c, want_c)
+        else:
+            alld = amd.oi.ENUM_TO_METRIC[amd.oi.Metric(metric)](q, theirs.embeddings)
+            for g, w in zip(got_c, want_c):
+                assert g == w or abs(alld[theirs.chunk_ids == g][0] - alld[theirs.chunk_ids == w][0]) <= COS_NOISE
+    c, d = ix.find_in_doc(q, mine[1])
+    assert len(c) == 0 and len(d) == 0
+
+
+def test_eight_views_of_one_corpus_share_passes(amd):
+    rng = np.random.default_rng(8)
+    sizes = rng.integers(0, 60, 40)
+    sizes[5], sizes[2], sizes[9], sizes[12] = 0, 20, 15, 30
+    parts = [unit(rng.standard_normal((m, 384))) if m else np.zeros((0, 384), np.float32) for m in sizes]
+    parts[9][0] = parts[2][1]  # a tie across documents
+    chunks = [np.arange(m, dtype=np.int64) for m in sizes]
+    mine = [amd.ei.DocIndex(c, p) if len(p) else amd.ei.DocIndex() for c, p in zip(chunks, parts)]
+    corpus = amd.ci.CorpusIndex(mine)
+    view_docs = [[9, 2], [2, 9, 5], [0, 1, 2, 3], [30], [39, 38, 37], [5], list(range(40)), [12, 12]]
+    limits = [3, 7, 7, 1, 10, 4, 7, 100]
+    queries = rng.standard_normal((8, 6, 384))
+    queries[0, 0] = queries[1, 0] = parts[2][1].astype(np.float64)
+    views = [corpus.view(s, amd.RetrievalType.TEXT, "sqeuclidean_dist", lim) for s, lim in zip(view_docs, limits)]
+    got = [[None] * 6 for _ in range(8)]
+    start = threading.Barrier(8)
+
+    def worker(i):
+        start.wait()
+        for j in range(6):
+            got[i][j] = views[i].find(queries[i, j])
+
+    threads = [threading.Thread(target=worker, args=(i,)) for i in range(8)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert corpus._commit.calls == 48 and corpus._commit.passes < corpus._commit.calls
+    for i, (s, lim) in enumerate(zip(view_docs, limits)):
+        composed = amd.ei.EmbeddingsIndex(amd.RetrievalType.TEXT, [mine[j] for j in s], limit=lim)  # today's route
+        for j in range(6):
+            assert got[i][j] == composed.find(queries[i, j]), (i, j)
+    assert [(d.metadata["doc_id"], d.metadata["chunk_id"]) for d in got[0][0][:2]] == [(0, 0), (1, 1)]
+    assert [(d.metadata["doc_id"], d.metadata["chunk_id"]) for d in got[1][0][:2]] == [(0, 1), (1, 0)]
+    # the explicit batch form gives the same rows
+    doc, chunk, _, cnt = corpus.find_many(queries[:, 0], view_docs, "sqeuclidean_dist", 7)
+    for i in range(8):
+        m = min(int(cnt[i]), limits[i])
+        want = [(d.metadata["doc_id"], d.metadata["chunk_id"]) for d in got[i][0]][:m]
+        assert [(int(a), int(b)) for a, b in zip(doc[i, :m], chunk[i, :m])] == want[:m]
