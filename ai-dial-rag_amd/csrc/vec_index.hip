@@ -367,6 +367,30 @@ struct Carver {
     }
 };
 
+// The six result arrays of a search: the caller's, or their staging in a workspace
+struct SearchOut {
+    int32_t *doc;    // [b][k]
+    int64_t *chunk;
+    int64_t *row;
+    double *dist;
+    int32_t *count;  // [b]
+    int32_t *flags;  // [b]
+};
+
+// host API staging of outputs: one contiguous [doc .. flags] span (host_round_trip copies it back whole); all null otherwise
+static SearchOut carve_out(Carver &c, int b, int k, bool host_api) {
+    if (!host_api) return SearchOut{};
+    const size_t bk = (size_t)b * k;
+    SearchOut o;
+    o.doc = c.take<int32_t>(bk);
+    o.chunk = c.take<int64_t>(bk);
+    o.row = c.take<int64_t>(bk);
+    o.dist = c.take<double>(bk);
+    o.count = c.take<int32_t>(b);
+    o.flags = c.take<int32_t>(b);
+    return o;
+}
+
 struct SearchBuffers {
     double *q;       // [b][d]      (host API only)
     uint4 *qsplit;   // [ngroups][ksteps][2][64]
@@ -392,12 +416,7 @@ struct SearchBuffers {
     float *sv_candv;        // [2][nwg][kSieveRegion]
     uint32_t *sv_ccount;    // [2][nwg]
     SieveLists sv;          // rv / row [b][kSieveQueryCap]; count / over [b] live in the zeroed control block
-    int32_t *o_doc;  // host API staging of outputs, [b][k]
-    int64_t *o_chunk;
-    int64_t *o_row;
-    double *o_dist;
-    int32_t *o_count;  // [b]
-    int32_t *o_flags;  // [b]
+    SearchOut out;          // host API staging of outputs
 };
 
 // How a search runs (plan()): `ngroups` launches of the filter scan, `qpw` queries each, on `nwg` workgroups
@@ -412,15 +431,18 @@ struct SearchPlan {
     uint32_t sample_tpw = 0;  // the sieve's threshold sample: tiles per sample workgroup
 };
 
-static size_t carve(SearchBuffers &sb, char *base, int b, int k, int d, int ksteps, const SearchPlan &pl, bool host_api, size_t i8_rows = 0) {
+// Lays a search's buffers out from `base` (null: sizes the slab only) and returns the bytes the slab needs
+static size_t carve(SearchBuffers &sb, char *base, const mir_index *ix, int b, int k, const SearchPlan &pl, bool host_api) {
     const int ngroups = pl.ngroups, nwg = pl.nwg, klist = pl.klist, qpw = pl.qpw;
+    const int d = ix->d, ksteps = std::max(ix->ksteps, ix->ks16);  // (a wide16 index's ks16 where that is larger)
+    const bool i8 = ix->i8 && pl.sieve;  // the int8 first stage may serve this call (enqueue_search)
     Carver c{base};
     sb.q = host_api ? c.take<double>((size_t)b * d) : nullptr;
-    sb.qsplit = c.take<uint4>((size_t)ngroups * (qpw / 32) * ksteps * 128);  // (ksteps: the caller passes a wide16 index's ks16 when that is larger)
+    sb.qsplit = c.take<uint4>((size_t)ngroups * (qpw / 32) * ksteps * 128);
     sb.q_sq = c.take<double>(b);
     sb.q_err = c.take<double>(b);
     sb.q_norm = c.take<double>(b);
-    sb.q_amax = c.take<float>(i8_rows ? b : 0);
+    sb.q_amax = c.take<float>(i8 ? b : 0);
     sb.qscale = c.take<float>((size_t)ngroups * std::max(128, qpw));
     sb.part = c.take<uint64_t>(pl.sieve ? 0 : (size_t)ngroups * nwg * qpw * klist);  // per-workgroup lists of the list scans (the sieve has its own regions: 33.5 MB per launch group saved)
     // one zeroed control block: gthr | nflag | arrive[b] | sieve over[b] | sieve count[b][32]  (u32 arrays padded to u64)
@@ -439,23 +461,13 @@ static size_t carve(SearchBuffers &sb, char *base, int b, int k, int d, int kste
     sb.qt = c.take<double>((size_t)((b + kXbQ - 1) / kXbQ) * xb_dpad(d) * kXbQ);
     sb.part_sample = c.take<uint64_t>(pl.sieve ? (size_t)kSampleWgs * std::max(128, qpw) * 2 : 0);  // the sieve's sample: two floats and their two rows per workgroup and query
     const size_t sv_q = pl.sieve ? (size_t)b * kSieveQueryCap : 0;
-    const size_t region = i8_rows ? (size_t)kI8Region : (size_t)kSieveRegion;  // (the int8 filter: eight wave-private parts per workgroup)
+    const size_t region = i8 ? (size_t)kI8Region : (size_t)kSieveRegion;  // (the int8 filter: eight wave-private parts per workgroup)
     sb.sv_cand = c.take<uint64_t>(pl.sieve ? (size_t)2 * nwg * region : 0);
     sb.sv_candv = c.take<float>(pl.sieve ? (size_t)2 * nwg * region : 0);
-    sb.sv_ccount = c.take<uint32_t>(pl.sieve ? (size_t)2 * nwg * (i8_rows ? 8 : 1) : 0);
+    sb.sv_ccount = c.take<uint32_t>(pl.sieve ? (size_t)2 * nwg * (i8 ? 8 : 1) : 0);
     sb.sv.rv = c.take<float>(sv_q);
     sb.sv.row = c.take<uint32_t>(sv_q);
-    if (host_api) {
-        sb.o_doc = c.take<int32_t>((size_t)b * k);
-        sb.o_chunk = c.take<int64_t>((size_t)b * k);
-        sb.o_row = c.take<int64_t>((size_t)b * k);
-        sb.o_dist = c.take<double>((size_t)b * k);
-        sb.o_count = c.take<int32_t>(b);
-        sb.o_flags = c.take<int32_t>(b);
-    } else {
-        sb.o_doc = nullptr; sb.o_chunk = nullptr; sb.o_row = nullptr; sb.o_dist = nullptr;
-        sb.o_count = nullptr; sb.o_flags = nullptr;
-    }
+    sb.out = carve_out(c, b, k, host_api);
     return c.off + 256;
 }
 
@@ -518,72 +530,138 @@ static void release_ws(mir_index *ix, Workspace *w, hipStream_t used, bool pendi
     ix->pool.push_back(w);
 }
 
+// Size, acquire, carve, run, release.  `layout(base)` carves the call's slab from `base` and returns the bytes it needs (a null
+// base: the size alone), so a call states its layout once.  `body(w, s)` enqueues on `s`: the caller's `stream` for the device
+// forms, whose workspace goes back pending on it; the workspace's own for the host forms (host_api), which have synchronised it
+// - after an error too - by the time the workspace goes back.
+template <typename Layout, typename Body>
+static int32_t with_workspace(mir_index *ix, hipStream_t stream, bool host_api, Layout layout, Body body) {
+    Workspace *w = nullptr;
+    int32_t rc = acquire_ws(ix, host_api ? nullptr : stream, layout(nullptr), &w);
+    if (rc != MIR_OK) return rc;
+    layout(static_cast<char *>(w->buf));
+    hipStream_t s = host_api ? w->stream : stream;
+    rc = body(w, s);
+    release_ws(ix, w, s, !host_api);
+    return rc;
+}
+
+// A HIP call that must succeed: sets the message and returns `on_fail` (the caller's clean-up, an expression) when it does not
+#define MIR_TRY(call, on_fail)                                                                     \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            set_error("%s failed: %s", #call, hipGetErrorString(e_));                              \
+            return on_fail;                                                                        \
+        }                                                                                          \
+    } while (0)
+
+// One array of a host form's input: where it lies in the workspace's input span, and the caller's
+struct HostPiece {
+    const void *dev;
+    const void *host;
+    size_t bytes;
+};
+
+// The host forms' round trip on the workspace's stream `s`: the `pieces` go to their places in the device span [in0, in0 + in_bytes),
+// `enqueue(out)` runs on the staging block `st` - null for each array the caller did not ask for - and the results land in `user`.
+// One pinned staging buffer per workspace: the inputs go in through it and ALL result arrays come
+// back in ONE copy of the contiguous [doc .. flags] span.  With pageable user buffers every
+// hipMemcpyAsync is a synchronous staged copy of its own (~10-15 us each, six of them on the way
+// out): on a 1k-row index they were most of a 195 us call.
+template <typename Enqueue>
+static int32_t host_round_trip(Workspace *w, hipStream_t s, const HostPiece *pieces, int npieces, void *in0, size_t in_bytes,
+                               const SearchOut &st, const SearchOut &user, int b, int k, Enqueue enqueue) {
+    auto bail = [&](int32_t code) {  // nothing of this call is in flight when the workspace goes back
+        (void)hipStreamSynchronize(s);
+        return code;
+    };
+    const size_t in_pad = (in_bytes + 255) & ~(size_t)255;
+    const char *span0 = reinterpret_cast<const char *>(st.doc);
+    const size_t span = (size_t)(reinterpret_cast<const char *>(st.flags) + (size_t)b * 4 - span0);
+    if (w->pin_cap < in_pad + span) {
+        if (w->pin) (void)hipHostFree(w->pin);
+        w->pin = nullptr;
+        w->pin_cap = 0;
+        MIR_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->pin), in_pad + span, hipHostMallocDefault), bail(MIR_ERR_HIP));
+        w->pin_cap = in_pad + span;
+    }
+    for (int i = 0; i < npieces; ++i)
+        std::memcpy(w->pin + (static_cast<const char *>(pieces[i].dev) - static_cast<const char *>(in0)), pieces[i].host, pieces[i].bytes);
+    MIR_TRY(hipMemcpyAsync(in0, w->pin, in_bytes, hipMemcpyHostToDevice, s), bail(MIR_ERR_HIP));
+    const SearchOut out{user.doc ? st.doc : nullptr, user.chunk ? st.chunk : nullptr, user.row ? st.row : nullptr,
+                        user.dist ? st.dist : nullptr, st.count, st.flags};
+    const int32_t rc = enqueue(out);
+    if (rc != MIR_OK) return bail(rc);
+    const size_t bk = (size_t)b * k;
+    char *res = w->pin + in_pad;
+    MIR_TRY(hipMemcpyAsync(res, span0, span, hipMemcpyDeviceToHost, s), bail(MIR_ERR_HIP));
+    MIR_TRY(hipStreamSynchronize(s), bail(MIR_ERR_HIP));
+    auto at = [&](const void *dev_ptr) { return res + (reinterpret_cast<const char *>(dev_ptr) - span0); };
+    if (user.doc) std::memcpy(user.doc, at(st.doc), bk * 4);
+    if (user.chunk) std::memcpy(user.chunk, at(st.chunk), bk * 8);
+    if (user.row) std::memcpy(user.row, at(st.row), bk * 8);
+    if (user.dist) std::memcpy(user.dist, at(st.dist), bk * 8);
+    std::memcpy(user.count, at(st.count), (size_t)b * 4);
+    if (user.flags) std::memcpy(user.flags, at(st.flags), (size_t)b * 4);
+    return MIR_OK;
+}
+
+// a scan's per-row term: squared norms (L2), inverse norms (cosine), nothing (inner product)
+template <int KIND>
+static const float *scan_aux(const mir_index *ix) {
+    return KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
+}
+
+// Launch of a kernel with `lds` bytes of dynamic LDS
+template <typename Kernel, typename... Args>
+static int32_t launch_dyn(Kernel kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+    MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    kern<<<grid, block, lds, stream>>>(args...);
+    MIR_HIP(hipGetLastError());
+    return MIR_OK;
+}
+
 template <int KIND>
 static int32_t launch_scan(const mir_index *ix, const uint4 *qsplit_g, int nq, int klist, int nwg,
                            uint64_t *part_g, hipStream_t stream) {
-    const float *aux = KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
+    const float *aux = scan_aux<KIND>(ix);
     const size_t lds = ((size_t)klist * 256 + 32 * (size_t)klist) * 8;
     const uint32_t n_rows = (uint32_t)ix->n;
-#define MIR_SCAN_CASE(KS)                                                                                    \
-    case KS: {                                                                                               \
-        auto kern = scan_topk_kernel<KS, KIND>;                                                              \
-        MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                    \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
-        kern<<<dim3(nwg), dim3(256), lds, stream>>>(ix->d_split, aux, qsplit_g, n_rows, ix->n_tiles, nq,     \
-                                                    klist, part_g);                                          \
-        break;                                                                                               \
-    }
+    auto go = [&](auto kern) {
+        return launch_dyn(kern, dim3(nwg), dim3(256), lds, stream, ix->d_split, aux, qsplit_g, n_rows, ix->n_tiles, nq, klist, part_g);
+    };
     switch (ix->ksteps) {
-        MIR_SCAN_CASE(1)
-        MIR_SCAN_CASE(2)
-        MIR_SCAN_CASE(4)  // (8 / 16 / 24 k-steps = d padded to 128 / 256 / 384 are layout16 indexes: launch_scan_q16)
-        default: {
-            auto kern = scan_topk_generic_kernel<KIND>;
-            MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            kern<<<dim3(nwg), dim3(256), lds, stream>>>(ix->d_split, aux, qsplit_g, ix->ksteps, n_rows,
-                                                        ix->n_tiles, nq, klist, part_g);
-            break;
-        }
+        case 1: return go(scan_topk_kernel<1, KIND>);
+        case 2: return go(scan_topk_kernel<2, KIND>);
+        case 4: return go(scan_topk_kernel<4, KIND>);  // (8 / 16 / 24 k-steps = d padded to 128 / 256 / 384 are layout16 indexes: launch_scan_q16)
+        default:
+            return launch_dyn(scan_topk_generic_kernel<KIND>, dim3(nwg), dim3(256), lds, stream, ix->d_split, aux, qsplit_g, ix->ksteps,
+                              n_rows, ix->n_tiles, nq, klist, part_g);
     }
-#undef MIR_SCAN_CASE
-    MIR_HIP(hipGetLastError());
-    return MIR_OK;
 }
 
 // float32 layout16 scan: 128 queries per launch, 16 per wave (vec_kernels_q16.h)
 template <int KIND>
 static int32_t launch_scan_q16(const mir_index *ix, const uint4 *qsplit_g, const double *q_norm_g, int nq, int klist, int nwg,
                                uint64_t *part_g, hipStream_t stream) {
-    const float *aux = KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
+    const float *aux = scan_aux<KIND>(ix);
     const int ks32 = ix->ksteps / 2;
     const size_t lds = q16_lds_bytes(ks32, klist);
     const uint32_t n_rows = (uint32_t)ix->n;
-    const int ns = q16_ring_stages(klist);
-#define MIR_Q16_LAUNCH(KS, NSV)                                                                                        \
-    do {                                                                                                               \
-        auto kern = scan_topk_q16_kernel<KS, KIND, NSV>;                                                               \
-        MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        kern<<<dim3(nwg), dim3(512), lds, stream>>>(ix->d_split, aux, qsplit_g, q_norm_g, ix->d_maxnorm, n_rows, ix->n_tiles, nq, \
-                                                    klist, part_g);                                                    \
-    } while (0)
-#define MIR_Q16_CASE(KS)                                                                                               \
-    case KS:                                                                                                           \
-        if (ns == 5) MIR_Q16_LAUNCH(KS, 5);                                                                            \
-        else MIR_Q16_LAUNCH(KS, 4);                                                                                    \
-        break;
+    const bool five = q16_ring_stages(klist) == 5;  // ring stages: 5, else 4
+    auto go = [&](auto kern) {
+        return launch_dyn(kern, dim3(nwg), dim3(512), lds, stream, ix->d_split, aux, qsplit_g, q_norm_g, ix->d_maxnorm, n_rows,
+                          ix->n_tiles, nq, klist, part_g);
+    };
     switch (ks32) {
-        MIR_Q16_CASE(4)
-        MIR_Q16_CASE(8)
-        MIR_Q16_CASE(12)
+        case 4: return five ? go(scan_topk_q16_kernel<4, KIND, 5>) : go(scan_topk_q16_kernel<4, KIND, 4>);
+        case 8: return five ? go(scan_topk_q16_kernel<8, KIND, 5>) : go(scan_topk_q16_kernel<8, KIND, 4>);
+        case 12: return five ? go(scan_topk_q16_kernel<12, KIND, 5>) : go(scan_topk_q16_kernel<12, KIND, 4>);
         default:
             set_error("internal: q16 scan has no instance for %d k-steps of 32", ks32);
             return MIR_ERR_UNSUPPORTED;
     }
-#undef MIR_Q16_CASE
-#undef MIR_Q16_LAUNCH
-    MIR_HIP(hipGetLastError());
-    return MIR_OK;
 }
 
 // the sieve's filter launch over tiles [tile0, tile0 + n_tiles) (vec_kernels_sieve.h); sample = the threshold pre-pass
@@ -592,34 +670,27 @@ static int32_t launch_sieve(const mir_index *ix, int qpw, const uint4 *qsplit_g,
                             const double *q_err_g, int nq, int nwg,
                             uint32_t tile0, uint32_t n_tiles, int nan_guard, const uint64_t *gthr_g, uint64_t *cand, float *candv,
                             uint32_t *ccount, float *part_sample, bool sample, unsigned long long *stat, hipStream_t stream) {
-    const float *aux = KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
+    const float *aux = scan_aux<KIND>(ix);
     const int ks32 = ix->ksteps / 2;
     const size_t lds = sieve_lds_bytes(ks32);
     const uint32_t n_rows = (uint32_t)ix->n;
 #define MIR_SIEVE_PICK(KS, P)                                                                                          \
     (qpw > 128 ? (sample ? sieve_q16_kernel<KS, KIND, true, 2, P> : sieve_q16_kernel<KS, KIND, false, 2, P>)           \
                : (sample ? sieve_q16_kernel<KS, KIND, true, 1, P> : sieve_q16_kernel<KS, KIND, false, 1, P>))
-#define MIR_SIEVE_CASE(KS)                                                                                             \
-    case KS: {                                                                                                         \
-        auto kern = ix->norms_spread ? MIR_SIEVE_PICK(KS, true) : MIR_SIEVE_PICK(KS, false);                           \
-        MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        kern<<<dim3(nwg), dim3(512), lds, stream>>>(ix->d_split, aux, qsplit_g, q_norm_g, q_sq_g, q_err_g, ix->d_maxnorm, n_rows, tile0, n_tiles, \
-                                                    nq, nan_guard, gthr_g, cand, candv, ccount, part_sample, stat,     \
-                                                    (uint32_t)(ks32 * 2 * 64), ix->d_tilemax); /* (a tile's hi blocks) */ \
-        break;                                                                                                         \
-    }
+    auto go = [&](auto kern) {
+        return launch_dyn(kern, dim3(nwg), dim3(512), lds, stream, ix->d_split, aux, qsplit_g, q_norm_g, q_sq_g, q_err_g, ix->d_maxnorm,
+                          n_rows, tile0, n_tiles, nq, nan_guard, gthr_g, cand, candv, ccount, part_sample, stat,
+                          (uint32_t)(ks32 * 2 * 64), ix->d_tilemax);  // (a tile's hi blocks)
+    };
     switch (ks32) {
-        MIR_SIEVE_CASE(4)
-        MIR_SIEVE_CASE(8)
-        MIR_SIEVE_CASE(12)
+        case 4: return go(ix->norms_spread ? MIR_SIEVE_PICK(4, true) : MIR_SIEVE_PICK(4, false));
+        case 8: return go(ix->norms_spread ? MIR_SIEVE_PICK(8, true) : MIR_SIEVE_PICK(8, false));
+        case 12: return go(ix->norms_spread ? MIR_SIEVE_PICK(12, true) : MIR_SIEVE_PICK(12, false));
         default:
             set_error("internal: the sieve has no instance for %d k-steps of 32", ks32);
             return MIR_ERR_UNSUPPORTED;
     }
-#undef MIR_SIEVE_CASE
 #undef MIR_SIEVE_PICK
-    MIR_HIP(hipGetLastError());
-    return MIR_OK;
 }
 
 // the int8 filter's launch over 64-row stages [stage0, stage0 + n_stages) (vec_kernels_i8.h)
@@ -640,26 +711,20 @@ static int32_t launch_sieve_i8(const mir_index *ix, int qpw, const float *q_scal
                        : (sample ? sieve_i8_kernel<KS, KIND, true, 2, 4> : sieve_i8_kernel<KS, KIND, false, 2, 4>))    \
           : (qpw > 128 ? (sample ? sieve_i8_kernel<KS, KIND, true, 2, 8> : sieve_i8_kernel<KS, KIND, false, 2, 8>)     \
                        : (sample ? sieve_i8_kernel<KS, KIND, true, 1, 8> : sieve_i8_kernel<KS, KIND, false, 1, 8>)))
-#define MIR_I8_CASE(KS)                                                                                                \
-    case KS: {                                                                                                         \
-        auto kern = MIR_I8_PICK(KS);                                                                                   \
-        MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        kern<<<dim3(grid), dim3(four ? 256 : 512), lds, stream>>>(ix->d_i8, ix->d_i8rec + (KIND == SCAN_COS ? (size_t)ix->n_stages * 72 : 0), qfrag_g, q_norm_g, q_sq_g, q_err_g, ix->d_i8stats, q_scale_g, n_rows, \
-                                                    stage0, n_stages, nq, nan_guard, gthr_g, cand, candv, ccount, part_sample, stat); \
-        break;                                                                                                         \
-    }
+    auto go = [&](auto kern) {
+        return launch_dyn(kern, dim3(grid), dim3(four ? 256 : 512), lds, stream, ix->d_i8,
+                          ix->d_i8rec + (KIND == SCAN_COS ? (size_t)ix->n_stages * 72 : 0), qfrag_g, q_norm_g, q_sq_g, q_err_g, ix->d_i8stats,
+                          q_scale_g, n_rows, stage0, n_stages, nq, nan_guard, gthr_g, cand, candv, ccount, part_sample, stat);
+    };
     switch (ix->ks64) {
-        MIR_I8_CASE(2)
-        MIR_I8_CASE(4)
-        MIR_I8_CASE(6)
+        case 2: return go(MIR_I8_PICK(2));
+        case 4: return go(MIR_I8_PICK(4));
+        case 6: return go(MIR_I8_PICK(6));
         default:
             set_error("internal: the int8 filter has no instance for %d k-steps of 64", ix->ks64);
             return MIR_ERR_UNSUPPORTED;
     }
-#undef MIR_I8_CASE
 #undef MIR_I8_PICK
-    MIR_HIP(hipGetLastError());
-    return MIR_OK;
 }
 
 // the float16-native sieve's filter launch (vec_kernels_sieve.h, sieve_h16_kernel)
@@ -669,92 +734,64 @@ static int32_t launch_sieve16(const mir_index *ix, const uint4 *qfrag_g, const f
                               int nq, int nwg, uint32_t tile0, uint32_t n_tiles, int nan_guard, const uint64_t *gthr_g, uint64_t *cand,
                               float *candv, uint32_t *ccount, float *part_sample, bool sample, unsigned long long *stat, hipStream_t stream,
                               const double *q_err_g = nullptr) {
-    const float *aux = KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
+    const float *aux = scan_aux<KIND>(ix);
     const size_t lds = sieve16_lds_bytes();
     const uint32_t n_rows = (uint32_t)ix->n;
     const uint4 *image = BF ? ix->d_hi16 : ix->d_split;
     const int ks = BF ? ix->ks16 : ix->ksteps;
-#define MIR_SIEVE16_CASE(KS)                                                                                           \
-    do {                                                                                                               \
-        auto kern = sample ? sieve_h16_kernel<KS, KIND, true, BF> : sieve_h16_kernel<KS, KIND, false, BF>;             \
-        MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        kern<<<dim3(nwg), dim3(512), lds, stream>>>(image, aux, qfrag_g, qscale_g, q_norm_g, q_sq_g, q_err_g, ix->d_maxnorm, n_rows, tile0, \
-                                                    n_tiles, nq, nan_guard, gthr_g, cand, candv, ccount, part_sample, stat); \
-    } while (0)
-    if (ks == 64) MIR_SIEVE16_CASE(32);
-    else if (ks == 32) MIR_SIEVE16_CASE(16);
-    else {
-        set_error("internal: the float16 sieve has no instance for %d k-steps", ks);
-        return MIR_ERR_UNSUPPORTED;
-    }
-#undef MIR_SIEVE16_CASE
-    MIR_HIP(hipGetLastError());
-    return MIR_OK;
+    auto go = [&](auto kern) {
+        return launch_dyn(kern, dim3(nwg), dim3(512), lds, stream, image, aux, qfrag_g, qscale_g, q_norm_g, q_sq_g, q_err_g, ix->d_maxnorm,
+                          n_rows, tile0, n_tiles, nq, nan_guard, gthr_g, cand, candv, ccount, part_sample, stat);
+    };
+    if (ks == 64) return go(sample ? sieve_h16_kernel<32, KIND, true, BF> : sieve_h16_kernel<32, KIND, false, BF>);
+    if (ks == 32) return go(sample ? sieve_h16_kernel<16, KIND, true, BF> : sieve_h16_kernel<16, KIND, false, BF>);
+    set_error("internal: the float16 sieve has no instance for %d k-steps", ks);
+    return MIR_ERR_UNSUPPORTED;
 }
 
 // float16-native scan: 128 queries per launch, 16 per wave, one float16 product per fragment (vec_kernels_h16.h)
 template <int KIND>
 static int32_t launch_scan_h16(const mir_index *ix, const uint4 *qfrag_g, const float *qscale_g, int nq, int klist, int nwg,
                                uint64_t *part_g, const uint64_t *gthr_g, hipStream_t stream) {
-    const float *aux = KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
+    const float *aux = scan_aux<KIND>(ix);
     const size_t lds = h16_lds_bytes(klist);
     const uint32_t n_rows = (uint32_t)ix->n;
     const int ns = h16_ring_stages(klist);
-#define MIR_H16_LAUNCH(KS, NSV)                                                                                        \
-    do {                                                                                                               \
-        auto kern = scan_topk_h16_kernel<KS, KIND, NSV, H16_QT>;                                                       \
-        MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        kern<<<dim3(nwg), dim3(512 / H16_QT), lds, stream>>>(ix->d_split, aux, qfrag_g, qscale_g, n_rows, 0, ix->n_tiles, nq, klist, part_g, \
-                                                    gthr_g);  /* (zeroed thresholds: see the kernel) */                \
-    } while (0)
+    auto go = [&](auto kern) {
+        return launch_dyn(kern, dim3(nwg), dim3(512 / H16_QT), lds, stream, ix->d_split, aux, qfrag_g, qscale_g, n_rows, 0, ix->n_tiles, nq,
+                          klist, part_g, gthr_g);  // (zeroed thresholds: see the kernel)
+    };
     // ksteps = 64: 512 < d <= 1024, 32 k-steps of 32 columns (128 VGPRs of query fragments per wave); 32: 256 < d <= 512
-#define MIR_H16_CASES(KS)                                                                                              \
-    switch (ns) {                                                                                                      \
-        case 4: MIR_H16_LAUNCH(KS, 4); break;                                                                          \
-        case 3: MIR_H16_LAUNCH(KS, 3); break;                                                                          \
-        default: MIR_H16_LAUNCH(KS, 2); break;                                                                         \
-    }
-    if (ix->ksteps == 64) {
-        MIR_H16_CASES(32)
-    } else if (ix->ksteps == 32) {
-        MIR_H16_CASES(16)
-    } else {
-        set_error("internal: float16 scan has no instance for %d k-steps", ix->ksteps);
-        return MIR_ERR_UNSUPPORTED;
-    }
-#undef MIR_H16_CASES
-#undef MIR_H16_LAUNCH
-    MIR_HIP(hipGetLastError());
-    return MIR_OK;
+    if (ix->ksteps == 64)
+        return ns == 4   ? go(scan_topk_h16_kernel<32, KIND, 4, H16_QT>)
+               : ns == 3 ? go(scan_topk_h16_kernel<32, KIND, 3, H16_QT>)
+                         : go(scan_topk_h16_kernel<32, KIND, 2, H16_QT>);
+    if (ix->ksteps == 32)
+        return ns == 4   ? go(scan_topk_h16_kernel<16, KIND, 4, H16_QT>)
+               : ns == 3 ? go(scan_topk_h16_kernel<16, KIND, 3, H16_QT>)
+                         : go(scan_topk_h16_kernel<16, KIND, 2, H16_QT>);
+    set_error("internal: float16 scan has no instance for %d k-steps", ix->ksteps);
+    return MIR_ERR_UNSUPPORTED;
 }
 
 // float32 rows with 384 < d <= 1024: the 64-query K-split scan over the bf16 hi/lo image
 template <int KIND>
 static int32_t launch_scan_f16(const mir_index *ix, const uint4 *qfrag_g, int nq, int klist, int nwg,
                                uint64_t *part_g, hipStream_t stream) {
-    const float *aux = KIND == SCAN_L2 ? ix->d_docsq : KIND == SCAN_COS ? ix->d_invnorm : nullptr;
+    const float *aux = scan_aux<KIND>(ix);
     const size_t lds = f16_lds_bytes(klist);
     const uint32_t n_rows = (uint32_t)ix->n;
-#define MIR_SCAN_CASE_SPLIT(KS)                                                                              \
-    case KS: {                                                                                               \
-        auto kern = scan_topk_f16_kernel<KS, KIND>;                                                          \
-        MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                                    \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
-        kern<<<dim3(nwg), dim3(512), lds, stream>>>(ix->d_split, aux, qfrag_g, n_rows, ix->n_tiles, nq,      \
-                                                    klist, part_g);                                          \
-        break;                                                                                               \
-    }
+    auto go = [&](auto kern) {
+        return launch_dyn(kern, dim3(nwg), dim3(512), lds, stream, ix->d_split, aux, qfrag_g, n_rows, ix->n_tiles, nq, klist, part_g);
+    };
     switch (ix->ksteps) {
-        MIR_SCAN_CASE_SPLIT(32)
-        MIR_SCAN_CASE_SPLIT(48)
-        MIR_SCAN_CASE_SPLIT(64)
+        case 32: return go(scan_topk_f16_kernel<32, KIND>);
+        case 48: return go(scan_topk_f16_kernel<48, KIND>);
+        case 64: return go(scan_topk_f16_kernel<64, KIND>);
         default:
             set_error("internal: wide split scan has no instance for %d k-steps", ix->ksteps);
             return MIR_ERR_UNSUPPORTED;
     }
-#undef MIR_SCAN_CASE_SPLIT
-    MIR_HIP(hipGetLastError());
-    return MIR_OK;
 }
 
 static int32_t check_search_args(const mir_index *ix, const void *queries, int32_t b, int32_t k, int32_t metric,
@@ -768,60 +805,123 @@ static int32_t check_search_args(const mir_index *ix, const void *queries, int32
     return MIR_OK;
 }
 
-// Enqueue prep + scan(s) + finalize for device-resident queries/outputs.
-static int32_t enqueue_search(mir_index *ix, const double *dq, int b, int k, int metric, const SearchBuffers &sb,
-                              const SearchPlan &pl, int32_t *o_doc, int64_t *o_chunk, int64_t *o_row,
-                              double *o_dist, int32_t *o_count, int32_t *o_flags, hipStream_t stream) {
-    const int ngroups = pl.ngroups, nwg = pl.nwg, klist = pl.klist, qpw = pl.qpw;
-    const int d = ix->d;
-    const int ntiles32 = ngroups * (qpw / 32);  // 32-query fragment tiles, padded to whole launches
-    // the sieve's thresholds + the exact pass's control words: zeroed by the first blocks of the prep kernel
-    unsigned long long *gz = reinterpret_cast<unsigned long long *>(sb.gthr);
-    const int gwords = sb.ctl_words;
-    // (blocks past the fragment and per-query blocks only zero their 64 words and return)
-    const int prep_blocks = std::max(ntiles32 * ix->ksteps + b, (gwords + 63) / 64);
-    ExactBatchArgs ea;
-    ea.docs = ix->d_orig; ea.docs16 = ix->d_f16; ea.doc_sq = ix->d_docsq; ea.dnorm = ix->d_dnorm; ea.n_rows = (uint32_t)ix->n; ea.d = d;
-    ea.metric = metric; ea.qt = sb.qt; ea.q_sq = sb.q_sq; ea.nflag = sb.nflag; ea.flagged = sb.flagged;
-    ExactArgs es;  // the serial pass's view of the same buffers (one or two flagged queries)
-    es.docs = ix->d_orig; es.docs16 = ix->d_f16; es.doc_sq = ix->d_docsq; es.n_rows = (uint32_t)ix->n; es.d = d; es.metric = metric;
-    es.q = dq; es.q_sq = sb.q_sq; es.q_norm = sb.q_norm; es.nflag = sb.nflag; es.flagged = sb.flagged;
-    auto exact_pass = [&]() {  // device-gated: exits at once when no query was flagged
-        es.k = ea.k; es.round = ea.round; es.list_stride = ea.list_stride; es.part = ea.part; es.arrive = ea.arrive;
-        es.bound_dist = ea.bound_dist; es.bound_row = ea.bound_row; es.chunk_ids = ea.chunk_ids; es.doc_ids = ea.doc_ids;
-        es.row_offset = ea.row_offset; es.out_doc = ea.out_doc; es.out_chunk = ea.out_chunk; es.out_row = ea.out_row;
-        es.out_dist = ea.out_dist; es.out_count = ea.out_count; es.out_flags = ea.out_flags;
-        const bool cosine = metric == MIR_METRIC_COSINE_SIM;
-        if (ix->native16 && cosine) exact_pass_kernel<_Float16, true><<<dim3(pl.exact_grid), dim3(kXbThreads), 0, stream>>>(ea, es);
-        else if (ix->native16) exact_pass_kernel<_Float16, false><<<dim3(pl.exact_grid), dim3(kXbThreads), 0, stream>>>(ea, es);
-        else if (cosine) exact_pass_kernel<float, true><<<dim3(pl.exact_grid), dim3(kXbThreads), 0, stream>>>(ea, es);
-        else exact_pass_kernel<float, false><<<dim3(pl.exact_grid), dim3(kXbThreads), 0, stream>>>(ea, es);
-    };
-    ea.k = k; ea.round = 0; ea.list_stride = std::min(k, kExactRound); ea.part = sb.part_exact; ea.arrive = sb.arrive;
-    ea.bound_dist = sb.bound_dist; ea.bound_row = sb.bound_row; ea.chunk_ids = ix->d_chunk; ea.doc_ids = ix->d_doc;
-    ea.row_offset = ix->row_offset; ea.out_doc = o_doc; ea.out_chunk = o_chunk; ea.out_row = o_row; ea.out_dist = o_dist;
-    ea.out_count = o_count; ea.out_flags = o_flags;
-    if (pl.exact_only) {
-        // k beyond the filter's candidate lists: no scan; every query is the reference's own computation.
-        // ceil(min(k, n) / 64) rounds, each one pass over the rows per query.
-        prep_queries_kernel<<<dim3(std::max(b, (gwords + 63) / 64)), dim3(64), 0, stream>>>(dq, b, d, ix->ksteps, 0, nullptr, sb.q_sq, sb.q_norm, gz, gwords);
-        flag_all_kernel<<<dim3(b), dim3(256), 0, stream>>>(b, sb.nflag, sb.flagged, dq, d, metric, sb.q_norm, sb.qt);
-        MIR_HIP(hipGetLastError());
-        const int64_t found = std::min<int64_t>(k, ix->n);
-        const int rounds = (int)std::max<int64_t>(1, (found + kExactRound - 1) / kExactRound);
-        for (int r = 0; r < rounds; ++r) {
-            ea.round = r;
-            exact_pass();
-            MIR_HIP(hipGetLastError());
+// One search call as its routes see it: device-resident queries `dq`, results to `out`, everything enqueued on `stream`
+struct SearchCall {
+    mir_index *ix;
+    const double *dq;
+    int b, k, metric;
+    const SearchBuffers &sb;
+    const SearchPlan &pl;
+    const SearchOut &out;
+    hipStream_t stream;
+    bool use_i8;  // the int8 first stage serves this call (enqueue_search)
+};
+
+// Event bracket around the dominant (full-shard) scan launches of a launch group, on an index that is being profiled
+// (mir_index_profile).  begin() takes two events from ix->prof_free, or creates them, and records the first; end() records the
+// second and appends the pair to ix->prof_events.  A bracket that goes away without end() - a launch inside it failed - puts
+// its events back on ix->prof_free.
+struct ProfileBracket {
+    mir_index *ix;
+    hipStream_t stream;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    ProfileBracket(mir_index *ix_, hipStream_t stream_) : ix(ix_), stream(stream_) {}
+    ProfileBracket(const ProfileBracket &) = delete;
+    ProfileBracket &operator=(const ProfileBracket &) = delete;
+    int32_t begin() {
+        if (!ix->profiling) return MIR_OK;
+        {
+            std::lock_guard<std::mutex> lk(ix->mu);
+            if (ix->prof_free.size() >= 2) {
+                ev0 = ix->prof_free.back(); ix->prof_free.pop_back();
+                ev1 = ix->prof_free.back(); ix->prof_free.pop_back();
+            }
         }
+        if (!ev0) {
+            MIR_HIP(hipEventCreate(&ev0));
+            MIR_HIP(hipEventCreate(&ev1));
+        }
+        MIR_HIP(hipEventRecord(ev0, stream));
         return MIR_OK;
     }
-    // the int8 first stage serves this call: the shard has the image, the metric ranks in the rows' own units
-    // ... and k is small: the int8 margin is 4.3 x the bf16 filter's, its lists grow with k (10M x 384: 4.2k candidates per query at k = 10,
-    // 7.5k at 20, 11k at 32 - where the first queries overflow their 16384-entry lists and take the exact pass; the bf16 filter
-    // lists 3.8k at k = 64) - beyond kI8MaxK the same index's bf16 image serves the call
-    const bool use_i8 = ix->i8 && pl.sieve && sb.q_amax != nullptr && k <= kI8MaxK;
-    if (use_i8) {
+    int32_t end() {
+        if (!ev0) return MIR_OK;
+        MIR_HIP(hipEventRecord(ev1, stream));
+        std::lock_guard<std::mutex> lk(ix->mu);
+        ix->prof_events.emplace_back(ev0, ev1);
+        ev0 = ev1 = nullptr;
+        return MIR_OK;
+    }
+    ~ProfileBracket() {
+        if (!ev0 && !ev1) return;
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (ev0) ix->prof_free.push_back(ev0);
+        if (ev1) ix->prof_free.push_back(ev1);
+    }
+};
+
+// what the batched exact pass and the serial one (one or two flagged queries) are both told about a call: A = ExactBatchArgs / ExactArgs
+template <typename A>
+static void set_exact_args(A &a, const SearchCall &c, int round) {
+    const mir_index *ix = c.ix;
+    const SearchBuffers &sb = c.sb;
+    a.docs = ix->d_orig; a.docs16 = ix->d_f16; a.doc_sq = ix->d_docsq; a.n_rows = (uint32_t)ix->n; a.d = ix->d; a.metric = c.metric;
+    a.q_sq = sb.q_sq; a.nflag = sb.nflag; a.flagged = sb.flagged;
+    a.k = c.k; a.round = round; a.list_stride = std::min(c.k, kExactRound); a.part = sb.part_exact; a.arrive = sb.arrive;
+    a.bound_dist = sb.bound_dist; a.bound_row = sb.bound_row; a.chunk_ids = ix->d_chunk; a.doc_ids = ix->d_doc;
+    a.row_offset = ix->row_offset; a.out_doc = c.out.doc; a.out_chunk = c.out.chunk; a.out_row = c.out.row; a.out_dist = c.out.dist;
+    a.out_count = c.out.count; a.out_flags = c.out.flags;
+}
+
+// Round `round` of the exact pass over the flagged queries.  Device-gated: exits at once when no query was flagged.
+static int32_t exact_pass(const SearchCall &c, int round) {
+    const mir_index *ix = c.ix;
+    ExactBatchArgs ea;
+    set_exact_args(ea, c, round);
+    ea.dnorm = ix->d_dnorm; ea.qt = c.sb.qt;
+    ExactArgs es;  // the serial pass's view of the same buffers
+    set_exact_args(es, c, round);
+    es.q = c.dq; es.q_norm = c.sb.q_norm;
+    const bool cosine = c.metric == MIR_METRIC_COSINE_SIM;
+    const dim3 grid(c.pl.exact_grid), block(kXbThreads);
+    if (ix->native16 && cosine) exact_pass_kernel<_Float16, true><<<grid, block, 0, c.stream>>>(ea, es);
+    else if (ix->native16) exact_pass_kernel<_Float16, false><<<grid, block, 0, c.stream>>>(ea, es);
+    else if (cosine) exact_pass_kernel<float, true><<<grid, block, 0, c.stream>>>(ea, es);
+    else exact_pass_kernel<float, false><<<grid, block, 0, c.stream>>>(ea, es);
+    MIR_HIP(hipGetLastError());
+    return MIR_OK;
+}
+
+// k beyond the filter's candidate lists: no scan; every query is the reference's own computation.
+// ceil(min(k, n) / 64) rounds, each one pass over the rows per query.
+static int32_t enqueue_exact_only(const SearchCall &c) {
+    const mir_index *ix = c.ix;
+    const SearchBuffers &sb = c.sb;
+    const int b = c.b, d = ix->d, gwords = sb.ctl_words;
+    prep_queries_kernel<<<dim3(std::max(b, (gwords + 63) / 64)), dim3(64), 0, c.stream>>>(
+        c.dq, b, d, ix->ksteps, 0, nullptr, sb.q_sq, sb.q_norm, reinterpret_cast<unsigned long long *>(sb.gthr), gwords);
+    flag_all_kernel<<<dim3(b), dim3(256), 0, c.stream>>>(b, sb.nflag, sb.flagged, c.dq, d, c.metric, sb.q_norm, sb.qt);
+    MIR_HIP(hipGetLastError());
+    const int64_t found = std::min<int64_t>(c.k, ix->n);
+    const int rounds = (int)std::max<int64_t>(1, (found + kExactRound - 1) / kExactRound);
+    for (int r = 0; r < rounds; ++r) {
+        int32_t rc = exact_pass(c, r);
+        if (rc != MIR_OK) return rc;
+    }
+    return MIR_OK;
+}
+
+// Query preparation: the fragment image the call's first scan reads (one of five), the per-query norms, and the control block -
+// the sieve's thresholds + the exact pass's control words - zeroed by the first blocks of the kernel
+static int32_t prep_queries(const SearchCall &c) {
+    const mir_index *ix = c.ix;
+    const SearchBuffers &sb = c.sb;
+    const hipStream_t stream = c.stream;
+    const double *dq = c.dq;
+    const int b = c.b, d = ix->d, ngroups = c.pl.ngroups, qpw = c.pl.qpw;
+    unsigned long long *gz = reinterpret_cast<unsigned long long *>(sb.gthr);
+    const int gwords = sb.ctl_words;
+    if (c.use_i8) {
         const int ntiles16 = ngroups * (qpw / 16);
         prep_queries_i8_stats_kernel<<<dim3(std::max(b, (gwords + 63) / 64)), dim3(64), 0, stream>>>(dq, b, d, sb.q_sq, sb.q_norm, sb.q_amax, gz, gwords);
         prep_queries_i8_quant_kernel<<<dim3(ntiles16 * ix->ks64 + b), dim3(64), 0, stream>>>(dq, b, d, ix->ks64, ntiles16, sb.q_amax, sb.qsplit,
@@ -830,7 +930,7 @@ static int32_t enqueue_search(mir_index *ix, const double *dq, int b, int k, int
         const int ks32 = ix->ksteps / 2, ntiles16 = ngroups * (qpw / 16);
         prep_queries16_kernel<<<dim3(std::max(ntiles16 * ks32 + b, (gwords + 63) / 64)), dim3(64), 0, stream>>>(
             dq, b, d, ks32, ntiles16, sb.qsplit, sb.q_sq, sb.q_norm, gz, gwords, sb.q_err);
-    } else if (ix->wide16 && pl.sieve) {  // bf16 hi (and lo, unread) fragments of 16 queries x 32 columns, |q - bf16(q)|
+    } else if (ix->wide16 && c.pl.sieve) {  // bf16 hi (and lo, unread) fragments of 16 queries x 32 columns, |q - bf16(q)|
         const int ks32 = ix->ks16 / 2, ntiles16 = ngroups * (kQ16Queries / 16);
         prep_queries16_kernel<<<dim3(std::max(ntiles16 * ks32 + b, (gwords + 63) / 64)), dim3(64), 0, stream>>>(
             dq, b, d, ks32, ntiles16, sb.qsplit, sb.q_sq, sb.q_norm, gz, gwords, sb.q_err);
@@ -838,170 +938,204 @@ static int32_t enqueue_search(mir_index *ix, const double *dq, int b, int k, int
         const int ks32 = ix->ksteps / 2, ntiles16 = ngroups * (kQ16Queries / 16);
         query_stats_h16_kernel<<<dim3(std::max(b, (gwords + 63) / 64)), dim3(64), 0, stream>>>(dq, b, d, sb.q_sq, sb.q_norm, sb.qscale, gz, gwords);
         prep_queries_h16_kernel<<<dim3(ntiles16 * ks32), dim3(64), 0, stream>>>(dq, b, d, ks32, sb.qscale, sb.qsplit);
-    } else
-        prep_queries_kernel<<<dim3(prep_blocks), dim3(64), 0, stream>>>(dq, b, d, ix->ksteps, ntiles32,
-                                                                                    sb.qsplit, sb.q_sq, sb.q_norm, gz, gwords);
-    MIR_HIP(hipGetLastError());
-    for (int g = 0; g < ngroups; ++g) {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        auto begin_profile = [&]() -> int32_t {  // brackets the dominant (full-shard) scan launch only
-            if (!ix->profiling) return MIR_OK;
-            {
-                std::lock_guard<std::mutex> lk(ix->mu);
-                if (ix->prof_free.size() >= 2) {
-                    ev0 = ix->prof_free.back(); ix->prof_free.pop_back();
-                    ev1 = ix->prof_free.back(); ix->prof_free.pop_back();
-                }
-            }
-            if (!ev0) {
-                MIR_HIP(hipEventCreate(&ev0));
-                MIR_HIP(hipEventCreate(&ev1));
-            }
-            MIR_HIP(hipEventRecord(ev0, stream));
-            return MIR_OK;
-        };
-        const uint4 *qs = sb.qsplit + (size_t)g * (qpw / 32) * ix->ksteps * 128;
-        uint64_t *pg = sb.part + (size_t)g * nwg * qpw * klist;
-        const int nq = std::min(qpw, b - qpw * g);
-        int32_t rc;
-        if (pl.sieve) {
-            // filter (hi blocks only) -> scatter to the queries' lists -> select (reference formula for the rows that can be among
-            // the first k): exact by construction
-            uint64_t *gt = sb.gthr + (size_t)g * std::max(128, qpw);
-            const int q0 = qpw * g;
-            const double *qn = sb.q_norm + q0, *qsq = sb.q_sq + q0, *qerr = sb.q_err + q0;
-            const int guard = metric == MIR_METRIC_EUCLIDEAN_DIST ? 1 : 0;
-            const uint4 *qs16 = sb.qsplit + (size_t)g * (kQ16Queries / 16) * (ix->ksteps / 2) * 64;  // native16: hi fragments only
-            const float *qsc = sb.qscale + (size_t)g * qpw;
-            auto sieve = [&](uint32_t t0, uint32_t nt, int wgs, uint64_t *cand, float *cv, uint32_t *cc, bool smp) {
-                float *ps = reinterpret_cast<float *>(sb.part_sample);
-                unsigned long long *st = smp ? nullptr : ix->d_stats + (t0 ? 1 : 0);
-                if (use_i8) {  // tiles -> 64-row stages: [t0 / 2, (t0 + nt + 1) / 2) (t0 is even or 0 wherever two launches meet: see below)
-                    const uint32_t s0 = t0 / 2, s1 = std::min<uint32_t>((t0 + nt + 1) / 2, ix->n_stages);
-                    const uint4 *qf = sb.qsplit + (size_t)g * (qpw / 16) * ix->ks64 * 64;
-                    return with_kind(metric, [&](auto kind) {
-                        return launch_sieve_i8<kind()>(ix, qpw, sb.qscale + q0, qf, qn, qsq, qerr, nq, wgs, s0, s1 - s0, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                    });
-                }
-                if (ix->native16)
-                    return with_kind(metric, [&](auto kind) {
-                        return launch_sieve16<kind()>(ix, qs16, qsc, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                    });
-                if (ix->wide16) {  // (fragments of group g: 8 query tiles x ks16 / 2 k-steps x (hi, lo) blocks)
-                    const uint4 *qw = sb.qsplit + (size_t)g * (kQ16Queries / 16) * (ix->ks16 / 2) * 128;
-                    return with_kind(metric, [&](auto kind) {
-                        return launch_sieve16<kind(), true>(ix, qw, nullptr, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream, qerr);
-                    });
-                }
-                return with_kind(metric, [&](auto kind) {
-                    return launch_sieve<kind()>(ix, qpw, qs, qn, qsq, qerr, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
-                });
-            };
-            SieveScatterArgs ca;
-            ca.q0 = q0; ca.nq = nq; ca.l = sb.sv;
-            SieveSelectArgs sa;
-            sa.l = sb.sv; sa.q0 = q0; sa.nq = nq; sa.k = k; sa.metric = metric; sa.d = d; sa.nan_guard = guard;
-            sa.rel_err = ix->native16 ? (float)kH16RelErr : kHiHiRelErr;
-            sa.extra_slop = ix->wide16 ? wide_accum_slop(ix->ks16 * 16) : 0.f;
-            sa.docs = ix->d_orig; sa.docs16 = ix->d_f16; sa.doc_sq = ix->d_docsq;
-            sa.dnorm = (ix->native16 || !ix->norms_spread) ? nullptr : ix->d_dnorm;
-            sa.q = dq; sa.q_sq = sb.q_sq; sa.q_norm = sb.q_norm; sa.max_norm = ix->d_maxnorm;
-            sa.q_err = ix->native16 ? nullptr : sb.q_err;
-            sa.i8_qscale = nullptr;
-            sa.i8_tparam = nullptr;
-            if (use_i8) {  // the margin of the int8 filter's values: its statistics, its query residuals and scales (i8_margin)
-                sa.max_norm = ix->d_i8stats;
-                sa.i8_qscale = sb.qscale;
-                sa.i8_tparam = ix->d_i8tp;
-                sa.dnorm = nullptr;
-            }
-            sa.gthr = reinterpret_cast<unsigned long long *>(gt);
-            sa.chunk_ids = ix->d_chunk; sa.doc_ids = ix->d_doc; sa.row_offset = ix->row_offset;
-            sa.out_doc = o_doc; sa.out_chunk = o_chunk; sa.out_row = o_row; sa.out_dist = o_dist; sa.out_count = o_count;
-            sa.out_flags = o_flags; sa.nflag = sb.nflag; sa.flagged = sb.flagged; sa.stats = ix->d_stats; sa.qt = sb.qt;
-            rc = sieve(0, (uint32_t)kSampleWgs * pl.sample_tpw, kSampleWgs, nullptr, nullptr, nullptr, true);
-            if (rc != MIR_OK) return rc;
-            if (use_i8) {  // (the int8 filter's sample records its rows: T0 from their exact values)
-                SieveSampleArgs ta;
-                ta.part = reinterpret_cast<const float *>(sb.part_sample); ta.nwg = kSampleWgs; ta.qpw = qpw; ta.k = k; ta.nq = nq;
-                ta.q0 = q0; ta.d = d; ta.metric = metric; ta.docs = ix->d_orig; ta.doc_sq = ix->d_docsq;
-                ta.q = dq; ta.q_sq = sb.q_sq; ta.q_norm = sb.q_norm; ta.gthr = reinterpret_cast<unsigned long long *>(gt);
-                sieve_sample_threshold_kernel<<<dim3(nq), dim3(256), 0, stream>>>(ta);
-            } else {
-                sample_threshold_kernel<<<dim3(nq), dim3(256), 0, stream>>>(reinterpret_cast<const float *>(sb.part_sample), kSampleWgs, qpw,
-                                                                            k, nq, reinterpret_cast<unsigned long long *>(gt));
-            }
-            MIR_HIP(hipGetLastError());
-            rc = begin_profile();
-            if (rc != MIR_OK) return rc;
-            for (int phase = pl.tiles_first ? 0 : 1; phase < 2 && rc == MIR_OK; ++phase) {  // (one launch: the final phase alone)
-                const size_t region = use_i8 ? (size_t)kI8Region : (size_t)kSieveRegion;
-                uint64_t *cand = sb.sv_cand + (size_t)phase * nwg * region;
-                float *cv = sb.sv_candv + (size_t)phase * nwg * region;
-                uint32_t *cc = sb.sv_ccount + (size_t)phase * nwg * (use_i8 ? 8 : 1);
-                rc = phase == 0 ? sieve(0, pl.tiles_first, nwg, cand, cv, cc, false)
-                                : sieve(pl.tiles_first, ix->n_tiles - pl.tiles_first, nwg, cand, cv, cc, false);
-                if (rc != MIR_OK) break;
-                if (phase == 1 && ev0) {  // the bracket: both filter launches and what runs between them
-                    MIR_HIP(hipEventRecord(ev1, stream));
-                    std::lock_guard<std::mutex> lk(ix->mu);
-                    ix->prof_events.emplace_back(ev0, ev1);
-                    ev1 = nullptr;
-                }
-                ca.cand = cand; ca.candv = cv; ca.ccount = cc;
-                if (use_i8) sieve_scatter_i8_kernel<<<dim3(nwg * 8), dim3(256), 0, stream>>>(ca);
-                else sieve_scatter_kernel<<<dim3(nwg * kSieveScatterSplit), dim3(256), 0, stream>>>(ca);
-                sa.mode = phase;
-                MIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sieve_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)sieve_select_lds_bytes()));
-                sieve_select_kernel<<<dim3(nq), dim3(kSieveSelectThreads), sieve_select_lds_bytes(), stream>>>(sa);
-                MIR_HIP(hipGetLastError());
-            }
-            if (rc != MIR_OK) return rc;
-            continue;
-        }
-        // the list scans: one launch over the whole shard (every shard with a sample to seed thresholds from is the sieve's)
-        rc = begin_profile();
-        if (rc != MIR_OK) return rc;
-        if (qpw == 32) {
-            rc = with_kind(metric, [&](auto kind) { return launch_scan<kind()>(ix, qs, nq, klist, nwg, pg, stream); });
-        } else if (ix->native16) {
-            const uint4 *qs16 = sb.qsplit + (size_t)g * (kQ16Queries / 16) * (ix->ksteps / 2) * 64;  // hi fragments only
-            const float *qsc = sb.qscale + (size_t)g * qpw;
-            rc = with_kind(metric, [&](auto kind) { return launch_scan_h16<kind()>(ix, qs16, qsc, nq, klist, nwg, pg, sb.gthr + (size_t)g * 128, stream); });
-        } else if (ix->layout16) {
-            const double *qn = sb.q_norm + (size_t)g * qpw;
-            rc = with_kind(metric, [&](auto kind) { return launch_scan_q16<kind()>(ix, qs, qn, nq, klist, nwg, pg, stream); });
-        } else {  // wide64_split(ix): plan() gives 64 queries per launch to no other index
-            rc = with_kind(metric, [&](auto kind) { return launch_scan_f16<kind()>(ix, qs, nq, klist, nwg, pg, stream); });
-        }
-        if (ev1) {
-            (void)hipEventRecord(ev1, stream);
-            std::lock_guard<std::mutex> lk(ix->mu);
-            ix->prof_events.emplace_back(ev0, ev1);
-        }
-        if (rc != MIR_OK) return rc;
+    } else {
+        const int ntiles32 = ngroups * (qpw / 32);  // 32-query fragment tiles, padded to whole launches
+        // (blocks past the fragment and per-query blocks only zero their 64 words and return)
+        const int prep_blocks = std::max(ntiles32 * ix->ksteps + b, (gwords + 63) / 64);
+        prep_queries_kernel<<<dim3(prep_blocks), dim3(64), 0, stream>>>(dq, b, d, ix->ksteps, ntiles32, sb.qsplit, sb.q_sq, sb.q_norm, gz, gwords);
     }
-    if (pl.sieve) {  // the select kernel wrote the results; queries whose buffers overflowed take the exact pass
-        exact_pass();
-        MIR_HIP(hipGetLastError());
-        return MIR_OK;
-    }
-    FinalizeArgs fa;
-    fa.part = sb.part; fa.nwg = nwg; fa.qpw = qpw; fa.klist = klist; fa.k = k; fa.b = b; fa.d = d; fa.metric = metric;
-    fa.docs = ix->d_orig; fa.docs16 = ix->d_f16; fa.doc_sq = ix->d_docsq; fa.max_norm = ix->d_maxnorm;
-    fa.scan_rel_err = ix->native16 ? kH16RelErr : scan_rel_err(d);  // the bound of the scan whose values the lists hold
-    fa.q = dq; fa.q_sq = sb.q_sq; fa.q_norm = sb.q_norm;
-    fa.chunk_ids = ix->d_chunk; fa.doc_ids = ix->d_doc; fa.row_offset = ix->row_offset;
-    fa.out_doc = o_doc; fa.out_chunk = o_chunk; fa.out_row = o_row; fa.out_dist = o_dist;
-    fa.out_count = o_count; fa.out_flags = o_flags; fa.nflag = sb.nflag; fa.flagged = sb.flagged; fa.qt = sb.qt;
-    finalize_kernel<<<dim3(b), dim3(256), 0, stream>>>(fa);
-    MIR_HIP(hipGetLastError());
-    // queries whose candidate set finalize could not prove complete: exact pass, gated on the device (it exits at
-    // once when there are none)
-    exact_pass();
     MIR_HIP(hipGetLastError());
     return MIR_OK;
+}
+
+// One launch group of the sieve, queries [q0, q0 + nq) of the batch
+struct SieveGroup {
+    int g, q0, nq;
+    int guard;       // euclidean_dist: NaN guard of the filter and the select
+    uint64_t *gthr;  // the group's thresholds
+};
+
+// One filter launch of group `sg` over tiles [t0, t0 + nt) on `wgs` workgroups, candidates to cand / cv / cc; smp = the threshold sample
+static int32_t sieve_filter(const SearchCall &c, const SieveGroup &sg, uint32_t t0, uint32_t nt, int wgs, uint64_t *cand, float *cv,
+                            uint32_t *cc, bool smp) {
+    mir_index *ix = c.ix;
+    const SearchBuffers &sb = c.sb;
+    const hipStream_t stream = c.stream;
+    const int g = sg.g, q0 = sg.q0, nq = sg.nq, guard = sg.guard, qpw = c.pl.qpw;
+    uint64_t *gt = sg.gthr;
+    const double *qn = sb.q_norm + q0, *qsq = sb.q_sq + q0, *qerr = sb.q_err + q0;
+    float *ps = reinterpret_cast<float *>(sb.part_sample);
+    unsigned long long *st = smp ? nullptr : ix->d_stats + (t0 ? 1 : 0);
+    if (c.use_i8) {  // tiles -> 64-row stages: [t0 / 2, (t0 + nt + 1) / 2) (t0 is even or 0 wherever two launches meet: plan())
+        const uint32_t s0 = t0 / 2, s1 = std::min<uint32_t>((t0 + nt + 1) / 2, ix->n_stages);
+        const uint4 *qf = sb.qsplit + (size_t)g * (qpw / 16) * ix->ks64 * 64;
+        return with_kind(c.metric, [&](auto kind) {
+            return launch_sieve_i8<kind()>(ix, qpw, sb.qscale + q0, qf, qn, qsq, qerr, nq, wgs, s0, s1 - s0, guard, gt, cand, cv, cc, ps, smp, st, stream);
+        });
+    }
+    if (ix->native16) {
+        const uint4 *qs16 = sb.qsplit + (size_t)g * (kQ16Queries / 16) * (ix->ksteps / 2) * 64;  // native16: hi fragments only
+        const float *qsc = sb.qscale + (size_t)g * qpw;
+        return with_kind(c.metric, [&](auto kind) {
+            return launch_sieve16<kind()>(ix, qs16, qsc, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
+        });
+    }
+    if (ix->wide16) {  // (fragments of group g: 8 query tiles x ks16 / 2 k-steps x (hi, lo) blocks)
+        const uint4 *qw = sb.qsplit + (size_t)g * (kQ16Queries / 16) * (ix->ks16 / 2) * 128;
+        return with_kind(c.metric, [&](auto kind) {
+            return launch_sieve16<kind(), true>(ix, qw, nullptr, qn, qsq, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream, qerr);
+        });
+    }
+    const uint4 *qs = sb.qsplit + (size_t)g * (qpw / 32) * ix->ksteps * 128;
+    return with_kind(c.metric, [&](auto kind) {
+        return launch_sieve<kind()>(ix, qpw, qs, qn, qsq, qerr, nq, wgs, t0, nt, guard, gt, cand, cv, cc, ps, smp, st, stream);
+    });
+}
+
+// what the select kernel is told about group `sg` (its `mode` is set per phase)
+static SieveSelectArgs sieve_select_args(const SearchCall &c, const SieveGroup &sg) {
+    const mir_index *ix = c.ix;
+    const SearchBuffers &sb = c.sb;
+    SieveSelectArgs sa;
+    sa.l = sb.sv; sa.q0 = sg.q0; sa.nq = sg.nq; sa.k = c.k; sa.metric = c.metric; sa.d = ix->d; sa.nan_guard = sg.guard;
+    sa.rel_err = ix->native16 ? (float)kH16RelErr : kHiHiRelErr;
+    sa.extra_slop = ix->wide16 ? wide_accum_slop(ix->ks16 * 16) : 0.f;
+    sa.docs = ix->d_orig; sa.docs16 = ix->d_f16; sa.doc_sq = ix->d_docsq;
+    sa.dnorm = (ix->native16 || !ix->norms_spread) ? nullptr : ix->d_dnorm;
+    sa.q = c.dq; sa.q_sq = sb.q_sq; sa.q_norm = sb.q_norm; sa.max_norm = ix->d_maxnorm;
+    sa.q_err = ix->native16 ? nullptr : sb.q_err;
+    sa.i8_qscale = nullptr;
+    sa.i8_tparam = nullptr;
+    if (c.use_i8) {  // the margin of the int8 filter's values: its statistics, its query residuals and scales (i8_margin)
+        sa.max_norm = ix->d_i8stats;
+        sa.i8_qscale = sb.qscale;
+        sa.i8_tparam = ix->d_i8tp;
+        sa.dnorm = nullptr;
+    }
+    sa.gthr = reinterpret_cast<unsigned long long *>(sg.gthr);
+    sa.chunk_ids = ix->d_chunk; sa.doc_ids = ix->d_doc; sa.row_offset = ix->row_offset;
+    sa.out_doc = c.out.doc; sa.out_chunk = c.out.chunk; sa.out_row = c.out.row; sa.out_dist = c.out.dist; sa.out_count = c.out.count;
+    sa.out_flags = c.out.flags; sa.nflag = sb.nflag; sa.flagged = sb.flagged; sa.stats = ix->d_stats; sa.qt = sb.qt;
+    return sa;
+}
+
+// Launch group `g` of the sieve: sample -> threshold, then per filter launch: filter (hi blocks only) -> scatter to the queries'
+// lists -> select (reference formula for the rows that can be among the first k): exact by construction
+static int32_t enqueue_sieve_group(const SearchCall &c, int g) {
+    mir_index *ix = c.ix;
+    const SearchBuffers &sb = c.sb;
+    const SearchPlan &pl = c.pl;
+    const hipStream_t stream = c.stream;
+    const int nwg = pl.nwg, qpw = pl.qpw, k = c.k;
+    SieveGroup sg;
+    sg.g = g; sg.q0 = qpw * g; sg.nq = std::min(qpw, c.b - qpw * g);
+    sg.guard = c.metric == MIR_METRIC_EUCLIDEAN_DIST ? 1 : 0;
+    sg.gthr = sb.gthr + (size_t)g * std::max(128, qpw);
+    const int nq = sg.nq;
+    unsigned long long *gt = reinterpret_cast<unsigned long long *>(sg.gthr);
+    SieveScatterArgs ca;
+    ca.q0 = sg.q0; ca.nq = nq; ca.l = sb.sv;
+    SieveSelectArgs sa = sieve_select_args(c, sg);
+    int32_t rc = sieve_filter(c, sg, 0, (uint32_t)kSampleWgs * pl.sample_tpw, kSampleWgs, nullptr, nullptr, nullptr, true);
+    if (rc != MIR_OK) return rc;
+    if (c.use_i8) {  // (the int8 filter's sample records its rows: T0 from their exact values)
+        SieveSampleArgs ta;
+        ta.part = reinterpret_cast<const float *>(sb.part_sample); ta.nwg = kSampleWgs; ta.qpw = qpw; ta.k = k; ta.nq = nq;
+        ta.q0 = sg.q0; ta.d = ix->d; ta.metric = c.metric; ta.docs = ix->d_orig; ta.doc_sq = ix->d_docsq;
+        ta.q = c.dq; ta.q_sq = sb.q_sq; ta.q_norm = sb.q_norm; ta.gthr = gt;
+        sieve_sample_threshold_kernel<<<dim3(nq), dim3(256), 0, stream>>>(ta);
+    } else {
+        sample_threshold_kernel<<<dim3(nq), dim3(256), 0, stream>>>(reinterpret_cast<const float *>(sb.part_sample), kSampleWgs, qpw, k, nq, gt);
+    }
+    MIR_HIP(hipGetLastError());
+    ProfileBracket prof(ix, stream);  // the bracket: both filter launches and what runs between them
+    rc = prof.begin();
+    if (rc != MIR_OK) return rc;
+    for (int phase = pl.tiles_first ? 0 : 1; phase < 2; ++phase) {  // (one launch: the final phase alone)
+        const size_t region = c.use_i8 ? (size_t)kI8Region : (size_t)kSieveRegion;
+        uint64_t *cand = sb.sv_cand + (size_t)phase * nwg * region;
+        float *cv = sb.sv_candv + (size_t)phase * nwg * region;
+        uint32_t *cc = sb.sv_ccount + (size_t)phase * nwg * (c.use_i8 ? 8 : 1);
+        rc = phase == 0 ? sieve_filter(c, sg, 0, pl.tiles_first, nwg, cand, cv, cc, false)
+                        : sieve_filter(c, sg, pl.tiles_first, ix->n_tiles - pl.tiles_first, nwg, cand, cv, cc, false);
+        if (rc == MIR_OK && phase == 1) rc = prof.end();
+        if (rc != MIR_OK) return rc;
+        ca.cand = cand; ca.candv = cv; ca.ccount = cc;
+        if (c.use_i8) sieve_scatter_i8_kernel<<<dim3(nwg * 8), dim3(256), 0, stream>>>(ca);
+        else sieve_scatter_kernel<<<dim3(nwg * kSieveScatterSplit), dim3(256), 0, stream>>>(ca);
+        sa.mode = phase;
+        rc = launch_dyn(sieve_select_kernel, dim3(nq), dim3(kSieveSelectThreads), sieve_select_lds_bytes(), stream, sa);
+        if (rc != MIR_OK) return rc;
+    }
+    return MIR_OK;
+}
+
+// Launch group `g` of the list scans: one launch over the whole shard (every shard with a sample to seed thresholds from is the sieve's)
+static int32_t enqueue_list_group(const SearchCall &c, int g) {
+    const mir_index *ix = c.ix;
+    const SearchBuffers &sb = c.sb;
+    const hipStream_t stream = c.stream;
+    const int nwg = c.pl.nwg, klist = c.pl.klist, qpw = c.pl.qpw, metric = c.metric;
+    const uint4 *qs = sb.qsplit + (size_t)g * (qpw / 32) * ix->ksteps * 128;
+    uint64_t *pg = sb.part + (size_t)g * nwg * qpw * klist;
+    const int nq = std::min(qpw, c.b - qpw * g);
+    ProfileBracket prof(c.ix, stream);
+    int32_t rc = prof.begin();
+    if (rc != MIR_OK) return rc;
+    if (qpw == 32) {
+        rc = with_kind(metric, [&](auto kind) { return launch_scan<kind()>(ix, qs, nq, klist, nwg, pg, stream); });
+    } else if (ix->native16) {
+        const uint4 *qs16 = sb.qsplit + (size_t)g * (kQ16Queries / 16) * (ix->ksteps / 2) * 64;  // hi fragments only
+        const float *qsc = sb.qscale + (size_t)g * qpw;
+        rc = with_kind(metric, [&](auto kind) { return launch_scan_h16<kind()>(ix, qs16, qsc, nq, klist, nwg, pg, sb.gthr + (size_t)g * 128, stream); });
+    } else if (ix->layout16) {
+        const double *qn = sb.q_norm + (size_t)g * qpw;
+        rc = with_kind(metric, [&](auto kind) { return launch_scan_q16<kind()>(ix, qs, qn, nq, klist, nwg, pg, stream); });
+    } else {  // wide64_split(ix): plan() gives 64 queries per launch to no other index
+        rc = with_kind(metric, [&](auto kind) { return launch_scan_f16<kind()>(ix, qs, nq, klist, nwg, pg, stream); });
+    }
+    if (rc != MIR_OK) return rc;
+    return prof.end();
+}
+
+// The list scans' last step: the workgroups' lists merged and re-scored into the results
+static int32_t enqueue_finalize(const SearchCall &c) {
+    const mir_index *ix = c.ix;
+    const SearchBuffers &sb = c.sb;
+    FinalizeArgs fa;
+    fa.part = sb.part; fa.nwg = c.pl.nwg; fa.qpw = c.pl.qpw; fa.klist = c.pl.klist; fa.k = c.k; fa.b = c.b; fa.d = ix->d; fa.metric = c.metric;
+    fa.docs = ix->d_orig; fa.docs16 = ix->d_f16; fa.doc_sq = ix->d_docsq; fa.max_norm = ix->d_maxnorm;
+    fa.scan_rel_err = ix->native16 ? kH16RelErr : scan_rel_err(ix->d);  // the bound of the scan whose values the lists hold
+    fa.q = c.dq; fa.q_sq = sb.q_sq; fa.q_norm = sb.q_norm;
+    fa.chunk_ids = ix->d_chunk; fa.doc_ids = ix->d_doc; fa.row_offset = ix->row_offset;
+    fa.out_doc = c.out.doc; fa.out_chunk = c.out.chunk; fa.out_row = c.out.row; fa.out_dist = c.out.dist;
+    fa.out_count = c.out.count; fa.out_flags = c.out.flags; fa.nflag = sb.nflag; fa.flagged = sb.flagged; fa.qt = sb.qt;
+    finalize_kernel<<<dim3(c.b), dim3(256), 0, c.stream>>>(fa);
+    MIR_HIP(hipGetLastError());
+    return MIR_OK;
+}
+
+// Enqueue prep + scan(s) + finalize for device-resident queries/outputs.
+static int32_t enqueue_search(mir_index *ix, const double *dq, int b, int k, int metric, const SearchBuffers &sb,
+                              const SearchPlan &pl, const SearchOut &out, hipStream_t stream) {
+    // the int8 first stage serves this call: the shard has the image, the metric ranks in the rows' own units
+    // ... and k is small: the int8 margin is 4.3 x the bf16 filter's, its lists grow with k (10M x 384: 4.2k candidates per query at k = 10,
+    // 7.5k at 20, 11k at 32 - where the first queries overflow their 16384-entry lists and take the exact pass; the bf16 filter
+    // lists 3.8k at k = 64) - beyond kI8MaxK the same index's bf16 image serves the call
+    const bool use_i8 = ix->i8 && pl.sieve && sb.q_amax != nullptr && k <= kI8MaxK;
+    const SearchCall c{ix, dq, b, k, metric, sb, pl, out, stream, use_i8};
+    if (pl.exact_only) return enqueue_exact_only(c);
+    int32_t rc = prep_queries(c);
+    for (int g = 0; g < pl.ngroups && rc == MIR_OK; ++g) rc = pl.sieve ? enqueue_sieve_group(c, g) : enqueue_list_group(c, g);
+    if (rc != MIR_OK) return rc;
+    // the sieve's select kernel wrote the results; the list scans' come from finalize
+    if (!pl.sieve) {
+        rc = enqueue_finalize(c);
+        if (rc != MIR_OK) return rc;
+    }
+    // queries whose buffers overflowed (the sieve) or whose candidate set finalize could not prove complete: exact pass, gated
+    // on the device (it exits at once when there are none)
+    return exact_pass(c, 0);
 }
 
 // How an index is searched.  Nothing but the index, b and k decides it:
@@ -1193,35 +1327,27 @@ static int32_t create_common(const RowSource &src, int64_t n, int32_t d, int32_t
         free_index(ix);
         return code;
     };
-#define MIR_TRY(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_error("%s failed: %s", #call, hipGetErrorString(e_));                              \
-            return fail(MIR_ERR_HIP);                                                              \
-        }                                                                                          \
-    } while (0)
     const size_t orig_bytes = (size_t)n * d * sizeof(float);
     // float16 rows with 256 < d <= 1024: kept as they are and scanned as 2-byte fragments, columns
     // zero-padded to 512 or 1024 (vec_kernels_h16.h); everything else goes through the float32 / bf16-split
     // layout (at d <= 256 the padding to 512 columns would scan as many bytes as that does)
     ix->native16 = dtype == MIR_DTYPE_F16 && d > 256 && d <= 1024;
     if (ix->native16) {
-        MIR_TRY(hipMalloc(reinterpret_cast<void **>(&ix->d_f16), std::max<size_t>(orig_bytes / 2, 16)));
+        MIR_TRY(hipMalloc(reinterpret_cast<void **>(&ix->d_f16), std::max<size_t>(orig_bytes / 2, 16)), fail(MIR_ERR_HIP));
         ix->hbm_bytes += orig_bytes / 2;
-        MIR_TRY(copy_rows(src, ix->d_f16, n, d, 2, stream));
+        MIR_TRY(copy_rows(src, ix->d_f16, n, d, 2, stream), fail(MIR_ERR_HIP));
     } else {
-    MIR_TRY(hipMalloc(&ix->d_orig, std::max<size_t>(orig_bytes, 16)));
+    MIR_TRY(hipMalloc(&ix->d_orig, std::max<size_t>(orig_bytes, 16)), fail(MIR_ERR_HIP));
     ix->hbm_bytes += orig_bytes;
     }
     if (ix->native16) {
     } else if (n > 0 && dtype == MIR_DTYPE_F32) {
-        MIR_TRY(copy_rows(src, ix->d_orig, n, d, 4, stream));
+        MIR_TRY(copy_rows(src, ix->d_orig, n, d, 4, stream), fail(MIR_ERR_HIP));
     } else if (n > 0) {
         // float16 input: widened exactly to float32 on the device.  Every float16 is hi + lo in
         // bfloat16 exactly (11 significant bits <= 8 + 8), so the scan is EXACT on such an index.
         void *tmp = nullptr;
-        MIR_TRY(hipMalloc(&tmp, orig_bytes / 2));
+        MIR_TRY(hipMalloc(&tmp, orig_bytes / 2), fail(MIR_ERR_HIP));
         hipError_t e1 = copy_rows(src, tmp, n, d, 2, stream);
         if (e1 == hipSuccess) {
             const int64_t total = n * (int64_t)d;
@@ -1231,29 +1357,28 @@ static int32_t create_common(const RowSource &src, int64_t n, int32_t d, int32_t
         }
         if (e1 == hipSuccess) e1 = hipStreamSynchronize(stream);
         (void)hipFree(tmp);
-        MIR_TRY(e1);
+        MIR_TRY(e1, fail(MIR_ERR_HIP));
     }
     if (src.parts && n > 0) {  // chunk ids of the blocks, doc id = the block's
-        MIR_TRY(hipMalloc(&ix->d_chunk, (size_t)n * 8));
-        MIR_TRY(hipMalloc(&ix->d_doc, (size_t)n * 4));
+        MIR_TRY(hipMalloc(&ix->d_chunk, (size_t)n * 8), fail(MIR_ERR_HIP));
+        MIR_TRY(hipMalloc(&ix->d_doc, (size_t)n * 4), fail(MIR_ERR_HIP));
         ix->hbm_bytes += (size_t)n * 12;
         const std::vector<ConcatItem> items = concat_items(src, 1, 8, 1);
         MIR_TRY(run_items(items, stream, [&](const ConcatItem *di, unsigned ni) {
             concat_kernel<uint64_t><<<dim3(ni), dim3(256), 0, stream>>>(di, reinterpret_cast<uint64_t *>(ix->d_chunk));
             fill_doc_kernel<<<dim3(ni), dim3(256), 0, stream>>>(di, ix->d_doc);
-        }));
+        }), fail(MIR_ERR_HIP));
     }
     if (chunk_ids && n > 0) {
-        MIR_TRY(hipMalloc(&ix->d_chunk, (size_t)n * 8));
-        MIR_TRY(hipMemcpyAsync(ix->d_chunk, chunk_ids, (size_t)n * 8, kind, stream));
+        MIR_TRY(hipMalloc(&ix->d_chunk, (size_t)n * 8), fail(MIR_ERR_HIP));
+        MIR_TRY(hipMemcpyAsync(ix->d_chunk, chunk_ids, (size_t)n * 8, kind, stream), fail(MIR_ERR_HIP));
         ix->hbm_bytes += (size_t)n * 8;
     }
     if (doc_ids && n > 0) {
-        MIR_TRY(hipMalloc(&ix->d_doc, (size_t)n * 4));
-        MIR_TRY(hipMemcpyAsync(ix->d_doc, doc_ids, (size_t)n * 4, kind, stream));
+        MIR_TRY(hipMalloc(&ix->d_doc, (size_t)n * 4), fail(MIR_ERR_HIP));
+        MIR_TRY(hipMemcpyAsync(ix->d_doc, doc_ids, (size_t)n * 4, kind, stream), fail(MIR_ERR_HIP));
         ix->hbm_bytes += (size_t)n * 4;
     }
-#undef MIR_TRY
     rc = build_derived(ix, stream);
     if (rc != MIR_OK) return fail(rc);
     hipError_t e = hipStreamSynchronize(stream);
@@ -1472,23 +1597,16 @@ int32_t mir_index_search_device(mir_index *idx, const double *queries_device, in
     int32_t rc = check_search_args(idx, queries_device, b, k, metric, out_count);
     if (rc != MIR_OK) return rc;
     if (b == 0) return MIR_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     rc = use_device(idx->device, nullptr);
     if (rc != MIR_OK) return rc;
     SearchPlan pl;
     rc = plan(idx, b, k, &pl);
     if (rc != MIR_OK) return rc;
     SearchBuffers sb;
-    const size_t i8_rows = (idx->i8 && pl.sieve) ? (size_t)idx->n_stages * 64 : 0;
-    const size_t need = carve(sb, nullptr, b, k, idx->d, std::max(idx->ksteps, idx->ks16), pl, false, i8_rows);
-    Workspace *w = nullptr;
-    rc = acquire_ws(idx, stream, need, &w);
-    if (rc != MIR_OK) return rc;
-    carve(sb, static_cast<char *>(w->buf), b, k, idx->d, std::max(idx->ksteps, idx->ks16), pl, false, i8_rows);
-    rc = enqueue_search(idx, queries_device, b, k, metric, sb, pl, out_doc, out_chunk, out_row,
-                        out_dist, out_count, out_flags, stream);
-    release_ws(idx, w, stream, true);
-    return rc;
+    const SearchOut out{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    return with_workspace(
+        idx, static_cast<hipStream_t>(stream_), false, [&](char *base) { return carve(sb, base, idx, b, k, pl, false); },
+        [&](Workspace *, hipStream_t s) { return enqueue_search(idx, queries_device, b, k, metric, sb, pl, out, s); });
 }
 
 int32_t mir_index_search(mir_index *idx, const double *queries_host, int32_t b, int32_t k, int32_t metric,
@@ -1503,61 +1621,16 @@ int32_t mir_index_search(mir_index *idx, const double *queries_host, int32_t b, 
     rc = plan(idx, b, k, &pl);
     if (rc != MIR_OK) return rc;
     SearchBuffers sb;
-    const size_t i8_rows = (idx->i8 && pl.sieve) ? (size_t)idx->n_stages * 64 : 0;
-    const size_t need = carve(sb, nullptr, b, k, idx->d, std::max(idx->ksteps, idx->ks16), pl, true, i8_rows);
-    Workspace *w = nullptr;
-    rc = acquire_ws(idx, nullptr, need, &w);
-    if (rc != MIR_OK) return rc;
-    carve(sb, static_cast<char *>(w->buf), b, k, idx->d, std::max(idx->ksteps, idx->ks16), pl, true, i8_rows);
-    hipStream_t s = w->stream;
-    auto bail = [&](int32_t code) {
-        (void)hipStreamSynchronize(s);
-        release_ws(idx, w, s, false);
-        return code;
-    };
-#define MIR_TRY(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_error("%s failed: %s", #call, hipGetErrorString(e_));                              \
-            return bail(MIR_ERR_HIP);                                                              \
-        }                                                                                          \
-    } while (0)
-    // One pinned staging buffer per workspace: the queries go in through it and ALL result arrays come
-    // back in ONE copy of the contiguous [o_doc .. o_flags] span.  With pageable user buffers every
-    // hipMemcpyAsync is a synchronous staged copy of its own (~10-15 us each, six of them on the way
-    // out): on a 1k-row index they were most of a 195 us call.
-    const size_t q_bytes = (size_t)b * idx->d * sizeof(double);
-    const size_t q_pad = (q_bytes + 255) & ~(size_t)255;
-    const char *span0 = reinterpret_cast<const char *>(sb.o_doc);
-    const size_t span = (size_t)(reinterpret_cast<const char *>(sb.o_flags) + (size_t)b * 4 - span0);
-    if (w->pin_cap < q_pad + span) {
-        if (w->pin) (void)hipHostFree(w->pin);
-        w->pin = nullptr;
-        w->pin_cap = 0;
-        MIR_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->pin), q_pad + span, hipHostMallocDefault));
-        w->pin_cap = q_pad + span;
-    }
-    std::memcpy(w->pin, queries_host, q_bytes);
-    MIR_TRY(hipMemcpyAsync(sb.q, w->pin, q_bytes, hipMemcpyHostToDevice, s));
-    rc = enqueue_search(idx, sb.q, b, k, metric, sb, pl, out_doc ? sb.o_doc : nullptr,
-                        out_chunk ? sb.o_chunk : nullptr, out_row ? sb.o_row : nullptr,
-                        out_dist ? sb.o_dist : nullptr, sb.o_count, sb.o_flags, s);
-    if (rc != MIR_OK) return bail(rc);
-    const size_t bk = (size_t)b * k;
-    char *res = w->pin + q_pad;
-    MIR_TRY(hipMemcpyAsync(res, span0, span, hipMemcpyDeviceToHost, s));
-    MIR_TRY(hipStreamSynchronize(s));
-    auto at = [&](const void *dev_ptr) { return res + (reinterpret_cast<const char *>(dev_ptr) - span0); };
-    if (out_doc) std::memcpy(out_doc, at(sb.o_doc), bk * 4);
-    if (out_chunk) std::memcpy(out_chunk, at(sb.o_chunk), bk * 8);
-    if (out_row) std::memcpy(out_row, at(sb.o_row), bk * 8);
-    if (out_dist) std::memcpy(out_dist, at(sb.o_dist), bk * 8);
-    std::memcpy(out_count, at(sb.o_count), (size_t)b * 4);
-    if (out_flags) std::memcpy(out_flags, at(sb.o_flags), (size_t)b * 4);
-#undef MIR_TRY
-    release_ws(idx, w, s, false);
-    return MIR_OK;
+    const SearchOut user{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    return with_workspace(
+        idx, nullptr, true, [&](char *base) { return carve(sb, base, idx, b, k, pl, true); },
+        [&](Workspace *w, hipStream_t s) {
+            const size_t q_bytes = (size_t)b * idx->d * sizeof(double);
+            const HostPiece in[] = {{sb.q, queries_host, q_bytes}};
+            return host_round_trip(w, s, in, 1, sb.q, q_bytes, sb.out, user, b, k, [&](const SearchOut &out) {
+                return enqueue_search(idx, sb.q, b, k, metric, sb, pl, out, s);
+            });
+        });
 }
 
 }  // extern "C"
@@ -1577,12 +1650,7 @@ struct ScopedBuffers {
     double *bound_dist;
     uint32_t *bound_pos;
     uint64_t *part;       // [b][P][min(k, 64)][2]
-    int32_t *o_doc;       // host API staging of outputs, [b][k]
-    int64_t *o_chunk;
-    int64_t *o_row;
-    double *o_dist;
-    int32_t *o_count;
-    int32_t *o_flags;
+    SearchOut out;        // host API staging of outputs
 };
 
 static size_t carve_scoped(ScopedBuffers &sb, char *base, int b, int k, int d, int P, size_t nseg, bool host_api) {
@@ -1598,17 +1666,7 @@ static size_t carve_scoped(ScopedBuffers &sb, char *base, int b, int k, int d, i
     sb.bound_dist = c.take<double>(b);
     sb.bound_pos = c.take<uint32_t>(b);
     sb.part = c.take<uint64_t>(P > 1 ? (size_t)b * P * std::min(k, kExactRound) * 2 : 0);
-    if (host_api) {
-        sb.o_doc = c.take<int32_t>((size_t)b * k);
-        sb.o_chunk = c.take<int64_t>((size_t)b * k);
-        sb.o_row = c.take<int64_t>((size_t)b * k);
-        sb.o_dist = c.take<double>((size_t)b * k);
-        sb.o_count = c.take<int32_t>(b);
-        sb.o_flags = c.take<int32_t>(b);
-    } else {
-        sb.o_doc = nullptr; sb.o_chunk = nullptr; sb.o_row = nullptr; sb.o_dist = nullptr;
-        sb.o_count = nullptr; sb.o_flags = nullptr;
-    }
+    sb.out = carve_out(c, b, k, host_api);
     return c.off + 256;
 }
 
@@ -1631,8 +1689,7 @@ static int32_t check_scoped_args(const mir_index *ix, const void *queries, int32
 }
 
 static int32_t enqueue_scoped(mir_index *ix, const double *dq, int b, int k, int metric, int P, const ScopedBuffers &sb,
-                              const int32_t *scope_ptr, const int64_t *seg_begin, const int64_t *seg_end, int32_t *o_doc,
-                              int64_t *o_chunk, int64_t *o_row, double *o_dist, int32_t *o_count, int32_t *o_flags,
+                              const int32_t *scope_ptr, const int64_t *seg_begin, const int64_t *seg_end, const SearchOut &out,
                               hipStream_t stream) {
     const int d = ix->d;
     // per-query norms (ngroups = 0: no fragments) + the arrival counters zeroed
@@ -1644,7 +1701,7 @@ static int32_t enqueue_scoped(mir_index *ix, const double *dq, int b, int k, int
     a.q = dq; a.q_sq = sb.q_sq; a.q_norm = sb.q_norm; a.scope_ptr = scope_ptr; a.seg_begin = seg_begin; a.seg_end = seg_end;
     a.k = k; a.list_stride = std::min(k, kExactRound); a.part = sb.part; a.arrive = reinterpret_cast<uint32_t *>(sb.arrive);
     a.bound_dist = sb.bound_dist; a.bound_pos = sb.bound_pos; a.chunk_ids = ix->d_chunk; a.row_offset = ix->row_offset;
-    a.out_doc = o_doc; a.out_chunk = o_chunk; a.out_row = o_row; a.out_dist = o_dist; a.out_count = o_count; a.out_flags = o_flags;
+    a.out_doc = out.doc; a.out_chunk = out.chunk; a.out_row = out.row; a.out_dist = out.dist; a.out_count = out.count; a.out_flags = out.flags;
     const bool qlds = d <= kScopedLdsDim;
     const size_t lds = qlds ? (size_t)d * sizeof(double) : 0;
     constexpr int kSlice = 32768;  // queries per launch (grid.y)
@@ -1674,20 +1731,16 @@ int32_t mir_index_search_scoped_device(mir_index *idx, const double *queries_dev
     int32_t rc = check_scoped_args(idx, queries_device, b, k, metric, scope_ptr_device, out_count);
     if (rc != MIR_OK) return rc;
     if (b == 0) return MIR_OK;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
     rc = use_device(idx->device, nullptr);
     if (rc != MIR_OK) return rc;
     const int P = scoped_split(idx, b, 0);
     ScopedBuffers sb;
-    const size_t need = carve_scoped(sb, nullptr, b, k, idx->d, P, 0, false);
-    Workspace *w = nullptr;
-    rc = acquire_ws(idx, stream, need, &w);
-    if (rc != MIR_OK) return rc;
-    carve_scoped(sb, static_cast<char *>(w->buf), b, k, idx->d, P, 0, false);
-    rc = enqueue_scoped(idx, queries_device, b, k, metric, P, sb, scope_ptr_device, seg_begin_device, seg_end_device, out_doc,
-                        out_chunk, out_row, out_dist, out_count, out_flags, stream);
-    release_ws(idx, w, stream, true);
-    return rc;
+    const SearchOut out{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    return with_workspace(
+        idx, static_cast<hipStream_t>(stream_), false, [&](char *base) { return carve_scoped(sb, base, b, k, idx->d, P, 0, false); },
+        [&](Workspace *, hipStream_t s) {
+            return enqueue_scoped(idx, queries_device, b, k, metric, P, sb, scope_ptr_device, seg_begin_device, seg_end_device, out, s);
+        });
 }
 
 int32_t mir_index_search_scoped(mir_index *idx, const double *queries_host, int32_t b, int32_t k, int32_t metric,
@@ -1719,64 +1772,19 @@ int32_t mir_index_search_scoped(mir_index *idx, const double *queries_host, int3
     if (rc != MIR_OK) return rc;
     const int P = scoped_split(idx, b, max_rows);
     ScopedBuffers sb;
-    const size_t need = carve_scoped(sb, nullptr, b, k, idx->d, P, nseg, true);
-    Workspace *w = nullptr;
-    rc = acquire_ws(idx, nullptr, need, &w);
-    if (rc != MIR_OK) return rc;
-    carve_scoped(sb, static_cast<char *>(w->buf), b, k, idx->d, P, nseg, true);
-    hipStream_t s = w->stream;
-    auto bail = [&](int32_t code) {
-        (void)hipStreamSynchronize(s);
-        release_ws(idx, w, s, false);
-        return code;
-    };
-#define MIR_TRY(call)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_error("%s failed: %s", #call, hipGetErrorString(e_));                              \
-            return bail(MIR_ERR_HIP);                                                              \
-        }                                                                                          \
-    } while (0)
-    // the pinned staging buffer of mir_index_search: [q | scope_ptr | seg_begin | seg_end] goes in as ONE copy of the span
-    // carved in that order, [o_doc .. o_flags] comes back as one
-    const char *in0 = reinterpret_cast<const char *>(sb.q);
-    const size_t in_pad = (sb.in_span + 255) & ~(size_t)255;
-    const char *span0 = reinterpret_cast<const char *>(sb.o_doc);
-    const size_t span = (size_t)(reinterpret_cast<const char *>(sb.o_flags) + (size_t)b * 4 - span0);
-    if (w->pin_cap < in_pad + span) {
-        if (w->pin) (void)hipHostFree(w->pin);
-        w->pin = nullptr;
-        w->pin_cap = 0;
-        MIR_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->pin), in_pad + span, hipHostMallocDefault));
-        w->pin_cap = in_pad + span;
-    }
-    auto in_at = [&](const void *dev_ptr) { return w->pin + (reinterpret_cast<const char *>(dev_ptr) - in0); };
-    std::memcpy(in_at(sb.q), queries_host, (size_t)b * idx->d * sizeof(double));
-    std::memcpy(in_at(sb.scope_ptr), scope_ptr_host, ((size_t)b + 1) * 4);
-    if (nseg) {
-        std::memcpy(in_at(sb.seg_begin), seg_begin_host, nseg * 8);
-        std::memcpy(in_at(sb.seg_end), seg_end_host, nseg * 8);
-    }
-    MIR_TRY(hipMemcpyAsync(sb.q, w->pin, sb.in_span, hipMemcpyHostToDevice, s));
-    rc = enqueue_scoped(idx, sb.q, b, k, metric, P, sb, sb.scope_ptr, sb.seg_begin, sb.seg_end, out_doc ? sb.o_doc : nullptr,
-                        out_chunk ? sb.o_chunk : nullptr, out_row ? sb.o_row : nullptr, out_dist ? sb.o_dist : nullptr,
-                        sb.o_count, sb.o_flags, s);
-    if (rc != MIR_OK) return bail(rc);
-    const size_t bk = (size_t)b * k;
-    char *res = w->pin + in_pad;
-    MIR_TRY(hipMemcpyAsync(res, span0, span, hipMemcpyDeviceToHost, s));
-    MIR_TRY(hipStreamSynchronize(s));
-    auto at = [&](const void *dev_ptr) { return res + (reinterpret_cast<const char *>(dev_ptr) - span0); };
-    if (out_doc) std::memcpy(out_doc, at(sb.o_doc), bk * 4);
-    if (out_chunk) std::memcpy(out_chunk, at(sb.o_chunk), bk * 8);
-    if (out_row) std::memcpy(out_row, at(sb.o_row), bk * 8);
-    if (out_dist) std::memcpy(out_dist, at(sb.o_dist), bk * 8);
-    std::memcpy(out_count, at(sb.o_count), (size_t)b * 4);
-    if (out_flags) std::memcpy(out_flags, at(sb.o_flags), (size_t)b * 4);
-#undef MIR_TRY
-    release_ws(idx, w, s, false);
-    return MIR_OK;
+    const SearchOut user{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    return with_workspace(
+        idx, nullptr, true, [&](char *base) { return carve_scoped(sb, base, b, k, idx->d, P, nseg, true); },
+        [&](Workspace *w, hipStream_t s) {
+            // [q | scope_ptr | seg_begin | seg_end] goes in as ONE copy of the span carved in that order
+            const HostPiece in[] = {{sb.q, queries_host, (size_t)b * idx->d * sizeof(double)},
+                                    {sb.scope_ptr, scope_ptr_host, ((size_t)b + 1) * 4},
+                                    {sb.seg_begin, seg_begin_host, nseg * 8},
+                                    {sb.seg_end, seg_end_host, nseg * 8}};
+            return host_round_trip(w, s, in, nseg ? 4 : 2, sb.q, sb.in_span, sb.out, user, b, k, [&](const SearchOut &out) {
+                return enqueue_scoped(idx, sb.q, b, k, metric, P, sb, sb.scope_ptr, sb.seg_begin, sb.seg_end, out, s);
+            });
+        });
 }
 
 }  // extern "C"
@@ -1792,40 +1800,39 @@ int32_t mir_index_metric_eval(mir_index *idx, const double *query_host, int32_t 
     if (rc != MIR_OK) return rc;
     const int d = idx->d;
     const int64_t n = idx->n;
-    // slab: q[d] | q_sq | q_norm | out[n]
-    Carver c{nullptr};
-    c.take<double>(d); c.take<double>(1); c.take<double>(1); c.take<double>(n);
-    const size_t need = c.off + 256;
-    Workspace *w = nullptr;
-    rc = acquire_ws(idx, nullptr, need, &w);
-    if (rc != MIR_OK) return rc;
-    Carver cc{static_cast<char *>(w->buf)};
-    double *dq = cc.take<double>(d);
-    double *dsq = cc.take<double>(1);
-    double *dnm = cc.take<double>(1);
-    double *dout = cc.take<double>(n);
-    hipStream_t s = w->stream;
-    hipError_t e = hipMemcpyAsync(dq, query_host, (size_t)d * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        // ngroups = 0: only the per-query norm block runs
-        prep_queries_kernel<<<dim3(1), dim3(64), 0, s>>>(dq, 1, d, idx->ksteps, 0, nullptr, dsq, dnm, nullptr, 0);
-        if (idx->native16)
-            metric_eval_kernel<_Float16><<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(idx->d_f16, idx->d_docsq, n, d,
-                                                                                            dq, dsq, dnm, metric, dout);
-        else
-            metric_eval_kernel<float><<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(idx->d_orig, idx->d_docsq, n, d, dq,
-                                                                                         dsq, dnm, metric, dout);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_host, dout, (size_t)n * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    else (void)hipStreamSynchronize(s);
-    release_ws(idx, w, s, false);
-    if (e != hipSuccess) {
-        set_error("metric_eval failed: %s", hipGetErrorString(e));
-        return MIR_ERR_HIP;
-    }
-    return MIR_OK;
+    double *dq = nullptr, *dsq = nullptr, *dnm = nullptr, *dout = nullptr;
+    return with_workspace(
+        idx, nullptr, true,
+        [&](char *base) {  // slab: q[d] | q_sq | q_norm | out[n]
+            Carver c{base};
+            dq = c.take<double>(d);
+            dsq = c.take<double>(1);
+            dnm = c.take<double>(1);
+            dout = c.take<double>(n);
+            return c.off + 256;
+        },
+        [&](Workspace *, hipStream_t s) {
+            hipError_t e = hipMemcpyAsync(dq, query_host, (size_t)d * 8, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) {
+                // ngroups = 0: only the per-query norm block runs
+                prep_queries_kernel<<<dim3(1), dim3(64), 0, s>>>(dq, 1, d, idx->ksteps, 0, nullptr, dsq, dnm, nullptr, 0);
+                if (idx->native16)
+                    metric_eval_kernel<_Float16><<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(idx->d_f16, idx->d_docsq, n, d,
+                                                                                                    dq, dsq, dnm, metric, dout);
+                else
+                    metric_eval_kernel<float><<<dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s>>>(idx->d_orig, idx->d_docsq, n, d, dq,
+                                                                                                 dsq, dnm, metric, dout);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(out_host, dout, (size_t)n * 8, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            else (void)hipStreamSynchronize(s);
+            if (e != hipSuccess) {
+                set_error("metric_eval failed: %s", hipGetErrorString(e));
+                return (int32_t)MIR_ERR_HIP;
+            }
+            return (int32_t)MIR_OK;
+        });
 }
 
 int32_t mir_metric_eval(const void *docs_host, int64_t n, int32_t d, int32_t dtype, const double *query_host,
@@ -1838,28 +1845,42 @@ int32_t mir_metric_eval(const void *docs_host, int64_t n, int32_t d, int32_t dty
     return rc;
 }
 
+// The merge entries' arguments; b = 0 merges nothing and needs no buffers
+static int32_t check_merge_args(const double *dist, const int64_t *row, const int32_t *count, int32_t s, int64_t shard_stride_bytes,
+                                int32_t b, int32_t k, const double *out_dist, const int64_t *out_row, const int32_t *out_count) {
+    MIR_REQUIRE(s >= 1 && b >= 0 && k >= 1, "bad merge shape s=%d b=%d k=%d", s, b, k);
+    MIR_REQUIRE(shard_stride_bytes >= 0 && shard_stride_bytes % 8 == 0, "shard stride must be a multiple of 8");
+    MIR_REQUIRE(b == 0 || (dist && row && count && out_dist && out_row && out_count), "NULL buffer");
+    return MIR_OK;
+}
+
+// bytes from one shard's array to the next: the caller's stride, or (0) dense [s][b][k] / [s][b] arrays
+struct MergeStrides {
+    int64_t dist, row, count;
+};
+static MergeStrides merge_strides(int64_t shard_stride_bytes, int32_t b, int32_t k) {
+    if (shard_stride_bytes) return {shard_stride_bytes, shard_stride_bytes, shard_stride_bytes};
+    return {(int64_t)b * k * 8, (int64_t)b * k * 8, (int64_t)b * 4};
+}
+
 int32_t mir_topk_merge_device(const double *dist, const int64_t *row, const int32_t *count, int32_t s,
                               int64_t shard_stride_bytes, int32_t b, int32_t k, int32_t descending_scores,
                               double *out_dist, int64_t *out_row, int32_t *out_count, int32_t device,
                               void *stream) {
-    MIR_REQUIRE(s >= 1 && b >= 0 && k >= 1, "bad merge shape s=%d b=%d k=%d", s, b, k);
-    MIR_REQUIRE(shard_stride_bytes >= 0 && shard_stride_bytes % 8 == 0, "shard stride must be a multiple of 8");
-    if (b == 0) return MIR_OK;
-    MIR_REQUIRE(dist && row && count && out_dist && out_row && out_count, "NULL buffer");
-    int32_t rc = use_device(device, nullptr);
+    int32_t rc = check_merge_args(dist, row, count, s, shard_stride_bytes, b, k, out_dist, out_row, out_count);
+    if (rc != MIR_OK || b == 0) return rc;
+    rc = use_device(device, nullptr);
     if (rc != MIR_OK) return rc;
-    const int64_t sd = shard_stride_bytes ? shard_stride_bytes : (int64_t)b * k * 8;
-    const int64_t sr = shard_stride_bytes ? shard_stride_bytes : (int64_t)b * k * 8;
-    const int64_t sc = shard_stride_bytes ? shard_stride_bytes : (int64_t)b * 4;
+    const MergeStrides st = merge_strides(shard_stride_bytes, b, k);
     const int64_t nk = (int64_t)s * k;
     if (nk <= kMergeLds)
         merge_topk_kernel<<<dim3(b), dim3(nk <= 64 ? 64 : nk <= 128 ? 128 : 256), 0, static_cast<hipStream_t>(stream)>>>(
             reinterpret_cast<const char *>(dist), reinterpret_cast<const char *>(row),
-            reinterpret_cast<const char *>(count), s, sd, sr, sc, b, k, descending_scores, out_dist, out_row, out_count);
+            reinterpret_cast<const char *>(count), s, st.dist, st.row, st.count, b, k, descending_scores, out_dist, out_row, out_count);
     else
         merge_topk_global_kernel<<<dim3(b), dim3(64), 0, static_cast<hipStream_t>(stream)>>>(
             reinterpret_cast<const char *>(dist), reinterpret_cast<const char *>(row),
-            reinterpret_cast<const char *>(count), s, sd, sr, sc, b, k, descending_scores, out_dist, out_row, out_count);
+            reinterpret_cast<const char *>(count), s, st.dist, st.row, st.count, b, k, descending_scores, out_dist, out_row, out_count);
     MIR_HIP(hipGetLastError());
     return MIR_OK;
 }
@@ -1867,13 +1888,9 @@ int32_t mir_topk_merge_device(const double *dist, const int64_t *row, const int3
 int32_t mir_topk_merge_host(const double *dist, const int64_t *row, const int32_t *count, int32_t s,
                             int64_t shard_stride_bytes, int32_t b, int32_t k, int32_t descending_scores,
                             double *out_dist, int64_t *out_row, int32_t *out_count) {
-    MIR_REQUIRE(s >= 1 && b >= 0 && k >= 1, "bad merge shape s=%d b=%d k=%d", s, b, k);
-    MIR_REQUIRE(shard_stride_bytes >= 0 && shard_stride_bytes % 8 == 0, "shard stride must be a multiple of 8");
-    if (b == 0) return MIR_OK;
-    MIR_REQUIRE(dist && row && count && out_dist && out_row && out_count, "NULL buffer");
-    const int64_t sd = shard_stride_bytes ? shard_stride_bytes : (int64_t)b * k * 8;
-    const int64_t sr = shard_stride_bytes ? shard_stride_bytes : (int64_t)b * k * 8;
-    const int64_t sc = shard_stride_bytes ? shard_stride_bytes : (int64_t)b * 4;
+    const int32_t rc = check_merge_args(dist, row, count, s, shard_stride_bytes, b, k, out_dist, out_row, out_count);
+    if (rc != MIR_OK || b == 0) return rc;
+    const MergeStrides st = merge_strides(shard_stride_bytes, b, k);
     struct Item {
         double d;
         int64_t r;
@@ -1882,10 +1899,10 @@ int32_t mir_topk_merge_host(const double *dist, const int64_t *row, const int32_
     for (int q = 0; q < b; ++q) {
         items.clear();
         for (int sh = 0; sh < s; ++sh) {
-            const int c = reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(count) + sh * sc)[q];
+            const int c = reinterpret_cast<const int32_t *>(reinterpret_cast<const char *>(count) + sh * st.count)[q];
             MIR_REQUIRE(c >= 0 && c <= k, "count[%d][%d]=%d out of range", sh, q, c);
-            const double *dp = reinterpret_cast<const double *>(reinterpret_cast<const char *>(dist) + sh * sd);
-            const int64_t *rp = reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(row) + sh * sr);
+            const double *dp = reinterpret_cast<const double *>(reinterpret_cast<const char *>(dist) + sh * st.dist);
+            const int64_t *rp = reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(row) + sh * st.row);
             for (int p = 0; p < c; ++p) items.push_back({dp[(size_t)q * k + p], rp[(size_t)q * k + p]});
         }
         if (!descending_scores) {

@@ -714,3 +714,78 @@ def test_float32_wide_dims_k_split_scan(amd, metric, d, n):
         wrows, _, alld = oracle_flat_with_copies(oi, qs[i], docs, metric, 40, copies)
         alld = alld if metric == "cosine_sim" else None
         assert_same_ids(metric, rows40[i], wrows, (lambda r: alld[r]) if alld is not None else None, f"{metric} d={d} k=40 q={i}")
+
+
+# ---------------------------------------------------------------- one handle, many differently laid-out calls
+
+def test_host_forms_share_a_workspace_pool(amd):
+    """Host-form calls of different layouts on ONE handle - its workspace slab and pinned staging buffer are reused,
+    regrown and carved anew from call to call - answer exactly as a freshly built index (empty pool) does, and leave
+    alone the outputs the caller did not ask for.  Arrays are compared bit for bit over what the C ABI defines: the
+    first count[q] entries of row q (miretr.h: the rest of a row is not written)."""
+    nat, ei = amd.nat, amd.ei
+    rng = np.random.default_rng(20250)
+    n, d = 2000, 48
+    emb = (unit(rng.standard_normal((n, d))) * (1.0 + 0.01 * rng.standard_normal((n, 1)))).astype(np.float32)
+    chunk_ids = rng.permutation(n).astype(np.int64) + 7
+
+    def build():
+        return ei.DeviceIndex.from_host(emb, chunk_ids=chunk_ids)
+
+    def scopes(b):  # three segments per query, ragged, one of them empty
+        begin = rng.integers(0, n - 60, size=(b, 3))
+        length = rng.integers(1, 50, size=(b, 3))
+        length[np.arange(b), rng.integers(0, 3, size=b)] = 0
+        return np.arange(b + 1, dtype=np.int32) * 3, begin.reshape(-1).astype(np.int64), (begin + length).reshape(-1).astype(np.int64)
+
+    def q(b):
+        return rng.standard_normal((b, d))
+
+    calls = [
+        ("search", (q(1), 1, "sqeuclidean_dist")),
+        ("search_scoped", (q(40), 70, "cosine_sim") + scopes(40)),
+        ("search", (q(33), 100, "inner_product")),  # k beyond the lists: the exact pass, and a larger pinned buffer
+        ("metric_eval", (q(1), "euclidean_dist")),
+        ("search_scoped", (q(1), 1, "sqeuclidean_dist") + scopes(1)),
+        ("search", (q(1), 10, "cosine_sim")),
+    ]
+
+    def defined(res):  # bytes of the entries the ABI defines
+        if isinstance(res, np.ndarray):
+            return [res.tobytes()]
+        cnt = res[4]
+        keep = np.arange(res[0].shape[1])[None, :] < cnt[:, None]
+        return [np.where(keep, a, a.dtype.type(0)).tobytes() for a in res[:4]] + [cnt.tobytes(), res[5].tobytes()]
+
+    used = build()
+    got = []
+    for name, args in calls:
+        got.append(getattr(used, name)(*args))
+        fresh = build()
+        want = getattr(fresh, name)(*args)
+        fresh.close()
+        assert defined(got[-1]) == defined(want), f"{name} on a used handle differs from a fresh one"
+    assert (got[1][4] < 70).any() and (got[1][4] > 0).all() and (got[2][5] == nat.FLAG_EXACT_PASS).all()
+
+    # out_doc, out_chunk, out_dist, out_flags absent: rows and counts as in the full call, nothing else written
+    guard, row_fill, cnt_fill = 64, -0x0123456789ABCDEF, 0x5A5A5A5A
+    for ci in (1, 2):
+        name, args = calls[ci]
+        qs, k, metric = nat.as_f64_queries(args[0], d), args[1], nat.METRIC_CODES[args[2]]
+        b = qs.shape[0]
+        row_buf = np.full(guard + b * k + guard, row_fill, np.int64)
+        cnt_buf = np.full(guard + b + guard, cnt_fill, np.int32)
+        row, cnt = row_buf[guard:guard + b * k].reshape(b, k), cnt_buf[guard:guard + b]
+        if name == "search":
+            rc = nat.lib.mir_index_search(used.handle, nat.ptr(qs), b, k, metric, None, None, row.ctypes.data, None, cnt.ctypes.data, None)
+        else:
+            sp, s0, s1 = args[3:]
+            rc = nat.lib.mir_index_search_scoped(used.handle, nat.ptr(qs), b, k, metric, nat.ptr(sp), nat.ptr(s0), nat.ptr(s1), None, None,
+                                                 row.ctypes.data, None, cnt.ctypes.data, None)
+        nat.check(rc)
+        np.testing.assert_array_equal(cnt, got[ci][4])
+        keep = np.arange(k)[None, :] < cnt[:, None]
+        np.testing.assert_array_equal(np.where(keep, row, 0), np.where(keep, got[ci][2], 0))
+        for buf, m, fill in ((row_buf, b * k, row_fill), (cnt_buf, b, cnt_fill)):  # the caller's memory before and after each array
+            assert (buf[:guard] == fill).all() and (buf[guard + m:] == fill).all(), name
+    used.close()
