@@ -18,7 +18,7 @@ METRIC_CODES = {"cosine_sim": 0, "euclidean_dist": 1, "sqeuclidean_dist": 2, "in
 DTYPE_F32, DTYPE_F16 = 0, 1
 FLAG_UNCERTAIN = 1  # never returned since ABI 2
 FLAG_EXACT_PASS = 2  # the query was answered by the exact pass (exact_topk_kernel)
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class NativeLibraryMissing(ImportError):
@@ -95,6 +95,13 @@ def _load():
         "mir_bm25_search": ([vp, vp, vp, i32, i32, vp, vp, vp], i32),
         "mir_bm25_workspace_bytes": ([vp, i32, i32], i64),
         "mir_bm25_search_device": ([vp, vp, vp, i32, i32, vp, vp, vp, vp, vp], i32),
+        "mir_bm25_create_corpus": ([vp, vp, i64, i32, C.c_double, C.c_double, C.c_double, i32, vp], i32),
+        "mir_bm25_scope_create": ([vp, vp, vp, i32, vp], i32),
+        "mir_bm25_scope_destroy": ([vp], i32),
+        "mir_bm25_scope_info": ([vp, vp, vp, vp, vp, vp, vp], i32),
+        "mir_bm25_scope_idf": ([vp, vp], i32),
+        "mir_bm25_scores_scoped": ([vp, vp, vp, i32, vp], i32),
+        "mir_bm25_search_scoped": ([vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp], i32),
         "mir_encoder_create": ([i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp], i32),
         "mir_encoder_destroy": ([vp], i32),
         "mir_encoder_info": ([vp, vp, vp, vp], i32),

@@ -31,6 +31,8 @@
 //                       flags the queries short of k positive documents
 //   bm25_tile_kernel    the exact dense pass (all 8192 documents of a tile, zeros and negatives included) for the flagged
 //                       queries, whose last tile merges them; also get_scores
+// Scoped BM25 - every query ranks its own document segments of one model, with that request's idf and avgdl - has its
+// own kernels in bm25_scoped.h and its entries at the end of this file.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1189,22 +1191,21 @@ __device__ __forceinline__ void bm25_wave_insert(double ns, int64_t ni, int kk, 
     else if (lane == pos) { my_s = ns; my_i = ni; }
     cnt = cnt < kk ? cnt + 1 : kk;
 }
-__global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const double *__restrict__ scores, int64_t n_docs, int k, int round,
-                                                                     int64_t doc_offset, int q0, double *__restrict__ bound_s,
-                                                                     int64_t *__restrict__ bound_i, int64_t *__restrict__ out_idx,
-                                                                     double *__restrict__ out_score, int32_t *__restrict__ out_count) {
+// One query's round: `sc[n_docs]` its dense scores, `bound_s` / `bound_i` its slot of the rounds' bounds, emit(slot in the
+// query's result row, score, index) on the owning thread.  false: nothing left for this round (uniform).
+template <typename EmitF>
+__device__ __forceinline__ bool bm25_dense_topk_body(const double *__restrict__ sc, int64_t n_docs, int k, int round, double *__restrict__ bound_s,
+                                                     int64_t *__restrict__ bound_i, EmitF emit) {
     __shared__ double s_s[kDkThreads];
     __shared__ int64_t s_i[kDkThreads];
     __shared__ int s_c[kDkWaves];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ql = blockIdx.x, q = q0 + ql;
-    const double *sc = scores + (size_t)ql * n_docs;
     const int64_t found = k < n_docs ? k : n_docs;
     const int kk = (int)((found - (int64_t)kDkRound * round) < kDkRound ? (found - (int64_t)kDkRound * round) : kDkRound);
-    if (kk <= 0) return;
+    if (kk <= 0) return false;
     const bool bounded = round > 0;
-    const double b_s = bounded ? bound_s[ql] : 0.0;
-    const int64_t b_i = bounded ? bound_i[ql] : 0;
+    const double b_s = bounded ? *bound_s : 0.0;
+    const int64_t b_i = bounded ? *bound_i : 0;
     double my_s = 0.0;
     int64_t my_i = 0;
     int cnt = 0;
@@ -1238,15 +1239,26 @@ __global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const doubl
     }
     const int kout = total < kk ? total : kk;
     if (valid && rank < kout) {
-        const size_t o = (size_t)q * k + (size_t)kDkRound * round + rank;
-        out_score[o] = my_s;
-        out_idx[o] = doc_offset + my_i;
-        if (rank == kout - 1) { bound_s[ql] = my_s; bound_i[ql] = my_i; }
+        emit((size_t)kDkRound * round + rank, my_s, my_i);
+        if (rank == kout - 1) { *bound_s = my_s; *bound_i = my_i; }
     }
-    if (tid == 0 && round == 0) out_count[q] = (int)found;
+    return true;
+}
+__global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const double *__restrict__ scores, int64_t n_docs, int k, int round,
+                                                                     int64_t doc_offset, int q0, double *__restrict__ bound_s,
+                                                                     int64_t *__restrict__ bound_i, int64_t *__restrict__ out_idx,
+                                                                     double *__restrict__ out_score, int32_t *__restrict__ out_count) {
+    const int ql = blockIdx.x, q = q0 + ql;
+    const bool ran = bm25_dense_topk_body(scores + (size_t)ql * n_docs, n_docs, k, round, bound_s + ql, bound_i + ql, [&](size_t slot, double s, int64_t i) {
+        out_score[(size_t)q * k + slot] = s;
+        out_idx[(size_t)q * k + slot] = doc_offset + i;
+    });
+    if (ran && threadIdx.x == 0 && round == 0) out_count[q] = (int)(k < n_docs ? k : n_docs);
 }
 
 }  // namespace mir
+
+#include "bm25_scoped.h"
 
 using namespace mir;
 
@@ -1267,6 +1279,9 @@ struct mir_bm25 {
     double *idf = nullptr;
     int32_t *p_tf = nullptr;      // term frequency per posting and tokens per document: what the weights derive from
     int32_t *d_doclen = nullptr;  // (mir_bm25_set_global_stats re-derives them for a sharded corpus's global avgdl)
+    int32_t *d_tokens = nullptr;  // mir_bm25_create_corpus only: the token stream (text order) and indptr, what a scope's
+    int64_t *d_indptr = nullptr;  // first-appearance order is read from (bm25_scoped.h)
+    std::vector<int64_t> h_indptr;  // the same indptr on the host, rebased to 0: a scope's token counts
     double k1 = 1.5, b = 0.75, epsilon = 0.25;
     int64_t total_tokens = 0;
     std::vector<int64_t> h_df, h_first;  // per term: documents containing it, position of its first token (INT64_MAX = absent)
@@ -1278,6 +1293,20 @@ struct mir_bm25 {
     size_t pin_cap = 0;
     hipStream_t stream = nullptr;
     int qc_pin = 0;  // mir_bm25_tune: queries per workgroup of the fast pass (0 = chosen per call)
+};
+
+// A scope of a corpus model (mir_bm25_scope_create): immutable once built, shared by any number of searches.
+struct mir_bm25_scope {
+    mir_bm25 *model = nullptr;  // compared, never dereferenced after creation: the scope may outlive its model
+    int device = 0;
+    int32_t n_seg = 0, n_terms = 0;
+    int64_t n_pos = 0, total_tokens = 0;  // L chunks (N of the scope's corpus), their tokens
+    double avgdl = 0.0, average_idf = 0.0;
+    std::vector<double> h_idf;
+    int32_t *seg_begin = nullptr;  // [n_seg] in HBM, clamped
+    int64_t *seg_pos = nullptr;    // [n_seg + 1] prefix of the segments' lengths
+    double *idf = nullptr;         // [vocab]
+    int64_t hbm_bytes = 0;
 };
 
 namespace mir {
@@ -1292,6 +1321,8 @@ static void free_bm25(mir_bm25 *h) {
     (void)hipFree(h->idf);
     (void)hipFree(h->p_tf);
     (void)hipFree(h->d_doclen);
+    (void)hipFree(h->d_tokens);
+    (void)hipFree(h->d_indptr);
     (void)hipFree(h->scratch);
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1353,9 +1384,9 @@ int32_t mir_bm25_idf_from_stats(const int64_t *df, const int64_t *first_pos, int
 // idf[vocab] and `avgdl_override` the average length (global statistics of a
 // sharded corpus); otherwise both are derived from these documents exactly as
 // BM25Okapi.__init__ does.
-int32_t mir_bm25_create(const int64_t *indptr, const int32_t *term_ids, int64_t n_docs, int32_t vocab, double k1,
-                        double b, double epsilon, const double *idf_override, double avgdl_override,
-                        int32_t device, int64_t doc_offset, mir_bm25 **out) {
+static int32_t bm25_create_impl(const int64_t *indptr, const int32_t *term_ids, int64_t n_docs, int32_t vocab, double k1,
+                                double b, double epsilon, const double *idf_override, double avgdl_override,
+                                int32_t device, int64_t doc_offset, bool keep_stream, mir_bm25 **out) {
     MIR_REQUIRE(out != nullptr, "out is NULL");
     *out = nullptr;
     MIR_REQUIRE(n_docs >= 0 && n_docs < ((int64_t)1 << 31), "n_docs=%lld out of range", (long long)n_docs);
@@ -1381,7 +1412,8 @@ int32_t mir_bm25_create(const int64_t *indptr, const int32_t *term_ids, int64_t 
 
     // ---- postings, weights, per-term and per-tile offsets: built on the device (bm25_build.hip) ----
     Bm25Built built;
-    rc = bm25_build_device(indptr, term_ids, n_docs, vocab, k1, b, h->avgdl, kBm25Tile, &built);
+    rc = bm25_build_device(indptr, term_ids, n_docs, vocab, k1, b, h->avgdl, kBm25Tile, &built, keep_stream);
+    h->d_tokens = built.tokens; h->d_indptr = built.indptr;
     h->p_doc = built.p_doc; h->p_w = built.p_w; h->t_ptr = built.t_ptr; h->t_tile = built.t_tile;  // freed with h
     h->p_tf = built.p_tf; h->d_doclen = built.doc_len; h->k1 = k1; h->b = b; h->epsilon = epsilon; h->total_tokens = total;
     h->n_postings = built.n_postings; h->ntiles = std::max(1, built.ntiles); h->hbm_bytes += built.hbm_bytes;
@@ -1429,8 +1461,24 @@ int32_t mir_bm25_create(const int64_t *indptr, const int32_t *term_ids, int64_t 
     MIR_TRY(up((void **)&h->idf, h->h_idf.data(), (size_t)vocab * 8));
     MIR_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
 #undef MIR_TRY
+    if (keep_stream) {
+        h->h_indptr.resize((size_t)n_docs + 1);
+        for (int64_t i = 0; i <= n_docs; ++i) h->h_indptr[i] = indptr[i] - indptr[0];
+    }
     *out = h;
     return MIR_OK;
+}
+
+int32_t mir_bm25_create(const int64_t *indptr, const int32_t *term_ids, int64_t n_docs, int32_t vocab, double k1,
+                        double b, double epsilon, const double *idf_override, double avgdl_override,
+                        int32_t device, int64_t doc_offset, mir_bm25 **out) {
+    return bm25_create_impl(indptr, term_ids, n_docs, vocab, k1, b, epsilon, idf_override, avgdl_override, device, doc_offset, false, out);
+}
+
+// The same model, which also keeps its token stream and indptr in HBM: what the scope entries below need.
+int32_t mir_bm25_create_corpus(const int64_t *indptr, const int32_t *term_ids, int64_t n_docs, int32_t vocab, double k1,
+                               double b, double epsilon, int32_t device, mir_bm25 **out) {
+    return bm25_create_impl(indptr, term_ids, n_docs, vocab, k1, b, epsilon, nullptr, 0.0, device, 0, true, out);
 }
 
 // Host utility for callers that keep term ids in a vocabulary LARGER than one corpus (a process-wide one):
@@ -1718,6 +1766,249 @@ int32_t mir_bm25_search_device(mir_bm25 *h, const int32_t *q_terms_device, const
     if (rc != MIR_OK) return rc;
     return bm25_run(h, q_terms_device, q_ptr_device, b, k, nullptr, out_idx, out_score, out_count, workspace,
                     static_cast<hipStream_t>(stream));
+}
+
+
+// ---- scoped BM25 (bm25_scoped.h): one resident corpus model, every query ranks its own document segments ----------
+
+static void free_scope(mir_bm25_scope *sc) {
+    if (!sc) return;
+    (void)hipSetDevice(sc->device);
+    (void)hipFree(sc->seg_begin);
+    (void)hipFree(sc->seg_pos);
+    (void)hipFree(sc->idf);
+    delete sc;
+}
+
+static Bm25ScopedModel scoped_view(const mir_bm25 *h) {
+    Bm25ScopedModel m;
+    m.p_doc = h->p_doc; m.p_tf = h->p_tf; m.doc_len = h->d_doclen; m.t_ptr = h->t_ptr; m.vocab = h->vocab; m.k1 = h->k1; m.b = h->b;
+    return m;
+}
+
+#define MIR_REQUIRE_CORPUS(h)                                                                                              \
+    MIR_REQUIRE((h)->d_tokens != nullptr, "this model keeps no token stream: scopes need a model from mir_bm25_create_corpus")
+
+int32_t mir_bm25_scope_create(mir_bm25 *h, const int64_t *seg_begin, const int64_t *seg_end, int32_t n_seg, mir_bm25_scope **out) {
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    MIR_REQUIRE(h != nullptr, "handle is NULL");
+    MIR_REQUIRE_CORPUS(h);
+    MIR_REQUIRE(n_seg >= 0 && (n_seg == 0 || (seg_begin && seg_end)), "bad segment arrays (n_seg=%d)", n_seg);
+    // host check first: nothing is launched for a malformed scope
+    std::vector<int32_t> begin((size_t)n_seg);
+    std::vector<int64_t> pos((size_t)n_seg + 1, 0), tok((size_t)n_seg + 1, 0);
+    for (int32_t s = 0; s < n_seg; ++s) {
+        MIR_REQUIRE(seg_begin[s] >= 0 && seg_begin[s] <= h->n_docs && seg_end[s] >= 0 && seg_end[s] <= h->n_docs,
+                    "segment %d = [%lld, %lld) outside [0, %lld]", s, (long long)seg_begin[s], (long long)seg_end[s], (long long)h->n_docs);
+        const int64_t a = seg_begin[s], e = std::max(seg_end[s], a);  // end < begin: empty (it keeps its ordinal)
+        begin[s] = (int32_t)a;
+        pos[s + 1] = pos[s] + (e - a);
+        tok[s + 1] = tok[s] + (h->h_indptr[e] - h->h_indptr[a]);
+    }
+    const int64_t L = pos[n_seg], total = tok[n_seg];
+    MIR_REQUIRE(L < ((int64_t)1 << 31) && total < ((int64_t)1 << 40), "scope of %lld chunks / %lld tokens is too large", (long long)L, (long long)total);
+    if (total == 0) {
+        set_error("Text index is empty.");  // bm25_retriever.py:75-76 on the request's own documents
+        return MIR_ERR_EMPTY;
+    }
+    int32_t rc = use_device(h->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    mir_bm25_scope *sc = new (std::nothrow) mir_bm25_scope();
+    MIR_REQUIRE(sc != nullptr, "out of host memory");
+    sc->model = h; sc->device = h->device; sc->n_seg = n_seg; sc->n_pos = L; sc->total_tokens = total;
+    sc->avgdl = (double)total / (double)L;
+    const int32_t V = h->vocab;
+    int64_t *d_tok = nullptr, *d_df = nullptr;
+    unsigned long long *d_first = nullptr;
+    std::vector<int64_t> df((size_t)V), first((size_t)V);
+    auto run = [&]() -> int32_t {
+        MIR_HIP(hipMalloc((void **)&sc->seg_begin, (size_t)n_seg * 4));
+        MIR_HIP(hipMalloc((void **)&sc->seg_pos, ((size_t)n_seg + 1) * 8));
+        MIR_HIP(hipMalloc((void **)&sc->idf, (size_t)V * 8));
+        MIR_HIP(hipMalloc((void **)&d_tok, ((size_t)n_seg + 1) * 8));
+        MIR_HIP(hipMalloc((void **)&d_df, (size_t)V * 8));
+        MIR_HIP(hipMalloc((void **)&d_first, (size_t)V * 8));
+        sc->hbm_bytes = (int64_t)n_seg * 4 + ((int64_t)n_seg + 1) * 8 + (int64_t)V * 8;
+        std::lock_guard<std::mutex> lk(h->mu);
+        hipStream_t s = h->stream;
+        MIR_HIP(hipMemcpyAsync(sc->seg_begin, begin.data(), (size_t)n_seg * 4, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemcpyAsync(sc->seg_pos, pos.data(), ((size_t)n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemcpyAsync(d_tok, tok.data(), ((size_t)n_seg + 1) * 8, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemsetAsync(d_first, 0xff, (size_t)V * 8, s));
+        bm25_scope_df_kernel<<<dim3((unsigned)((V + 255) / 256)), dim3(256), 0, s>>>(h->p_doc, h->t_ptr, V, sc->seg_begin, sc->seg_pos, n_seg, d_df);
+        MIR_HIP(hipGetLastError());
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 1 << 16));
+        bm25_scope_first_kernel<<<dim3(grid), dim3(256), 0, s>>>(h->d_tokens, h->d_indptr, sc->seg_begin, d_tok, n_seg, total, h->total_tokens, V, d_first);
+        MIR_HIP(hipGetLastError());
+        MIR_HIP(hipMemcpyAsync(df.data(), d_df, (size_t)V * 8, hipMemcpyDeviceToHost, s));
+        MIR_HIP(hipMemcpyAsync(first.data(), d_first, (size_t)V * 8, hipMemcpyDeviceToHost, s));
+        MIR_HIP(hipStreamSynchronize(s));
+        // BM25Okapi._calc_idf over the scope's corpus: N = L, first-appearance order of the scope's own token stream
+        for (int32_t t = 0; t < V; ++t) {
+            if (df[t] > 0) ++sc->n_terms;
+            if (df[t] <= 0 || first[t] < 0) first[t] = INT64_MAX;  // (~0 = absent)
+        }
+        sc->h_idf.assign((size_t)V, 0.0);
+        int32_t rc2 = mir_bm25_idf_from_stats(df.data(), first.data(), V, L, h->epsilon, sc->h_idf.data(), &sc->average_idf);
+        if (rc2 != MIR_OK) return rc2;
+        MIR_HIP(hipMemcpyAsync(sc->idf, sc->h_idf.data(), (size_t)V * 8, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipStreamSynchronize(s));
+        return MIR_OK;
+    };
+    rc = run();
+    (void)hipFree(d_tok);
+    (void)hipFree(d_df);
+    (void)hipFree(d_first);
+    if (rc != MIR_OK) {
+        free_scope(sc);
+        return rc;
+    }
+    *out = sc;
+    return MIR_OK;
+}
+
+int32_t mir_bm25_scope_destroy(mir_bm25_scope *scope) {
+    free_scope(scope);
+    return MIR_OK;
+}
+
+int32_t mir_bm25_scope_info(const mir_bm25_scope *scope, int64_t *n_chunks, int64_t *total_tokens, int32_t *n_terms, double *avgdl,
+                            double *average_idf, int64_t *hbm_bytes) {
+    MIR_REQUIRE(scope != nullptr, "scope is NULL");
+    if (n_chunks) *n_chunks = scope->n_pos;
+    if (total_tokens) *total_tokens = scope->total_tokens;
+    if (n_terms) *n_terms = scope->n_terms;
+    if (avgdl) *avgdl = scope->avgdl;
+    if (average_idf) *average_idf = scope->average_idf;
+    if (hbm_bytes) *hbm_bytes = scope->hbm_bytes;
+    return MIR_OK;
+}
+
+int32_t mir_bm25_scope_idf(const mir_bm25_scope *scope, double *out_idf_host) {
+    MIR_REQUIRE(scope != nullptr && out_idf_host != nullptr, "NULL argument");
+    std::memcpy(out_idf_host, scope->h_idf.data(), sizeof(double) * scope->h_idf.size());
+    return MIR_OK;
+}
+
+static ScopeDev scope_dev(const mir_bm25_scope *sc, int64_t out_base) {
+    ScopeDev d;
+    d.seg_begin = sc->seg_begin; d.seg_pos = sc->seg_pos; d.idf = sc->idf; d.avgdl = sc->avgdl; d.L = sc->n_pos;
+    d.out_base = out_base; d.n_seg = sc->n_seg;
+    return d;
+}
+
+// BM25Okapi(the scope's chunks).get_scores(query) -> float64[L]
+int32_t mir_bm25_scores_scoped(mir_bm25 *h, const mir_bm25_scope *scope, const int32_t *q_terms_host, int32_t nq, double *out_scores_host) {
+    MIR_REQUIRE(h != nullptr, "handle is NULL");
+    MIR_REQUIRE_CORPUS(h);
+    MIR_REQUIRE(scope != nullptr && scope->model == h, "the scope is not one of this model");
+    MIR_REQUIRE(nq >= 0 && (nq == 0 || q_terms_host), "bad query");
+    MIR_REQUIRE(out_scores_host != nullptr, "out_scores is NULL");
+    int32_t rc = use_device(h->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int64_t L = scope->n_pos;
+    const size_t o_ptr = ((size_t)nq * 4 + 255) & ~(size_t)255, o_sd = o_ptr + 256, o_sc = o_sd + 256;
+    static_assert(sizeof(ScopeDev) <= 256, "one slot");
+    rc = ensure_scratch(h, o_sc + (size_t)L * 8);
+    if (rc != MIR_OK) return rc;
+    char *base = static_cast<char *>(h->scratch);
+    const int32_t ptr2[2] = {0, nq};
+    const ScopeDev sd = scope_dev(scope, 0);
+    hipStream_t s = h->stream;
+    if (nq) MIR_HIP(hipMemcpyAsync(base, q_terms_host, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    MIR_HIP(hipMemcpyAsync(base + o_ptr, ptr2, 8, hipMemcpyHostToDevice, s));
+    MIR_HIP(hipMemcpyAsync(base + o_sd, &sd, sizeof(sd), hipMemcpyHostToDevice, s));
+    const int tiles = (int)((L + kBm25Tile - 1) / kBm25Tile);
+    bm25_scoped_tile_kernel<<<dim3(tiles, 1), dim3(256), 0, s>>>(scoped_view(h), reinterpret_cast<const ScopeDev *>(base + o_sd),
+                                                                 reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
+                                                                 reinterpret_cast<double *>(base + o_sc));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); set_error("bm25_scoped_tile_kernel: %s", hipGetErrorString(e)); return MIR_ERR_HIP; }
+    MIR_HIP(hipMemcpyAsync(out_scores_host, base + o_sc, (size_t)L * 8, hipMemcpyDeviceToHost, s));
+    MIR_HIP(hipStreamSynchronize(s));
+    return MIR_OK;
+}
+
+// _get_top_n_indexes of b requests in one call: query i ranks the chunks of scopes[i].
+int32_t mir_bm25_search_scoped(mir_bm25 *h, const mir_bm25_scope *const *scopes, const int32_t *q_terms_host, const int32_t *q_ptr_host,
+                               int32_t b, int32_t k, int64_t *out_pos, int32_t *out_ord, int64_t *out_doc, double *out_score,
+                               int32_t *out_count) {
+    MIR_REQUIRE(h != nullptr, "handle is NULL");
+    MIR_REQUIRE_CORPUS(h);
+    MIR_REQUIRE(b >= 0 && k >= 1, "bad shape b=%d k=%d", b, k);
+    if (b == 0) return MIR_OK;
+    MIR_REQUIRE(scopes && q_ptr_host, "NULL buffer");
+    const int nt = q_ptr_host[b];
+    MIR_REQUIRE(q_ptr_host[0] == 0 && nt >= 0 && (nt == 0 || q_terms_host), "bad q_ptr");
+    for (int i = 0; i < b; ++i) {
+        MIR_REQUIRE(q_ptr_host[i + 1] >= q_ptr_host[i], "q_ptr not monotone");
+        MIR_REQUIRE(scopes[i] != nullptr && scopes[i]->model == h, "scope %d is not one of this model", i);
+    }
+    // the dense scores of a group of queries share the workspace: groups of at most 2^27 scores (1 GiB) and 65535 queries
+    const int64_t cap = (int64_t)1 << 27;
+    std::vector<ScopeDev> sd((size_t)b);
+    std::vector<int> group_start{0};
+    int64_t acc = 0, need = 0;
+    for (int i = 0; i < b; ++i) {
+        const int64_t L = scopes[i]->n_pos;
+        if (acc > 0 && (acc + L > cap || i - group_start.back() >= 65535)) { group_start.push_back(i); acc = 0; }
+        sd[i] = scope_dev(scopes[i], acc);
+        acc += L;
+        need = std::max(need, acc);
+    }
+    group_start.push_back(b);
+    int32_t rc = use_device(h->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    const size_t bk = (size_t)b * k;
+    const size_t o_terms = take((size_t)nt * 4 + 4), o_ptr = take((size_t)(b + 1) * 4), o_sd = take((size_t)b * sizeof(ScopeDev));
+    const size_t o_pos = take(bk * 8), o_doc = take(bk * 8), o_sc = take(bk * 8), o_ord = take(bk * 4), o_cnt = take((size_t)b * 4);
+    const size_t o_bs = take((size_t)b * 8), o_bi = take((size_t)b * 8), o_dense = take((size_t)need * 8);
+    rc = ensure_scratch(h, off);
+    if (rc != MIR_OK) return rc;
+    char *base = static_cast<char *>(h->scratch);
+    hipStream_t s = h->stream;
+    auto launch = [&]() -> int32_t {
+        if (nt) MIR_HIP(hipMemcpyAsync(base + o_terms, q_terms_host, (size_t)nt * 4, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemcpyAsync(base + o_ptr, q_ptr_host, (size_t)(b + 1) * 4, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemcpyAsync(base + o_sd, sd.data(), (size_t)b * sizeof(ScopeDev), hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemsetAsync(base + o_pos, 0, o_bs - o_pos, s));  // rows past a query's count read as zeros
+        const ScopeDev *d_sd = reinterpret_cast<const ScopeDev *>(base + o_sd);
+        const int32_t *d_ptr = reinterpret_cast<const int32_t *>(base + o_ptr);
+        for (size_t g = 0; g + 1 < group_start.size(); ++g) {
+            const int g0 = group_start[g], nq = group_start[g + 1] - g0;
+            int64_t maxL = 0;
+            for (int i = g0; i < g0 + nq; ++i) maxL = std::max(maxL, scopes[i]->n_pos);
+            if (maxL == 0) continue;
+            const int tiles = (int)((maxL + kBm25Tile - 1) / kBm25Tile);
+            bm25_scoped_tile_kernel<<<dim3(tiles, nq), dim3(256), 0, s>>>(scoped_view(h), d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
+                                                                          d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
+            MIR_HIP(hipGetLastError());
+            const int64_t found = std::min<int64_t>(k, maxL);
+            const int rounds = (int)((found + kDkRound - 1) / kDkRound);
+            for (int r = 0; r < rounds; ++r) {
+                bm25_scoped_topk_kernel<<<dim3(nq), dim3(kDkThreads), 0, s>>>(
+                    d_sd, reinterpret_cast<const double *>(base + o_dense), k, r, g0, reinterpret_cast<double *>(base + o_bs),
+                    reinterpret_cast<int64_t *>(base + o_bi), reinterpret_cast<int64_t *>(base + o_pos), reinterpret_cast<int32_t *>(base + o_ord),
+                    reinterpret_cast<int64_t *>(base + o_doc), reinterpret_cast<double *>(base + o_sc), reinterpret_cast<int32_t *>(base + o_cnt));
+                MIR_HIP(hipGetLastError());
+            }
+        }
+        if (out_pos) MIR_HIP(hipMemcpyAsync(out_pos, base + o_pos, bk * 8, hipMemcpyDeviceToHost, s));
+        if (out_doc) MIR_HIP(hipMemcpyAsync(out_doc, base + o_doc, bk * 8, hipMemcpyDeviceToHost, s));
+        if (out_score) MIR_HIP(hipMemcpyAsync(out_score, base + o_sc, bk * 8, hipMemcpyDeviceToHost, s));
+        if (out_ord) MIR_HIP(hipMemcpyAsync(out_ord, base + o_ord, bk * 4, hipMemcpyDeviceToHost, s));
+        if (out_count) MIR_HIP(hipMemcpyAsync(out_count, base + o_cnt, (size_t)b * 4, hipMemcpyDeviceToHost, s));
+        return MIR_OK;
+    };
+    rc = launch();
+    if (rc != MIR_OK) { (void)hipStreamSynchronize(s); return rc; }
+    MIR_HIP(hipStreamSynchronize(s));
+    return MIR_OK;
 }
 
 }  // extern "C"

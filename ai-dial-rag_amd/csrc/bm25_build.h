@@ -13,6 +13,8 @@ struct Bm25Built {
     int32_t *doc_len = nullptr; // [n_docs] tokens per document
     int64_t *t_ptr = nullptr;   // [vocab + 1]
     uint32_t *t_tile = nullptr; // [vocab][ntiles + 1]
+    int32_t *tokens = nullptr;  // [total tokens] the term ids in text order, and
+    int64_t *indptr = nullptr;  // [n_docs + 1] the caller's indptr: only with keep_stream (scoped BM25), else freed
     int64_t n_postings = 0;
     int ntiles = 0;
     int64_t hbm_bytes = 0;
@@ -27,6 +29,6 @@ int32_t bm25_reweight_device(const int32_t *p_doc, const int32_t *p_tf, const in
                              double b, double avgdl, double *p_w, void *stream);
 
 int32_t bm25_build_device(const int64_t *indptr, const int32_t *term_ids, int64_t n_docs, int32_t vocab, double k1,
-                          double b, double avgdl, int tile, Bm25Built *out);
+                          double b, double avgdl, int tile, Bm25Built *out, bool keep_stream = false);
 
 }  // namespace mir

@@ -123,6 +123,7 @@ struct Scratch {  // frees what the build allocated and no longer needs, on ever
         if (e == hipSuccess) ptrs.push_back(*out);
         return e;
     }
+    void release(void *p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }  // the caller keeps it
 };
 
 unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16)); }
@@ -139,7 +140,7 @@ unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<in
     } while (0)
 
 int32_t bm25_build_device(const int64_t *indptr, const int32_t *term_ids, int64_t n_docs, int32_t vocab, double k1,
-                          double b, double avgdl, int tile, Bm25Built *out) {
+                          double b, double avgdl, int tile, Bm25Built *out, bool keep_stream) {
     const int64_t total = n_docs ? indptr[n_docs] - indptr[0] : 0;
     MIR_REQUIRE(total < ((int64_t)1 << 31), "%lld tokens: more than 2^31 - 1 in one model", (long long)total);
     const int T = (int)std::max<int64_t>(1, (n_docs + tile - 1) / tile);
@@ -219,6 +220,13 @@ int32_t bm25_build_device(const int64_t *indptr, const int32_t *term_ids, int64_
     BUILD_TRY(hipMemcpyAsync(out->t_ptr_host.data(), out->t_ptr, (size_t)(vocab + 1) * 8, hipMemcpyDeviceToHost, s));
     BUILD_TRY(hipMemcpyAsync(out->first_pos.data(), d_first, (size_t)vocab * 8, hipMemcpyDeviceToHost, s));
     BUILD_TRY(hipStreamSynchronize(s));
+    if (keep_stream) {  // a corpus model (mir_bm25_create_corpus): the token stream and indptr stay in HBM for the scopes
+        tmp.release(d_terms);
+        tmp.release(d_indptr);
+        out->tokens = d_terms;
+        out->indptr = d_indptr;
+        out->hbm_bytes += total * 4 + (n_docs + 1) * 8;
+    }
     return MIR_OK;
 }
 

@@ -25,6 +25,43 @@ from ..index_record import Document, RetrievalType, to_metadata_doc
 from ._group_commit import _GroupCommit
 
 
+class BM25Scope:
+    """Owner of one ``mir_bm25_scope``: an ordered list of document segments of a ``DeviceBM25`` built with
+    ``keep_tokens=True``, with the statistics rank-bm25 would derive from those chunks alone.  Immutable; any number of
+    searches may use it at once.  It keeps its model alive."""
+
+    def __init__(self, handle, model: "DeviceBM25", n_seg: int):
+        self._h, self.model, self.n_seg = handle, model, n_seg
+        self.n_chunks = self.info()["n_chunks"]
+
+    def info(self) -> dict:
+        n, tot, nt = C.c_int64(), C.c_int64(), C.c_int32()
+        a, ai, hb = C.c_double(), C.c_double(), C.c_int64()
+        nat.check(nat.lib.mir_bm25_scope_info(self._h, C.byref(n), C.byref(tot), C.byref(nt), C.byref(a), C.byref(ai), C.byref(hb)))
+        return {"n_chunks": n.value, "total_tokens": tot.value, "n_terms": nt.value, "avgdl": a.value, "average_idf": ai.value,
+                "hbm_bytes": hb.value}
+
+    def idf(self) -> np.ndarray:
+        out = np.zeros(self.model.vocab, np.float64)
+        nat.check(nat.lib.mir_bm25_scope_idf(self._h, nat.ptr(out)))
+        return out
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            nat.lib.mir_bm25_scope_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceBM25:
     """Owner of one ``mir_bm25`` handle over token-id documents."""
 
@@ -34,9 +71,18 @@ class DeviceBM25:
     @classmethod
     def from_token_ids(cls, indptr: np.ndarray, term_ids: np.ndarray, vocab: int, k1: float = 1.5, b: float = 0.75,
                        epsilon: float = 0.25, idf: Optional[np.ndarray] = None, avgdl: float = 0.0, device: int = 0,
-                       doc_offset: int = 0):
+                       doc_offset: int = 0, keep_tokens: bool = False):
+        """``keep_tokens=True``: the model also keeps its token stream in HBM (``mir_bm25_create_corpus``), which is
+        what ``scope`` / ``get_scores_scoped`` / ``search_scoped`` need; everything else is the same model."""
         indptr = np.ascontiguousarray(indptr, dtype=np.int64)
         term_ids = np.ascontiguousarray(term_ids, dtype=np.int32)
+        if keep_tokens:
+            if idf is not None or doc_offset != 0:
+                raise ValueError("keep_tokens=True takes no idf override and no doc_offset: a corpus model is not a shard")
+            h = C.c_void_p()
+            nat.check(nat.lib.mir_bm25_create_corpus(nat.ptr(indptr), nat.ptr(term_ids) if len(term_ids) else None, len(indptr) - 1,
+                                                     vocab, k1, b, epsilon, device, C.byref(h)))
+            return cls(h, len(indptr) - 1, vocab, device)
         idf_c = None if idf is None else np.ascontiguousarray(idf, dtype=np.float64)
         if idf_c is not None and len(idf_c) != vocab:
             raise ValueError("idf override must have `vocab` entries")
@@ -95,6 +141,42 @@ class DeviceBM25:
         nat.check(nat.lib.mir_bm25_search(self._h, nat.ptr(flat) if len(flat) else None, nat.ptr(ptr), b, k, nat.ptr(idx),
                                           nat.ptr(sc), nat.ptr(cnt)))
         return idx, sc, cnt
+
+    # ---- scoped: every query ranks its own documents of this model (keep_tokens=True models only) --------------
+    def scope(self, seg_begin: Sequence[int], seg_end: Sequence[int]) -> BM25Scope:
+        """The scope whose corpus is the chunks [seg_begin[s], seg_end[s]) of this model, segment after segment."""
+        sb = np.ascontiguousarray(seg_begin, dtype=np.int64).reshape(-1)
+        se = np.ascontiguousarray(seg_end, dtype=np.int64).reshape(-1)
+        if len(sb) != len(se):
+            raise ValueError(f"{len(sb)} segment begins for {len(se)} ends")
+        h = C.c_void_p()
+        nat.check(nat.lib.mir_bm25_scope_create(self._h, nat.ptr(sb) if len(sb) else None, nat.ptr(se) if len(se) else None, len(sb), C.byref(h)))
+        return BM25Scope(h, self, len(sb))
+
+    def get_scores_scoped(self, scope: BM25Scope, query_ids: Sequence[int]) -> np.ndarray:
+        """``BM25Okapi(the scope's chunks).get_scores(query)`` -> float64[scope.n_chunks]."""
+        q = np.ascontiguousarray(query_ids, dtype=np.int32)
+        out = np.zeros(scope.n_chunks, np.float64)
+        nat.check(nat.lib.mir_bm25_scores_scoped(self._h, scope.handle, nat.ptr(q) if len(q) else None, len(q), nat.ptr(out)))
+        return out
+
+    def search_scoped(self, scopes: Sequence[BM25Scope], queries_ids: Sequence[Sequence[int]], k: int):
+        """Query i ranks ``scopes[i]`` -> (pos[b,k] i64 scope positions, ord[b,k] i32 segment ordinals, doc[b,k] i64
+        documents of the model, score[b,k] f64, count[b] i32), best first."""
+        b = len(queries_ids)
+        if len(scopes) != b:
+            raise ValueError(f"{len(scopes)} scopes for {b} queries")
+        ptr = np.zeros(b + 1, np.int32)
+        ptr[1:] = np.cumsum([len(q) for q in queries_ids])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(q, np.int32) for q in queries_ids]) if ptr[-1] else np.zeros(0, np.int32))
+        handles = (C.c_void_p * max(b, 1))(*[s.handle for s in scopes])
+        pos, doc = np.zeros((b, k), np.int64), np.zeros((b, k), np.int64)
+        order = np.zeros((b, k), np.int32)
+        sc = np.zeros((b, k), np.float64)
+        cnt = np.zeros(b, np.int32)
+        nat.check(nat.lib.mir_bm25_search_scoped(self._h, handles, nat.ptr(flat) if len(flat) else None, nat.ptr(ptr), b, k, nat.ptr(pos),
+                                                 nat.ptr(order), nat.ptr(doc), nat.ptr(sc), nat.ptr(cnt)))
+        return pos, order, doc, sc, cnt
 
     def workspace_bytes(self, b: int, k: int) -> int:
         """HBM scratch `search_device` needs for a batch of b queries."""

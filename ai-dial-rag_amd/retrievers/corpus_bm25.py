@@ -1,0 +1,241 @@
+"""One resident BM25 model for MANY documents; every request ranks its own documents of it.
+
+The counterpart of ``corpus_index.py`` for the keyword leg.  The reference builds ``BM25Okapi`` from the chunks of the
+documents a request names (bm25_retriever.py:64-79); the chunks of a ``CorpusBM25`` are the chunks of all its documents
+flattened in (document, chunk) order, so a document is one contiguous chunk range and a request's document list is a
+short list of ranges: a *scope* of ``DeviceBM25.search_scoped``.  The scope's idf, its average and
+avgdl are those of the request's own chunks, so scores and order are the reference's for that request, bit for bit;
+a result is (position of the document in the request, chunk id), which is what ``BM25Retriever.get_metadata_doc``
+yields.  No model is composed per document set, and queries of different requests ride one launch.
+
+``BM25Retriever`` and the device cache do not use this ("what it is not for").
+"""
+
+import threading
+from collections import OrderedDict
+from typing import Hashable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from ..index_record import Document, RetrievalType, to_metadata_doc
+from ._group_commit import _GroupCommit
+from .bm25_retriever import _VOCAB, BM25Scope, DeviceBM25, _doc_token_ids
+from .embeddings_index import scope_segments
+from .sharded_bm25 import fuse_batch
+
+__all__ = ["CorpusBM25", "CorpusBM25View", "CorpusHybrid"]
+
+
+def _document_arrays(doc) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """One document -> (chunk ids i64[c], tokens per chunk i64[c], term ids i32[tokens]).  Accepted: None (no text
+    index), that triple itself as a TUPLE, or a LIST: a text index (items with ``chunk_index`` / ``tokenized_text``:
+    ids of the process-wide vocabulary) or per-chunk term-id arrays (chunk ids 0, 1, ...).  A tuple is never read as
+    per-chunk arrays."""
+    if doc is None:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32)
+    if isinstance(doc, tuple):
+        if len(doc) != 3:
+            raise ValueError(f"a tuple is the (chunk ids, tokens per chunk, term ids) triple, not {len(doc)} items; pass per-chunk arrays as a list")
+        chunk, lens, ids = (np.asarray(a) for a in doc)
+        if not (chunk.ndim == lens.ndim == ids.ndim == 1 and len(chunk) == len(lens) and all(a.dtype.kind in "iu" or a.size == 0 for a in (chunk, lens, ids))
+                and (lens.size == 0 or int(lens.min()) >= 0) and int(lens.sum()) == len(ids)):
+            raise ValueError("a tuple is the (chunk ids[c], tokens per chunk[c], term ids[sum of tokens]) triple: these three arrays are not "
+                             "one; pass per-chunk arrays as a list")
+        return chunk.astype(np.int64), lens.astype(np.int64), ids.astype(np.int32)
+    if not isinstance(doc, list):
+        raise TypeError(f"a document is None, a triple (tuple) or a list of chunks, not {type(doc).__name__}")
+    if doc and hasattr(doc[0], "tokenized_text"):
+        return _doc_token_ids(doc)[0]
+    lens = np.fromiter((len(c) for c in doc), np.int64, len(doc))
+    ids = np.concatenate([np.asarray(c, np.int32).reshape(-1) for c in doc]) if int(lens.sum()) else np.zeros(0, np.int32)
+    return np.arange(len(doc), dtype=np.int64), lens, ids
+
+
+class CorpusBM25View:
+    """``BM25Retriever``'s retrieval surface over some documents of a corpus.  ``doc_id`` of a result = the position
+    of its document in ``doc_positions``.  The scope (the request's statistics, in HBM) is built at first use and kept."""
+
+    def __init__(self, corpus: "CorpusBM25", doc_positions: Sequence[int], k: int):
+        self.corpus = corpus
+        self.doc_positions = [int(p) for p in doc_positions]
+        self.limit = int(k)
+        if self.limit < 1:
+            raise ValueError(f"k={k} must be >= 1")
+        self.seg_begin, self.seg_end = scope_segments(corpus.doc_lengths, self.doc_positions)
+        self._scope: Optional[BM25Scope] = None
+        self._scope_lock = threading.Lock()
+        self._parent: Optional["CorpusBM25View"] = None  # a view that differs only in its limit shares the scope
+
+    def scope(self) -> BM25Scope:
+        if self._parent is not None:
+            return self._parent.scope()
+        with self._scope_lock:
+            if self._scope is None:
+                self._scope = self.corpus._make_scope(self.seg_begin, self.seg_end)  # no token: "Text index is empty."
+            return self._scope
+
+    def _with_limit(self, n: int) -> "CorpusBM25View":
+        if n == self.limit:
+            return self
+        v = CorpusBM25View.__new__(CorpusBM25View)
+        v.__dict__.update(self.__dict__)
+        v.limit, v._parent, v._scope = int(n), (self._parent or self), None
+        if v.limit < 1:
+            raise ValueError(f"n={n} must be >= 1")
+        return v
+
+    def _get_top_n_indexes(self, query_ids: Sequence[Hashable], n: int = 5) -> np.ndarray:
+        """bm25_retriever.py:81-84 over the request's own flattened chunk list; concurrent callers of ANY view of
+        the corpus share passes."""
+        pos, _doc, _chunk, _score, cnt = self.corpus._commit.submit((query_ids, self._with_limit(n)))
+        return pos[: int(cnt)]
+
+    def search_batch(self, queries_ids: Sequence[Sequence[Hashable]]) -> List[List[Tuple[int, int]]]:
+        """-> per query the (doc position in the request, chunk id) pairs, best first."""
+        qs = [self.corpus._ids(q) for q in queries_ids]
+        _pos, doc, chunk, _score, cnt = self.corpus._search_views(qs, [self] * len(qs), self.limit)
+        return [[(int(doc[i, j]), int(chunk[i, j])) for j in range(int(cnt[i]))] for i in range(len(qs))]
+
+    def get_relevant_documents(self, query_ids: Sequence[Hashable]) -> List[Document]:
+        _pos, doc, chunk, _score, cnt = self.corpus._commit.submit((query_ids, self))
+        return [to_metadata_doc(int(doc[j]), int(chunk[j]), RetrievalType.TEXT) for j in range(int(cnt))]
+
+    def close(self):
+        with self._scope_lock:
+            if self._scope is not None:
+                self._scope.close()
+                self._scope = None
+
+
+class CorpusBM25:
+    """``documents``: see ``_document_arrays``.  ``vocab``: the size of the term-id space (default: largest id + 1).
+    The device model is built at the first search.  ``max_scopes``: how many document lists ``find_many`` keeps the scope
+    of (a scope holds 8 bytes of HBM per vocabulary entry)."""
+
+    def __init__(self, documents: Sequence, vocab: Optional[int] = None, device: int = 0, max_batch: int = 256, max_scopes: int = 256):
+        docs = [_document_arrays(d) for d in documents]
+        self.device = device
+        self.doc_lengths = np.array([len(d[0]) for d in docs], dtype=np.int64)  # chunks per document
+        self.chunk_of = np.concatenate([d[0] for d in docs]) if docs else np.zeros(0, np.int64)
+        lens = np.concatenate([d[1] for d in docs]) if docs else np.zeros(0, np.int64)
+        self._indptr = np.zeros(len(lens) + 1, np.int64)
+        np.cumsum(lens, out=self._indptr[1:])
+        self._ids_flat = np.concatenate([d[2] for d in docs]) if docs else np.zeros(0, np.int32)
+        top = int(self._ids_flat.max()) + 1 if len(self._ids_flat) else 1
+        self.vocab = int(vocab) if vocab is not None else top
+        if self.vocab < top:
+            raise ValueError(f"term id {top - 1} outside vocab={self.vocab}")
+        self._dev: Optional[DeviceBM25] = None
+        self._lock = threading.Lock()
+        self._cached: "OrderedDict[tuple, CorpusBM25View]" = OrderedDict()  # find_many's scopes by document list, LRU
+        self._cached_lock = threading.Lock()
+        self._max_scopes = max(0, int(max_scopes))
+        self._commit = _GroupCommit(self._run_pass, max_batch=max_batch, validate=self._check_item)
+
+    # ---- the device model -------------------------------------------------------------------------------------
+    def _device_model(self) -> DeviceBM25:
+        with self._lock:
+            if self._dev is None:
+                if self._ids_flat is None:
+                    raise RuntimeError("this CorpusBM25 is closed")
+                self._dev = DeviceBM25.from_token_ids(self._indptr, self._ids_flat, self.vocab, device=self.device, keep_tokens=True)
+                self._ids_flat = None  # the stream lives in HBM from here on
+            return self._dev
+
+    def hbm_bytes(self) -> int:
+        return self._device_model().info()["hbm_bytes"]
+
+    def _make_scope(self, seg_begin: np.ndarray, seg_end: np.ndarray) -> BM25Scope:
+        return self._device_model().scope(seg_begin, seg_end)
+
+    def _search_scoped(self, queries_ids: Sequence[Sequence[int]], views: Sequence[CorpusBM25View], k: int):
+        """The device search: (pos, ord, doc, score, count).  The one place that touches the GPU."""
+        return self._device_model().search_scoped([v.scope() for v in views], queries_ids, k)
+
+    def _search_views(self, queries_ids, views, k: int):
+        """-> (scope position, doc position in the request, chunk id, score)[b, k], count[b]."""
+        pos, order, doc, score, cnt = self._search_scoped(queries_ids, views, k)
+        chunk = self.chunk_of[doc] if len(self.chunk_of) else np.zeros_like(doc)  # (rows past a query's count hold document 0)
+        return pos, order, chunk, score, cnt
+
+    def _ids(self, tokens: Sequence[Hashable]) -> List[int]:
+        """Term ids pass through; other tokens go through the process-wide vocabulary (-1: never indexed)."""
+        return [int(t) if isinstance(t, (int, np.integer)) else _VOCAB.get(t, -1) for t in tokens]
+
+    # ---- the public surface -----------------------------------------------------------------------------------
+    def view(self, doc_positions: Sequence[int], k: int = 4) -> CorpusBM25View:
+        return CorpusBM25View(self, doc_positions, k)
+
+    def find_many(self, queries: Sequence[Sequence[Hashable]], scopes: Sequence[Sequence[int]], k: int = 4):
+        """The explicit batch form: query i ranks the documents ``scopes[i]`` (positions in the corpus) ->
+        (doc_ids[b, k] = positions inside scopes[i], chunk_ids[b, k], score[b, k], count[b]).  Equal document lists
+        share one scope, and the scopes of the ``max_scopes`` most recently used lists are kept, so a list seen again
+        pays no scope creation.  A list without any token fails the whole call ("Text index is empty.")."""
+        if len(scopes) != len(queries):
+            raise ValueError(f"{len(scopes)} scopes for {len(queries)} queries")
+        if int(k) < 1:
+            raise ValueError(f"k={k} must be >= 1")
+        keys = [tuple(int(p) for p in s) for s in scopes]
+        made = {key: self._cached_view(key) for key in dict.fromkeys(keys)}  # (holds evicted ones alive for this call)
+        views = [made[key] for key in keys]
+        _pos, doc, chunk, score, cnt = self._search_views([self._ids(q) for q in queries], views, int(k))
+        return doc, chunk, score, cnt
+
+    def _cached_view(self, key: tuple) -> CorpusBM25View:
+        """An evicted view is only dropped: its scope is released with the last search that still holds it."""
+        with self._cached_lock:
+            v = self._cached.pop(key, None) or self.view(key, 1)
+            if self._max_scopes > 0:
+                self._cached[key] = v  # (most recently used last)
+                while len(self._cached) > self._max_scopes:
+                    self._cached.popitem(last=False)
+            return v
+
+    def close(self):
+        """Drops the cached scopes and the device model; no search may be in flight."""
+        with self._cached_lock:
+            self._cached.clear()
+        with self._lock:
+            if self._dev is not None:
+                self._dev.close()
+                self._dev = None
+
+    # ---- shared passes: an item is (query ids, view) ----------------------------------------------------------
+    def _check_item(self, item):
+        """In the submitting thread: the ids, and the view's scope, so that a document list without any token ("Text
+        index is empty.") or one the device refuses fails its own caller and never reaches a shared pass."""
+        query, view = item
+        view.scope()
+        return self._ids(query), view
+
+    def _run_pass(self, items):
+        """One search with the largest limit among the items; an item keeps the first `limit` of its row (the order
+        is total, so a top-k' is a prefix of a top-k)."""
+        k = max(view.limit for _, view in items)
+        pos, doc, chunk, score, cnt = self._search_views([q for q, _ in items], [v for _, v in items], k)
+        out = []
+        for i, (_, view) in enumerate(items):
+            m = min(int(cnt[i]), view.limit)
+            out.append((pos[i, :m], doc[i, :m], chunk[i, :m], score[i, :m], m))
+        return tuple([o[c] for o in out] for c in range(5))
+
+
+class CorpusHybrid:
+    """Vector + BM25 + weighted reciprocal-rank fusion over two corpora that hold the SAME documents in the same
+    order: both scoped legs take the request's document list, their (doc position, chunk id) results are fused by
+    ``fuse_batch`` (``mir_rrf_fuse_batch``).  Host glue only; the BM25 leg's scopes come from ``CorpusBM25.find_many``'s
+    cache, so a document list seen before pays no scope creation."""
+
+    def __init__(self, corpus_index, corpus_bm25: CorpusBM25):
+        self.vector, self.keywords = corpus_index, corpus_bm25
+
+    def find_many(self, query_vectors, query_ids, scopes, metric, k: int, weights: Sequence[float] = (1.0, 1.0), c: int = 60):
+        """-> (doc_ids[b, 2k], chunk_ids[b, 2k], rrf score[b, 2k], count[b]), best first."""
+        v_doc, v_chunk, _dist, v_cnt = self.vector.find_many(query_vectors, scopes, metric, k)
+        t_doc, t_chunk, _score, t_cnt = self.keywords.find_many(query_ids, scopes, k)
+        for chunk in (v_chunk, t_chunk):
+            if np.any((np.asarray(chunk) < 0) | (np.asarray(chunk) >= 2**31)):
+                raise ValueError("chunk id outside [0, 2^31): it does not fit the fused key")
+        key = lambda doc, chunk: (np.asarray(doc, np.int64) << 32) | np.asarray(chunk, np.int64)  # one key per (doc, chunk)
+        ids, scores, cnt = fuse_batch([(key(v_doc, v_chunk), v_cnt), (key(t_doc, t_chunk), t_cnt)], weights, c)
+        return (ids >> 32).astype(np.int64), (ids & 0xFFFFFFFF).astype(np.int64), scores, cnt

@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 5 /* 5: mir_index_search_scoped[_device];
+#define MIR_ABI_VERSION 6 /* 6: scoped BM25: mir_bm25_create_corpus, mir_bm25_scope_*, mir_bm25_scores_scoped / _search_scoped;
+                            5: mir_index_search_scoped[_device];
                             4: mir_keywords_preprocess / mir_kwp_result_*;
                             3: 2: results always exact (exact pass), any k; mir_bm25_tune / _corpus_stats / _idf_from_stats /
                              _set_global_stats, mir_rrf_fuse_batch, mir_wordpiece_* added
@@ -330,6 +331,50 @@ int64_t mir_bm25_workspace_bytes(const mir_bm25 *h, int32_t b, int32_t k);
 int32_t mir_bm25_search_device(mir_bm25 *h, const int32_t *q_terms_device, const int32_t *q_ptr_device,
                                int32_t b, int32_t k, int64_t *out_idx, double *out_score, int32_t *out_count,
                                void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Scoped BM25 (ABI 6): one resident model over MANY documents, every query ranks the documents its request names.
+ *
+ * mir_bm25_create_corpus builds an ordinary mir_bm25 (every entry above works on it with identical results) that
+ * also keeps its token stream (int32 per token) and indptr (int64) in HBM; mir_bm25_info's hbm_bytes counts them.
+ * A model from plain mir_bm25_create keeps neither and answers the entries below with MIR_ERR_INVALID.
+ *
+ * A scope is an ordered list of segments [seg_begin[s], seg_end[s]) of the model's documents (the BM25 chunks in the
+ * flattened order of bm25_retriever.py:68-72, so a doc_record is one segment).  Segments may be empty (end <= begin;
+ * they keep their ordinal), repeat, overlap and come in any order; a bound outside [0, n_docs] or a NULL array with
+ * n_seg > 0 is MIR_ERR_INVALID and launches nothing.  The scope's corpus is the concatenation of its segments'
+ * chunks in the order given, L chunks; a chunk listed twice is two chunks of it.  Results are those of
+ * BM25Okapi(that list) with the model's k1 / b / epsilon, bit for bit: N = L, avgdl = scope tokens / L, nd[t] counted
+ * over the scope's positions, idf by the routine behind mir_bm25_idf_from_stats with the average summed in order of
+ * first appearance in the scope's own token stream; a term of the model that the scope lacks contributes +0.0.
+ * A scope without any token is MIR_ERR_EMPTY ("Text index is empty.").  A scope is immutable, may serve any number
+ * of concurrent searches, and must not be searched after its model is destroyed; destroying it (or reading its
+ * info / idf) after the model is harmless, it keeps its own device ordinal and host copies.
+ *   mir_bm25_scope_info   N = L, tokens, terms present, avgdl, average_idf, bytes of HBM the scope holds
+ *   mir_bm25_scope_idf    float64[vocab], 0 where a term is absent from the scope
+ * ---------------------------------------------------------------------- */
+typedef struct mir_bm25_scope mir_bm25_scope;
+
+int32_t mir_bm25_create_corpus(const int64_t *indptr_host, const int32_t *term_ids_host, int64_t n_docs, int32_t vocab,
+                               double k1, double b, double epsilon, int32_t device, mir_bm25 **out);
+int32_t mir_bm25_scope_create(mir_bm25 *h, const int64_t *seg_begin_host, const int64_t *seg_end_host, int32_t n_seg,
+                              mir_bm25_scope **out);
+int32_t mir_bm25_scope_destroy(mir_bm25_scope *scope);
+int32_t mir_bm25_scope_info(const mir_bm25_scope *scope, int64_t *n_chunks, int64_t *total_tokens, int32_t *n_terms,
+                            double *avgdl, double *average_idf, int64_t *hbm_bytes);
+int32_t mir_bm25_scope_idf(const mir_bm25_scope *scope, double *out_idf_host);
+
+/* get_scores for the scope: float64[L] over the scope's positions. */
+int32_t mir_bm25_scores_scoped(mir_bm25 *h, const mir_bm25_scope *scope, const int32_t *q_terms_host, int32_t nq,
+                               double *out_scores_host);
+/* _get_top_n_indexes for b requests in one synchronous call: query i ranks scopes[i] (one handle per query; queries
+ * of different scopes ride one call, a handle may repeat).  Outputs [b][k], best first, ties to the HIGHEST scope
+ * position; out_count[q] = min(k, L_q), rows past it are zero.  out_pos = the scope position (what
+ * _get_top_n_indexes returns for the request's own flattened list), out_ord = the ordinal of its segment in the
+ * scope, out_doc = the model's document index.  Any k >= 1.  An output passed as NULL is not written. */
+int32_t mir_bm25_search_scoped(mir_bm25 *h, const mir_bm25_scope *const *scopes, const int32_t *q_terms_host,
+                               const int32_t *q_ptr_host, int32_t b, int32_t k, int64_t *out_pos, int32_t *out_ord,
+                               int64_t *out_doc, double *out_score, int32_t *out_count);
 
 /* ------------------------------------------------------------------------
  * Rank fusion: langchain EnsembleRetriever.weighted_reciprocal_rank as wired
