@@ -69,6 +69,11 @@ def _load():
         "mir_index_search_device": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_index_search_scoped": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_index_search_scoped_device": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "mir_rows_desc": ([vp, vp], i32),
+        "mir_blocks_create": ([i32, i32, i32, vp], i32),
+        "mir_blocks_destroy": ([vp], i32),
+        "mir_blocks_search": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "mir_blocks_search_device": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_index_profile": ([vp, i32], i32),
         "mir_index_profile_read": ([vp, i32, vp, vp], i32),
         "mir_index_scan_stats": ([vp, i32, vp], i32),
@@ -124,6 +129,12 @@ def _load():
 
 
 lib, DECLARED_SYMBOLS = _load()
+
+
+class BlockDesc(C.Structure):
+    """mir_block_desc: one row block as the device form of the block search reads it (device pointers)."""
+
+    _fields_ = [("emb", C.c_void_p), ("doc_sq", C.c_void_p), ("chunk", C.c_void_p), ("n", C.c_int64)]
 
 
 def last_error() -> str:

@@ -141,7 +141,13 @@ struct mir_rows {
     int dtype = MIR_DTYPE_F32;
     void *d_emb = nullptr;       // n x d, as given (float32 or float16)
     int64_t *d_chunk = nullptr;  // n
+    float *d_docsq = nullptr;    // n: float32 squared norms, bit for bit an index's d_docsq of these rows (mir_blocks_search)
     int64_t hbm_bytes = 0;
+};
+
+// A searcher over row blocks (mir_blocks_search): a row-less mir_index, held for its device, shape and workspace pool.
+struct mir_blocks {
+    mir_index *ix = nullptr;
 };
 
 namespace mir {
@@ -1443,6 +1449,7 @@ int32_t mir_rows_create(const void *emb_host, int64_t n, int32_t d, int32_t dtyp
     if (n > 0) {
         e = hipMalloc(&r->d_emb, eb);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_chunk), (size_t)n * 8);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&r->d_docsq), (size_t)n * 4);
         if (e == hipSuccess) e = hipMemcpy(r->d_emb, emb_host, eb, hipMemcpyHostToDevice);
         if (e == hipSuccess) {
             if (chunk_ids_host) {
@@ -1453,11 +1460,18 @@ int32_t mir_rows_create(const void *emb_host, int64_t n, int32_t d, int32_t dtyp
                 e = hipMemcpy(r->d_chunk, ar.data(), (size_t)n * 8, hipMemcpyHostToDevice);
             }
         }
-        r->hbm_bytes = (int64_t)eb + n * 8;
+        if (e == hipSuccess) {  // (the null stream: behind the copies above, done before this returns)
+            const dim3 grid((unsigned)((n + 255) / 256));
+            if (dtype == MIR_DTYPE_F16) row_sq_kernel<_Float16><<<grid, dim3(256)>>>(static_cast<const _Float16 *>(r->d_emb), n, d, r->d_docsq);
+            else row_sq_kernel<float><<<grid, dim3(256)>>>(static_cast<const float *>(r->d_emb), n, d, r->d_docsq);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        }
+        r->hbm_bytes = (int64_t)eb + n * 12;
     }
     if (e != hipSuccess) {
         set_error("mir_rows_create: %s", hipGetErrorString(e));
-        (void)hipFree(r->d_emb); (void)hipFree(r->d_chunk);
+        (void)hipFree(r->d_emb); (void)hipFree(r->d_chunk); (void)hipFree(r->d_docsq);
         delete r;
         return MIR_ERR_HIP;
     }
@@ -1475,11 +1489,19 @@ int32_t mir_rows_info(const mir_rows *rows, int64_t *n, int32_t *d, int32_t *dty
     return MIR_OK;
 }
 
+int32_t mir_rows_desc(const mir_rows *rows, mir_block_desc *out) {
+    MIR_REQUIRE(rows != nullptr, "handle is NULL");
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = mir_block_desc{rows->d_emb, rows->d_docsq, rows->d_chunk, rows->n};
+    return MIR_OK;
+}
+
 int32_t mir_rows_destroy(mir_rows *rows) {
     if (!rows) return MIR_OK;
     (void)hipSetDevice(rows->device);
     (void)hipFree(rows->d_emb);
     (void)hipFree(rows->d_chunk);
+    (void)hipFree(rows->d_docsq);
     delete rows;
     return MIR_OK;
 }
@@ -1644,7 +1666,8 @@ struct ScopedBuffers {
     int32_t *scope_ptr;   // host API: [b + 1]
     int64_t *seg_begin;   // host API: [nseg]
     int64_t *seg_end;     // host API: [nseg]
-    size_t in_span;       // host API: bytes from q to the end of seg_end (one copy in)
+    mir_block_desc *table;  // host API of the block search: [nseg], in place of seg_begin / seg_end
+    size_t in_span;       // host API: bytes from q to the end of seg_end / table (one copy in)
     double *q_sq, *q_norm;
     unsigned long long *arrive;  // [ceil(b / 2)] words = b counters, zeroed by the prep kernel
     double *bound_dist;
@@ -1653,12 +1676,13 @@ struct ScopedBuffers {
     SearchOut out;        // host API staging of outputs
 };
 
-static size_t carve_scoped(ScopedBuffers &sb, char *base, int b, int k, int d, int P, size_t nseg, bool host_api) {
+static size_t carve_scoped(ScopedBuffers &sb, char *base, int b, int k, int d, int P, size_t nseg, bool host_api, bool blocks = false) {
     Carver c{base};
     sb.q = host_api ? c.take<double>((size_t)b * d) : nullptr;
     sb.scope_ptr = host_api ? c.take<int32_t>((size_t)b + 1) : nullptr;
-    sb.seg_begin = host_api ? c.take<int64_t>(nseg) : nullptr;
-    sb.seg_end = host_api ? c.take<int64_t>(nseg) : nullptr;
+    sb.seg_begin = host_api && !blocks ? c.take<int64_t>(nseg) : nullptr;
+    sb.seg_end = host_api && !blocks ? c.take<int64_t>(nseg) : nullptr;
+    sb.table = host_api && blocks ? c.take<mir_block_desc>(nseg) : nullptr;
     sb.in_span = c.off;
     sb.q_sq = c.take<double>(b);
     sb.q_norm = c.take<double>(b);
@@ -1688,17 +1712,29 @@ static int32_t check_scoped_args(const mir_index *ix, const void *queries, int32
     return MIR_OK;
 }
 
+// The segments of a scoped search: row ranges of the index (seg_begin / seg_end), or row blocks (a descriptor table)
+struct ScopedSegments {
+    const int64_t *seg_begin = nullptr, *seg_end = nullptr;
+    const mir_block_desc *blocks = nullptr;
+};
+
+template <typename T, bool BLOCKS>
+static void launch_scoped(const ScopedArgs &a, bool qlds, dim3 grid, size_t lds, hipStream_t stream) {
+    if (qlds) scoped_topk_kernel<T, true, BLOCKS><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
+    else scoped_topk_kernel<T, false, BLOCKS><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
+}
+
 static int32_t enqueue_scoped(mir_index *ix, const double *dq, int b, int k, int metric, int P, const ScopedBuffers &sb,
-                              const int32_t *scope_ptr, const int64_t *seg_begin, const int64_t *seg_end, const SearchOut &out,
-                              hipStream_t stream) {
+                              const int32_t *scope_ptr, const ScopedSegments &seg, const SearchOut &out, hipStream_t stream) {
     const int d = ix->d;
+    const bool f16 = seg.blocks ? ix->dtype == MIR_DTYPE_F16 : ix->d_f16 != nullptr;  // (blocks keep float16 as given at any d)
     // per-query norms (ngroups = 0: no fragments) + the arrival counters zeroed
     const int arrive_words = (b + 1) / 2;
     prep_queries_kernel<<<dim3(std::max(b, (arrive_words + 63) / 64)), dim3(64), 0, stream>>>(dq, b, d, ix->ksteps, 0, nullptr, sb.q_sq,
                                                                                                 sb.q_norm, sb.arrive, arrive_words);
     ScopedArgs a;
     a.docs = ix->d_orig; a.docs16 = ix->d_f16; a.doc_sq = ix->d_docsq; a.n_rows = (uint32_t)ix->n; a.d = d; a.metric = metric;
-    a.q = dq; a.q_sq = sb.q_sq; a.q_norm = sb.q_norm; a.scope_ptr = scope_ptr; a.seg_begin = seg_begin; a.seg_end = seg_end;
+    a.q = dq; a.q_sq = sb.q_sq; a.q_norm = sb.q_norm; a.scope_ptr = scope_ptr; a.seg_begin = seg.seg_begin; a.seg_end = seg.seg_end; a.blocks = seg.blocks;
     a.k = k; a.list_stride = std::min(k, kExactRound); a.part = sb.part; a.arrive = reinterpret_cast<uint32_t *>(sb.arrive);
     a.bound_dist = sb.bound_dist; a.bound_pos = sb.bound_pos; a.chunk_ids = ix->d_chunk; a.row_offset = ix->row_offset;
     a.out_doc = out.doc; a.out_chunk = out.chunk; a.out_row = out.row; a.out_dist = out.dist; a.out_count = out.count; a.out_flags = out.flags;
@@ -1710,10 +1746,10 @@ static int32_t enqueue_scoped(mir_index *ix, const double *dq, int b, int k, int
         for (int q0 = 0; q0 < b; q0 += kSlice) {
             a.q0 = q0;
             const dim3 grid((unsigned)P, (unsigned)std::min(kSlice, b - q0));
-            if (ix->d_f16 && qlds) scoped_topk_kernel<_Float16, true><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
-            else if (ix->d_f16) scoped_topk_kernel<_Float16, false><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
-            else if (qlds) scoped_topk_kernel<float, true><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
-            else scoped_topk_kernel<float, false><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
+            if (seg.blocks && f16) launch_scoped<_Float16, true>(a, qlds, grid, lds, stream);
+            else if (seg.blocks) launch_scoped<float, true>(a, qlds, grid, lds, stream);
+            else if (f16) launch_scoped<_Float16, false>(a, qlds, grid, lds, stream);
+            else launch_scoped<float, false>(a, qlds, grid, lds, stream);
         }
     }
     MIR_HIP(hipGetLastError());
@@ -1739,7 +1775,7 @@ int32_t mir_index_search_scoped_device(mir_index *idx, const double *queries_dev
     return with_workspace(
         idx, static_cast<hipStream_t>(stream_), false, [&](char *base) { return carve_scoped(sb, base, b, k, idx->d, P, 0, false); },
         [&](Workspace *, hipStream_t s) {
-            return enqueue_scoped(idx, queries_device, b, k, metric, P, sb, scope_ptr_device, seg_begin_device, seg_end_device, out, s);
+            return enqueue_scoped(idx, queries_device, b, k, metric, P, sb, scope_ptr_device, ScopedSegments{seg_begin_device, seg_end_device}, out, s);
         });
 }
 
@@ -1782,7 +1818,110 @@ int32_t mir_index_search_scoped(mir_index *idx, const double *queries_host, int3
                                     {sb.seg_begin, seg_begin_host, nseg * 8},
                                     {sb.seg_end, seg_end_host, nseg * 8}};
             return host_round_trip(w, s, in, nseg ? 4 : 2, sb.q, sb.in_span, sb.out, user, b, k, [&](const SearchOut &out) {
-                return enqueue_scoped(idx, sb.q, b, k, metric, P, sb, sb.scope_ptr, sb.seg_begin, sb.seg_end, out, s);
+                return enqueue_scoped(idx, sb.q, b, k, metric, P, sb, sb.scope_ptr, ScopedSegments{sb.seg_begin, sb.seg_end}, out, s);
+            });
+        });
+}
+
+// ---- block search: the scoped search over row blocks (a mir_blocks searcher holds no rows)
+
+int32_t mir_blocks_create(int32_t d, int32_t dtype, int32_t device, mir_blocks **out) {
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    mir_index *dummy = nullptr;
+    int32_t rc = check_create_args(0, d, dtype, &dummy);
+    if (rc != MIR_OK) return rc;
+    int cus = 0;
+    rc = use_device(device, &cus);
+    if (rc != MIR_OK) return rc;
+    mir_blocks *s = new (std::nothrow) mir_blocks();
+    mir_index *ix = new (std::nothrow) mir_index();
+    if (!s || !ix) {
+        delete s;
+        delete ix;
+        set_error("out of host memory");
+        return MIR_ERR_INVALID;
+    }
+    ix->device = device; ix->num_cus = cus; ix->d = d; ix->dtype = dtype;
+    s->ix = ix;
+    *out = s;
+    return MIR_OK;
+}
+
+int32_t mir_blocks_destroy(mir_blocks *s) {
+    if (!s) return MIR_OK;
+    free_index(s->ix);
+    delete s;
+    return MIR_OK;
+}
+
+int32_t mir_blocks_search_device(mir_blocks *s_, const double *queries_device, int32_t b, int32_t k, int32_t metric,
+                                 const int32_t *scope_ptr_device, const mir_block_desc *table_device, int32_t *out_doc,
+                                 int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags,
+                                 void *stream_) {
+    MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
+    mir_index *ix = s_->ix;
+    int32_t rc = check_scoped_args(ix, queries_device, b, k, metric, scope_ptr_device, out_count);
+    if (rc != MIR_OK) return rc;
+    if (b == 0) return MIR_OK;
+    rc = use_device(ix->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    const int P = scoped_split(ix, b, 0);
+    ScopedBuffers sb;
+    ScopedSegments seg;
+    seg.blocks = table_device;
+    const SearchOut out{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    return with_workspace(
+        ix, static_cast<hipStream_t>(stream_), false, [&](char *base) { return carve_scoped(sb, base, b, k, ix->d, P, 0, false, true); },
+        [&](Workspace *, hipStream_t s) { return enqueue_scoped(ix, queries_device, b, k, metric, P, sb, scope_ptr_device, seg, out, s); });
+}
+
+int32_t mir_blocks_search(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                          const int32_t *scope_ptr_host, const mir_rows *const *blocks_host, int32_t *out_doc, int64_t *out_chunk,
+                          int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags) {
+    MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
+    mir_index *ix = s_->ix;
+    int32_t rc = check_scoped_args(ix, queries_host, b, k, metric, scope_ptr_host, out_count);
+    if (rc != MIR_OK) return rc;
+    if (b == 0) return MIR_OK;
+    // everything the device form trusts is checked here, before anything is launched
+    MIR_REQUIRE(scope_ptr_host[0] == 0, "scope_ptr[0]=%d must be 0", scope_ptr_host[0]);
+    for (int q = 0; q < b; ++q)
+        MIR_REQUIRE(scope_ptr_host[q + 1] >= scope_ptr_host[q], "scope_ptr decreases at query %d", q);
+    const size_t nseg = (size_t)scope_ptr_host[b];
+    MIR_REQUIRE(nseg == 0 || blocks_host != nullptr, "the block table is NULL");
+    std::vector<mir_block_desc> table(nseg);
+    uint64_t max_rows = 1;
+    for (int q = 0; q < b; ++q) {
+        uint64_t rows = 0;
+        for (int t = scope_ptr_host[q]; t < scope_ptr_host[q + 1]; ++t) {
+            const mir_rows *r = blocks_host[t];
+            MIR_REQUIRE(r != nullptr, "block %d of query %d is NULL", t - scope_ptr_host[q], q);
+            MIR_REQUIRE(r->d == ix->d && r->dtype == ix->dtype && r->device == ix->device,
+                        "block %d of query %d is %d-dimensional dtype %d on device %d, the searcher %d-dimensional dtype %d on device %d",
+                        t - scope_ptr_host[q], q, r->d, r->dtype, r->device, ix->d, ix->dtype, ix->device);
+            table[(size_t)t] = mir_block_desc{r->d_emb, r->d_docsq, r->d_chunk, r->n};
+            rows += (uint64_t)r->n;
+            MIR_REQUIRE(rows < (1ull << 32), "the scope of query %d holds 2^32 rows or more", q);
+        }
+        max_rows = std::max(max_rows, rows);
+    }
+    rc = use_device(ix->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    const int P = scoped_split(ix, b, max_rows);
+    ScopedBuffers sb;
+    const SearchOut user{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    return with_workspace(
+        ix, nullptr, true, [&](char *base) { return carve_scoped(sb, base, b, k, ix->d, P, nseg, true, true); },
+        [&](Workspace *w, hipStream_t s) {
+            // [q | scope_ptr | table] goes in as ONE copy of the span carved in that order
+            const HostPiece in[] = {{sb.q, queries_host, (size_t)b * ix->d * sizeof(double)},
+                                    {sb.scope_ptr, scope_ptr_host, ((size_t)b + 1) * 4},
+                                    {sb.table, table.data(), nseg * sizeof(mir_block_desc)}};
+            ScopedSegments seg;
+            seg.blocks = sb.table;
+            return host_round_trip(w, s, in, nseg ? 3 : 2, sb.q, sb.in_span, sb.out, user, b, k, [&](const SearchOut &out) {
+                return enqueue_scoped(ix, sb.q, b, k, metric, P, sb, sb.scope_ptr, seg, out, s);
             });
         });
 }

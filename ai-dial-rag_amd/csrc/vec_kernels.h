@@ -251,6 +251,14 @@ __global__ __launch_bounds__(256) void row_norms_kernel(const T *__restrict__ sr
     if ((threadIdx.x & 63) == 0 && nrm > 0.f) atomicMax(max_norm_bits, __float_as_uint(nrm));
 }
 
+// doc_sq alone, one thread per row: a row block's squared norms (mir_rows_create), by the routine of the two kernels
+// around this one, so a block's value is bit for bit the one an index of the same rows holds
+template <typename T>
+__global__ __launch_bounds__(256) void row_sq_kernel(const T *__restrict__ src, int64_t n, int d, float *__restrict__ doc_sq) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row < n) doc_sq[row] = np_pairwise_sq<12>(src + row * (int64_t)d, d);
+}
+
 // The same per-row arithmetic with the rows staged through LDS: a workgroup copies `rows_per_wg` consecutive rows
 // (one contiguous piece of HBM, read coalesced by all 256 threads), then thread r sums row r out of LDS (row
 // stride odd in banks: no conflicts).  One thread per row straight from HBM reads every row as its own stream of

@@ -19,6 +19,13 @@
 //     position finds its segment by binary search there): any number of segments, nothing capped at an LDS size.
 //   * Safety: begin / end are clamped into [0, n] and end < begin is empty, so a row index is always begin + offset with
 //     offset < length: whatever the segment arrays hold, no row outside [0, n) is read.
+//
+// BLOCKS (mir_blocks_search): the same search over row blocks that stand on their own in HBM instead of over ranges of one
+// index.  Segment s is the block table[s]: its length is the block's n (clamped into [0, 2^32 - 1]), and its `emb` / `doc_sq`
+// pointers sit in LDS beside start[].  A row is emb[t] + (pos - start[t]) * d, its norm doc_sq[t][pos - start[t]]: the offset
+// is below the segment's length by construction, nothing is clamped against an n_rows, no row outside a listed block is read.
+// The result walk reads the block's chunk ids (null: the row number) and reports the row INSIDE its block.  Selection,
+// rounds, merge, arrival counter and bound cursor are the same code.
 #pragma once
 #include "vec_kernels.h"
 #include "vec_kernels_sieve.h"
@@ -46,6 +53,7 @@ struct ScopedArgs {
     const int32_t *scope_ptr;  // [b + 1]
     const int64_t *seg_begin;
     const int64_t *seg_end;
+    const mir_block_desc *blocks;  // BLOCKS: one descriptor per segment, in place of docs / docs16 / doc_sq / n_rows / seg_begin / seg_end / chunk_ids
     int k;
     int round;
     int list_stride;           // min(k, kExactRound)
@@ -70,18 +78,30 @@ __device__ __forceinline__ V scoped_max(V x, V y) { return x > y ? x : y; }
 
 struct ScopedWalk {
     uint64_t *start;   // [kScopedSegs] scope position of a segment's first row
-    uint32_t *row0;    // [kScopedSegs] its first row (clamped)
+    uint32_t *row0;    // [kScopedSegs] its first row (clamped); unused with BLOCKS
     uint64_t *wsum;    // [kScopedWaves]
+    const void **emb;     // BLOCKS: [kScopedSegs] the segment's rows
+    const float **dsq;    // BLOCKS: [kScopedSegs] their float32 squared norms
 };
 
 // Block-wide: segments [seg0, seg0 + kScopedSegs) of a list that ends at seg_hi -> their first positions and rows in LDS,
 // `base` = the position of segment seg0's first row.  Returns the position after the last of them.
+template <bool BLOCKS>
 __device__ __forceinline__ uint64_t scoped_load_segments(const ScopedArgs &a, int seg0, int seg_hi, uint64_t base, const ScopedWalk &w,
                                                          int tid) {
     const int lane = tid & 63, wave = tid >> 6;
     const int s = seg0 + tid;
     uint32_t begin = 0, len = 0;
-    if (s < seg_hi) {
+    const void *emb = nullptr;
+    const float *dsq = nullptr;
+    if constexpr (BLOCKS) {
+        if (s < seg_hi) {
+            const mir_block_desc bd = a.blocks[s];
+            len = (uint32_t)scoped_min(scoped_max(bd.n, (int64_t)0), (int64_t)0xffffffffll);
+            emb = bd.emb;
+            dsq = bd.doc_sq;
+        }
+    } else if (s < seg_hi) {
         const int64_t n = (int64_t)a.n_rows;
         const int64_t b = scoped_min(scoped_max(a.seg_begin[s], (int64_t)0), n), e = scoped_min(scoped_max(a.seg_end[s], (int64_t)0), n);
         begin = (uint32_t)b;
@@ -103,7 +123,12 @@ __device__ __forceinline__ uint64_t scoped_load_segments(const ScopedArgs &a, in
         total += t;
     }
     w.start[tid] = before + x - len;
-    w.row0[tid] = begin;
+    if constexpr (BLOCKS) {
+        w.emb[tid] = emb;
+        w.dsq[tid] = dsq;
+    } else {
+        w.row0[tid] = begin;
+    }
     __syncthreads();
     return total;
 }
@@ -120,7 +145,7 @@ __device__ __forceinline__ int scoped_find_segment(const ScopedWalk &w, int cn, 
     return t;
 }
 
-template <typename T, bool QLDS>
+template <typename T, bool QLDS, bool BLOCKS = false>
 __global__ __launch_bounds__(kScopedThreads) void scoped_topk_kernel(ScopedArgs a) {
     extern __shared__ __attribute__((aligned(16))) double s_q[];  // QLDS: the query (sieve_metric_g16 reads it as double2)
     __shared__ double s_d[kScopedThreads];
@@ -130,7 +155,9 @@ __global__ __launch_bounds__(kScopedThreads) void scoped_topk_kernel(ScopedArgs 
     __shared__ uint32_t s_row0[kScopedSegs];
     __shared__ uint64_t s_wsum[kScopedWaves];
     __shared__ int s_last;
-    const ScopedWalk walk{s_start, s_row0, s_wsum};
+    __shared__ const void *s_emb[BLOCKS ? kScopedSegs : 1];
+    __shared__ const float *s_dsq[BLOCKS ? kScopedSegs : 1];
+    const ScopedWalk walk{s_start, s_row0, s_wsum, s_emb, s_dsq};
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int qi = a.q0 + (int)blockIdx.y;
     const uint32_t P = gridDim.x, p = blockIdx.x;
@@ -147,7 +174,7 @@ __global__ __launch_bounds__(kScopedThreads) void scoped_topk_kernel(ScopedArgs 
 
     // ---- L = the scope's rows; this workgroup's share of the positions
     uint64_t L = 0;
-    for (int c = seg_lo; c < seg_hi; c += kScopedSegs) L = scoped_load_segments(a, c, seg_hi, L, walk, tid);
+    for (int c = seg_lo; c < seg_hi; c += kScopedSegs) L = scoped_load_segments<BLOCKS>(a, c, seg_hi, L, walk, tid);
     L = L < 0xffffffffull ? L : 0xffffffffull;  // positions are 32 bits
     const uint64_t share = (L + P - 1) / P;
     const uint64_t lo = scoped_min(L, (uint64_t)p * share), hi = scoped_min(L, lo + share);
@@ -163,18 +190,28 @@ __global__ __launch_bounds__(kScopedThreads) void scoped_topk_kernel(ScopedArgs 
     int cnt = 0;
     uint64_t base = 0;
     for (int c = seg_lo; c < seg_hi && base < hi; c += kScopedSegs) {  // (block-uniform)
-        const uint64_t end = scoped_load_segments(a, c, seg_hi, base, walk, tid);
+        const uint64_t end = scoped_load_segments<BLOCKS>(a, c, seg_hi, base, walk, tid);
         const int cn = min(kScopedSegs, seg_hi - c);
         const uint64_t p0 = scoped_max(lo, base), p1 = scoped_min(hi, end);
         for (uint64_t i0 = p0 + (uint64_t)wave * GPW; i0 < p1; i0 += (uint64_t)kScopedWaves * GPW) {
             const bool live = i0 + sub < p1;
             const uint64_t pos = live ? i0 + sub : i0;  // (a group without a row repeats the wave's first: no divergence)
             const int t = scoped_find_segment(walk, cn, pos);
-            uint32_t row = s_row0[t] + (uint32_t)(pos - s_start[t]);
-            row = min(row, a.n_rows - 1u);  // (already inside its segment; n_rows = 0 has no positions)
+            const T *rowp;
+            float row_sq;
+            if constexpr (BLOCKS) {
+                const uint32_t off = (uint32_t)(pos - s_start[t]);  // (below the block's n: the position lies inside segment t)
+                rowp = static_cast<const T *>(s_emb[t]) + (size_t)off * d;
+                row_sq = s_dsq[t][off];
+            } else {
+                uint32_t row = s_row0[t] + (uint32_t)(pos - s_start[t]);
+                row = min(row, a.n_rows - 1u);  // (already inside its segment; n_rows = 0 has no positions)
+                rowp = docs + (size_t)row * d;
+                row_sq = a.doc_sq[row];
+            }
             double rv, dist;
-            if (vec4) dist = sieve_metric_g16<T>(docs + (size_t)row * d, qv, d, a.metric, a.doc_sq[row], q_sq, q_norm, lg, &rv);
-            else dist = exact_metric_wave<T, GW, 8>(docs + (size_t)row * d, qv, d, a.metric, a.doc_sq[row], q_sq, q_norm, lg, &rv);
+            if (vec4) dist = sieve_metric_g16<T>(rowp, qv, d, a.metric, row_sq, q_sq, q_norm, lg, &rv);
+            else dist = exact_metric_wave<T, GW, 8>(rowp, qv, d, a.metric, row_sq, q_sq, q_norm, lg, &rv);
             const double worst_d = __shfl(my_d, kk - 1, 64);
             const uint32_t worst_p = __shfl(my_p, kk - 1, 64);
             bool ok = live && lg == 0 && (cnt < kk || dist_before(dist, (uint32_t)pos, worst_d, worst_p));
@@ -241,13 +278,20 @@ __global__ __launch_bounds__(kScopedThreads) void scoped_topk_kernel(ScopedArgs 
     if (a.out_doc || a.out_chunk || a.out_row) {
         base = 0;
         for (int c = seg_lo; c < seg_hi && base < L; c += kScopedSegs) {
-            const uint64_t end = scoped_load_segments(a, c, seg_hi, base, walk, tid);
+            const uint64_t end = scoped_load_segments<BLOCKS>(a, c, seg_hi, base, walk, tid);
             if (res && my_p >= base && my_p < end) {
                 const int t = scoped_find_segment(walk, min(kScopedSegs, seg_hi - c), my_p);
-                const uint32_t row = min(s_row0[t] + (uint32_t)(my_p - s_start[t]), a.n_rows - 1u);
                 if (a.out_doc) a.out_doc[o] = c - seg_lo + t;
-                if (a.out_chunk) a.out_chunk[o] = a.chunk_ids ? a.chunk_ids[row] : (int64_t)row;
-                if (a.out_row) a.out_row[o] = a.row_offset + (int64_t)row;
+                if constexpr (BLOCKS) {
+                    const uint32_t off = (uint32_t)(my_p - s_start[t]);
+                    const int64_t *chunk = a.blocks[c + t].chunk;
+                    if (a.out_chunk) a.out_chunk[o] = chunk ? chunk[off] : (int64_t)off;
+                    if (a.out_row) a.out_row[o] = (int64_t)off;
+                } else {
+                    const uint32_t row = min(s_row0[t] + (uint32_t)(my_p - s_start[t]), a.n_rows - 1u);
+                    if (a.out_chunk) a.out_chunk[o] = a.chunk_ids ? a.chunk_ids[row] : (int64_t)row;
+                    if (a.out_row) a.out_row[o] = a.row_offset + (int64_t)row;
+                }
             }
             base = end;
         }

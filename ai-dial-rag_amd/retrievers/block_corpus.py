@@ -1,0 +1,150 @@
+"""A corpus that changes: documents come and go, every request searches its own documents, nothing is built.
+
+``CorpusIndex`` takes its documents in its constructor: one new attachment means a new index over everything.  A
+``BlockCorpus`` holds each document as the ``DeviceRows`` block it already is in HBM, and a request's document list
+is a list of blocks: a *scope* of ``BlockSearcher.search`` (csrc/vec_kernels_scoped.h, BLOCKS).  No index is composed,
+no row is copied, a document is searchable as soon as its block exists and gone when its last holder is.  The result
+is the reference's for that request's document list (embeddings_index.py:62-89): the stable order on (distance,
+position of the document in the request, row), doc ids numbered by position in the request.
+
+Documents are named by KEYS that count up from 0 and are never reused; while nothing has been removed a key is the
+document's position, so a ``BlockCorpus`` stands where a ``CorpusIndex`` does (``CorpusHybrid``).
+"""
+
+import threading
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+from .. import _native as nat
+from ..index_record import Document, RetrievalType, to_metadata_doc
+from ._group_commit import _GroupCommit
+from .corpus_index import check_pass_item, run_grouped_pass
+from .embeddings_index import BlockSearcher, DeviceRows, DocIndex
+from .embeddings_metrics import Metric
+
+__all__ = ["BlockCorpus", "BlockView"]
+
+
+class BlockView:
+    """``CorpusView``'s surface over some documents of a ``BlockCorpus``: ``find(query)`` and ``find_batch``.
+    ``doc_id`` of a result = the position of its document in ``keys``.  The view HOLDS its blocks: it answers as it
+    did when it was made, whatever is removed from the corpus afterwards."""
+
+    def __init__(self, corpus: "BlockCorpus", keys: Sequence[int], retrieval_type: RetrievalType, metric, limit: int):
+        self.corpus = corpus
+        self.keys = [int(k) for k in keys]
+        self.retrieval_type = retrieval_type
+        self.metric = metric
+        self.limit = int(limit)
+        Metric(metric)  # unknown metric -> ValueError, as embeddings_index.py:54
+        if self.limit < 1:
+            raise ValueError(f"limit={limit} must be >= 1")
+        self.blocks = corpus._blocks_of(self.keys)  # KeyError for a removed key
+
+    def _documents(self, doc, chunk, cnt) -> List[Document]:
+        return [to_metadata_doc(int(doc[j]), int(chunk[j]), retrieval_type=self.retrieval_type) for j in range(int(cnt))]
+
+    def find(self, query: np.ndarray) -> List[Document]:
+        """One query; concurrent callers of ANY view of the corpus share passes."""
+        doc, chunk, _dist, cnt = self.corpus._commit.submit((query, self))
+        return self._documents(doc, chunk, cnt)
+
+    def find_batch(self, queries: np.ndarray) -> List[List[Document]]:
+        q = np.atleast_2d(np.asarray(queries, dtype=np.float64))
+        doc, chunk, _dist, cnt = self.corpus._search_blocks(q, self.limit, self.metric, [self.blocks] * len(q))
+        return [self._documents(doc[i], chunk[i], cnt[i]) for i in range(len(q))]
+
+
+class BlockCorpus:
+    """``add`` / ``remove`` / ``view`` / ``find_many`` may be called from any thread, also while searches run: a search
+    works on the ``DeviceRows`` objects it took when it was submitted."""
+
+    def __init__(self, device: int = 0, max_batch: int = 256):
+        self.device = device
+        self.d: Optional[int] = None      # fixed by the first non-empty document, with
+        self.dtype: Optional[int] = None  # its storage type
+        self._docs: Dict[int, Optional[DeviceRows]] = {}  # key -> block; None = a document without rows (any d)
+        self._next_key = 0
+        self._lock = threading.Lock()
+        self._searcher: Optional[BlockSearcher] = None
+        self._empty: Optional[DeviceRows] = None  # what an empty document is to the device search: a block of 0 rows
+        self._commit = _GroupCommit(self._run_pass, max_batch=max_batch, validate=lambda item: check_pass_item(item, self.d))
+
+    # ---- documents --------------------------------------------------------------------------------------------
+    def _upload(self, doc: DocIndex) -> DeviceRows:
+        return DeviceRows.from_host(np.asarray(doc.embeddings), np.asarray(doc.chunk_ids, dtype=np.int64), self.device)
+
+    def add(self, doc) -> int:
+        """``doc``: a ``DocIndex`` (uploaded once as a block) or a ``DeviceRows`` (adopted, not copied) -> its key."""
+        if isinstance(doc, DeviceRows):
+            block = doc if doc.n > 0 else None
+        else:
+            block = self._upload(doc) if len(doc.embeddings) > 0 else None
+        with self._lock:
+            if block is not None:
+                if block.device != self.device:
+                    raise ValueError(f"the block lives on device {block.device}, the corpus on {self.device}")
+                if self.d is None:
+                    self.d, self.dtype = block.d, block.dtype
+                elif (block.d, block.dtype) != (self.d, self.dtype):
+                    raise ValueError(f"document is {block.d}-dimensional dtype {block.dtype}, the corpus {self.d}-dimensional dtype {self.dtype}")
+            key = self._next_key
+            self._next_key += 1
+            self._docs[key] = block
+            return key
+
+    def remove(self, key: int) -> None:
+        """The corpus forgets the block; its HBM goes with the last view or running search that holds it."""
+        with self._lock:
+            del self._docs[int(key)]  # KeyError: unknown or removed
+
+    def _blocks_of(self, keys: Sequence[int]) -> List[Optional[DeviceRows]]:
+        with self._lock:
+            return [self._docs[int(k)] for k in keys]
+
+    def __len__(self) -> int:
+        with self._lock:
+            return len(self._docs)
+
+    def __contains__(self, key) -> bool:
+        with self._lock:
+            return key in self._docs
+
+    def hbm_bytes(self) -> int:
+        with self._lock:
+            blocks = [b for b in self._docs.values() if b is not None]
+        return sum(b.hbm_bytes() for b in blocks)
+
+    # ---- the device search ------------------------------------------------------------------------------------
+    def _search_blocks(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence[Optional[DeviceRows]]]):
+        """(doc, chunk, dist, count); a scope lists blocks, None = a document without rows.  The one place that touches
+        the GPU."""
+        with self._lock:
+            d, dtype = self.d, self.dtype
+            if d is not None and self._searcher is None:
+                self._searcher = BlockSearcher(d, dtype, self.device)
+                self._empty = DeviceRows.from_host(np.zeros((0, d), np.float16 if dtype == nat.DTYPE_F16 else np.float32), None, self.device)
+            searcher, empty = self._searcher, self._empty
+        if searcher is None:  # no document with rows yet
+            b = len(queries)
+            return np.zeros((b, k), np.int32), np.zeros((b, k), np.int64), np.zeros((b, k)), np.zeros(b, np.int32)
+        doc, chunk, _row, dist, cnt, _flags = searcher.search(queries, k, metric, [[empty if blk is None else blk for blk in s] for s in scopes])
+        return doc, chunk, dist, cnt
+
+    # ---- the public surface -----------------------------------------------------------------------------------
+    def view(self, keys: Sequence[int], retrieval_type: RetrievalType, metric=Metric.SQEUCLIDEAN_DIST, limit: int = 1) -> BlockView:
+        return BlockView(self, keys, retrieval_type, metric, limit)
+
+    def find_many(self, queries: np.ndarray, scopes: Sequence[Sequence[int]], metric=Metric.SQEUCLIDEAN_DIST, limit: int = 1):
+        """The explicit batch form: query i searches the documents ``scopes[i]`` (keys of the corpus) ->
+        (doc_ids[b, limit] = positions inside scopes[i], chunk_ids[b, limit], dist[b, limit], count[b])."""
+        Metric(metric)
+        q = np.atleast_2d(np.asarray(queries, dtype=np.float64))
+        if len(scopes) != len(q):
+            raise ValueError(f"{len(scopes)} scopes for {len(q)} queries")
+        return self._search_blocks(q, int(limit), metric, [self._blocks_of(s) for s in scopes])
+
+    def _run_pass(self, items):
+        """``run_grouped_pass`` over the blocks the views hold."""
+        return run_grouped_pass(items, lambda q, views, metric, k: self._search_blocks(q, k, metric, [v.blocks for v in views]))

@@ -24,6 +24,38 @@ from .embeddings_metrics import Metric
 __all__ = ["CorpusIndex", "CorpusView", "scope_segments"]
 
 
+def check_pass_item(item, d: Optional[int]):
+    """(query, view) of a shared pass, checked in the caller's thread: ONE float64 vector of the corpus's dimension."""
+    query, view = item
+    q = np.asarray(query, dtype=np.float64)
+    if q.ndim != 1:
+        raise ValueError(f"query must be one vector, got shape {q.shape}")
+    if d is not None and q.shape[0] != d:
+        raise ValueError(f"query shape {q.shape} does not match index dimension {d}")
+    return q, view
+
+
+def run_grouped_pass(items, search):
+    """One shared pass over (query, view) items of any views of one corpus (``CorpusIndex``, ``BlockCorpus``):
+    one ``search(queries, views, metric, k) -> (doc, chunk, dist, count)`` per metric among the items, with the largest
+    limit among them; an item keeps the first `limit` of its row (the order is total, so a top-k' is a prefix of a
+    top-k).  The results of an item do not depend on its fellow riders, its latency does: the kernel scans every scope
+    of the launch once per round of 64 results, so one view with limit > 64 makes each rider of that pass pay
+    ceil(limit / 64) scans."""
+    out = [None] * len(items)
+    groups: dict = {}
+    for i, (_, view) in enumerate(items):
+        groups.setdefault(Metric(view.metric), []).append(i)
+    for metric, members in groups.items():
+        k = max(items[i][1].limit for i in members)
+        q = np.stack([items[i][0] for i in members])
+        doc, chunk, dist, cnt = search(q, [items[i][1] for i in members], metric, k)
+        for j, i in enumerate(members):
+            m = min(int(cnt[j]), items[i][1].limit)
+            out[i] = (doc[j, :m], chunk[j, :m], dist[j, :m], m)
+    return tuple([o[c] for o in out] for c in range(4))
+
+
 class CorpusView:
     """The reference's ``EmbeddingsIndex`` surface over some documents of a corpus: ``find(query)`` and
     ``find_batch``.  ``doc_id`` of a result = the position of its document in ``doc_positions``."""
@@ -118,28 +150,8 @@ class CorpusIndex:
 
     # ---- shared passes: an item is (query, view) --------------------------------------------------------------
     def _check_item(self, item):
-        query, view = item
-        q = np.asarray(query, dtype=np.float64)
-        if q.ndim != 1:
-            raise ValueError(f"query must be one vector, got shape {q.shape}")
-        if self.d is not None and q.shape[0] != self.d:
-            raise ValueError(f"query shape {q.shape} does not match index dimension {self.d}")
-        return q, view
+        return check_pass_item(item, self.d)
 
     def _run_pass(self, items):
-        """One search per metric among the items, with the largest limit among them; an item keeps the first
-        `limit` of its row (the order is total, so a top-k' is a prefix of a top-k).  The results of an item do not
-        depend on its fellow riders, its latency does: the kernel scans every scope of the launch once per round of
-        64 results, so one view with limit > 64 makes each rider of that pass pay ceil(limit / 64) scans."""
-        out = [None] * len(items)
-        groups: dict = {}
-        for i, (_, view) in enumerate(items):
-            groups.setdefault(Metric(view.metric), []).append(i)
-        for metric, members in groups.items():
-            k = max(items[i][1].limit for i in members)
-            q = np.stack([items[i][0] for i in members])
-            doc, chunk, dist, cnt = self._search_segments(q, [(items[i][1].seg_begin, items[i][1].seg_end) for i in members], metric, k)
-            for j, i in enumerate(members):
-                m = min(int(cnt[j]), items[i][1].limit)
-                out[i] = (doc[j, :m], chunk[j, :m], dist[j, :m], m)
-        return tuple([o[c] for o in out] for c in range(4))
+        """``run_grouped_pass`` over this corpus's row segments."""
+        return run_grouped_pass(items, lambda q, views, metric, k: self._search_segments(q, [(v.seg_begin, v.seg_end) for v in views], metric, k))

@@ -58,8 +58,8 @@ class DeviceRows:
     """Owner of one ``mir_rows`` handle: ONE document's rows (and chunk ids) resident in HBM.  Indexes over any
     set of documents are composed from these device-to-device (``DeviceIndex.from_rows``)."""
 
-    def __init__(self, handle: C.c_void_p, n: int, d: int, device: int):
-        self._h, self.n, self.d, self.device = handle, n, d, device
+    def __init__(self, handle: C.c_void_p, n: int, d: int, device: int, dtype: int = nat.DTYPE_F32):
+        self._h, self.n, self.d, self.device, self.dtype = handle, n, d, device, dtype
 
     @classmethod
     def from_host(cls, emb: np.ndarray, chunk_ids=None, device: int = 0):
@@ -74,7 +74,7 @@ class DeviceRows:
             raise ValueError(f"{len(ci)} chunk ids for {n} rows")
         h = C.c_void_p()
         nat.check(nat.lib.mir_rows_create(nat.ptr(emb), n, d, dtype, nat.ptr(ci), device, C.byref(h)))
-        return cls(h, n, d, device)
+        return cls(h, n, d, device, dtype)
 
     @property
     def handle(self):
@@ -85,9 +85,79 @@ class DeviceRows:
         nat.check(nat.lib.mir_rows_info(self._h, None, None, None, None, C.byref(b)))
         return int(b.value)
 
+    def desc(self) -> Tuple[int, int, int, int]:
+        """(emb, doc_sq, chunk, n): the block's device pointers as ints and its row count - one entry of the descriptor
+        table ``BlockSearcher.search_device`` reads (32 bytes: three pointers and an int64, in this order)."""
+        out = nat.BlockDesc()
+        nat.check(nat.lib.mir_rows_desc(self._h, C.byref(out)))
+        return int(out.emb or 0), int(out.doc_sq or 0), int(out.chunk or 0), int(out.n)
+
     def close(self):
         if self._h:
             nat.lib.mir_rows_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BlockSearcher:
+    """Owner of one ``mir_blocks`` handle: a searcher over ``DeviceRows`` blocks of one (d, dtype, device).  It holds
+    workspaces only; the rows stay in their blocks, nothing is composed or copied (csrc/vec_kernels_scoped.h, BLOCKS)."""
+
+    def __init__(self, d: int, dtype: int = nat.DTYPE_F32, device: int = 0):
+        h = C.c_void_p()
+        nat.check(nat.lib.mir_blocks_create(d, dtype, device, C.byref(h)))
+        self._h, self.d, self.dtype, self.device = h, d, dtype, device
+
+    @property
+    def handle(self):
+        return self._h
+
+    def search(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence["DeviceRows"]]) -> Tuple[np.ndarray, ...]:
+        """Query q searches the rows of ``scopes[q]``'s blocks concatenated in that order.  Returns the six arrays of
+        ``DeviceIndex.search_scoped``: doc = the ordinal of the block inside the scope, chunk = the block's chunk id,
+        row = the row INSIDE its block, count[q] = min(k, rows of the scope).  The blocks are held until the call returns."""
+        q = nat.as_f64_queries(queries, self.d)
+        b = q.shape[0]
+        code = nat.METRIC_CODES[Metric(metric).value]
+        if len(scopes) != b:
+            raise ValueError(f"{len(scopes)} scopes for {b} queries")
+        held = [blk for s in scopes for blk in s]  # (alive across the call)
+        sp = np.zeros(b + 1, np.int32)
+        np.cumsum([len(s) for s in scopes], out=sp[1:])
+        table = (C.c_void_p * max(len(held), 1))(*[blk.handle for blk in held])
+        return self._search_raw(q, k, code, sp, table)
+
+    def _search_raw(self, q: np.ndarray, k: int, code: int, sp: np.ndarray, table) -> Tuple[np.ndarray, ...]:
+        b = q.shape[0]
+        doc = np.zeros((b, max(k, 0)), np.int32)
+        chunk = np.zeros((b, max(k, 0)), np.int64)
+        row = np.zeros((b, max(k, 0)), np.int64)
+        dist = np.zeros((b, max(k, 0)), np.float64)
+        cnt = np.zeros(b, np.int32)
+        flg = np.zeros(b, np.int32)
+        nat.check(nat.lib.mir_blocks_search(self._h, nat.ptr(q), b, k, code, nat.ptr(sp), table, nat.ptr(doc), nat.ptr(chunk), nat.ptr(row),
+                                            nat.ptr(dist), nat.ptr(cnt), nat.ptr(flg)))
+        return doc, chunk, row, dist, cnt, flg
+
+    def search_device(self, q_ptr: int, b: int, k: int, metric, scope_ptr_ptr: int, table_ptr: int, out_row_ptr: int, out_dist_ptr: int,
+                      out_count_ptr: int, out_flags_ptr: int = 0, out_doc_ptr: int = 0, out_chunk_ptr: int = 0, stream: int = 0) -> None:
+        """Asynchronous block search with every buffer in HBM (pointers as ints).  ``table_ptr``: one 32-byte descriptor
+        per listed block (``DeviceRows.desc()``).  Nothing in scope_ptr or the table is validated: both are trusted, a
+        descriptor that does not describe its block makes the kernel read outside it.  The caller keeps the blocks alive
+        until the stream has passed the call."""
+        code = nat.METRIC_CODES[Metric(metric).value]
+        nat.check(nat.lib.mir_blocks_search_device(self._h, q_ptr, b, k, code, scope_ptr_ptr or None, table_ptr or None, out_doc_ptr or None,
+                                                   out_chunk_ptr or None, out_row_ptr or None, out_dist_ptr or None, out_count_ptr,
+                                                   out_flags_ptr or None, stream or None))
+
+    def close(self):
+        if self._h:
+            nat.lib.mir_blocks_destroy(self._h)
             self._h = None
 
     def __del__(self):

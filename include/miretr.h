@@ -32,7 +32,11 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: scoped BM25: mir_bm25_create_corpus, mir_bm25_scope_*, mir_bm25_scores_scoped / _search_scoped;
+#define MIR_ABI_VERSION 6 /* 6: block search, ADDED without a new number (no entry of ABI 6 changed its signature or meaning, a caller
+                               built against the earlier header runs unchanged): mir_blocks_create / _destroy / _search /
+                               _search_device, mir_rows_desc; a mir_rows block keeps its rows' float32 squared norms
+                               (mir_rows_info's hbm_bytes grew by 4 n);
+                            6: scoped BM25: mir_bm25_create_corpus, mir_bm25_scope_*, mir_bm25_scores_scoped / _search_scoped;
                             5: mir_index_search_scoped[_device];
                             4: mir_keywords_preprocess / mir_kwp_result_*;
                             3: 2: results always exact (exact pass), any k; mir_bm25_tune / _corpus_stats / _idf_from_stats /
@@ -123,6 +127,7 @@ int32_t mir_index_create_from_device(const void *emb_device, int64_t n, int32_t 
 typedef struct mir_rows mir_rows;
 int32_t mir_rows_create(const void *emb_host, int64_t n, int32_t d, int32_t dtype,
                         const int64_t *chunk_ids_host, int32_t device, mir_rows **out);
+/* hbm_bytes: the rows, their chunk ids and (since the block search) their float32 squared norms */
 int32_t mir_rows_info(const mir_rows *rows, int64_t *n, int32_t *d, int32_t *dtype, int32_t *device,
                       int64_t *hbm_bytes);
 int32_t mir_rows_destroy(mir_rows *rows);
@@ -183,6 +188,41 @@ int32_t mir_index_search_scoped_device(mir_index *idx, const double *queries_dev
                                        const int64_t *seg_begin_device, const int64_t *seg_end_device,
                                        int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist,
                                        int32_t *out_count, int32_t *out_flags, void *stream);
+
+/* Block search (added within ABI 6): the scoped search over row blocks themselves, no index to build (csrc/vec_kernels_scoped.h, BLOCKS).
+ * A mir_blocks handle is a SEARCHER: it owns workspaces only, no rows, and serves concurrent calls like an index handle.
+ * Query q searches blocks[scope_ptr[q] .. scope_ptr[q + 1]) in that order: its scope is their rows concatenated, one
+ * segment per listed block.  Semantics are mir_index_search_scoped's: the answer is the first out_count[q] = min(k, L_q)
+ * scope positions under (distance ascending, NaN last, position ascending), distances by the reference's float64 formula
+ * from the stored rows and the block's float32 squared norms (computed at mir_rows_create by the routine the index's
+ * norm kernels use: bit for bit the values an index composed of the blocks holds).
+ *   out_doc   : the ORDINAL of the row's block inside the query's scope
+ *   out_chunk : the block's chunk id of the row;  out_row : the row INSIDE its block;  out_flags : 0
+ * An empty block (n = 0) keeps its ordinal; a block may be listed twice; a scope holds fewer than 2^32 rows; any k >= 1.
+ * float16 blocks are read as float16 at any d.  Any of out_doc / out_chunk / out_row / out_dist / out_flags may be NULL.
+ * The host form returns MIR_ERR_INVALID, before anything is launched, for a NULL handle, scope_ptr[0] != 0, a decreasing
+ * scope_ptr, a NULL entry of `blocks`, a block whose d, dtype or device differs from the searcher's, a scope of 2^32 rows or
+ * more, k < 1 and an unknown metric.  The caller keeps every listed block alive until the call returns. */
+typedef struct mir_blocks mir_blocks;
+int32_t mir_blocks_create(int32_t d, int32_t dtype, int32_t device, mir_blocks **out);
+int32_t mir_blocks_destroy(mir_blocks *s);
+int32_t mir_blocks_search(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                          const int32_t *scope_ptr_host, const mir_rows *const *blocks_host, int32_t *out_doc,
+                          int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags);
+
+/* The same with every buffer in HBM, asynchronous on `stream` (no synchronisation).  table_device holds one descriptor
+ * per listed block (mir_rows_desc gives a block's: DEVICE pointers; an empty block has n = 0 and null pointers; a null
+ * `chunk` means the row number).  This form cannot see scope_ptr or the table and validates nothing in them: it TRUSTS
+ * that scope_ptr is non-decreasing from 0 and indexes inside the table, and that every descriptor names n rows of the
+ * searcher's d and dtype with their n squared norms; the kernel only clamps n into [0, 2^32 - 1] and cuts a scope off at
+ * 2^32 - 1 rows.  A descriptor that lies about its block makes the kernel read outside it.  The caller keeps every
+ * listed block alive until `stream` has passed the call. */
+typedef struct { const void *emb; const float *doc_sq; const int64_t *chunk; int64_t n; } mir_block_desc;
+int32_t mir_rows_desc(const mir_rows *rows, mir_block_desc *out);
+int32_t mir_blocks_search_device(mir_blocks *s, const double *queries_device, int32_t b, int32_t k, int32_t metric,
+                                 const int32_t *scope_ptr_device, const mir_block_desc *table_device, int32_t *out_doc,
+                                 int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
+                                 int32_t *out_flags, void *stream);
 
 /* Benchmark instrumentation: when enabled, every launch of the scan kernel (the
  * dominant, HBM-streaming kernel) is bracketed by HIP events on the stream it
