@@ -107,6 +107,17 @@ def _load():
         "mir_bm25_scope_idf": ([vp, vp], i32),
         "mir_bm25_scores_scoped": ([vp, vp, vp, i32, vp], i32),
         "mir_bm25_search_scoped": ([vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp], i32),
+        "mir_bm25_doc_create": ([vp, vp, i64, vp, i32, vp], i32),
+        "mir_bm25_doc_info": ([vp, vp, vp, vp, vp, vp, vp], i32),
+        "mir_bm25_doc_destroy": ([vp], i32),
+        "mir_bm25_blocks_create": ([C.c_double, C.c_double, C.c_double, i32, vp], i32),
+        "mir_bm25_blocks_destroy": ([vp], i32),
+        "mir_bm25_blocks_scope_create": ([vp, vp, i32, vp], i32),
+        "mir_bm25_blocks_scope_info": ([vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "mir_bm25_blocks_scope_idf": ([vp, vp], i32),
+        "mir_bm25_blocks_scope_destroy": ([vp], i32),
+        "mir_bm25_blocks_scores": ([vp, vp, vp, i32, vp], i32),
+        "mir_bm25_blocks_search": ([vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp], i32),
         "mir_encoder_create": ([i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp], i32),
         "mir_encoder_destroy": ([vp], i32),
         "mir_encoder_info": ([vp, vp, vp, vp], i32),

@@ -32,7 +32,8 @@
 //   bm25_tile_kernel    the exact dense pass (all 8192 documents of a tile, zeros and negatives included) for the flagged
 //                       queries, whose last tile merges them; also get_scores
 // Scoped BM25 - every query ranks its own document segments of one model, with that request's idf and avgdl - has its
-// own kernels in bm25_scoped.h and its entries at the end of this file.
+// own kernels in bm25_scoped.h and its entries near the end of this file.  Block BM25 - the same over resident per-document
+// keyword blocks, no corpus model - has its kernels in bm25_blocks.h and its entries after those.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1259,6 +1260,7 @@ __global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const doubl
 }  // namespace mir
 
 #include "bm25_scoped.h"
+#include "bm25_blocks.h"
 
 using namespace mir;
 
@@ -2002,6 +2004,382 @@ int32_t mir_bm25_search_scoped(mir_bm25 *h, const mir_bm25_scope *const *scopes,
         if (out_doc) MIR_HIP(hipMemcpyAsync(out_doc, base + o_doc, bk * 8, hipMemcpyDeviceToHost, s));
         if (out_score) MIR_HIP(hipMemcpyAsync(out_score, base + o_sc, bk * 8, hipMemcpyDeviceToHost, s));
         if (out_ord) MIR_HIP(hipMemcpyAsync(out_ord, base + o_ord, bk * 4, hipMemcpyDeviceToHost, s));
+        if (out_count) MIR_HIP(hipMemcpyAsync(out_count, base + o_cnt, (size_t)b * 4, hipMemcpyDeviceToHost, s));
+        return MIR_OK;
+    };
+    rc = launch();
+    if (rc != MIR_OK) { (void)hipStreamSynchronize(s); return rc; }
+    MIR_HIP(hipStreamSynchronize(s));
+    return MIR_OK;
+}
+
+// ---- block BM25 (bm25_blocks.h): resident per-document keyword blocks, every query ranks its own list of them ----------
+
+struct mir_bm25_doc {
+    int device = 0;
+    int64_t n_chunks = 0, n_tokens = 0, U = 0, P = 0;
+    int32_t max_term = -1;  // the largest term id (-1: no token)
+    int64_t hbm_bytes = 0;
+    Bm25DocBuilt d;
+};
+
+// A searcher: the stream, the scratch and the mutex of the block route; it owns no documents.
+struct mir_bm25_blocks {
+    int device = 0;
+    double k1 = 1.5, b = 0.75, epsilon = 0.25;
+    std::mutex mu;  // serialises use of the scratch below
+    void *scratch = nullptr;
+    size_t scratch_cap = 0;
+    hipStream_t stream = nullptr;
+};
+
+// A scope of a searcher (mir_bm25_blocks_scope_create): immutable once built, shared by any number of searches.
+struct mir_bm25_blocks_scope {
+    mir_bm25_blocks *searcher = nullptr;  // compared, never dereferenced after creation
+    int device = 0;
+    int32_t n_blk = 0, n_terms = 0, vocab = 0;
+    int64_t n_pos = 0, total_tokens = 0;
+    double avgdl = 0.0, average_idf = 0.0;
+    std::vector<double> h_idf;
+    Bm25BlockDev *blk = nullptr;  // [n_blk] in HBM
+    int64_t *pos = nullptr;       // [n_blk + 1]
+    double *idf = nullptr;        // [vocab]
+    int64_t hbm_bytes = 0;
+};
+
+static void free_doc(mir_bm25_doc *d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    (void)hipFree(d->d.terms);
+    (void)hipFree(d->d.t_ptr);
+    (void)hipFree(d->d.first);
+    (void)hipFree(d->d.p_chunk);
+    (void)hipFree(d->d.p_tf);
+    (void)hipFree(d->d.doc_len);
+    (void)hipFree(d->d.chunk);
+    delete d;
+}
+
+static void free_blocks_scope(mir_bm25_blocks_scope *sc) {
+    if (!sc) return;
+    (void)hipSetDevice(sc->device);
+    (void)hipFree(sc->blk);
+    (void)hipFree(sc->pos);
+    (void)hipFree(sc->idf);
+    delete sc;
+}
+
+static int32_t blocks_scratch(mir_bm25_blocks *h, size_t need) {
+    if (h->scratch_cap >= need) return MIR_OK;
+    if (h->scratch) (void)hipFree(h->scratch);
+    h->scratch = nullptr;
+    h->scratch_cap = 0;
+    MIR_HIP(hipMalloc(&h->scratch, need));
+    h->scratch_cap = need;
+    return MIR_OK;
+}
+
+int32_t mir_bm25_doc_create(const int64_t *indptr, const int32_t *term_ids, int64_t n_chunks, const int64_t *chunk_ids, int32_t device,
+                            mir_bm25_doc **out) {
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    // host checks first: nothing is allocated for a malformed document
+    MIR_REQUIRE(n_chunks >= 0 && n_chunks < ((int64_t)1 << 31), "n_chunks=%lld out of range", (long long)n_chunks);
+    MIR_REQUIRE(n_chunks == 0 || indptr != nullptr, "indptr is NULL");
+    for (int64_t i = 0; i < n_chunks; ++i) MIR_REQUIRE(indptr[i + 1] >= indptr[i], "indptr decreases at %lld", (long long)i);
+    const int64_t total = n_chunks ? indptr[n_chunks] - indptr[0] : 0;
+    MIR_REQUIRE(total < ((int64_t)1 << 31), "%lld tokens: more than 2^31 - 1 in one document", (long long)total);
+    MIR_REQUIRE(total == 0 || term_ids != nullptr, "term_ids is NULL");
+    int32_t max_term = -1;
+    for (int64_t j = 0; j < total; ++j) {
+        const int32_t t = term_ids[indptr[0] + j];
+        MIR_REQUIRE(t >= 0, "term id %d at token %lld is negative", t, (long long)j);
+        max_term = std::max(max_term, t);
+    }
+    int32_t rc = use_device(device, nullptr);
+    if (rc != MIR_OK) return rc;
+    mir_bm25_doc *d = new (std::nothrow) mir_bm25_doc();
+    MIR_REQUIRE(d != nullptr, "out of host memory");
+    d->device = device; d->n_chunks = n_chunks; d->n_tokens = total; d->max_term = max_term;
+    int term_bits = 1;
+    while (term_bits < 31 && ((int64_t)1 << term_bits) <= (int64_t)max_term) ++term_bits;
+    rc = bm25_doc_build_device(indptr, term_ids, n_chunks, chunk_ids, term_bits, &d->d);
+    if (rc != MIR_OK) {
+        free_doc(d);
+        return rc;
+    }
+    d->U = d->d.U; d->P = d->d.P; d->hbm_bytes = d->d.hbm_bytes;
+    *out = d;
+    return MIR_OK;
+}
+
+int32_t mir_bm25_doc_destroy(mir_bm25_doc *doc) {
+    free_doc(doc);
+    return MIR_OK;
+}
+
+int32_t mir_bm25_doc_info(const mir_bm25_doc *doc, int64_t *n_chunks, int64_t *n_tokens, int64_t *n_terms, int64_t *n_postings,
+                          int32_t *max_term, int64_t *hbm_bytes) {
+    MIR_REQUIRE(doc != nullptr, "document block is NULL");
+    if (n_chunks) *n_chunks = doc->n_chunks;
+    if (n_tokens) *n_tokens = doc->n_tokens;
+    if (n_terms) *n_terms = doc->U;
+    if (n_postings) *n_postings = doc->P;
+    if (max_term) *max_term = doc->max_term;
+    if (hbm_bytes) *hbm_bytes = doc->hbm_bytes;
+    return MIR_OK;
+}
+
+int32_t mir_bm25_blocks_create(double k1, double b, double epsilon, int32_t device, mir_bm25_blocks **out) {
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    int32_t rc = use_device(device, nullptr);
+    if (rc != MIR_OK) return rc;
+    mir_bm25_blocks *h = new (std::nothrow) mir_bm25_blocks();
+    MIR_REQUIRE(h != nullptr, "out of host memory");
+    h->device = device; h->k1 = k1; h->b = b; h->epsilon = epsilon;
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        set_error("hipStreamCreateWithFlags failed: %s", hipGetErrorString(e));
+        delete h;
+        return MIR_ERR_HIP;
+    }
+    *out = h;
+    return MIR_OK;
+}
+
+int32_t mir_bm25_blocks_destroy(mir_bm25_blocks *h) {
+    if (!h) return MIR_OK;
+    (void)hipSetDevice(h->device);
+    (void)hipFree(h->scratch);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return MIR_OK;
+}
+
+int32_t mir_bm25_blocks_scope_create(mir_bm25_blocks *h, const mir_bm25_doc *const *docs, int32_t n, mir_bm25_blocks_scope **out) {
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    MIR_REQUIRE(h != nullptr, "searcher is NULL");
+    MIR_REQUIRE(n >= 0 && (n == 0 || docs != nullptr), "bad document list (n=%d)", n);
+    // host check first: nothing is launched for a malformed scope
+    std::vector<Bm25BlockDev> table((size_t)n);
+    std::vector<int64_t> pos((size_t)n + 1, 0), tok((size_t)n + 1, 0), upre((size_t)n + 1, 0);
+    int32_t max_term = -1;
+    for (int32_t s = 0; s < n; ++s) {
+        const mir_bm25_doc *d = docs[s];
+        MIR_REQUIRE(d != nullptr, "document block %d is NULL", s);
+        MIR_REQUIRE(d->device == h->device, "document block %d lives on device %d, the searcher on %d", s, d->device, h->device);
+        Bm25BlockDev &t = table[s];
+        t.terms = d->d.terms; t.t_ptr = d->d.t_ptr; t.first = d->d.first; t.p_chunk = d->d.p_chunk; t.p_tf = d->d.p_tf;
+        t.doc_len = d->d.doc_len; t.chunk = d->d.chunk; t.U = (int32_t)d->U; t.n_chunks = (int32_t)d->n_chunks;
+        pos[s + 1] = pos[s] + d->n_chunks;
+        tok[s + 1] = tok[s] + d->n_tokens;
+        upre[s + 1] = upre[s] + d->U;
+        max_term = std::max(max_term, d->max_term);
+    }
+    const int64_t L = pos[n], total = tok[n], total_u = upre[n];
+    MIR_REQUIRE(L < ((int64_t)1 << 31), "scope of %lld chunks: 2^31 or more", (long long)L);
+    if (total == 0) {
+        set_error("Text index is empty.");  // bm25_retriever.py:75-76 on the request's own documents
+        return MIR_ERR_EMPTY;
+    }
+    int32_t rc = use_device(h->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    mir_bm25_blocks_scope *sc = new (std::nothrow) mir_bm25_blocks_scope();
+    MIR_REQUIRE(sc != nullptr, "out of host memory");
+    const int32_t V = max_term + 1;  // >= 1: there is a token
+    sc->searcher = h; sc->device = h->device; sc->n_blk = n; sc->vocab = V; sc->n_pos = L; sc->total_tokens = total;
+    sc->avgdl = (double)total / (double)L;
+    int64_t *d_tok = nullptr, *d_upre = nullptr;
+    unsigned long long *d_df = nullptr, *d_first = nullptr;
+    std::vector<int64_t> df((size_t)V), first((size_t)V);
+    auto run = [&]() -> int32_t {
+        MIR_HIP(hipMalloc((void **)&sc->blk, (size_t)n * sizeof(Bm25BlockDev)));
+        MIR_HIP(hipMalloc((void **)&sc->pos, ((size_t)n + 1) * 8));
+        MIR_HIP(hipMalloc((void **)&sc->idf, (size_t)V * 8));
+        MIR_HIP(hipMalloc((void **)&d_tok, ((size_t)n + 1) * 8));
+        MIR_HIP(hipMalloc((void **)&d_upre, ((size_t)n + 1) * 8));
+        MIR_HIP(hipMalloc((void **)&d_df, (size_t)V * 8));
+        MIR_HIP(hipMalloc((void **)&d_first, (size_t)V * 8));
+        sc->hbm_bytes = (int64_t)n * (int64_t)sizeof(Bm25BlockDev) + ((int64_t)n + 1) * 8 + (int64_t)V * 8;
+        std::lock_guard<std::mutex> lk(h->mu);
+        hipStream_t s = h->stream;
+        MIR_HIP(hipMemcpyAsync(sc->blk, table.data(), (size_t)n * sizeof(Bm25BlockDev), hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemcpyAsync(sc->pos, pos.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemcpyAsync(d_tok, tok.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemcpyAsync(d_upre, upre.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemsetAsync(d_df, 0, (size_t)V * 8, s));
+        MIR_HIP(hipMemsetAsync(d_first, 0xff, (size_t)V * 8, s));
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total_u + 255) / 256, 1 << 16));
+        bm25_blocks_stats_kernel<<<dim3(grid), dim3(256), 0, s>>>(sc->blk, d_upre, d_tok, n, total_u, V, d_df, d_first);
+        MIR_HIP(hipGetLastError());
+        MIR_HIP(hipMemcpyAsync(df.data(), d_df, (size_t)V * 8, hipMemcpyDeviceToHost, s));
+        MIR_HIP(hipMemcpyAsync(first.data(), d_first, (size_t)V * 8, hipMemcpyDeviceToHost, s));
+        MIR_HIP(hipStreamSynchronize(s));
+        // BM25Okapi._calc_idf over the scope's corpus: N = L, first-appearance order of the scope's own token stream
+        for (int32_t t = 0; t < V; ++t) {
+            if (df[t] > 0) ++sc->n_terms;
+            if (df[t] <= 0 || first[t] < 0) first[t] = INT64_MAX;  // (~0 = absent)
+        }
+        sc->h_idf.assign((size_t)V, 0.0);
+        int32_t rc2 = mir_bm25_idf_from_stats(df.data(), first.data(), V, L, h->epsilon, sc->h_idf.data(), &sc->average_idf);
+        if (rc2 != MIR_OK) return rc2;
+        MIR_HIP(hipMemcpyAsync(sc->idf, sc->h_idf.data(), (size_t)V * 8, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipStreamSynchronize(s));
+        return MIR_OK;
+    };
+    rc = run();
+    (void)hipFree(d_tok);
+    (void)hipFree(d_upre);
+    (void)hipFree(d_df);
+    (void)hipFree(d_first);
+    if (rc != MIR_OK) {
+        free_blocks_scope(sc);
+        return rc;
+    }
+    *out = sc;
+    return MIR_OK;
+}
+
+int32_t mir_bm25_blocks_scope_destroy(mir_bm25_blocks_scope *scope) {
+    free_blocks_scope(scope);
+    return MIR_OK;
+}
+
+int32_t mir_bm25_blocks_scope_info(const mir_bm25_blocks_scope *scope, int64_t *n_chunks, int64_t *total_tokens, int32_t *n_terms,
+                                   int32_t *vocab, double *avgdl, double *average_idf, int64_t *hbm_bytes) {
+    MIR_REQUIRE(scope != nullptr, "scope is NULL");
+    if (n_chunks) *n_chunks = scope->n_pos;
+    if (total_tokens) *total_tokens = scope->total_tokens;
+    if (n_terms) *n_terms = scope->n_terms;
+    if (vocab) *vocab = scope->vocab;
+    if (avgdl) *avgdl = scope->avgdl;
+    if (average_idf) *average_idf = scope->average_idf;
+    if (hbm_bytes) *hbm_bytes = scope->hbm_bytes;
+    return MIR_OK;
+}
+
+int32_t mir_bm25_blocks_scope_idf(const mir_bm25_blocks_scope *scope, double *out_idf_host) {
+    MIR_REQUIRE(scope != nullptr && out_idf_host != nullptr, "NULL argument");
+    std::memcpy(out_idf_host, scope->h_idf.data(), sizeof(double) * scope->h_idf.size());
+    return MIR_OK;
+}
+
+static BlockScopeDev blocks_scope_dev(const mir_bm25_blocks_scope *sc, int64_t out_base) {
+    BlockScopeDev d;
+    d.blk = sc->blk; d.pos = sc->pos; d.idf = sc->idf; d.avgdl = sc->avgdl; d.L = sc->n_pos;
+    d.out_base = out_base; d.n_blk = sc->n_blk; d.vocab = sc->vocab;
+    return d;
+}
+
+// BM25Okapi(the scope's chunks).get_scores(query) -> float64[L]
+int32_t mir_bm25_blocks_scores(mir_bm25_blocks *h, const mir_bm25_blocks_scope *scope, const int32_t *q_terms_host, int32_t nq,
+                               double *out_scores_host) {
+    MIR_REQUIRE(h != nullptr, "searcher is NULL");
+    MIR_REQUIRE(scope != nullptr && scope->searcher == h, "the scope is not one of this searcher");
+    MIR_REQUIRE(nq >= 0 && (nq == 0 || q_terms_host), "bad query");
+    MIR_REQUIRE(out_scores_host != nullptr, "out_scores is NULL");
+    int32_t rc = use_device(h->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int64_t L = scope->n_pos;
+    const size_t o_ptr = ((size_t)nq * 4 + 255) & ~(size_t)255, o_sd = o_ptr + 256, o_sc = o_sd + 256;
+    static_assert(sizeof(BlockScopeDev) <= 256, "one slot");
+    rc = blocks_scratch(h, o_sc + (size_t)L * 8);
+    if (rc != MIR_OK) return rc;
+    char *base = static_cast<char *>(h->scratch);
+    const int32_t ptr2[2] = {0, nq};
+    const BlockScopeDev sd = blocks_scope_dev(scope, 0);
+    hipStream_t s = h->stream;
+    if (nq) MIR_HIP(hipMemcpyAsync(base, q_terms_host, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    MIR_HIP(hipMemcpyAsync(base + o_ptr, ptr2, 8, hipMemcpyHostToDevice, s));
+    MIR_HIP(hipMemcpyAsync(base + o_sd, &sd, sizeof(sd), hipMemcpyHostToDevice, s));
+    const int tiles = (int)((L + kBm25Tile - 1) / kBm25Tile);
+    bm25_blocks_tile_kernel<<<dim3(tiles, 1), dim3(256), 0, s>>>(h->k1, h->b, reinterpret_cast<const BlockScopeDev *>(base + o_sd),
+                                                                 reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
+                                                                 reinterpret_cast<double *>(base + o_sc));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); set_error("bm25_blocks_tile_kernel: %s", hipGetErrorString(e)); return MIR_ERR_HIP; }
+    MIR_HIP(hipMemcpyAsync(out_scores_host, base + o_sc, (size_t)L * 8, hipMemcpyDeviceToHost, s));
+    MIR_HIP(hipStreamSynchronize(s));
+    return MIR_OK;
+}
+
+// _get_top_n_indexes of b requests in one call: query i ranks the chunks of scopes[i].
+int32_t mir_bm25_blocks_search(mir_bm25_blocks *h, const mir_bm25_blocks_scope *const *scopes, const int32_t *q_terms_host,
+                               const int32_t *q_ptr_host, int32_t b, int32_t k, int64_t *out_pos, int32_t *out_ord, int32_t *out_local,
+                               int64_t *out_chunk, double *out_score, int32_t *out_count) {
+    MIR_REQUIRE(h != nullptr, "searcher is NULL");
+    MIR_REQUIRE(b >= 0 && k >= 1, "bad shape b=%d k=%d", b, k);
+    if (b == 0) return MIR_OK;
+    MIR_REQUIRE(scopes && q_ptr_host, "NULL buffer");
+    const int nt = q_ptr_host[b];
+    MIR_REQUIRE(q_ptr_host[0] == 0 && nt >= 0 && (nt == 0 || q_terms_host), "bad q_ptr");
+    for (int i = 0; i < b; ++i) {
+        MIR_REQUIRE(q_ptr_host[i + 1] >= q_ptr_host[i], "q_ptr not monotone");
+        MIR_REQUIRE(scopes[i] != nullptr && scopes[i]->searcher == h, "scope %d is not one of this searcher", i);
+        MIR_REQUIRE(scopes[i]->n_pos < ((int64_t)1 << 31), "scope %d holds 2^31 chunks or more", i);
+    }
+    // the dense scores of a group of queries share the workspace: groups of at most 2^27 scores (1 GiB) and 65535 queries
+    const int64_t cap = (int64_t)1 << 27;
+    std::vector<BlockScopeDev> sd((size_t)b);
+    std::vector<int> group_start{0};
+    int64_t acc = 0, need = 0;
+    for (int i = 0; i < b; ++i) {
+        const int64_t L = scopes[i]->n_pos;
+        if (acc > 0 && (acc + L > cap || i - group_start.back() >= 65535)) { group_start.push_back(i); acc = 0; }
+        sd[i] = blocks_scope_dev(scopes[i], acc);
+        acc += L;
+        need = std::max(need, acc);
+    }
+    group_start.push_back(b);
+    int32_t rc = use_device(h->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    const size_t bk = (size_t)b * k;
+    const size_t o_terms = take((size_t)nt * 4 + 4), o_ptr = take((size_t)(b + 1) * 4), o_sd = take((size_t)b * sizeof(BlockScopeDev));
+    const size_t o_pos = take(bk * 8), o_chunk = take(bk * 8), o_sc = take(bk * 8), o_ord = take(bk * 4), o_loc = take(bk * 4);
+    const size_t o_cnt = take((size_t)b * 4);
+    const size_t o_bs = take((size_t)b * 8), o_bi = take((size_t)b * 8), o_dense = take((size_t)need * 8);
+    rc = blocks_scratch(h, off);
+    if (rc != MIR_OK) return rc;
+    char *base = static_cast<char *>(h->scratch);
+    hipStream_t s = h->stream;
+    auto launch = [&]() -> int32_t {
+        if (nt) MIR_HIP(hipMemcpyAsync(base + o_terms, q_terms_host, (size_t)nt * 4, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemcpyAsync(base + o_ptr, q_ptr_host, (size_t)(b + 1) * 4, hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemcpyAsync(base + o_sd, sd.data(), (size_t)b * sizeof(BlockScopeDev), hipMemcpyHostToDevice, s));
+        MIR_HIP(hipMemsetAsync(base + o_pos, 0, o_bs - o_pos, s));  // rows past a query's count read as zeros
+        const BlockScopeDev *d_sd = reinterpret_cast<const BlockScopeDev *>(base + o_sd);
+        const int32_t *d_ptr = reinterpret_cast<const int32_t *>(base + o_ptr);
+        for (size_t g = 0; g + 1 < group_start.size(); ++g) {
+            const int g0 = group_start[g], nq = group_start[g + 1] - g0;
+            int64_t maxL = 0;
+            for (int i = g0; i < g0 + nq; ++i) maxL = std::max(maxL, scopes[i]->n_pos);
+            if (maxL == 0) continue;
+            const int tiles = (int)((maxL + kBm25Tile - 1) / kBm25Tile);
+            bm25_blocks_tile_kernel<<<dim3(tiles, nq), dim3(256), 0, s>>>(h->k1, h->b, d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
+                                                                          d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
+            MIR_HIP(hipGetLastError());
+            const int64_t found = std::min<int64_t>(k, maxL);
+            const int rounds = (int)((found + kDkRound - 1) / kDkRound);
+            for (int r = 0; r < rounds; ++r) {
+                bm25_blocks_topk_kernel<<<dim3(nq), dim3(kDkThreads), 0, s>>>(
+                    d_sd, reinterpret_cast<const double *>(base + o_dense), k, r, g0, reinterpret_cast<double *>(base + o_bs),
+                    reinterpret_cast<int64_t *>(base + o_bi), reinterpret_cast<int64_t *>(base + o_pos), reinterpret_cast<int32_t *>(base + o_ord),
+                    reinterpret_cast<int32_t *>(base + o_loc), reinterpret_cast<int64_t *>(base + o_chunk), reinterpret_cast<double *>(base + o_sc),
+                    reinterpret_cast<int32_t *>(base + o_cnt));
+                MIR_HIP(hipGetLastError());
+            }
+        }
+        if (out_pos) MIR_HIP(hipMemcpyAsync(out_pos, base + o_pos, bk * 8, hipMemcpyDeviceToHost, s));
+        if (out_chunk) MIR_HIP(hipMemcpyAsync(out_chunk, base + o_chunk, bk * 8, hipMemcpyDeviceToHost, s));
+        if (out_score) MIR_HIP(hipMemcpyAsync(out_score, base + o_sc, bk * 8, hipMemcpyDeviceToHost, s));
+        if (out_ord) MIR_HIP(hipMemcpyAsync(out_ord, base + o_ord, bk * 4, hipMemcpyDeviceToHost, s));
+        if (out_local) MIR_HIP(hipMemcpyAsync(out_local, base + o_loc, bk * 4, hipMemcpyDeviceToHost, s));
         if (out_count) MIR_HIP(hipMemcpyAsync(out_count, base + o_cnt, (size_t)b * 4, hipMemcpyDeviceToHost, s));
         return MIR_OK;
     };

@@ -230,6 +230,150 @@ int32_t bm25_build_device(const int64_t *indptr, const int32_t *term_ids, int64_
     return MIR_OK;
 }
 
+// ---- one document's keyword block (Bm25DocBuilt): the same pieces over one document, plus a run-length pass over the
+// term half of the unique (term, chunk) keys, which yields the document's own term table
+namespace {
+
+// key[j] = term << 32 | local chunk; val[j] = j, the token's position (carried through the stable sort: the first
+// value of a term's run is the position of its first token)
+__global__ __launch_bounds__(256) void doc_keys_kernel(const int32_t *__restrict__ terms, const int64_t *__restrict__ indptr, int64_t n_chunks,
+                                                       int64_t total, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+    const int64_t base = indptr[0];
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < total; j += (int64_t)gridDim.x * 256) {
+        int64_t lo = 0, hi = n_chunks;  // the last c with indptr[c] - base <= j (chunks without tokens share a boundary)
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (indptr[mid] - base <= j) lo = mid; else hi = mid;
+        }
+        keys[j] = ((uint64_t)(uint32_t)terms[j] << 32) | (uint64_t)(uint32_t)lo;
+        vals[j] = (uint32_t)j;
+    }
+}
+
+__global__ __launch_bounds__(256) void doc_postings_kernel(const uint64_t *__restrict__ uniq, const int32_t *__restrict__ tf, int64_t n_post,
+                                                           int32_t *__restrict__ p_chunk, int32_t *__restrict__ p_tf,
+                                                           int32_t *__restrict__ term_half) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_post; i += (int64_t)gridDim.x * 256) {
+        p_chunk[i] = (int32_t)(uint32_t)uniq[i];
+        p_tf[i] = tf[i];
+        term_half[i] = (int32_t)(uniq[i] >> 32);
+    }
+}
+
+// first index of keys[0, n) whose term half is >= t
+__device__ __forceinline__ int64_t doc_term_lower_bound(const uint64_t *__restrict__ keys, int64_t n, int64_t t) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)(keys[mid] >> 32) < t) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// per term u of the document: its posting range (in the unique keys) and its first token (in the sorted tokens)
+__global__ __launch_bounds__(256) void doc_term_table_kernel(const int32_t *__restrict__ terms, int64_t U, const uint64_t *__restrict__ uniq,
+                                                             int64_t n_post, const uint64_t *__restrict__ sorted,
+                                                             const uint32_t *__restrict__ sorted_pos, int64_t total,
+                                                             int64_t *__restrict__ t_ptr, int64_t *__restrict__ first) {
+    const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (u > U) return;
+    if (u == U) { t_ptr[U] = n_post; return; }
+    const int64_t t = terms[u];
+    t_ptr[u] = doc_term_lower_bound(uniq, n_post, t);
+    const int64_t at = doc_term_lower_bound(sorted, total, t);
+    first[u] = at < total ? (int64_t)sorted_pos[at] : 0;
+}
+
+__global__ __launch_bounds__(256) void iota_i64_kernel(int64_t *p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = i;
+}
+
+}  // namespace
+
+int32_t bm25_doc_build_device(const int64_t *indptr, const int32_t *term_ids, int64_t n_chunks, const int64_t *chunk_ids,
+                              int term_bits, Bm25DocBuilt *out) {
+    const int64_t total = n_chunks ? indptr[n_chunks] - indptr[0] : 0;
+    hipStream_t s = nullptr;
+    Scratch tmp;
+    int64_t *d_indptr = nullptr, *d_nruns = nullptr;
+    int32_t *d_terms = nullptr, *d_tf = nullptr, *d_half = nullptr, *d_uterms = nullptr, *d_ucnt = nullptr;
+    uint64_t *d_keys = nullptr, *d_sorted = nullptr, *d_uniq = nullptr;
+    uint32_t *d_vals = nullptr, *d_svals = nullptr;
+    int64_t n_post = 0, n_terms = 0;
+    BUILD_TRY(tmp.take((void **)&d_indptr, (size_t)(n_chunks + 1) * 8));
+    BUILD_TRY(tmp.take((void **)&d_nruns, 16));
+    if (n_chunks) BUILD_TRY(hipMemcpyAsync(d_indptr, indptr, (size_t)(n_chunks + 1) * 8, hipMemcpyHostToDevice, s));
+    if (total) {
+        BUILD_TRY(tmp.take((void **)&d_terms, (size_t)total * 4));
+        BUILD_TRY(tmp.take((void **)&d_keys, (size_t)total * 8));
+        BUILD_TRY(tmp.take((void **)&d_sorted, (size_t)total * 8));
+        BUILD_TRY(tmp.take((void **)&d_vals, (size_t)total * 4));
+        BUILD_TRY(tmp.take((void **)&d_svals, (size_t)total * 4));
+        BUILD_TRY(tmp.take((void **)&d_tf, (size_t)total * 4));
+        BUILD_TRY(hipMemcpyAsync(d_terms, term_ids + indptr[0], (size_t)total * 4, hipMemcpyHostToDevice, s));
+        doc_keys_kernel<<<dim3(grid_for(total)), dim3(256), 0, s>>>(d_terms, d_indptr, n_chunks, total, d_keys, d_vals);
+        BUILD_TRY(hipGetLastError());
+        size_t sort_bytes = 0, rle_bytes = 0;
+        BUILD_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_keys, d_sorted, d_vals, d_svals, (int)total, 32, 32 + term_bits, s));
+        void *d_tmp = nullptr;
+        BUILD_TRY(tmp.take(&d_tmp, sort_bytes));
+        BUILD_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, sort_bytes, d_keys, d_sorted, d_vals, d_svals, (int)total, 32, 32 + term_bits, s));
+        d_uniq = d_keys;  // (free again)
+        BUILD_TRY(hipMemsetAsync(d_nruns, 0, 16, s));
+        BUILD_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, d_sorted, d_uniq, d_tf, d_nruns, (int)total, s));
+        void *d_tmp2 = nullptr;
+        BUILD_TRY(tmp.take(&d_tmp2, rle_bytes));
+        BUILD_TRY(hipcub::DeviceRunLengthEncode::Encode(d_tmp2, rle_bytes, d_sorted, d_uniq, d_tf, d_nruns, (int)total, s));
+        BUILD_TRY(hipMemcpyAsync(&n_post, d_nruns, 8, hipMemcpyDeviceToHost, s));
+        BUILD_TRY(hipStreamSynchronize(s));
+        MIR_REQUIRE(n_post >= 1 && n_post <= total, "run-length encode returned %lld postings for %lld tokens", (long long)n_post, (long long)total);
+    }
+    // products: owned by the caller from here on (freed by it on failure too)
+    BUILD_TRY(hipMalloc((void **)&out->p_chunk, std::max<size_t>((size_t)n_post * 4, 16)));
+    BUILD_TRY(hipMalloc((void **)&out->p_tf, std::max<size_t>((size_t)n_post * 4, 16)));
+    BUILD_TRY(hipMalloc((void **)&out->doc_len, std::max<size_t>((size_t)n_chunks * 4, 16)));
+    BUILD_TRY(hipMalloc((void **)&out->chunk, std::max<size_t>((size_t)n_chunks * 8, 16)));
+    if (n_post) {
+        // the term half of the unique keys, run-length encoded once more: the document's distinct terms, ascending
+        BUILD_TRY(tmp.take((void **)&d_half, (size_t)n_post * 4));
+        BUILD_TRY(tmp.take((void **)&d_uterms, (size_t)n_post * 4));
+        BUILD_TRY(tmp.take((void **)&d_ucnt, (size_t)n_post * 4));
+        doc_postings_kernel<<<dim3(grid_for(n_post)), dim3(256), 0, s>>>(d_uniq, d_tf, n_post, out->p_chunk, out->p_tf, d_half);
+        BUILD_TRY(hipGetLastError());
+        size_t rle_bytes = 0;
+        BUILD_TRY(hipMemsetAsync(d_nruns, 0, 16, s));
+        BUILD_TRY(hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, d_half, d_uterms, d_ucnt, d_nruns, (int)n_post, s));
+        void *d_tmp3 = nullptr;
+        BUILD_TRY(tmp.take(&d_tmp3, rle_bytes));
+        BUILD_TRY(hipcub::DeviceRunLengthEncode::Encode(d_tmp3, rle_bytes, d_half, d_uterms, d_ucnt, d_nruns, (int)n_post, s));
+        BUILD_TRY(hipMemcpyAsync(&n_terms, d_nruns, 8, hipMemcpyDeviceToHost, s));
+        BUILD_TRY(hipStreamSynchronize(s));
+        MIR_REQUIRE(n_terms >= 1 && n_terms <= n_post, "run-length encode returned %lld terms for %lld postings", (long long)n_terms, (long long)n_post);
+    }
+    BUILD_TRY(hipMalloc((void **)&out->terms, std::max<size_t>((size_t)n_terms * 4, 16)));
+    BUILD_TRY(hipMalloc((void **)&out->t_ptr, (size_t)(n_terms + 1) * 8));
+    BUILD_TRY(hipMalloc((void **)&out->first, std::max<size_t>((size_t)n_terms * 8, 16)));
+    out->U = n_terms;
+    out->P = n_post;
+    out->hbm_bytes = n_terms * 12 + (n_terms + 1) * 8 + n_post * 8 + n_chunks * 12;
+    if (n_terms) BUILD_TRY(hipMemcpyAsync(out->terms, d_uterms, (size_t)n_terms * 4, hipMemcpyDeviceToDevice, s));
+    doc_term_table_kernel<<<dim3((unsigned)((n_terms + 1 + 255) / 256)), dim3(256), 0, s>>>(out->terms, n_terms, d_uniq, n_post, d_sorted, d_svals, total,
+                                                                                          out->t_ptr, out->first);
+    BUILD_TRY(hipGetLastError());
+    if (n_chunks) {
+        doc_len_kernel<<<dim3(grid_for(n_chunks)), dim3(256), 0, s>>>(d_indptr, n_chunks, out->doc_len);
+        BUILD_TRY(hipGetLastError());
+        if (chunk_ids) {
+            BUILD_TRY(hipMemcpyAsync(out->chunk, chunk_ids, (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
+        } else {
+            iota_i64_kernel<<<dim3(grid_for(n_chunks)), dim3(256), 0, s>>>(out->chunk, n_chunks);
+            BUILD_TRY(hipGetLastError());
+        }
+    }
+    BUILD_TRY(hipStreamSynchronize(s));
+    return MIR_OK;
+}
+
 int32_t bm25_reweight_device(const int32_t *p_doc, const int32_t *p_tf, const int32_t *doc_len, int64_t n_postings, double k1,
                              double b, double avgdl, double *p_w, void *stream) {
     if (n_postings == 0) return MIR_OK;

@@ -208,6 +208,153 @@ class DeviceBM25:
             pass
 
 
+class DeviceBM25Doc:
+    """Owner of one ``mir_bm25_doc``: ONE document's keyword block in HBM (its own term table and postings), built once
+    and listed by any number of ``BM25BlockScope``.  Term ids are those of the caller's id space (any int32 >= 0)."""
+
+    def __init__(self, handle, device: int):
+        self._h, self.device = handle, device
+        i = self.info()
+        self.n_chunks, self.n_tokens = i["n_chunks"], i["n_tokens"]
+
+    @classmethod
+    def from_token_ids(cls, indptr: np.ndarray, term_ids: np.ndarray, chunk_ids: Optional[np.ndarray] = None, device: int = 0):
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        term_ids = np.ascontiguousarray(term_ids, dtype=np.int32)
+        chunk = None if chunk_ids is None else np.ascontiguousarray(chunk_ids, dtype=np.int64)
+        if indptr.ndim != 1 or len(indptr) < 1:
+            raise ValueError("indptr holds one entry more than the document has chunks")
+        if chunk is not None and len(chunk) != len(indptr) - 1:
+            raise ValueError(f"{len(chunk)} chunk ids for {len(indptr) - 1} chunks")
+        if int(indptr[-1]) > len(term_ids) or int(indptr[0]) < 0:
+            raise ValueError(f"indptr spans [{int(indptr[0])}, {int(indptr[-1])}) of {len(term_ids)} term ids")
+        h = C.c_void_p()
+        nat.check(nat.lib.mir_bm25_doc_create(nat.ptr(indptr), nat.ptr(term_ids) if len(term_ids) else None, len(indptr) - 1,
+                                              nat.ptr(chunk) if chunk is not None and len(chunk) else None, device, C.byref(h)))
+        return cls(h, device)
+
+    def info(self) -> dict:
+        n, tok, u, p, hb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        top = C.c_int32()
+        nat.check(nat.lib.mir_bm25_doc_info(self._h, C.byref(n), C.byref(tok), C.byref(u), C.byref(p), C.byref(top), C.byref(hb)))
+        return {"n_chunks": n.value, "n_tokens": tok.value, "n_terms": u.value, "n_postings": p.value, "max_term": top.value,
+                "hbm_bytes": hb.value}
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            nat.lib.mir_bm25_doc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BM25BlockScope:
+    """Owner of one ``mir_bm25_blocks_scope``: an ordered list of document blocks with the statistics rank-bm25 would
+    derive from their chunks alone.  Immutable; any number of searches may use it at once.  It keeps its blocks and its
+    searcher alive."""
+
+    def __init__(self, handle, searcher: "BM25BlockSearcher", docs: Sequence[DeviceBM25Doc]):
+        self._h, self.searcher, self.docs = handle, searcher, list(docs)
+        i = self.info()
+        self.n_chunks, self.vocab = i["n_chunks"], i["vocab"]
+
+    def info(self) -> dict:
+        n, tot, nt, v = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        a, ai, hb = C.c_double(), C.c_double(), C.c_int64()
+        nat.check(nat.lib.mir_bm25_blocks_scope_info(self._h, C.byref(n), C.byref(tot), C.byref(nt), C.byref(v), C.byref(a), C.byref(ai),
+                                                     C.byref(hb)))
+        return {"n_chunks": n.value, "total_tokens": tot.value, "n_terms": nt.value, "vocab": v.value, "avgdl": a.value,
+                "average_idf": ai.value, "hbm_bytes": hb.value}
+
+    def idf(self) -> np.ndarray:
+        """float64[V_s], V_s = 1 + the largest term id of the listed blocks."""
+        out = np.zeros(self.vocab, np.float64)
+        nat.check(nat.lib.mir_bm25_blocks_scope_idf(self._h, nat.ptr(out)))
+        return out
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            nat.lib.mir_bm25_blocks_scope_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BM25BlockSearcher:
+    """Owner of one ``mir_bm25_blocks`` searcher: workspaces only, no documents (the counterpart of ``BlockSearcher``)."""
+
+    def __init__(self, k1: float = 1.5, b: float = 0.75, epsilon: float = 0.25, device: int = 0):
+        h = C.c_void_p()
+        nat.check(nat.lib.mir_bm25_blocks_create(k1, b, epsilon, device, C.byref(h)))
+        self._h, self.device = h, device
+
+    def scope(self, docs: Sequence[DeviceBM25Doc]) -> BM25BlockScope:
+        """The scope whose corpus is the chunks of ``docs``, block after block."""
+        docs = list(docs)
+        handles = (C.c_void_p * max(len(docs), 1))(*[d.handle for d in docs])
+        h = C.c_void_p()
+        nat.check(nat.lib.mir_bm25_blocks_scope_create(self._h, handles, len(docs), C.byref(h)))
+        return BM25BlockScope(h, self, docs)
+
+    def get_scores(self, scope: BM25BlockScope, query_ids: Sequence[int]) -> np.ndarray:
+        """``BM25Okapi(the scope's chunks).get_scores(query)`` -> float64[scope.n_chunks]."""
+        q = np.ascontiguousarray(query_ids, dtype=np.int32)
+        out = np.zeros(scope.n_chunks, np.float64)
+        nat.check(nat.lib.mir_bm25_blocks_scores(self._h, scope.handle, nat.ptr(q) if len(q) else None, len(q), nat.ptr(out)))
+        return out
+
+    def search(self, scopes: Sequence[BM25BlockScope], queries_ids: Sequence[Sequence[int]], k: int):
+        """Query i ranks ``scopes[i]`` -> (pos[b,k] i64 scope positions, ord[b,k] i32 block ordinals, local[b,k] i32 chunks
+        inside their blocks, chunk[b,k] i64 chunk ids, score[b,k] f64, count[b] i32), best first."""
+        b = len(queries_ids)
+        if len(scopes) != b:
+            raise ValueError(f"{len(scopes)} scopes for {b} queries")
+        if int(k) < 1:
+            raise ValueError(f"k={k} must be >= 1")
+        ptr = np.zeros(b + 1, np.int32)
+        ptr[1:] = np.cumsum([len(q) for q in queries_ids])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(q, np.int32) for q in queries_ids]) if ptr[-1] else np.zeros(0, np.int32))
+        handles = (C.c_void_p * max(b, 1))(*[s.handle for s in scopes])
+        pos, chunk = np.zeros((b, k), np.int64), np.zeros((b, k), np.int64)
+        order, local = np.zeros((b, k), np.int32), np.zeros((b, k), np.int32)
+        sc = np.zeros((b, k), np.float64)
+        cnt = np.zeros(b, np.int32)
+        nat.check(nat.lib.mir_bm25_blocks_search(self._h, handles, nat.ptr(flat) if len(flat) else None, nat.ptr(ptr), b, k, nat.ptr(pos),
+                                                 nat.ptr(order), nat.ptr(local), nat.ptr(chunk), nat.ptr(sc), nat.ptr(cnt)))
+        return pos, order, local, chunk, sc, cnt
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            nat.lib.mir_bm25_blocks_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class TextIndexItem:
     """index_record.py:9-15: one chunk's token list."""
 

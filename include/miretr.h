@@ -32,7 +32,10 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: block search, ADDED without a new number (no entry of ABI 6 changed its signature or meaning, a caller
+#define MIR_ABI_VERSION 6 /* 6: block BM25, ADDED without a new number (nothing of ABI 6 changed): mir_bm25_doc_create / _info / _destroy,
+                               mir_bm25_blocks_create / _destroy / _scope_create / _scope_info / _scope_idf / _scope_destroy /
+                               _scores / _search;
+                            6: block search, ADDED without a new number (no entry of ABI 6 changed its signature or meaning, a caller
                                built against the earlier header runs unchanged): mir_blocks_create / _destroy / _search /
                                _search_device, mir_rows_desc; a mir_rows block keeps its rows' float32 squared norms
                                (mir_rows_info's hbm_bytes grew by 4 n);
@@ -415,6 +418,67 @@ int32_t mir_bm25_scores_scoped(mir_bm25 *h, const mir_bm25_scope *scope, const i
 int32_t mir_bm25_search_scoped(mir_bm25 *h, const mir_bm25_scope *const *scopes, const int32_t *q_terms_host,
                                const int32_t *q_ptr_host, int32_t b, int32_t k, int64_t *out_pos, int32_t *out_ord,
                                int64_t *out_doc, double *out_score, int32_t *out_count);
+
+/* ------------------------------------------------------------------------
+ * Block BM25 (added within ABI 6): the scoped search over resident per-document keyword blocks, no corpus model
+ * (csrc/bm25_blocks.h).  The counterpart of the block search above for the keyword leg: a document's postings are
+ * built once, when the document is first seen, and a request's document list is a list of such blocks.
+ *
+ * mir_bm25_doc_create: one document = n_chunks chunks, chunk c holding term_ids[indptr[c] .. indptr[c + 1]) in text
+ * order.  Term ids live in the CALLER's id space: any int32 >= 0.  chunk_ids (int64[n_chunks]) may be NULL: 0 ..
+ * n_chunks - 1.  The block keeps in HBM its distinct terms (ascending), their posting ranges and first token
+ * positions, per posting the local chunk and the term frequency, and per chunk its token count and id; no token
+ * stream, no weight, nothing sized by a vocabulary.  A document without chunks, or with chunks but no token, is a
+ * valid block.  MIR_ERR_INVALID, with nothing allocated, for a negative term id, a decreasing indptr, n_chunks >= 2^31
+ * or 2^31 tokens or more.
+ *   mir_bm25_doc_info   chunks, tokens, distinct terms U, postings P, largest term id (-1: no token), bytes of HBM
+ *
+ * mir_bm25_blocks_create makes a SEARCHER: it owns a stream, scratch and a mutex, no documents.
+ *
+ * mir_bm25_blocks_scope_create: the scope's corpus is the listed blocks' chunks concatenated in list order, L chunks;
+ * a block listed twice is twice in it, an empty block keeps its ordinal.  Results are those of BM25Okapi(that list)
+ * with the searcher's k1 / b / epsilon, bit for bit, as mir_bm25_scope_create's: N = L, avgdl = tokens / L, nd[t] and
+ * the first-appearance order from the blocks' term tables, idf by the routine behind mir_bm25_idf_from_stats.  The
+ * scope's idf has V_s = 1 + the largest term id of any listed block entries; a query id outside [0, V_s) contributes
+ * +0.0.  A scope without any token is MIR_ERR_EMPTY ("Text index is empty.").  MIR_ERR_INVALID, before anything is
+ * launched, for a NULL searcher or block, a block on another device than the searcher's and L >= 2^31.  A scope is
+ * immutable, may serve any number of concurrent searches and belongs to its searcher; the caller keeps the listed
+ * blocks alive as long as the scope is searched.  Destroying a scope (or reading its info / idf) after its searcher
+ * or its blocks is harmless.
+ *   mir_bm25_blocks_scope_info   N = L, tokens, terms present, V_s, avgdl, average_idf, bytes of HBM the scope holds
+ *   mir_bm25_blocks_scope_idf    float64[V_s], 0 where a term is absent from the scope
+ * ---------------------------------------------------------------------- */
+typedef struct mir_bm25_doc mir_bm25_doc;
+typedef struct mir_bm25_blocks mir_bm25_blocks;
+typedef struct mir_bm25_blocks_scope mir_bm25_blocks_scope;
+
+int32_t mir_bm25_doc_create(const int64_t *indptr_host, const int32_t *term_ids_host, int64_t n_chunks,
+                            const int64_t *chunk_ids_host, int32_t device, mir_bm25_doc **out);
+int32_t mir_bm25_doc_info(const mir_bm25_doc *doc, int64_t *n_chunks, int64_t *n_tokens, int64_t *n_terms,
+                          int64_t *n_postings, int32_t *max_term, int64_t *hbm_bytes);
+int32_t mir_bm25_doc_destroy(mir_bm25_doc *doc);
+int32_t mir_bm25_blocks_create(double k1, double b, double epsilon, int32_t device, mir_bm25_blocks **out);
+int32_t mir_bm25_blocks_destroy(mir_bm25_blocks *s);
+int32_t mir_bm25_blocks_scope_create(mir_bm25_blocks *s, const mir_bm25_doc *const *docs, int32_t n,
+                                     mir_bm25_blocks_scope **out);
+int32_t mir_bm25_blocks_scope_info(const mir_bm25_blocks_scope *scope, int64_t *n_chunks, int64_t *total_tokens,
+                                   int32_t *n_terms, int32_t *vocab, double *avgdl, double *average_idf,
+                                   int64_t *hbm_bytes);
+int32_t mir_bm25_blocks_scope_idf(const mir_bm25_blocks_scope *scope, double *out_idf_host);
+int32_t mir_bm25_blocks_scope_destroy(mir_bm25_blocks_scope *scope);
+/* get_scores for the scope: float64[L] over the scope's positions. */
+int32_t mir_bm25_blocks_scores(mir_bm25_blocks *s, const mir_bm25_blocks_scope *scope, const int32_t *q_terms_host,
+                               int32_t nq, double *out_scores_host);
+/* _get_top_n_indexes for b requests in one synchronous call: query i ranks scopes[i] (a handle may repeat).  Outputs
+ * [b][k], best first, ties to the HIGHEST scope position; out_count[q] = min(k, L_q), rows past it are zero.
+ * out_pos = the scope position, out_ord = the ordinal of its block in the scope, out_local = the chunk inside its
+ * block, out_chunk = that chunk's id.  Any k >= 1.  An output passed as NULL is not written.  MIR_ERR_INVALID, before
+ * anything is launched and with the outputs untouched, for a NULL searcher or scope, a scope of another searcher,
+ * q_ptr not monotone from 0 and k < 1.  There is no device form. */
+int32_t mir_bm25_blocks_search(mir_bm25_blocks *s, const mir_bm25_blocks_scope *const *scopes,
+                               const int32_t *q_terms_host, const int32_t *q_ptr_host, int32_t b, int32_t k,
+                               int64_t *out_pos, int32_t *out_ord, int32_t *out_local, int64_t *out_chunk,
+                               double *out_score, int32_t *out_count);
 
 /* ------------------------------------------------------------------------
  * Rank fusion: langchain EnsembleRetriever.weighted_reciprocal_rank as wired
