@@ -18,6 +18,7 @@ METRIC_CODES = {"cosine_sim": 0, "euclidean_dist": 1, "sqeuclidean_dist": 2, "in
 DTYPE_F32, DTYPE_F16 = 0, 1
 FLAG_UNCERTAIN = 1  # never returned since ABI 2
 FLAG_EXACT_PASS = 2  # the query was answered by the exact pass (exact_topk_kernel)
+ROUTE_LIGHT, ROUTE_OVERFLOW, ROUTE_DENSE = 1, 2, 4  # mir_bm25_last_routes
 ABI_VERSION = 6
 
 
@@ -91,6 +92,7 @@ def _load():
         "mir_kwp_result_free": ([vp], i32),
         "mir_bm25_destroy": ([vp], i32),
         "mir_bm25_tune": ([vp, i32], i32),
+        "mir_bm25_last_routes": ([vp, i32, vp], i32),
         "mir_bm25_corpus_stats": ([vp, vp, vp, vp, vp], i32),
         "mir_bm25_idf_from_stats": ([vp, vp, i32, i64, C.c_double, vp, vp], i32),
         "mir_bm25_set_global_stats": ([vp, vp, C.c_double, C.c_double], i32),

@@ -265,6 +265,22 @@ struct DenseMerge {
 __device__ void bm25_merge_tail(double *part_score, const int32_t *part_idx, const int32_t *part_cnt, int ntiles, int k,
                                 const DenseMerge &dm, int q);
 
+// rank-bm25 scores EVERY document for every query term, tf * (k1 + 1) / (tf + k1 * (1 - b + b * dl / avgdl)), also where
+// tf = 0: with a length term of exactly 0.0 (every document when k1 = 0, an empty document when b = 1) that is 0 / 0 = NaN
+// for each query term the document lacks - a term outside the vocabulary included - and NaN it stays.  Parameters that
+// allow it (bm25_params_degenerate; never the defaults) take the DEG form of the dense kernels: it counts per document
+// the query terms that touch it, and a document with a zero length term that fewer than all of them touched scores NaN.
+// Searches with such parameters rank the dense scores (bm25_dense_topk_body puts NaN first, as argsort()[::-1] does).
+__host__ __device__ inline bool bm25_params_degenerate(double k1, double b) { return !(k1 > 0.0 && b >= 0.0 && b < 1.0); }
+__device__ __forceinline__ bool bm25_zero_length_term(double k1, double b, double dl, double avgdl) {
+    return k1 * ((1.0 - b) + (b * dl) / avgdl) == 0.0;
+}
+struct Bm25Deg {  // what the DEG form of bm25_tile_kernel needs beside the postings
+    const int32_t *doc_len = nullptr;
+    double k1 = 0.0, b = 0.0, avgdl = 1.0;
+};
+
+template <bool DEG>
 __global__ __launch_bounds__(256) void bm25_tile_kernel(Bm25Dev m, const int32_t *__restrict__ q_terms,
                                                         const int32_t *__restrict__ q_ptr, int k,
                                                         const int32_t *__restrict__ need_dense,
@@ -273,8 +289,9 @@ __global__ __launch_bounds__(256) void bm25_tile_kernel(Bm25Dev m, const int32_t
                                                         int32_t *__restrict__ part_idx,
                                                         int32_t *__restrict__ part_cnt, DenseMerge dm,
                                                         const int32_t *__restrict__ dense_list = nullptr,
-                                                        const int32_t *__restrict__ dense_n = nullptr) {
+                                                        const int32_t *__restrict__ dense_n = nullptr, Bm25Deg dg = Bm25Deg{}) {
     __shared__ double sc[kBm25Tile];
+    __shared__ uint32_t hit[DEG ? kBm25Tile : 1];  // DEG: query terms (repeats counted again) that touch the document
     __shared__ double red_s[4];
     __shared__ int64_t red_i[4];
     __shared__ int red_p[4];
@@ -296,6 +313,8 @@ __global__ __launch_bounds__(256) void bm25_tile_kernel(Bm25Dev m, const int32_t
     const int cnt = (int)((m.n_docs - base) < kBm25Tile ? (m.n_docs - base) : kBm25Tile);
     const int qb = q_ptr[q], qe = q_ptr[q + 1];
     for (int i = tid; i < kBm25Tile; i += 256) sc[i] = 0.0;
+    if (DEG)
+        for (int i = tid; i < kBm25Tile; i += 256) hit[i] = 0;
     for (int c0 = qb; c0 < qe; c0 += kBm25Chunk) {
         __syncthreads();  // the previous chunk's table is consumed (and sc / touched are zeroed)
         if (tid < 64) {   // wave 0, all lanes: one term each
@@ -310,7 +329,7 @@ __global__ __launch_bounds__(256) void bm25_tile_kernel(Bm25Dev m, const int32_t
                     const uint32_t a = to[0], b = to[1];
                     lo = m.t_ptr[t] + a;
                     n = (int)(b - a);
-                    valid = (w_idf != 0.0) && n > 0;  // `(self.idf.get(q) or 0)`: adds +-0
+                    valid = (DEG || w_idf != 0.0) && n > 0;  // `(self.idf.get(q) or 0)`: adds +-0 (DEG: but it does touch)
                 }
             }
             const unsigned long long mask = __ballot(valid);
@@ -357,6 +376,7 @@ __global__ __launch_bounds__(256) void bm25_tile_kernel(Bm25Dev m, const int32_t
                 for (int r = 0; r < kBm25Regs; ++r) {
                     if (tj[r] == j) {
                         sc[d[r]] = sc[d[r]] + x[r];  // ... and one for the sum; a document occurs once per term
+                        if (DEG) hit[d[r]] += 1;
                     }
                 }
                 __syncthreads();  // term j's adds are complete before term j+1 touches the same documents
@@ -364,6 +384,12 @@ __global__ __launch_bounds__(256) void bm25_tile_kernel(Bm25Dev m, const int32_t
         }
     }
     __syncthreads();
+    if (DEG) {
+        const uint32_t qlen = (uint32_t)(qe - qb);
+        for (int i = tid; i < cnt; i += 256)
+            if (hit[i] < qlen && bm25_zero_length_term(dg.k1, dg.b, (double)dg.doc_len[base + i], dg.avgdl)) sc[i] = __builtin_nan("");
+        __syncthreads();
+    }
     if (out_scores) {
         double *o = out_scores + (size_t)q * m.n_docs + base;
         for (int i = tid; i < cnt; i += 256) o[i] = sc[i];
@@ -1213,7 +1239,8 @@ __device__ __forceinline__ bool bm25_dense_topk_body(const double *__restrict__ 
     // 64 documents per wave step, one per lane; a step costs one vote unless a document enters the list
     for (int64_t d0 = (int64_t)wave * 64; d0 < n_docs; d0 += (int64_t)kDkWaves * 64) {
         const int64_t d = d0 + lane;
-        const double x = d < n_docs ? sc[d] : 0.0;
+        double x = d < n_docs ? sc[d] : 0.0;
+        if (x != x) x = __builtin_inf();  // NaN (the DEG kernels' only): argsort puts it last, the reversal first, highest index first
         const double worst_s = __shfl(my_s, kk - 1, 64);
         const int64_t worst_i = ((int64_t)__shfl((int)(my_i >> 32), kk - 1, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)my_i, kk - 1, 64);
         bool ok = d < n_docs && (cnt < kk || bm25_before(x, d, worst_s, worst_i));
@@ -1240,7 +1267,7 @@ __device__ __forceinline__ bool bm25_dense_topk_body(const double *__restrict__ 
     }
     const int kout = total < kk ? total : kk;
     if (valid && rank < kout) {
-        emit((size_t)kDkRound * round + rank, my_s, my_i);
+        emit((size_t)kDkRound * round + rank, sc[my_i], my_i);  // (the score as stored: NaN stays NaN)
         if (rank == kout - 1) { *bound_s = my_s; *bound_i = my_i; }
     }
     return true;
@@ -1295,6 +1322,10 @@ struct mir_bm25 {
     size_t pin_cap = 0;
     hipStream_t stream = nullptr;
     int qc_pin = 0;  // mir_bm25_tune: queries per workgroup of the fast pass (0 = chosen per call)
+    bool deg() const { return bm25_params_degenerate(k1, b); }
+    Bm25Deg deg_info() const { Bm25Deg d; d.doc_len = d_doclen; d.k1 = k1; d.b = b; d.avgdl = avgdl; return d; }
+    int route_b = 0;        // mir_bm25_last_routes: batch size of the last mir_bm25_search with k <= 64 whose routing words
+    size_t route_need = 0;  // still sit in the scratch (0 = none), and where its need_dense array starts there
 };
 
 // A scope of a corpus model (mir_bm25_scope_create): immutable once built, shared by any number of searches.
@@ -1339,6 +1370,7 @@ static Bm25Dev dev_view(const mir_bm25 *h) {
 }
 
 static int32_t ensure_scratch(mir_bm25 *h, size_t need) {
+    h->route_b = 0;  // whoever asks for the scratch overwrites the last search's routing words
     if (h->scratch_cap >= need) return MIR_OK;
     if (h->scratch) (void)hipFree(h->scratch);
     h->scratch = nullptr;
@@ -1570,12 +1602,16 @@ static int32_t bm25_run(mir_bm25 *h, const int32_t *d_terms, const int32_t *d_pt
                         int64_t *d_out_idx, double *d_out_score, int32_t *d_out_count, void *part, hipStream_t s) {
     const int T = h->ntiles;
     if (k <= 0) {  // get_scores: dense score vector only
-        bm25_tile_kernel<<<dim3(T, b), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, 0, nullptr, d_scores, nullptr,
+        if (h->deg())
+            bm25_tile_kernel<true><<<dim3(T, b), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, 0, nullptr, d_scores, nullptr, nullptr, nullptr,
+                                                                   DenseMerge{}, nullptr, nullptr, h->deg_info());
+        else
+            bm25_tile_kernel<false><<<dim3(T, b), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, 0, nullptr, d_scores, nullptr,
                                                                  nullptr, nullptr, DenseMerge{});
         MIR_HIP(hipGetLastError());
         return MIR_OK;
     }
-    if (k > kBm25MaxK) return bm25_run_large_k(h, d_terms, d_ptr, b, k, d_out_idx, d_out_score, d_out_count, part, s);
+    if (k > kBm25MaxK || h->deg()) return bm25_run_large_k(h, d_terms, d_ptr, b, k, d_out_idx, d_out_score, d_out_count, part, s);
     char *p = static_cast<char *>(part);
     double *part_score = reinterpret_cast<double *>(p);
     int32_t *part_idx = reinterpret_cast<int32_t *>(p + (size_t)b * T * k * 8);
@@ -1630,7 +1666,7 @@ static int32_t bm25_run(mir_bm25 *h, const int32_t *d_terms, const int32_t *d_pt
     DenseMerge dm;
     dm.arrive = pool.arrive; dm.doc_offset = h->doc_offset; dm.n_docs = h->n_docs; dm.need_dense = need;
     dm.out_idx = d_out_idx; dm.out_score = d_out_score; dm.out_count = d_out_count;
-    bm25_tile_kernel<<<dim3(T, std::min(b, 16)), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, k, need, nullptr, part_score, part_idx, part_cnt, dm,
+    bm25_tile_kernel<false><<<dim3(T, std::min(b, 16)), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, k, need, nullptr, part_score, part_idx, part_cnt, dm,
                                                                       pool.dense_list, pool.dense_n);
     MIR_HIP(hipGetLastError());
     return MIR_OK;
@@ -1663,7 +1699,11 @@ static int32_t bm25_run_large_k(mir_bm25 *h, const int32_t *d_terms, const int32
     for (int q0 = 0; q0 < b; q0 += chunk) {
         const int nq = std::min(chunk, b - q0);
         // (the tile kernel reads q_ptr[q], q_ptr[q + 1] of query q = blockIdx.y: offset the ptr array, scores land at [0, nq))
-        bm25_tile_kernel<<<dim3(h->ntiles, nq), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr + q0, 0, nullptr, scores, nullptr, nullptr, nullptr,
+        if (h->deg())
+            bm25_tile_kernel<true><<<dim3(h->ntiles, nq), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr + q0, 0, nullptr, scores, nullptr, nullptr,
+                                                                             nullptr, DenseMerge{}, nullptr, nullptr, h->deg_info());
+        else
+            bm25_tile_kernel<false><<<dim3(h->ntiles, nq), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr + q0, 0, nullptr, scores, nullptr, nullptr, nullptr,
                                                                    DenseMerge{});
         MIR_HIP(hipGetLastError());
         for (int r = 0; r < rounds; ++r) {
@@ -1718,7 +1758,7 @@ int32_t mir_bm25_search(mir_bm25 *h, const int32_t *q_terms_host, const int32_t 
     auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
     const size_t o_terms = take((size_t)nt * 4 + 4), o_ptr = take((size_t)(b + 1) * 4);
     const size_t o_idx = take((size_t)b * k * 8), o_sc = take((size_t)b * k * 8), o_cnt = take((size_t)b * 4);
-    const size_t o_part = take(k > kBm25MaxK ? large_k_bytes(h, b) : part_bytes(b, h->ntiles, k));
+    const size_t o_part = take(k > kBm25MaxK || h->deg() ? large_k_bytes(h, b) : part_bytes(b, h->ntiles, k));
     rc = ensure_scratch(h, off);
     if (rc != MIR_OK) return rc;
     char *base = static_cast<char *>(h->scratch);
@@ -1747,6 +1787,31 @@ int32_t mir_bm25_search(mir_bm25 *h, const int32_t *q_terms_host, const int32_t 
     std::memcpy(out_idx, res, (size_t)b * k * 8);
     std::memcpy(out_score, res + (o_sc - o_idx), (size_t)b * k * 8);
     std::memcpy(out_count, res + (o_cnt - o_idx), (size_t)b * 4);
+    if (k <= kBm25MaxK && !h->deg()) {  // (bm25_run's layout: the words after part_score | part_idx | part_cnt)
+        h->route_b = b;
+        h->route_need = o_part + (size_t)b * h->ntiles * k * 12 + (size_t)b * h->ntiles * 4;
+    }
+    return MIR_OK;
+}
+
+// Test hook: which way each query of the last mir_bm25_search went.  The plan's light flags, the count words and need_dense
+// are still in the scratch (the dense pass rewrites none of them): [need b | light b | off b | hlist b + 1 | arrive b |
+// dense_list b | dense_n 1 | count b x 32], one copy back.  The searches themselves do nothing for it.
+int32_t mir_bm25_last_routes(mir_bm25 *h, int32_t b, uint32_t *out_flags) {
+    MIR_REQUIRE(h != nullptr && out_flags != nullptr, "NULL argument");
+    int32_t rc = use_device(h->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    MIR_REQUIRE(h->route_b > 0, "no host-form search with k <= %d precedes", kBm25MaxK);
+    MIR_REQUIRE(b == h->route_b, "b=%d, the last search had %d queries", b, h->route_b);
+    const size_t words = (size_t)b * 6 + 2 + (size_t)b * kWvCountStride;
+    std::vector<uint32_t> w(words);
+    MIR_HIP(hipMemcpyAsync(w.data(), static_cast<char *>(h->scratch) + h->route_need, words * 4, hipMemcpyDeviceToHost, h->stream));
+    MIR_HIP(hipStreamSynchronize(h->stream));
+    const uint32_t *need = w.data(), *light = need + b, *count = need + (size_t)b * 6 + 2;
+    for (int q = 0; q < b; ++q)
+        out_flags[q] = (light[q] ? MIR_BM25_ROUTE_LIGHT : 0u) | ((count[(size_t)q * kWvCountStride] >> 31) ? MIR_BM25_ROUTE_OVERFLOW : 0u) |
+                       (need[q] ? MIR_BM25_ROUTE_DENSE : 0u);
     return MIR_OK;
 }
 
@@ -1754,7 +1819,7 @@ int32_t mir_bm25_search(mir_bm25 *h, const int32_t *q_terms_host, const int32_t 
 // mir_bm25_workspace_bytes(h, b, k) bytes and stay untouched until the stream has passed.
 int64_t mir_bm25_workspace_bytes(const mir_bm25 *h, int32_t b, int32_t k) {
     if (!h || b < 0 || k < 1) return -1;
-    return (int64_t)(k > kBm25MaxK ? large_k_bytes(h, b) : part_bytes(b, h->ntiles, k));
+    return (int64_t)(k > kBm25MaxK || h->deg() ? large_k_bytes(h, b) : part_bytes(b, h->ntiles, k));
 }
 
 int32_t mir_bm25_search_device(mir_bm25 *h, const int32_t *q_terms_device, const int32_t *q_ptr_device, int32_t b,
@@ -1923,7 +1988,12 @@ int32_t mir_bm25_scores_scoped(mir_bm25 *h, const mir_bm25_scope *scope, const i
     MIR_HIP(hipMemcpyAsync(base + o_ptr, ptr2, 8, hipMemcpyHostToDevice, s));
     MIR_HIP(hipMemcpyAsync(base + o_sd, &sd, sizeof(sd), hipMemcpyHostToDevice, s));
     const int tiles = (int)((L + kBm25Tile - 1) / kBm25Tile);
-    bm25_scoped_tile_kernel<<<dim3(tiles, 1), dim3(256), 0, s>>>(scoped_view(h), reinterpret_cast<const ScopeDev *>(base + o_sd),
+    if (h->deg())
+        bm25_scoped_tile_kernel<true><<<dim3(tiles, 1), dim3(256), 0, s>>>(scoped_view(h), reinterpret_cast<const ScopeDev *>(base + o_sd),
+                                                                 reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
+                                                                 reinterpret_cast<double *>(base + o_sc));
+    else
+        bm25_scoped_tile_kernel<false><<<dim3(tiles, 1), dim3(256), 0, s>>>(scoped_view(h), reinterpret_cast<const ScopeDev *>(base + o_sd),
                                                                  reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
                                                                  reinterpret_cast<double *>(base + o_sc));
     hipError_t e = hipGetLastError();
@@ -1987,7 +2057,11 @@ int32_t mir_bm25_search_scoped(mir_bm25 *h, const mir_bm25_scope *const *scopes,
             for (int i = g0; i < g0 + nq; ++i) maxL = std::max(maxL, scopes[i]->n_pos);
             if (maxL == 0) continue;
             const int tiles = (int)((maxL + kBm25Tile - 1) / kBm25Tile);
-            bm25_scoped_tile_kernel<<<dim3(tiles, nq), dim3(256), 0, s>>>(scoped_view(h), d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
+            if (h->deg())
+                bm25_scoped_tile_kernel<true><<<dim3(tiles, nq), dim3(256), 0, s>>>(scoped_view(h), d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
+                                                                          d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
+            else
+                bm25_scoped_tile_kernel<false><<<dim3(tiles, nq), dim3(256), 0, s>>>(scoped_view(h), d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
                                                                           d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
             MIR_HIP(hipGetLastError());
             const int64_t found = std::min<int64_t>(k, maxL);
@@ -2296,7 +2370,12 @@ int32_t mir_bm25_blocks_scores(mir_bm25_blocks *h, const mir_bm25_blocks_scope *
     MIR_HIP(hipMemcpyAsync(base + o_ptr, ptr2, 8, hipMemcpyHostToDevice, s));
     MIR_HIP(hipMemcpyAsync(base + o_sd, &sd, sizeof(sd), hipMemcpyHostToDevice, s));
     const int tiles = (int)((L + kBm25Tile - 1) / kBm25Tile);
-    bm25_blocks_tile_kernel<<<dim3(tiles, 1), dim3(256), 0, s>>>(h->k1, h->b, reinterpret_cast<const BlockScopeDev *>(base + o_sd),
+    if (bm25_params_degenerate(h->k1, h->b))
+        bm25_blocks_tile_kernel<true><<<dim3(tiles, 1), dim3(256), 0, s>>>(h->k1, h->b, reinterpret_cast<const BlockScopeDev *>(base + o_sd),
+                                                                 reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
+                                                                 reinterpret_cast<double *>(base + o_sc));
+    else
+        bm25_blocks_tile_kernel<false><<<dim3(tiles, 1), dim3(256), 0, s>>>(h->k1, h->b, reinterpret_cast<const BlockScopeDev *>(base + o_sd),
                                                                  reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
                                                                  reinterpret_cast<double *>(base + o_sc));
     hipError_t e = hipGetLastError();
@@ -2361,7 +2440,11 @@ int32_t mir_bm25_blocks_search(mir_bm25_blocks *h, const mir_bm25_blocks_scope *
             for (int i = g0; i < g0 + nq; ++i) maxL = std::max(maxL, scopes[i]->n_pos);
             if (maxL == 0) continue;
             const int tiles = (int)((maxL + kBm25Tile - 1) / kBm25Tile);
-            bm25_blocks_tile_kernel<<<dim3(tiles, nq), dim3(256), 0, s>>>(h->k1, h->b, d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
+            if (bm25_params_degenerate(h->k1, h->b))
+                bm25_blocks_tile_kernel<true><<<dim3(tiles, nq), dim3(256), 0, s>>>(h->k1, h->b, d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
+                                                                          d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
+            else
+                bm25_blocks_tile_kernel<false><<<dim3(tiles, nq), dim3(256), 0, s>>>(h->k1, h->b, d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
                                                                           d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
             MIR_HIP(hipGetLastError());
             const int64_t found = std::min<int64_t>(k, maxL);

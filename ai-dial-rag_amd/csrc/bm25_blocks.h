@@ -80,10 +80,13 @@ __device__ __forceinline__ int32_t bm25_find_term(const int32_t *__restrict__ te
 // the piece's first posting (p_chunk + x0, p_tf + x0), the block's doc_len and chunk count, and the shift from local
 // chunk to tile position; the postings loop reads through them.  Every index is begin + offset with offset < length:
 // positions < cnt, postings inside [t_ptr[u], t_ptr[u + 1]) with u < U, local chunks < n_chunks before doc_len is read.
+// DEG: the form for parameters with which rank-bm25 divides 0 by 0 (bm25_params_degenerate, bm25.hip).
+template <bool DEG>
 __global__ __launch_bounds__(256) void bm25_blocks_tile_kernel(double k1, double b, const BlockScopeDev *__restrict__ scopes,
                                                                const int32_t *__restrict__ q_terms, const int32_t *__restrict__ q_ptr,
                                                                double *__restrict__ dense) {
     __shared__ double sc[kBm25Tile];
+    __shared__ uint32_t hit[DEG ? kBm25Tile : 1];  // DEG: query terms (repeats counted again) that touch the position
     __shared__ const int32_t *pc_chunk[256];  // the piece's first posting: its local chunks ...
     __shared__ const int32_t *pc_tf[256];     // ... and term frequencies
     __shared__ const int32_t *pc_len[256];    // the block's doc_len
@@ -99,6 +102,8 @@ __global__ __launch_bounds__(256) void bm25_blocks_tile_kernel(double k1, double
     const int cnt = (int)((sd.L - P0) < kBm25Tile ? (sd.L - P0) : kBm25Tile);
     const int64_t P1 = P0 + cnt;
     for (int i = tid; i < kBm25Tile; i += 256) sc[i] = 0.0;
+    if (DEG)
+        for (int i = tid; i < kBm25Tile; i += 256) hit[i] = 0;
     // the blocks that overlap [P0, P1): from the first with pos[s + 1] > P0 to the first with pos[s] >= P1
     int32_t s_first, s_end;
     {
@@ -121,7 +126,7 @@ __global__ __launch_bounds__(256) void bm25_blocks_tile_kernel(double k1, double
         const int t = q_terms[j];
         if (t < 0 || t >= sd.vocab) continue;  // unknown term: `(doc.get(q) or 0)` everywhere
         const double idf = sd.idf[t];
-        if (idf == 0.0) continue;              // absent from the scope: `(self.idf.get(q) or 0)` adds +0.0
+        if (!DEG && idf == 0.0) continue;      // absent from the scope: `(self.idf.get(q) or 0)` adds +0.0
         for (int32_t r0 = s_first; r0 < s_end; r0 += 256) {
             int n = 0;
             {
@@ -182,12 +187,33 @@ __global__ __launch_bounds__(256) void bm25_blocks_tile_kernel(double k1, double
                 const double f = (double)pc_tf[pl][x];
                 const double w = (f * (k1 + 1.0)) / (f + denom_len);
                 const double add = idf * w;  // one rounding for the product ...
-                if (at >= 0 && at < cnt) sc[at] = sc[at] + add;  // ... and one for the sum
+                if (at >= 0 && at < cnt) {
+                    sc[at] = sc[at] + add;  // ... and one for the sum
+                    if (DEG) hit[at] += 1;
+                }
             }
             __syncthreads();  // the term's adds are complete (and the piece table is free) before the next round / token
         }
     }
     __syncthreads();
+    if (DEG) {
+        const uint32_t qlen = (uint32_t)(qe - qb);
+        for (int i = tid; i < cnt; i += 256) {
+            if (hit[i] >= qlen) continue;
+            const int64_t pos = P0 + i;
+            int32_t lo = s_first, hi = s_end;  // the block of the position: the first with pos[s + 1] > pos
+            while (lo < hi) {
+                const int32_t mid = (lo + hi) >> 1;
+                if (sd.pos[mid + 1] <= pos) lo = mid + 1; else hi = mid;
+            }
+            if (lo >= s_end) continue;  // (pos < P1 <= pos[s_end]: never)
+            const Bm25BlockDev blk = sd.blk[lo];
+            const int64_t local = pos - sd.pos[lo];
+            if (local < 0 || local >= blk.n_chunks) continue;
+            if (bm25_zero_length_term(k1, b, (double)blk.doc_len[local], sd.avgdl)) sc[i] = __builtin_nan("");
+        }
+        __syncthreads();
+    }
     double *o = dense + sd.out_base + P0;
     for (int i = tid; i < cnt; i += 256) o[i] = sc[i];
 }

@@ -93,10 +93,13 @@ __global__ __launch_bounds__(256) void bm25_scope_first_kernel(const int32_t *__
 // over the postings of all pieces.  A term touches a position at most once (a chunk listed twice is two positions),
 // so the adds need no atomics.  Every index is begin + offset with offset < length: positions < cnt, postings inside
 // [t_ptr[t], t_ptr[t + 1]), documents read from p_doc.
+// DEG: the form for parameters with which rank-bm25 divides 0 by 0 (bm25_params_degenerate, bm25.hip).
+template <bool DEG>
 __global__ __launch_bounds__(256) void bm25_scoped_tile_kernel(Bm25ScopedModel m, const ScopeDev *__restrict__ scopes,
                                                                const int32_t *__restrict__ q_terms, const int32_t *__restrict__ q_ptr,
                                                                double *__restrict__ dense) {
     __shared__ double sc[kBm25Tile];
+    __shared__ uint32_t hit[DEG ? kBm25Tile : 1];  // DEG: query terms (repeats counted again) that touch the position
     __shared__ int64_t pc_x0[256];     // first posting of the piece
     __shared__ int64_t pc_delta[256];  // position in the tile = document + delta
     __shared__ int pc_off[257];        // exclusive prefix of the pieces' posting counts
@@ -109,6 +112,8 @@ __global__ __launch_bounds__(256) void bm25_scoped_tile_kernel(Bm25ScopedModel m
     const int cnt = (int)((sd.L - P0) < kBm25Tile ? (sd.L - P0) : kBm25Tile);
     const int64_t P1 = P0 + cnt;
     for (int i = tid; i < kBm25Tile; i += 256) sc[i] = 0.0;
+    if (DEG)
+        for (int i = tid; i < kBm25Tile; i += 256) hit[i] = 0;
     // the segments that overlap [P0, P1): from the first with seg_pos[s + 1] > P0 to the first with seg_pos[s] >= P1
     int32_t s_first, s_end;
     {
@@ -131,7 +136,7 @@ __global__ __launch_bounds__(256) void bm25_scoped_tile_kernel(Bm25ScopedModel m
         const int t = q_terms[j];
         if (t < 0 || t >= m.vocab) continue;  // unknown term: `(doc.get(q) or 0)` everywhere
         const double idf = sd.idf[t];
-        if (idf == 0.0) continue;             // absent from the scope: `(self.idf.get(q) or 0)` adds +0.0
+        if (!DEG && idf == 0.0) continue;     // absent from the scope: `(self.idf.get(q) or 0)` adds +0.0
         const int64_t lo = m.t_ptr[t], hi = m.t_ptr[t + 1];
         if (hi <= lo) continue;
         for (int32_t r0 = s_first; r0 < s_end; r0 += 256) {
@@ -180,12 +185,31 @@ __global__ __launch_bounds__(256) void bm25_scoped_tile_kernel(Bm25ScopedModel m
                 const double f = (double)m.p_tf[x];
                 const double w = (f * (m.k1 + 1.0)) / (f + denom_len);
                 const double add = idf * w;  // one rounding for the product ...
-                if (at >= 0 && at < cnt) sc[at] = sc[at] + add;  // ... and one for the sum
+                if (at >= 0 && at < cnt) {
+                    sc[at] = sc[at] + add;  // ... and one for the sum
+                    if (DEG) hit[at] += 1;
+                }
             }
             __syncthreads();  // the term's adds are complete (and the piece table is free) before the next round / token
         }
     }
     __syncthreads();
+    if (DEG) {
+        const uint32_t qlen = (uint32_t)(qe - qb);
+        for (int i = tid; i < cnt; i += 256) {
+            if (hit[i] >= qlen) continue;
+            const int64_t pos = P0 + i;
+            int32_t lo = s_first, hi = s_end;  // the segment of the position: the first with seg_pos[s + 1] > pos
+            while (lo < hi) {
+                const int32_t mid = (lo + hi) >> 1;
+                if (sd.seg_pos[mid + 1] <= pos) lo = mid + 1; else hi = mid;
+            }
+            if (lo >= s_end) continue;  // (pos < P1 <= seg_pos[s_end]: never)
+            const double dl = (double)m.doc_len[(int64_t)sd.seg_begin[lo] + (pos - sd.seg_pos[lo])];
+            if (bm25_zero_length_term(m.k1, m.b, dl, sd.avgdl)) sc[i] = __builtin_nan("");
+        }
+        __syncthreads();
+    }
     double *o = dense + sd.out_base + P0;
     for (int i = tid; i < cnt; i += 256) o[i] = sc[i];
 }

@@ -118,6 +118,14 @@ class DeviceBM25:
         """Pin the fast pass's pipeline depth (1..64 queries per workgroup; 0 = per call).  Results do not depend on it."""
         nat.check(nat.lib.mir_bm25_tune(self._h, queries_per_workgroup))
 
+    def last_routes(self, b: int) -> np.ndarray:
+        """Test hook: uint32[b] route flags of the most recent ``search`` (k <= 64) on this model, one word per query -
+        ``_native.ROUTE_LIGHT`` (the plan made it light), ``ROUTE_OVERFLOW`` (one of its wave pairs overflowed its slots),
+        ``ROUTE_DENSE`` (the dense pass recomputed it).  ValueError without such a search or with another ``b``."""
+        out = np.zeros(max(int(b), 1), np.uint32)
+        nat.check(nat.lib.mir_bm25_last_routes(self._h, int(b), nat.ptr(out)))
+        return out[:b]
+
     def idf(self) -> np.ndarray:
         out = np.zeros(self.vocab, np.float64)
         nat.check(nat.lib.mir_bm25_idf(self._h, nat.ptr(out)))

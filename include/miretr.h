@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: block BM25, ADDED without a new number (nothing of ABI 6 changed): mir_bm25_doc_create / _info / _destroy,
+#define MIR_ABI_VERSION 6 /* 6: BM25 route report, ADDED without a new number (a test hook; nothing of ABI 6 changed): mir_bm25_last_routes;
+                            6: block BM25, ADDED without a new number (nothing of ABI 6 changed): mir_bm25_doc_create / _info / _destroy,
                                mir_bm25_blocks_create / _destroy / _scope_create / _scope_info / _scope_idf / _scope_destroy /
                                _scores / _search;
                             6: block search, ADDED without a new number (no entry of ABI 6 changed its signature or meaning, a caller
@@ -289,6 +290,11 @@ int32_t mir_topk_merge_host(const double *dist, const int64_t *row, const int32_
  * when there is no token at all.  For a document-sharded corpus pass the
  * GLOBAL idf[vocab] and average length as overrides and the shard's first
  * global document index as doc_offset; otherwise pass NULL / 0.
+ *
+ * k1, b, epsilon: any values.  Where the package's length term k1 * (1 - b + b * dl / avgdl) is 0.0 (every document
+ * with k1 = 0; an empty document with b = 1) the package divides 0 by 0 for each query term the document lacks, scores
+ * the document NaN and ranks it first; so does this library, in the corpus model, its scopes and block BM25 alike
+ * (a model with k1 <= 0 or b outside [0, 1) ranks dense scores for every k: slower, and without routes).
  * ---------------------------------------------------------------------- */
 typedef struct mir_bm25 mir_bm25;
 
@@ -352,6 +358,16 @@ int32_t mir_bm25_destroy(mir_bm25 *h);
  * (the depth of its software pipeline), 1..64; 0 = chosen per call from the batch size (the default).  Results do
  * not depend on it. */
 int32_t mir_bm25_tune(mir_bm25 *h, int32_t queries_per_workgroup);
+/* Test hook (added within ABI 6): which way each query of the most recent mir_bm25_search (the host form) on this handle
+ * went, one flag word per query, out_flags[b].  Results never depend on the route; tests use it to prove that they reach
+ * the route they are written for.  The words are read back from the handle's scratch, where that search left them: one
+ * device-to-host copy under the handle's mutex, and nothing at all is added to a search.  MIR_ERR_INVALID when no such
+ * search precedes (or any other entry has used the handle since), when `b` is not its batch size, or when it had k > 64
+ * (the large-k form has no routes). */
+#define MIR_BM25_ROUTE_LIGHT 1u    /* the plan gave the query to the wave kernel (one wave per (tile, query) pair) */
+#define MIR_BM25_ROUTE_OVERFLOW 2u /* one of its pairs listed more distinct documents than a wave has slots */
+#define MIR_BM25_ROUTE_DENSE 4u    /* the exact dense pass recomputed it */
+int32_t mir_bm25_last_routes(mir_bm25 *h, int32_t b, uint32_t *out_flags);
 int32_t mir_bm25_info(const mir_bm25 *h, int64_t *n_docs, int32_t *vocab, int64_t *n_postings, double *avgdl,
                       double *average_idf, int64_t *hbm_bytes);
 /* the model's idf table, float64[vocab] (0 for terms that never occur) */

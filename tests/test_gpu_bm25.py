@@ -103,8 +103,10 @@ def test_synthetic_vs_oracle_bit_exact(br, n, vocab):
         assert cnt[i] == 10
         np.testing.assert_array_equal(idx[i], top, err_msg=f"query {i} {q}")
         np.testing.assert_array_equal(sc[i], want[top])
-    # a query longer than the fast path's term table goes through the dense pass, batched with short ones
-    long_q = [int(t) for t in np.random.default_rng(5).integers(0, vocab, 45)]
+    # a query longer than the fast path's 64-term table (kBm25Chunk) goes through the dense pass, which walks its terms in
+    # chunks of 64; batched with short ones
+    long_q = [int(t) for t in np.random.default_rng(5).integers(0, vocab, 150)]
+    assert len(long_q) > 2 * 64
     i3, s3, c3 = dev.search([qs[1], long_q, qs[2]], 10)
     want = o.get_scores(long_q)
     np.testing.assert_array_equal(i3[1], ob.top_n_indexes(want, 10))
