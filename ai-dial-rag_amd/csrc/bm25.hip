@@ -34,6 +34,9 @@
 // Scoped BM25 - every query ranks its own document segments of one model, with that request's idf and avgdl - has its
 // own kernels in bm25_scoped.h and its entries near the end of this file.  Block BM25 - the same over resident per-document
 // keyword blocks, no corpus model - has its kernels in bm25_blocks.h and its entries after those.
+// Host side: bm25_layout.h lays out the model route's scratch and groups scoped queries (no HIP in it);
+// bm25_host.h holds what the scoped and the block route share - scratch, query check, scope statistics, the scores and the
+// search path; this file keeps the handles, the model route and the extern "C" entries.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -1288,6 +1291,7 @@ __global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const doubl
 
 #include "bm25_scoped.h"
 #include "bm25_blocks.h"
+#include "bm25_host.h"
 
 using namespace mir;
 
@@ -1316,8 +1320,7 @@ struct mir_bm25 {
     std::vector<int64_t> h_df, h_first;  // per term: documents containing it, position of its first token (INT64_MAX = absent)
     int64_t hbm_bytes = 0;
     std::mutex mu;  // serialises use of the scratch below (searches on one handle run one at a time)
-    void *scratch = nullptr;
-    size_t scratch_cap = 0;
+    DevScratch scratch;
     char *pin = nullptr;       // pinned host staging of mir_bm25_search: queries in, results out, one copy each
     size_t pin_cap = 0;
     hipStream_t stream = nullptr;
@@ -1325,7 +1328,12 @@ struct mir_bm25 {
     bool deg() const { return bm25_params_degenerate(k1, b); }
     Bm25Deg deg_info() const { Bm25Deg d; d.doc_len = d_doclen; d.k1 = k1; d.b = b; d.avgdl = avgdl; return d; }
     int route_b = 0;        // mir_bm25_last_routes: batch size of the last mir_bm25_search with k <= 64 whose routing words
-    size_t route_need = 0;  // still sit in the scratch (0 = none), and where its need_dense array starts there
+    size_t route_part = 0;  // still sit in the scratch (0 = none), where that search's part of the scratch starts, and
+    Bm25RouteLayout route_lay{};  // its layout
+    int32_t take_scratch(size_t need) {
+        route_b = 0;  // whoever asks for the scratch overwrites the last search's routing words
+        return scratch.ensure(need);
+    }
 };
 
 // A scope of a corpus model (mir_bm25_scope_create): immutable once built, shared by any number of searches.
@@ -1356,7 +1364,7 @@ static void free_bm25(mir_bm25 *h) {
     (void)hipFree(h->d_doclen);
     (void)hipFree(h->d_tokens);
     (void)hipFree(h->d_indptr);
-    (void)hipFree(h->scratch);
+    h->scratch.release();
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1369,15 +1377,25 @@ static Bm25Dev dev_view(const mir_bm25 *h) {
     return m;
 }
 
-static int32_t ensure_scratch(mir_bm25 *h, size_t need) {
-    h->route_b = 0;  // whoever asks for the scratch overwrites the last search's routing words
-    if (h->scratch_cap >= need) return MIR_OK;
-    if (h->scratch) (void)hipFree(h->scratch);
-    h->scratch = nullptr;
-    h->scratch_cap = 0;
-    MIR_HIP(hipMalloc(&h->scratch, need));
-    h->scratch_cap = need;
-    return MIR_OK;
+// the model route's scratch for b queries and k <= 64 (bm25_run): every offset into it comes from here
+static Bm25RouteLayout route_layout(const mir_bm25 *h, int b, int k) {
+    return bm25_route_layout(b, h->ntiles, k, wave_pool_capacity(b, h->ntiles), kWvCountStride);
+}
+
+// the one place that picks the DEG form of bm25_tile_kernel (bm25_params_degenerate)
+static void launch_tile(const mir_bm25 *h, bool deg, dim3 grid, hipStream_t s, const int32_t *d_terms, const int32_t *d_ptr, int k,
+                        const int32_t *need, double *out_scores, double *part_score, int32_t *part_idx, int32_t *part_cnt,
+                        const DenseMerge &dm, const int32_t *dense_list, const int32_t *dense_n) {
+    if (deg)
+        bm25_tile_kernel<true><<<grid, dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, k, need, out_scores, part_score, part_idx, part_cnt, dm,
+                                                          dense_list, dense_n, h->deg_info());
+    else
+        bm25_tile_kernel<false><<<grid, dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, k, need, out_scores, part_score, part_idx, part_cnt, dm,
+                                                           dense_list, dense_n);
+}
+// get_scores of the queries of a launch: dense[q][n_docs]
+static void launch_dense_scores(const mir_bm25 *h, int nq, hipStream_t s, const int32_t *d_terms, const int32_t *d_ptr, double *dense) {
+    launch_tile(h, h->deg(), dim3(h->ntiles, nq), s, d_terms, d_ptr, 0, nullptr, dense, nullptr, nullptr, nullptr, DenseMerge{}, nullptr, nullptr);
 }
 
 }  // namespace mir
@@ -1597,41 +1615,33 @@ static int32_t bm25_run_large_k(mir_bm25 *h, const int32_t *d_terms, const int32
                                 double *d_out_score, int32_t *d_out_count, void *ws, hipStream_t s);
 
 // Shared implementation: queries already on the device (q_terms[nt], q_ptr[b+1]).
-// part = [part_score f64 | part_idx i32 | part_cnt i32 | need_dense i32]
+// part: k <= 64 and regular parameters, Bm25RouteLayout (bm25_layout.h); else bm25_run_large_k's workspace
 static int32_t bm25_run(mir_bm25 *h, const int32_t *d_terms, const int32_t *d_ptr, int b, int k, double *d_scores,
                         int64_t *d_out_idx, double *d_out_score, int32_t *d_out_count, void *part, hipStream_t s) {
     const int T = h->ntiles;
     if (k <= 0) {  // get_scores: dense score vector only
-        if (h->deg())
-            bm25_tile_kernel<true><<<dim3(T, b), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, 0, nullptr, d_scores, nullptr, nullptr, nullptr,
-                                                                   DenseMerge{}, nullptr, nullptr, h->deg_info());
-        else
-            bm25_tile_kernel<false><<<dim3(T, b), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, 0, nullptr, d_scores, nullptr,
-                                                                 nullptr, nullptr, DenseMerge{});
+        launch_dense_scores(h, b, s, d_terms, d_ptr, d_scores);
         MIR_HIP(hipGetLastError());
         return MIR_OK;
     }
     if (k > kBm25MaxK || h->deg()) return bm25_run_large_k(h, d_terms, d_ptr, b, k, d_out_idx, d_out_score, d_out_count, part, s);
+    const Bm25RouteLayout lay = route_layout(h, b, k);
     char *p = static_cast<char *>(part);
-    double *part_score = reinterpret_cast<double *>(p);
-    int32_t *part_idx = reinterpret_cast<int32_t *>(p + (size_t)b * T * k * 8);
-    int32_t *part_cnt = reinterpret_cast<int32_t *>(p + (size_t)b * T * k * 12);
-    int32_t *need = part_cnt + (size_t)b * T;
+    double *part_score = reinterpret_cast<double *>(p + lay.part_score);
+    int32_t *part_idx = reinterpret_cast<int32_t *>(p + lay.part_idx);
+    int32_t *part_cnt = reinterpret_cast<int32_t *>(p + lay.part_cnt);
+    int32_t *need = reinterpret_cast<int32_t *>(p + lay.need);
     WavePool pool;
-    pool.capacity = wave_pool_capacity(b, T);
-    pool.light = need + b;
-    pool.off = reinterpret_cast<uint32_t *>(pool.light + b);
-    pool.hlist = reinterpret_cast<int32_t *>(pool.off + b);
-    pool.arrive = reinterpret_cast<uint32_t *>(pool.hlist + b + 1);
-    pool.dense_list = reinterpret_cast<int32_t *>(pool.arrive + b);
-    pool.dense_n = pool.dense_list + b;
-    pool.count = reinterpret_cast<uint32_t *>(pool.dense_n + 1);
-    {
-        size_t o = (size_t)b * T * k * 12 + (size_t)b * T * 4 + (size_t)b * 24 + 8 + (size_t)b * kWvCountStride * 4;
-        o = (o + 255) & ~(size_t)255;
-        pool.score = reinterpret_cast<double *>(p + o);
-        pool.doc = reinterpret_cast<int32_t *>(p + o + (size_t)pool.capacity * 8);
-    }
+    pool.capacity = lay.pool_capacity;
+    pool.light = reinterpret_cast<int32_t *>(p + lay.light);
+    pool.off = reinterpret_cast<uint32_t *>(p + lay.off);
+    pool.hlist = reinterpret_cast<int32_t *>(p + lay.hlist);
+    pool.arrive = reinterpret_cast<uint32_t *>(p + lay.arrive);
+    pool.dense_list = reinterpret_cast<int32_t *>(p + lay.dense_list);
+    pool.dense_n = reinterpret_cast<int32_t *>(p + lay.dense_n);
+    pool.count = reinterpret_cast<uint32_t *>(p + lay.count);
+    pool.score = reinterpret_cast<double *>(p + lay.pool_score);
+    pool.doc = reinterpret_cast<int32_t *>(p + lay.pool_doc);
     // 1. fast passes: positives among touched documents.  Light queries (bm25_plan_kernel) one wave per (tile, query) and one
     //    selection per query; the others on the tile kernel + merge
     if (b > 1024) {
@@ -1666,17 +1676,10 @@ static int32_t bm25_run(mir_bm25 *h, const int32_t *d_terms, const int32_t *d_pt
     DenseMerge dm;
     dm.arrive = pool.arrive; dm.doc_offset = h->doc_offset; dm.n_docs = h->n_docs; dm.need_dense = need;
     dm.out_idx = d_out_idx; dm.out_score = d_out_score; dm.out_count = d_out_count;
-    bm25_tile_kernel<false><<<dim3(T, std::min(b, 16)), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr, k, need, nullptr, part_score, part_idx, part_cnt, dm,
-                                                                      pool.dense_list, pool.dense_n);
+    launch_tile(h, false, dim3(T, std::min(b, 16)), s, d_terms, d_ptr, k, need, nullptr, part_score, part_idx, part_cnt, dm, pool.dense_list,
+                pool.dense_n);
     MIR_HIP(hipGetLastError());
     return MIR_OK;
-}
-
-// [part_score | part_idx | part_cnt | need, light, off (b each), hlist (b + 1), arrive (b), dense_list (b), dense_n (1) | count (b x 32) | pool scores | pool documents]
-static size_t part_bytes(int b, int T, int k) {
-    size_t o = (size_t)b * T * k * 12 + (size_t)b * T * 4 + (size_t)b * 24 + 8 + (size_t)b * kWvCountStride * 4;
-    o = (o + 255) & ~(size_t)255;
-    return o + (size_t)wave_pool_capacity(b, T) * 12 + 64;
 }
 
 // n > 64: dense scores for chunks of queries, then rounds of 64.  Workspace: [scores chunk x n_docs f64 | bound_s | bound_i]
@@ -1687,6 +1690,9 @@ static int large_k_chunk(const mir_bm25 *h, int b) {
 static size_t large_k_bytes(const mir_bm25 *h, int b) {
     const int c = large_k_chunk(h, b);
     return (size_t)c * (size_t)std::max<int64_t>(h->n_docs, 1) * 8 + (size_t)c * 16 + 256;
+}
+static size_t workspace_bytes(const mir_bm25 *h, int b, int k) {
+    return k > kBm25MaxK || h->deg() ? large_k_bytes(h, b) : route_layout(h, b, k).total;
 }
 static int32_t bm25_run_large_k(mir_bm25 *h, const int32_t *d_terms, const int32_t *d_ptr, int b, int k, int64_t *d_out_idx,
                                 double *d_out_score, int32_t *d_out_count, void *ws, hipStream_t s) {
@@ -1699,12 +1705,7 @@ static int32_t bm25_run_large_k(mir_bm25 *h, const int32_t *d_terms, const int32
     for (int q0 = 0; q0 < b; q0 += chunk) {
         const int nq = std::min(chunk, b - q0);
         // (the tile kernel reads q_ptr[q], q_ptr[q + 1] of query q = blockIdx.y: offset the ptr array, scores land at [0, nq))
-        if (h->deg())
-            bm25_tile_kernel<true><<<dim3(h->ntiles, nq), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr + q0, 0, nullptr, scores, nullptr, nullptr,
-                                                                             nullptr, DenseMerge{}, nullptr, nullptr, h->deg_info());
-        else
-            bm25_tile_kernel<false><<<dim3(h->ntiles, nq), dim3(256), 0, s>>>(dev_view(h), d_terms, d_ptr + q0, 0, nullptr, scores, nullptr, nullptr, nullptr,
-                                                                   DenseMerge{});
+        launch_dense_scores(h, nq, s, d_terms, d_ptr + q0, scores);
         MIR_HIP(hipGetLastError());
         for (int r = 0; r < rounds; ++r) {
             bm25_dense_topk_kernel<<<dim3(nq), dim3(kDkThreads), 0, s>>>(scores, h->n_docs, k, r, h->doc_offset, q0, bound_s, bound_i, d_out_idx,
@@ -1726,9 +1727,9 @@ int32_t mir_bm25_scores(mir_bm25 *h, const int32_t *q_terms_host, int32_t nq, do
     std::lock_guard<std::mutex> lk(h->mu);
     const size_t off_ptr = ((size_t)nq * 4 + 255) & ~(size_t)255;
     const size_t off_sc = off_ptr + 256;
-    rc = ensure_scratch(h, off_sc + (size_t)h->n_docs * 8);
+    rc = h->take_scratch(off_sc + (size_t)h->n_docs * 8);
     if (rc != MIR_OK) return rc;
-    char *base = static_cast<char *>(h->scratch);
+    char *base = static_cast<char *>(h->scratch.ptr);
     const int32_t ptr2[2] = {0, nq};
     if (nq) MIR_HIP(hipMemcpyAsync(base, q_terms_host, (size_t)nq * 4, hipMemcpyHostToDevice, h->stream));
     MIR_HIP(hipMemcpyAsync(base + off_ptr, ptr2, 8, hipMemcpyHostToDevice, h->stream));
@@ -1748,20 +1749,20 @@ int32_t mir_bm25_search(mir_bm25 *h, const int32_t *q_terms_host, const int32_t 
     MIR_REQUIRE(b >= 0 && k >= 1, "bad shape b=%d k=%d", b, k);
     if (b == 0) return MIR_OK;
     MIR_REQUIRE(q_ptr_host && out_idx && out_score && out_count, "NULL buffer");
-    const int nt = q_ptr_host[b];
-    MIR_REQUIRE(q_ptr_host[0] == 0 && nt >= 0 && (nt == 0 || q_terms_host), "bad q_ptr");
-    for (int i = 0; i < b; ++i) MIR_REQUIRE(q_ptr_host[i + 1] >= q_ptr_host[i], "q_ptr not monotone");
-    int32_t rc = use_device(h->device, nullptr);
+    int nt = 0;
+    int32_t rc = check_query_batch(q_terms_host, q_ptr_host, b, &nt);
+    if (rc != MIR_OK) return rc;
+    rc = use_device(h->device, nullptr);
     if (rc != MIR_OK) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
     const size_t o_terms = take((size_t)nt * 4 + 4), o_ptr = take((size_t)(b + 1) * 4);
     const size_t o_idx = take((size_t)b * k * 8), o_sc = take((size_t)b * k * 8), o_cnt = take((size_t)b * 4);
-    const size_t o_part = take(k > kBm25MaxK || h->deg() ? large_k_bytes(h, b) : part_bytes(b, h->ntiles, k));
-    rc = ensure_scratch(h, off);
+    const size_t o_part = take(workspace_bytes(h, b, k));
+    rc = h->take_scratch(off);
     if (rc != MIR_OK) return rc;
-    char *base = static_cast<char *>(h->scratch);
+    char *base = static_cast<char *>(h->scratch.ptr);
     hipStream_t s = h->stream;
     // pinned staging: [terms | ptr] go in with one copy, [idx | score | count] come back with one
     // (pageable buffers make every hipMemcpyAsync a synchronous staged copy of its own)
@@ -1787,9 +1788,10 @@ int32_t mir_bm25_search(mir_bm25 *h, const int32_t *q_terms_host, const int32_t 
     std::memcpy(out_idx, res, (size_t)b * k * 8);
     std::memcpy(out_score, res + (o_sc - o_idx), (size_t)b * k * 8);
     std::memcpy(out_count, res + (o_cnt - o_idx), (size_t)b * 4);
-    if (k <= kBm25MaxK && !h->deg()) {  // (bm25_run's layout: the words after part_score | part_idx | part_cnt)
+    if (k <= kBm25MaxK && !h->deg()) {
         h->route_b = b;
-        h->route_need = o_part + (size_t)b * h->ntiles * k * 12 + (size_t)b * h->ntiles * 4;
+        h->route_part = o_part;
+        h->route_lay = route_layout(h, b, k);
     }
     return MIR_OK;
 }
@@ -1804,11 +1806,12 @@ int32_t mir_bm25_last_routes(mir_bm25 *h, int32_t b, uint32_t *out_flags) {
     std::lock_guard<std::mutex> lk(h->mu);
     MIR_REQUIRE(h->route_b > 0, "no host-form search with k <= %d precedes", kBm25MaxK);
     MIR_REQUIRE(b == h->route_b, "b=%d, the last search had %d queries", b, h->route_b);
-    const size_t words = (size_t)b * 6 + 2 + (size_t)b * kWvCountStride;
-    std::vector<uint32_t> w(words);
-    MIR_HIP(hipMemcpyAsync(w.data(), static_cast<char *>(h->scratch) + h->route_need, words * 4, hipMemcpyDeviceToHost, h->stream));
+    const Bm25RouteLayout &lay = h->route_lay;
+    std::vector<uint32_t> w(lay.route_words);
+    MIR_HIP(hipMemcpyAsync(w.data(), static_cast<char *>(h->scratch.ptr) + h->route_part + lay.need, lay.route_words * 4, hipMemcpyDeviceToHost,
+                           h->stream));
     MIR_HIP(hipStreamSynchronize(h->stream));
-    const uint32_t *need = w.data(), *light = need + b, *count = need + (size_t)b * 6 + 2;
+    const uint32_t *need = w.data(), *light = need + (lay.light - lay.need) / 4, *count = need + (lay.count - lay.need) / 4;
     for (int q = 0; q < b; ++q)
         out_flags[q] = (light[q] ? MIR_BM25_ROUTE_LIGHT : 0u) | ((count[(size_t)q * kWvCountStride] >> 31) ? MIR_BM25_ROUTE_OVERFLOW : 0u) |
                        (need[q] ? MIR_BM25_ROUTE_DENSE : 0u);
@@ -1819,7 +1822,7 @@ int32_t mir_bm25_last_routes(mir_bm25 *h, int32_t b, uint32_t *out_flags) {
 // mir_bm25_workspace_bytes(h, b, k) bytes and stay untouched until the stream has passed.
 int64_t mir_bm25_workspace_bytes(const mir_bm25 *h, int32_t b, int32_t k) {
     if (!h || b < 0 || k < 1) return -1;
-    return (int64_t)(k > kBm25MaxK || h->deg() ? large_k_bytes(h, b) : part_bytes(b, h->ntiles, k));
+    return (int64_t)workspace_bytes(h, b, k);
 }
 
 int32_t mir_bm25_search_device(mir_bm25 *h, const int32_t *q_terms_device, const int32_t *q_ptr_device, int32_t b,
@@ -1886,16 +1889,16 @@ int32_t mir_bm25_scope_create(mir_bm25 *h, const int64_t *seg_begin, const int64
     sc->model = h; sc->device = h->device; sc->n_seg = n_seg; sc->n_pos = L; sc->total_tokens = total;
     sc->avgdl = (double)total / (double)L;
     const int32_t V = h->vocab;
-    int64_t *d_tok = nullptr, *d_df = nullptr;
-    unsigned long long *d_first = nullptr;
-    std::vector<int64_t> df((size_t)V), first((size_t)V);
+    DevTemps tmp;
     auto run = [&]() -> int32_t {
+        int64_t *d_tok = nullptr, *d_df = nullptr;
+        unsigned long long *d_first = nullptr;
         MIR_HIP(hipMalloc((void **)&sc->seg_begin, (size_t)n_seg * 4));
         MIR_HIP(hipMalloc((void **)&sc->seg_pos, ((size_t)n_seg + 1) * 8));
         MIR_HIP(hipMalloc((void **)&sc->idf, (size_t)V * 8));
-        MIR_HIP(hipMalloc((void **)&d_tok, ((size_t)n_seg + 1) * 8));
-        MIR_HIP(hipMalloc((void **)&d_df, (size_t)V * 8));
-        MIR_HIP(hipMalloc((void **)&d_first, (size_t)V * 8));
+        if ((rc = tmp.alloc(&d_tok, ((size_t)n_seg + 1) * 8)) != MIR_OK) return rc;
+        if ((rc = tmp.alloc(&d_df, (size_t)V * 8)) != MIR_OK) return rc;
+        if ((rc = tmp.alloc(&d_first, (size_t)V * 8)) != MIR_OK) return rc;
         sc->hbm_bytes = (int64_t)n_seg * 4 + ((int64_t)n_seg + 1) * 8 + (int64_t)V * 8;
         std::lock_guard<std::mutex> lk(h->mu);
         hipStream_t s = h->stream;
@@ -1908,25 +1911,9 @@ int32_t mir_bm25_scope_create(mir_bm25 *h, const int64_t *seg_begin, const int64
         const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 1 << 16));
         bm25_scope_first_kernel<<<dim3(grid), dim3(256), 0, s>>>(h->d_tokens, h->d_indptr, sc->seg_begin, d_tok, n_seg, total, h->total_tokens, V, d_first);
         MIR_HIP(hipGetLastError());
-        MIR_HIP(hipMemcpyAsync(df.data(), d_df, (size_t)V * 8, hipMemcpyDeviceToHost, s));
-        MIR_HIP(hipMemcpyAsync(first.data(), d_first, (size_t)V * 8, hipMemcpyDeviceToHost, s));
-        MIR_HIP(hipStreamSynchronize(s));
-        // BM25Okapi._calc_idf over the scope's corpus: N = L, first-appearance order of the scope's own token stream
-        for (int32_t t = 0; t < V; ++t) {
-            if (df[t] > 0) ++sc->n_terms;
-            if (df[t] <= 0 || first[t] < 0) first[t] = INT64_MAX;  // (~0 = absent)
-        }
-        sc->h_idf.assign((size_t)V, 0.0);
-        int32_t rc2 = mir_bm25_idf_from_stats(df.data(), first.data(), V, L, h->epsilon, sc->h_idf.data(), &sc->average_idf);
-        if (rc2 != MIR_OK) return rc2;
-        MIR_HIP(hipMemcpyAsync(sc->idf, sc->h_idf.data(), (size_t)V * 8, hipMemcpyHostToDevice, s));
-        MIR_HIP(hipStreamSynchronize(s));
-        return MIR_OK;
+        return scope_stats_tail(s, d_df, d_first, V, L, h->epsilon, &sc->n_terms, &sc->h_idf, &sc->average_idf, sc->idf);
     };
     rc = run();
-    (void)hipFree(d_tok);
-    (void)hipFree(d_df);
-    (void)hipFree(d_first);
     if (rc != MIR_OK) {
         free_scope(sc);
         return rc;
@@ -1958,12 +1945,37 @@ int32_t mir_bm25_scope_idf(const mir_bm25_scope *scope, double *out_idf_host) {
     return MIR_OK;
 }
 
-static ScopeDev scope_dev(const mir_bm25_scope *sc, int64_t out_base) {
-    ScopeDev d;
-    d.seg_begin = sc->seg_begin; d.seg_pos = sc->seg_pos; d.idf = sc->idf; d.avgdl = sc->avgdl; d.L = sc->n_pos;
-    d.out_base = out_base; d.n_seg = sc->n_seg;
-    return d;
+// the one place that picks the DEG form of bm25_scoped_tile_kernel
+static void launch_scoped_tile(bool deg, dim3 grid, hipStream_t s, const Bm25ScopedModel &m, const ScopeDev *sd, const int32_t *d_terms,
+                               const int32_t *d_ptr, double *dense) {
+    if (deg)
+        bm25_scoped_tile_kernel<true><<<grid, dim3(256), 0, s>>>(m, sd, d_terms, d_ptr, dense);
+    else
+        bm25_scoped_tile_kernel<false><<<grid, dim3(256), 0, s>>>(m, sd, d_terms, d_ptr, dense);
 }
+
+// The scoped route as bm25_host.h sees it.  Columns of a search: pos i64, doc i64, score f64, ord i32.
+struct ModelRoute {
+    using Owner = mir_bm25;
+    using Scope = mir_bm25_scope;
+    using Dev = ScopeDev;
+    static constexpr const char *kTileName = "bm25_scoped_tile_kernel";
+    const mir_bm25 *h;
+    Dev dev(const Scope *sc, int64_t out_base) const {
+        ScopeDev d;
+        d.seg_begin = sc->seg_begin; d.seg_pos = sc->seg_pos; d.idf = sc->idf; d.avgdl = sc->avgdl; d.L = sc->n_pos;
+        d.out_base = out_base; d.n_seg = sc->n_seg;
+        return d;
+    }
+    void tile(dim3 grid, hipStream_t s, const Dev *sd, const int32_t *d_terms, const int32_t *d_ptr, double *dense) const {
+        launch_scoped_tile(h->deg(), grid, s, scoped_view(h), sd, d_terms, d_ptr, dense);
+    }
+    void topk(int nq, hipStream_t s, const Dev *sd, const double *dense, int k, int round, int q0, double *bound_s, int64_t *bound_i, char *base,
+              const OutColumn *col, int32_t *count) const {
+        bm25_scoped_topk_kernel<<<dim3(nq), dim3(kDkThreads), 0, s>>>(sd, dense, k, round, q0, bound_s, bound_i, col[0].at<int64_t>(base),
+                                                                      col[3].at<int32_t>(base), col[1].at<int64_t>(base), col[2].at<double>(base), count);
+    }
+};
 
 // BM25Okapi(the scope's chunks).get_scores(query) -> float64[L]
 int32_t mir_bm25_scores_scoped(mir_bm25 *h, const mir_bm25_scope *scope, const int32_t *q_terms_host, int32_t nq, double *out_scores_host) {
@@ -1972,35 +1984,7 @@ int32_t mir_bm25_scores_scoped(mir_bm25 *h, const mir_bm25_scope *scope, const i
     MIR_REQUIRE(scope != nullptr && scope->model == h, "the scope is not one of this model");
     MIR_REQUIRE(nq >= 0 && (nq == 0 || q_terms_host), "bad query");
     MIR_REQUIRE(out_scores_host != nullptr, "out_scores is NULL");
-    int32_t rc = use_device(h->device, nullptr);
-    if (rc != MIR_OK) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    const int64_t L = scope->n_pos;
-    const size_t o_ptr = ((size_t)nq * 4 + 255) & ~(size_t)255, o_sd = o_ptr + 256, o_sc = o_sd + 256;
-    static_assert(sizeof(ScopeDev) <= 256, "one slot");
-    rc = ensure_scratch(h, o_sc + (size_t)L * 8);
-    if (rc != MIR_OK) return rc;
-    char *base = static_cast<char *>(h->scratch);
-    const int32_t ptr2[2] = {0, nq};
-    const ScopeDev sd = scope_dev(scope, 0);
-    hipStream_t s = h->stream;
-    if (nq) MIR_HIP(hipMemcpyAsync(base, q_terms_host, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-    MIR_HIP(hipMemcpyAsync(base + o_ptr, ptr2, 8, hipMemcpyHostToDevice, s));
-    MIR_HIP(hipMemcpyAsync(base + o_sd, &sd, sizeof(sd), hipMemcpyHostToDevice, s));
-    const int tiles = (int)((L + kBm25Tile - 1) / kBm25Tile);
-    if (h->deg())
-        bm25_scoped_tile_kernel<true><<<dim3(tiles, 1), dim3(256), 0, s>>>(scoped_view(h), reinterpret_cast<const ScopeDev *>(base + o_sd),
-                                                                 reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
-                                                                 reinterpret_cast<double *>(base + o_sc));
-    else
-        bm25_scoped_tile_kernel<false><<<dim3(tiles, 1), dim3(256), 0, s>>>(scoped_view(h), reinterpret_cast<const ScopeDev *>(base + o_sd),
-                                                                 reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
-                                                                 reinterpret_cast<double *>(base + o_sc));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { (void)hipStreamSynchronize(s); set_error("bm25_scoped_tile_kernel: %s", hipGetErrorString(e)); return MIR_ERR_HIP; }
-    MIR_HIP(hipMemcpyAsync(out_scores_host, base + o_sc, (size_t)L * 8, hipMemcpyDeviceToHost, s));
-    MIR_HIP(hipStreamSynchronize(s));
-    return MIR_OK;
+    return scoped_scores(ModelRoute{h}, h, scope, q_terms_host, nq, out_scores_host);
 }
 
 // _get_top_n_indexes of b requests in one call: query i ranks the chunks of scopes[i].
@@ -2012,79 +1996,12 @@ int32_t mir_bm25_search_scoped(mir_bm25 *h, const mir_bm25_scope *const *scopes,
     MIR_REQUIRE(b >= 0 && k >= 1, "bad shape b=%d k=%d", b, k);
     if (b == 0) return MIR_OK;
     MIR_REQUIRE(scopes && q_ptr_host, "NULL buffer");
-    const int nt = q_ptr_host[b];
-    MIR_REQUIRE(q_ptr_host[0] == 0 && nt >= 0 && (nt == 0 || q_terms_host), "bad q_ptr");
-    for (int i = 0; i < b; ++i) {
-        MIR_REQUIRE(q_ptr_host[i + 1] >= q_ptr_host[i], "q_ptr not monotone");
-        MIR_REQUIRE(scopes[i] != nullptr && scopes[i]->model == h, "scope %d is not one of this model", i);
-    }
-    // the dense scores of a group of queries share the workspace: groups of at most 2^27 scores (1 GiB) and 65535 queries
-    const int64_t cap = (int64_t)1 << 27;
-    std::vector<ScopeDev> sd((size_t)b);
-    std::vector<int> group_start{0};
-    int64_t acc = 0, need = 0;
-    for (int i = 0; i < b; ++i) {
-        const int64_t L = scopes[i]->n_pos;
-        if (acc > 0 && (acc + L > cap || i - group_start.back() >= 65535)) { group_start.push_back(i); acc = 0; }
-        sd[i] = scope_dev(scopes[i], acc);
-        acc += L;
-        need = std::max(need, acc);
-    }
-    group_start.push_back(b);
-    int32_t rc = use_device(h->device, nullptr);
+    int nt = 0;
+    const int32_t rc = check_query_batch(q_terms_host, q_ptr_host, b, &nt);
     if (rc != MIR_OK) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    const size_t bk = (size_t)b * k;
-    const size_t o_terms = take((size_t)nt * 4 + 4), o_ptr = take((size_t)(b + 1) * 4), o_sd = take((size_t)b * sizeof(ScopeDev));
-    const size_t o_pos = take(bk * 8), o_doc = take(bk * 8), o_sc = take(bk * 8), o_ord = take(bk * 4), o_cnt = take((size_t)b * 4);
-    const size_t o_bs = take((size_t)b * 8), o_bi = take((size_t)b * 8), o_dense = take((size_t)need * 8);
-    rc = ensure_scratch(h, off);
-    if (rc != MIR_OK) return rc;
-    char *base = static_cast<char *>(h->scratch);
-    hipStream_t s = h->stream;
-    auto launch = [&]() -> int32_t {
-        if (nt) MIR_HIP(hipMemcpyAsync(base + o_terms, q_terms_host, (size_t)nt * 4, hipMemcpyHostToDevice, s));
-        MIR_HIP(hipMemcpyAsync(base + o_ptr, q_ptr_host, (size_t)(b + 1) * 4, hipMemcpyHostToDevice, s));
-        MIR_HIP(hipMemcpyAsync(base + o_sd, sd.data(), (size_t)b * sizeof(ScopeDev), hipMemcpyHostToDevice, s));
-        MIR_HIP(hipMemsetAsync(base + o_pos, 0, o_bs - o_pos, s));  // rows past a query's count read as zeros
-        const ScopeDev *d_sd = reinterpret_cast<const ScopeDev *>(base + o_sd);
-        const int32_t *d_ptr = reinterpret_cast<const int32_t *>(base + o_ptr);
-        for (size_t g = 0; g + 1 < group_start.size(); ++g) {
-            const int g0 = group_start[g], nq = group_start[g + 1] - g0;
-            int64_t maxL = 0;
-            for (int i = g0; i < g0 + nq; ++i) maxL = std::max(maxL, scopes[i]->n_pos);
-            if (maxL == 0) continue;
-            const int tiles = (int)((maxL + kBm25Tile - 1) / kBm25Tile);
-            if (h->deg())
-                bm25_scoped_tile_kernel<true><<<dim3(tiles, nq), dim3(256), 0, s>>>(scoped_view(h), d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
-                                                                          d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
-            else
-                bm25_scoped_tile_kernel<false><<<dim3(tiles, nq), dim3(256), 0, s>>>(scoped_view(h), d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
-                                                                          d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
-            MIR_HIP(hipGetLastError());
-            const int64_t found = std::min<int64_t>(k, maxL);
-            const int rounds = (int)((found + kDkRound - 1) / kDkRound);
-            for (int r = 0; r < rounds; ++r) {
-                bm25_scoped_topk_kernel<<<dim3(nq), dim3(kDkThreads), 0, s>>>(
-                    d_sd, reinterpret_cast<const double *>(base + o_dense), k, r, g0, reinterpret_cast<double *>(base + o_bs),
-                    reinterpret_cast<int64_t *>(base + o_bi), reinterpret_cast<int64_t *>(base + o_pos), reinterpret_cast<int32_t *>(base + o_ord),
-                    reinterpret_cast<int64_t *>(base + o_doc), reinterpret_cast<double *>(base + o_sc), reinterpret_cast<int32_t *>(base + o_cnt));
-                MIR_HIP(hipGetLastError());
-            }
-        }
-        if (out_pos) MIR_HIP(hipMemcpyAsync(out_pos, base + o_pos, bk * 8, hipMemcpyDeviceToHost, s));
-        if (out_doc) MIR_HIP(hipMemcpyAsync(out_doc, base + o_doc, bk * 8, hipMemcpyDeviceToHost, s));
-        if (out_score) MIR_HIP(hipMemcpyAsync(out_score, base + o_sc, bk * 8, hipMemcpyDeviceToHost, s));
-        if (out_ord) MIR_HIP(hipMemcpyAsync(out_ord, base + o_ord, bk * 4, hipMemcpyDeviceToHost, s));
-        if (out_count) MIR_HIP(hipMemcpyAsync(out_count, base + o_cnt, (size_t)b * 4, hipMemcpyDeviceToHost, s));
-        return MIR_OK;
-    };
-    rc = launch();
-    if (rc != MIR_OK) { (void)hipStreamSynchronize(s); return rc; }
-    MIR_HIP(hipStreamSynchronize(s));
-    return MIR_OK;
+    for (int i = 0; i < b; ++i) MIR_REQUIRE(scopes[i] != nullptr && scopes[i]->model == h, "scope %d is not one of this model", i);
+    OutColumn cols[4] = {{out_pos, 8}, {out_doc, 8}, {out_score, 8}, {out_ord, 4}};
+    return scoped_search(ModelRoute{h}, h, scopes, q_terms_host, q_ptr_host, nt, b, k, cols, 4, out_count);
 }
 
 // ---- block BM25 (bm25_blocks.h): resident per-document keyword blocks, every query ranks its own list of them ----------
@@ -2102,9 +2019,9 @@ struct mir_bm25_blocks {
     int device = 0;
     double k1 = 1.5, b = 0.75, epsilon = 0.25;
     std::mutex mu;  // serialises use of the scratch below
-    void *scratch = nullptr;
-    size_t scratch_cap = 0;
+    DevScratch scratch;
     hipStream_t stream = nullptr;
+    int32_t take_scratch(size_t need) { return scratch.ensure(need); }
 };
 
 // A scope of a searcher (mir_bm25_blocks_scope_create): immutable once built, shared by any number of searches.
@@ -2141,16 +2058,6 @@ static void free_blocks_scope(mir_bm25_blocks_scope *sc) {
     (void)hipFree(sc->pos);
     (void)hipFree(sc->idf);
     delete sc;
-}
-
-static int32_t blocks_scratch(mir_bm25_blocks *h, size_t need) {
-    if (h->scratch_cap >= need) return MIR_OK;
-    if (h->scratch) (void)hipFree(h->scratch);
-    h->scratch = nullptr;
-    h->scratch_cap = 0;
-    MIR_HIP(hipMalloc(&h->scratch, need));
-    h->scratch_cap = need;
-    return MIR_OK;
 }
 
 int32_t mir_bm25_doc_create(const int64_t *indptr, const int32_t *term_ids, int64_t n_chunks, const int64_t *chunk_ids, int32_t device,
@@ -2225,7 +2132,7 @@ int32_t mir_bm25_blocks_create(double k1, double b, double epsilon, int32_t devi
 int32_t mir_bm25_blocks_destroy(mir_bm25_blocks *h) {
     if (!h) return MIR_OK;
     (void)hipSetDevice(h->device);
-    (void)hipFree(h->scratch);
+    h->scratch.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return MIR_OK;
@@ -2265,17 +2172,17 @@ int32_t mir_bm25_blocks_scope_create(mir_bm25_blocks *h, const mir_bm25_doc *con
     const int32_t V = max_term + 1;  // >= 1: there is a token
     sc->searcher = h; sc->device = h->device; sc->n_blk = n; sc->vocab = V; sc->n_pos = L; sc->total_tokens = total;
     sc->avgdl = (double)total / (double)L;
-    int64_t *d_tok = nullptr, *d_upre = nullptr;
-    unsigned long long *d_df = nullptr, *d_first = nullptr;
-    std::vector<int64_t> df((size_t)V), first((size_t)V);
+    DevTemps tmp;
     auto run = [&]() -> int32_t {
+        int64_t *d_tok = nullptr, *d_upre = nullptr;
+        unsigned long long *d_df = nullptr, *d_first = nullptr;
         MIR_HIP(hipMalloc((void **)&sc->blk, (size_t)n * sizeof(Bm25BlockDev)));
         MIR_HIP(hipMalloc((void **)&sc->pos, ((size_t)n + 1) * 8));
         MIR_HIP(hipMalloc((void **)&sc->idf, (size_t)V * 8));
-        MIR_HIP(hipMalloc((void **)&d_tok, ((size_t)n + 1) * 8));
-        MIR_HIP(hipMalloc((void **)&d_upre, ((size_t)n + 1) * 8));
-        MIR_HIP(hipMalloc((void **)&d_df, (size_t)V * 8));
-        MIR_HIP(hipMalloc((void **)&d_first, (size_t)V * 8));
+        if ((rc = tmp.alloc(&d_tok, ((size_t)n + 1) * 8)) != MIR_OK) return rc;
+        if ((rc = tmp.alloc(&d_upre, ((size_t)n + 1) * 8)) != MIR_OK) return rc;
+        if ((rc = tmp.alloc(&d_df, (size_t)V * 8)) != MIR_OK) return rc;
+        if ((rc = tmp.alloc(&d_first, (size_t)V * 8)) != MIR_OK) return rc;
         sc->hbm_bytes = (int64_t)n * (int64_t)sizeof(Bm25BlockDev) + ((int64_t)n + 1) * 8 + (int64_t)V * 8;
         std::lock_guard<std::mutex> lk(h->mu);
         hipStream_t s = h->stream;
@@ -2288,26 +2195,9 @@ int32_t mir_bm25_blocks_scope_create(mir_bm25_blocks *h, const mir_bm25_doc *con
         const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((total_u + 255) / 256, 1 << 16));
         bm25_blocks_stats_kernel<<<dim3(grid), dim3(256), 0, s>>>(sc->blk, d_upre, d_tok, n, total_u, V, d_df, d_first);
         MIR_HIP(hipGetLastError());
-        MIR_HIP(hipMemcpyAsync(df.data(), d_df, (size_t)V * 8, hipMemcpyDeviceToHost, s));
-        MIR_HIP(hipMemcpyAsync(first.data(), d_first, (size_t)V * 8, hipMemcpyDeviceToHost, s));
-        MIR_HIP(hipStreamSynchronize(s));
-        // BM25Okapi._calc_idf over the scope's corpus: N = L, first-appearance order of the scope's own token stream
-        for (int32_t t = 0; t < V; ++t) {
-            if (df[t] > 0) ++sc->n_terms;
-            if (df[t] <= 0 || first[t] < 0) first[t] = INT64_MAX;  // (~0 = absent)
-        }
-        sc->h_idf.assign((size_t)V, 0.0);
-        int32_t rc2 = mir_bm25_idf_from_stats(df.data(), first.data(), V, L, h->epsilon, sc->h_idf.data(), &sc->average_idf);
-        if (rc2 != MIR_OK) return rc2;
-        MIR_HIP(hipMemcpyAsync(sc->idf, sc->h_idf.data(), (size_t)V * 8, hipMemcpyHostToDevice, s));
-        MIR_HIP(hipStreamSynchronize(s));
-        return MIR_OK;
+        return scope_stats_tail(s, d_df, d_first, V, L, h->epsilon, &sc->n_terms, &sc->h_idf, &sc->average_idf, sc->idf);
     };
     rc = run();
-    (void)hipFree(d_tok);
-    (void)hipFree(d_upre);
-    (void)hipFree(d_df);
-    (void)hipFree(d_first);
     if (rc != MIR_OK) {
         free_blocks_scope(sc);
         return rc;
@@ -2340,12 +2230,38 @@ int32_t mir_bm25_blocks_scope_idf(const mir_bm25_blocks_scope *scope, double *ou
     return MIR_OK;
 }
 
-static BlockScopeDev blocks_scope_dev(const mir_bm25_blocks_scope *sc, int64_t out_base) {
-    BlockScopeDev d;
-    d.blk = sc->blk; d.pos = sc->pos; d.idf = sc->idf; d.avgdl = sc->avgdl; d.L = sc->n_pos;
-    d.out_base = out_base; d.n_blk = sc->n_blk; d.vocab = sc->vocab;
-    return d;
+// the one place that picks the DEG form of bm25_blocks_tile_kernel
+static void launch_blocks_tile(bool deg, dim3 grid, hipStream_t s, double k1, double b, const BlockScopeDev *sd, const int32_t *d_terms,
+                               const int32_t *d_ptr, double *dense) {
+    if (deg)
+        bm25_blocks_tile_kernel<true><<<grid, dim3(256), 0, s>>>(k1, b, sd, d_terms, d_ptr, dense);
+    else
+        bm25_blocks_tile_kernel<false><<<grid, dim3(256), 0, s>>>(k1, b, sd, d_terms, d_ptr, dense);
 }
+
+// The block route as bm25_host.h sees it.  Columns of a search: pos i64, chunk i64, score f64, ord i32, local i32.
+struct BlockRoute {
+    using Owner = mir_bm25_blocks;
+    using Scope = mir_bm25_blocks_scope;
+    using Dev = BlockScopeDev;
+    static constexpr const char *kTileName = "bm25_blocks_tile_kernel";
+    const mir_bm25_blocks *h;
+    Dev dev(const Scope *sc, int64_t out_base) const {
+        BlockScopeDev d;
+        d.blk = sc->blk; d.pos = sc->pos; d.idf = sc->idf; d.avgdl = sc->avgdl; d.L = sc->n_pos;
+        d.out_base = out_base; d.n_blk = sc->n_blk; d.vocab = sc->vocab;
+        return d;
+    }
+    void tile(dim3 grid, hipStream_t s, const Dev *sd, const int32_t *d_terms, const int32_t *d_ptr, double *dense) const {
+        launch_blocks_tile(bm25_params_degenerate(h->k1, h->b), grid, s, h->k1, h->b, sd, d_terms, d_ptr, dense);
+    }
+    void topk(int nq, hipStream_t s, const Dev *sd, const double *dense, int k, int round, int q0, double *bound_s, int64_t *bound_i, char *base,
+              const OutColumn *col, int32_t *count) const {
+        bm25_blocks_topk_kernel<<<dim3(nq), dim3(kDkThreads), 0, s>>>(sd, dense, k, round, q0, bound_s, bound_i, col[0].at<int64_t>(base),
+                                                                      col[3].at<int32_t>(base), col[4].at<int32_t>(base), col[1].at<int64_t>(base),
+                                                                      col[2].at<double>(base), count);
+    }
+};
 
 // BM25Okapi(the scope's chunks).get_scores(query) -> float64[L]
 int32_t mir_bm25_blocks_scores(mir_bm25_blocks *h, const mir_bm25_blocks_scope *scope, const int32_t *q_terms_host, int32_t nq,
@@ -2354,35 +2270,7 @@ int32_t mir_bm25_blocks_scores(mir_bm25_blocks *h, const mir_bm25_blocks_scope *
     MIR_REQUIRE(scope != nullptr && scope->searcher == h, "the scope is not one of this searcher");
     MIR_REQUIRE(nq >= 0 && (nq == 0 || q_terms_host), "bad query");
     MIR_REQUIRE(out_scores_host != nullptr, "out_scores is NULL");
-    int32_t rc = use_device(h->device, nullptr);
-    if (rc != MIR_OK) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    const int64_t L = scope->n_pos;
-    const size_t o_ptr = ((size_t)nq * 4 + 255) & ~(size_t)255, o_sd = o_ptr + 256, o_sc = o_sd + 256;
-    static_assert(sizeof(BlockScopeDev) <= 256, "one slot");
-    rc = blocks_scratch(h, o_sc + (size_t)L * 8);
-    if (rc != MIR_OK) return rc;
-    char *base = static_cast<char *>(h->scratch);
-    const int32_t ptr2[2] = {0, nq};
-    const BlockScopeDev sd = blocks_scope_dev(scope, 0);
-    hipStream_t s = h->stream;
-    if (nq) MIR_HIP(hipMemcpyAsync(base, q_terms_host, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-    MIR_HIP(hipMemcpyAsync(base + o_ptr, ptr2, 8, hipMemcpyHostToDevice, s));
-    MIR_HIP(hipMemcpyAsync(base + o_sd, &sd, sizeof(sd), hipMemcpyHostToDevice, s));
-    const int tiles = (int)((L + kBm25Tile - 1) / kBm25Tile);
-    if (bm25_params_degenerate(h->k1, h->b))
-        bm25_blocks_tile_kernel<true><<<dim3(tiles, 1), dim3(256), 0, s>>>(h->k1, h->b, reinterpret_cast<const BlockScopeDev *>(base + o_sd),
-                                                                 reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
-                                                                 reinterpret_cast<double *>(base + o_sc));
-    else
-        bm25_blocks_tile_kernel<false><<<dim3(tiles, 1), dim3(256), 0, s>>>(h->k1, h->b, reinterpret_cast<const BlockScopeDev *>(base + o_sd),
-                                                                 reinterpret_cast<const int32_t *>(base), reinterpret_cast<const int32_t *>(base + o_ptr),
-                                                                 reinterpret_cast<double *>(base + o_sc));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { (void)hipStreamSynchronize(s); set_error("bm25_blocks_tile_kernel: %s", hipGetErrorString(e)); return MIR_ERR_HIP; }
-    MIR_HIP(hipMemcpyAsync(out_scores_host, base + o_sc, (size_t)L * 8, hipMemcpyDeviceToHost, s));
-    MIR_HIP(hipStreamSynchronize(s));
-    return MIR_OK;
+    return scoped_scores(BlockRoute{h}, h, scope, q_terms_host, nq, out_scores_host);
 }
 
 // _get_top_n_indexes of b requests in one call: query i ranks the chunks of scopes[i].
@@ -2393,83 +2281,15 @@ int32_t mir_bm25_blocks_search(mir_bm25_blocks *h, const mir_bm25_blocks_scope *
     MIR_REQUIRE(b >= 0 && k >= 1, "bad shape b=%d k=%d", b, k);
     if (b == 0) return MIR_OK;
     MIR_REQUIRE(scopes && q_ptr_host, "NULL buffer");
-    const int nt = q_ptr_host[b];
-    MIR_REQUIRE(q_ptr_host[0] == 0 && nt >= 0 && (nt == 0 || q_terms_host), "bad q_ptr");
+    int nt = 0;
+    const int32_t rc = check_query_batch(q_terms_host, q_ptr_host, b, &nt);
+    if (rc != MIR_OK) return rc;
     for (int i = 0; i < b; ++i) {
-        MIR_REQUIRE(q_ptr_host[i + 1] >= q_ptr_host[i], "q_ptr not monotone");
         MIR_REQUIRE(scopes[i] != nullptr && scopes[i]->searcher == h, "scope %d is not one of this searcher", i);
         MIR_REQUIRE(scopes[i]->n_pos < ((int64_t)1 << 31), "scope %d holds 2^31 chunks or more", i);
     }
-    // the dense scores of a group of queries share the workspace: groups of at most 2^27 scores (1 GiB) and 65535 queries
-    const int64_t cap = (int64_t)1 << 27;
-    std::vector<BlockScopeDev> sd((size_t)b);
-    std::vector<int> group_start{0};
-    int64_t acc = 0, need = 0;
-    for (int i = 0; i < b; ++i) {
-        const int64_t L = scopes[i]->n_pos;
-        if (acc > 0 && (acc + L > cap || i - group_start.back() >= 65535)) { group_start.push_back(i); acc = 0; }
-        sd[i] = blocks_scope_dev(scopes[i], acc);
-        acc += L;
-        need = std::max(need, acc);
-    }
-    group_start.push_back(b);
-    int32_t rc = use_device(h->device, nullptr);
-    if (rc != MIR_OK) return rc;
-    std::lock_guard<std::mutex> lk(h->mu);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    const size_t bk = (size_t)b * k;
-    const size_t o_terms = take((size_t)nt * 4 + 4), o_ptr = take((size_t)(b + 1) * 4), o_sd = take((size_t)b * sizeof(BlockScopeDev));
-    const size_t o_pos = take(bk * 8), o_chunk = take(bk * 8), o_sc = take(bk * 8), o_ord = take(bk * 4), o_loc = take(bk * 4);
-    const size_t o_cnt = take((size_t)b * 4);
-    const size_t o_bs = take((size_t)b * 8), o_bi = take((size_t)b * 8), o_dense = take((size_t)need * 8);
-    rc = blocks_scratch(h, off);
-    if (rc != MIR_OK) return rc;
-    char *base = static_cast<char *>(h->scratch);
-    hipStream_t s = h->stream;
-    auto launch = [&]() -> int32_t {
-        if (nt) MIR_HIP(hipMemcpyAsync(base + o_terms, q_terms_host, (size_t)nt * 4, hipMemcpyHostToDevice, s));
-        MIR_HIP(hipMemcpyAsync(base + o_ptr, q_ptr_host, (size_t)(b + 1) * 4, hipMemcpyHostToDevice, s));
-        MIR_HIP(hipMemcpyAsync(base + o_sd, sd.data(), (size_t)b * sizeof(BlockScopeDev), hipMemcpyHostToDevice, s));
-        MIR_HIP(hipMemsetAsync(base + o_pos, 0, o_bs - o_pos, s));  // rows past a query's count read as zeros
-        const BlockScopeDev *d_sd = reinterpret_cast<const BlockScopeDev *>(base + o_sd);
-        const int32_t *d_ptr = reinterpret_cast<const int32_t *>(base + o_ptr);
-        for (size_t g = 0; g + 1 < group_start.size(); ++g) {
-            const int g0 = group_start[g], nq = group_start[g + 1] - g0;
-            int64_t maxL = 0;
-            for (int i = g0; i < g0 + nq; ++i) maxL = std::max(maxL, scopes[i]->n_pos);
-            if (maxL == 0) continue;
-            const int tiles = (int)((maxL + kBm25Tile - 1) / kBm25Tile);
-            if (bm25_params_degenerate(h->k1, h->b))
-                bm25_blocks_tile_kernel<true><<<dim3(tiles, nq), dim3(256), 0, s>>>(h->k1, h->b, d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
-                                                                          d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
-            else
-                bm25_blocks_tile_kernel<false><<<dim3(tiles, nq), dim3(256), 0, s>>>(h->k1, h->b, d_sd + g0, reinterpret_cast<const int32_t *>(base + o_terms),
-                                                                          d_ptr + g0, reinterpret_cast<double *>(base + o_dense));
-            MIR_HIP(hipGetLastError());
-            const int64_t found = std::min<int64_t>(k, maxL);
-            const int rounds = (int)((found + kDkRound - 1) / kDkRound);
-            for (int r = 0; r < rounds; ++r) {
-                bm25_blocks_topk_kernel<<<dim3(nq), dim3(kDkThreads), 0, s>>>(
-                    d_sd, reinterpret_cast<const double *>(base + o_dense), k, r, g0, reinterpret_cast<double *>(base + o_bs),
-                    reinterpret_cast<int64_t *>(base + o_bi), reinterpret_cast<int64_t *>(base + o_pos), reinterpret_cast<int32_t *>(base + o_ord),
-                    reinterpret_cast<int32_t *>(base + o_loc), reinterpret_cast<int64_t *>(base + o_chunk), reinterpret_cast<double *>(base + o_sc),
-                    reinterpret_cast<int32_t *>(base + o_cnt));
-                MIR_HIP(hipGetLastError());
-            }
-        }
-        if (out_pos) MIR_HIP(hipMemcpyAsync(out_pos, base + o_pos, bk * 8, hipMemcpyDeviceToHost, s));
-        if (out_chunk) MIR_HIP(hipMemcpyAsync(out_chunk, base + o_chunk, bk * 8, hipMemcpyDeviceToHost, s));
-        if (out_score) MIR_HIP(hipMemcpyAsync(out_score, base + o_sc, bk * 8, hipMemcpyDeviceToHost, s));
-        if (out_ord) MIR_HIP(hipMemcpyAsync(out_ord, base + o_ord, bk * 4, hipMemcpyDeviceToHost, s));
-        if (out_local) MIR_HIP(hipMemcpyAsync(out_local, base + o_loc, bk * 4, hipMemcpyDeviceToHost, s));
-        if (out_count) MIR_HIP(hipMemcpyAsync(out_count, base + o_cnt, (size_t)b * 4, hipMemcpyDeviceToHost, s));
-        return MIR_OK;
-    };
-    rc = launch();
-    if (rc != MIR_OK) { (void)hipStreamSynchronize(s); return rc; }
-    MIR_HIP(hipStreamSynchronize(s));
-    return MIR_OK;
+    OutColumn cols[5] = {{out_pos, 8}, {out_chunk, 8}, {out_score, 8}, {out_ord, 4}, {out_local, 4}};
+    return scoped_search(BlockRoute{h}, h, scopes, q_terms_host, q_ptr_host, nt, b, k, cols, 5, out_count);
 }
 
 }  // extern "C"

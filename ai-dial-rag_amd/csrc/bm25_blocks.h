@@ -14,6 +14,8 @@
 //   bm25_blocks_topk_kernel   bm25_dense_topk_body over the query's dense scores; a result's block by binary search in
 //                             the position prefix
 // The model route's kernels (bm25_scoped.h) are untouched: these are siblings, not template instances.
+// Kernels only.  The host side is bm25.hip's BlockRoute and entries over bm25_host.h, the path scoped BM25 shares
+// (DESIGN.md 4.9).
 #pragma once
 
 namespace mir {

@@ -10,6 +10,8 @@
 //   bm25_scoped_tile_kernel  scores of one tile of 8192 scope POSITIONS in LDS, query tokens one after the other;
 //                            the weight is computed from p_tf / d_doclen with the scope's avgdl (p_w is not read)
 //   bm25_scoped_topk_kernel  the reference's order over a query's dense scores, rounds of 64 (any k)
+// Kernels only.  The host side is bm25.hip's ModelRoute and entries over bm25_host.h, the path block BM25 shares
+// (DESIGN.md 4.9).
 #pragma once
 
 namespace mir {

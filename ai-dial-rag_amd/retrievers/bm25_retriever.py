@@ -25,10 +25,43 @@ from ..index_record import Document, RetrievalType, to_metadata_doc
 from ._group_commit import _GroupCommit
 
 
-class BM25Scope:
+class _HandleOwner:
+    """Owner of one native handle ``_h``: ``handle``, and ``close`` (also at collection) through the library's
+    ``_destroy`` entry."""
+
+    _h = None
+    _destroy: str
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            getattr(nat.lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _pack_queries(queries_ids: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (flat i32[tokens], ptr i32[b + 1]): query i is flat[ptr[i]:ptr[i + 1]]."""
+    ptr = np.zeros(len(queries_ids) + 1, np.int32)
+    ptr[1:] = np.cumsum([len(q) for q in queries_ids])
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(q, np.int32) for q in queries_ids]) if ptr[-1] else np.zeros(0, np.int32))
+    return flat, ptr
+
+
+class BM25Scope(_HandleOwner):
     """Owner of one ``mir_bm25_scope``: an ordered list of document segments of a ``DeviceBM25`` built with
     ``keep_tokens=True``, with the statistics rank-bm25 would derive from those chunks alone.  Immutable; any number of
     searches may use it at once.  It keeps its model alive."""
+
+    _destroy = "mir_bm25_scope_destroy"
 
     def __init__(self, handle, model: "DeviceBM25", n_seg: int):
         self._h, self.model, self.n_seg = handle, model, n_seg
@@ -46,24 +79,11 @@ class BM25Scope:
         nat.check(nat.lib.mir_bm25_scope_idf(self._h, nat.ptr(out)))
         return out
 
-    @property
-    def handle(self):
-        return self._h
 
-    def close(self):
-        if self._h:
-            nat.lib.mir_bm25_scope_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceBM25:
+class DeviceBM25(_HandleOwner):
     """Owner of one ``mir_bm25`` handle over token-id documents."""
+
+    _destroy = "mir_bm25_destroy"
 
     def __init__(self, handle, n_docs: int, vocab: int, device: int):
         self._h, self.n_docs, self.vocab, self.device = handle, n_docs, vocab, device
@@ -140,9 +160,7 @@ class DeviceBM25:
     def search(self, queries_ids: Sequence[Sequence[int]], k: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """-> (idx[b,k] i64, score[b,k] f64, count[b] i32), best first."""
         b = len(queries_ids)
-        ptr = np.zeros(b + 1, np.int32)
-        ptr[1:] = np.cumsum([len(q) for q in queries_ids])
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(q, np.int32) for q in queries_ids]) if ptr[-1] else np.zeros(0, np.int32))
+        flat, ptr = _pack_queries(queries_ids)
         idx = np.zeros((b, k), np.int64)
         sc = np.zeros((b, k), np.float64)
         cnt = np.zeros(b, np.int32)
@@ -174,9 +192,7 @@ class DeviceBM25:
         b = len(queries_ids)
         if len(scopes) != b:
             raise ValueError(f"{len(scopes)} scopes for {b} queries")
-        ptr = np.zeros(b + 1, np.int32)
-        ptr[1:] = np.cumsum([len(q) for q in queries_ids])
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(q, np.int32) for q in queries_ids]) if ptr[-1] else np.zeros(0, np.int32))
+        flat, ptr = _pack_queries(queries_ids)
         handles = (C.c_void_p * max(b, 1))(*[s.handle for s in scopes])
         pos, doc = np.zeros((b, k), np.int64), np.zeros((b, k), np.int64)
         order = np.zeros((b, k), np.int32)
@@ -200,25 +216,12 @@ class DeviceBM25:
         nat.check(nat.lib.mir_bm25_search_device(self._h, q_terms_ptr or None, q_ptr_ptr, b, k, out_idx_ptr, out_score_ptr,
                                                  out_count_ptr, workspace_ptr, stream or None))
 
-    @property
-    def handle(self):
-        return self._h
 
-    def close(self):
-        if self._h:
-            nat.lib.mir_bm25_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceBM25Doc:
+class DeviceBM25Doc(_HandleOwner):
     """Owner of one ``mir_bm25_doc``: ONE document's keyword block in HBM (its own term table and postings), built once
     and listed by any number of ``BM25BlockScope``.  Term ids are those of the caller's id space (any int32 >= 0)."""
+
+    _destroy = "mir_bm25_doc_destroy"
 
     def __init__(self, handle, device: int):
         self._h, self.device = handle, device
@@ -248,26 +251,13 @@ class DeviceBM25Doc:
         return {"n_chunks": n.value, "n_tokens": tok.value, "n_terms": u.value, "n_postings": p.value, "max_term": top.value,
                 "hbm_bytes": hb.value}
 
-    @property
-    def handle(self):
-        return self._h
 
-    def close(self):
-        if self._h:
-            nat.lib.mir_bm25_doc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BM25BlockScope:
+class BM25BlockScope(_HandleOwner):
     """Owner of one ``mir_bm25_blocks_scope``: an ordered list of document blocks with the statistics rank-bm25 would
     derive from their chunks alone.  Immutable; any number of searches may use it at once.  It keeps its blocks and its
     searcher alive."""
+
+    _destroy = "mir_bm25_blocks_scope_destroy"
 
     def __init__(self, handle, searcher: "BM25BlockSearcher", docs: Sequence[DeviceBM25Doc]):
         self._h, self.searcher, self.docs = handle, searcher, list(docs)
@@ -288,24 +278,11 @@ class BM25BlockScope:
         nat.check(nat.lib.mir_bm25_blocks_scope_idf(self._h, nat.ptr(out)))
         return out
 
-    @property
-    def handle(self):
-        return self._h
 
-    def close(self):
-        if self._h:
-            nat.lib.mir_bm25_blocks_scope_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BM25BlockSearcher:
+class BM25BlockSearcher(_HandleOwner):
     """Owner of one ``mir_bm25_blocks`` searcher: workspaces only, no documents (the counterpart of ``BlockSearcher``)."""
+
+    _destroy = "mir_bm25_blocks_destroy"
 
     def __init__(self, k1: float = 1.5, b: float = 0.75, epsilon: float = 0.25, device: int = 0):
         h = C.c_void_p()
@@ -335,9 +312,7 @@ class BM25BlockSearcher:
             raise ValueError(f"{len(scopes)} scopes for {b} queries")
         if int(k) < 1:
             raise ValueError(f"k={k} must be >= 1")
-        ptr = np.zeros(b + 1, np.int32)
-        ptr[1:] = np.cumsum([len(q) for q in queries_ids])
-        flat = np.ascontiguousarray(np.concatenate([np.asarray(q, np.int32) for q in queries_ids]) if ptr[-1] else np.zeros(0, np.int32))
+        flat, ptr = _pack_queries(queries_ids)
         handles = (C.c_void_p * max(b, 1))(*[s.handle for s in scopes])
         pos, chunk = np.zeros((b, k), np.int64), np.zeros((b, k), np.int64)
         order, local = np.zeros((b, k), np.int32), np.zeros((b, k), np.int32)
@@ -346,21 +321,6 @@ class BM25BlockSearcher:
         nat.check(nat.lib.mir_bm25_blocks_search(self._h, handles, nat.ptr(flat) if len(flat) else None, nat.ptr(ptr), b, k, nat.ptr(pos),
                                                  nat.ptr(order), nat.ptr(local), nat.ptr(chunk), nat.ptr(sc), nat.ptr(cnt)))
         return pos, order, local, chunk, sc, cnt
-
-    @property
-    def handle(self):
-        return self._h
-
-    def close(self):
-        if self._h:
-            nat.lib.mir_bm25_blocks_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class TextIndexItem:

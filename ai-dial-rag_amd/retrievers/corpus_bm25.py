@@ -12,14 +12,12 @@ yields.  No model is composed per document set, and queries of different request
 """
 
 import threading
-from collections import OrderedDict
-from typing import Hashable, List, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from ..index_record import Document, RetrievalType, to_metadata_doc
-from ._group_commit import _GroupCommit
-from .bm25_retriever import _VOCAB, BM25Scope, DeviceBM25, _doc_token_ids
+from ._scoped_bm25 import ScopedBM25Corpus, ScopedBM25View
+from .bm25_retriever import BM25Scope, DeviceBM25, _doc_token_ids
 from .embeddings_index import scope_segments
 from .sharded_bm25 import fuse_batch
 
@@ -51,63 +49,20 @@ def _document_arrays(doc) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     return np.arange(len(doc), dtype=np.int64), lens, ids
 
 
-class CorpusBM25View:
-    """``BM25Retriever``'s retrieval surface over some documents of a corpus.  ``doc_id`` of a result = the position
-    of its document in ``doc_positions``.  The scope (the request's statistics, in HBM) is built at first use and kept."""
+class CorpusBM25View(ScopedBM25View):
+    """``ScopedBM25View`` over some documents of a ``CorpusBM25``: ``doc_positions`` lists them, a scope is the list of
+    their chunk ranges."""
 
     def __init__(self, corpus: "CorpusBM25", doc_positions: Sequence[int], k: int):
-        self.corpus = corpus
         self.doc_positions = [int(p) for p in doc_positions]
-        self.limit = int(k)
-        if self.limit < 1:
-            raise ValueError(f"k={k} must be >= 1")
+        super().__init__(corpus, k)
         self.seg_begin, self.seg_end = scope_segments(corpus.doc_lengths, self.doc_positions)
-        self._scope: Optional[BM25Scope] = None
-        self._scope_lock = threading.Lock()
-        self._parent: Optional["CorpusBM25View"] = None  # a view that differs only in its limit shares the scope
 
-    def scope(self) -> BM25Scope:
-        if self._parent is not None:
-            return self._parent.scope()
-        with self._scope_lock:
-            if self._scope is None:
-                self._scope = self.corpus._make_scope(self.seg_begin, self.seg_end)  # no token: "Text index is empty."
-            return self._scope
-
-    def _with_limit(self, n: int) -> "CorpusBM25View":
-        if n == self.limit:
-            return self
-        v = CorpusBM25View.__new__(CorpusBM25View)
-        v.__dict__.update(self.__dict__)
-        v.limit, v._parent, v._scope = int(n), (self._parent or self), None
-        if v.limit < 1:
-            raise ValueError(f"n={n} must be >= 1")
-        return v
-
-    def _get_top_n_indexes(self, query_ids: Sequence[Hashable], n: int = 5) -> np.ndarray:
-        """bm25_retriever.py:81-84 over the request's own flattened chunk list; concurrent callers of ANY view of
-        the corpus share passes."""
-        pos, _doc, _chunk, _score, cnt = self.corpus._commit.submit((query_ids, self._with_limit(n)))
-        return pos[: int(cnt)]
-
-    def search_batch(self, queries_ids: Sequence[Sequence[Hashable]]) -> List[List[Tuple[int, int]]]:
-        """-> per query the (doc position in the request, chunk id) pairs, best first."""
-        qs = [self.corpus._ids(q) for q in queries_ids]
-        _pos, doc, chunk, _score, cnt = self.corpus._search_views(qs, [self] * len(qs), self.limit)
-        return [[(int(doc[i, j]), int(chunk[i, j])) for j in range(int(cnt[i]))] for i in range(len(qs))]
-
-    def get_relevant_documents(self, query_ids: Sequence[Hashable]) -> List[Document]:
-        _pos, doc, chunk, _score, cnt = self.corpus._commit.submit((query_ids, self))
-        return [to_metadata_doc(int(doc[j]), int(chunk[j]), RetrievalType.TEXT) for j in range(int(cnt))]
-
-    def close(self):
-        with self._scope_lock:
-            if self._scope is not None:
-                self._scope.close()
-                self._scope = None
+    def _new_scope(self) -> BM25Scope:
+        return self.corpus._make_scope(self.seg_begin, self.seg_end)
 
 
-class CorpusBM25:
+class CorpusBM25(ScopedBM25Corpus):
     """``documents``: see ``_document_arrays``.  ``vocab``: the size of the term-id space (default: largest id + 1).
     The device model is built at the first search.  ``max_scopes``: how many document lists ``find_many`` keeps the scope
     of (a scope holds 8 bytes of HBM per vocabulary entry)."""
@@ -127,10 +82,7 @@ class CorpusBM25:
             raise ValueError(f"term id {top - 1} outside vocab={self.vocab}")
         self._dev: Optional[DeviceBM25] = None
         self._lock = threading.Lock()
-        self._cached: "OrderedDict[tuple, CorpusBM25View]" = OrderedDict()  # find_many's scopes by document list, LRU
-        self._cached_lock = threading.Lock()
-        self._max_scopes = max(0, int(max_scopes))
-        self._commit = _GroupCommit(self._run_pass, max_batch=max_batch, validate=self._check_item)
+        super().__init__(max_batch, max_scopes)
 
     # ---- the device model -------------------------------------------------------------------------------------
     def _device_model(self) -> DeviceBM25:
@@ -158,38 +110,9 @@ class CorpusBM25:
         chunk = self.chunk_of[doc] if len(self.chunk_of) else np.zeros_like(doc)  # (rows past a query's count hold document 0)
         return pos, order, chunk, score, cnt
 
-    def _ids(self, tokens: Sequence[Hashable]) -> List[int]:
-        """Term ids pass through; other tokens go through the process-wide vocabulary (-1: never indexed)."""
-        return [int(t) if isinstance(t, (int, np.integer)) else _VOCAB.get(t, -1) for t in tokens]
-
     # ---- the public surface -----------------------------------------------------------------------------------
     def view(self, doc_positions: Sequence[int], k: int = 4) -> CorpusBM25View:
         return CorpusBM25View(self, doc_positions, k)
-
-    def find_many(self, queries: Sequence[Sequence[Hashable]], scopes: Sequence[Sequence[int]], k: int = 4):
-        """The explicit batch form: query i ranks the documents ``scopes[i]`` (positions in the corpus) ->
-        (doc_ids[b, k] = positions inside scopes[i], chunk_ids[b, k], score[b, k], count[b]).  Equal document lists
-        share one scope, and the scopes of the ``max_scopes`` most recently used lists are kept, so a list seen again
-        pays no scope creation.  A list without any token fails the whole call ("Text index is empty.")."""
-        if len(scopes) != len(queries):
-            raise ValueError(f"{len(scopes)} scopes for {len(queries)} queries")
-        if int(k) < 1:
-            raise ValueError(f"k={k} must be >= 1")
-        keys = [tuple(int(p) for p in s) for s in scopes]
-        made = {key: self._cached_view(key) for key in dict.fromkeys(keys)}  # (holds evicted ones alive for this call)
-        views = [made[key] for key in keys]
-        _pos, doc, chunk, score, cnt = self._search_views([self._ids(q) for q in queries], views, int(k))
-        return doc, chunk, score, cnt
-
-    def _cached_view(self, key: tuple) -> CorpusBM25View:
-        """An evicted view is only dropped: its scope is released with the last search that still holds it."""
-        with self._cached_lock:
-            v = self._cached.pop(key, None) or self.view(key, 1)
-            if self._max_scopes > 0:
-                self._cached[key] = v  # (most recently used last)
-                while len(self._cached) > self._max_scopes:
-                    self._cached.popitem(last=False)
-            return v
 
     def close(self):
         """Drops the cached scopes and the device model; no search may be in flight."""
@@ -199,25 +122,6 @@ class CorpusBM25:
             if self._dev is not None:
                 self._dev.close()
                 self._dev = None
-
-    # ---- shared passes: an item is (query ids, view) ----------------------------------------------------------
-    def _check_item(self, item):
-        """In the submitting thread: the ids, and the view's scope, so that a document list without any token ("Text
-        index is empty.") or one the device refuses fails its own caller and never reaches a shared pass."""
-        query, view = item
-        view.scope()
-        return self._ids(query), view
-
-    def _run_pass(self, items):
-        """One search with the largest limit among the items; an item keeps the first `limit` of its row (the order
-        is total, so a top-k' is a prefix of a top-k)."""
-        k = max(view.limit for _, view in items)
-        pos, doc, chunk, score, cnt = self._search_views([q for q, _ in items], [v for _, v in items], k)
-        out = []
-        for i, (_, view) in enumerate(items):
-            m = min(int(cnt[i]), view.limit)
-            out.append((pos[i, :m], doc[i, :m], chunk[i, :m], score[i, :m], m))
-        return tuple([o[c] for o in out] for c in range(5))
 
 
 class CorpusHybrid:
