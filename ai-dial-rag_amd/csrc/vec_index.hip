@@ -2031,8 +2031,9 @@ int32_t mir_topk_merge_host(const double *dist, const int64_t *row, const int32_
     if (rc != MIR_OK || b == 0) return rc;
     const MergeStrides st = merge_strides(shard_stride_bytes, b, k);
     struct Item {
-        double d;
+        uint64_t key;  // merge_order.h: the one order of the three merge implementations
         int64_t r;
+        double d;
     };
     std::vector<Item> items;
     for (int q = 0; q < b; ++q) {
@@ -2042,18 +2043,14 @@ int32_t mir_topk_merge_host(const double *dist, const int64_t *row, const int32_
             MIR_REQUIRE(c >= 0 && c <= k, "count[%d][%d]=%d out of range", sh, q, c);
             const double *dp = reinterpret_cast<const double *>(reinterpret_cast<const char *>(dist) + sh * st.dist);
             const int64_t *rp = reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(row) + sh * st.row);
-            for (int p = 0; p < c; ++p) items.push_back({dp[(size_t)q * k + p], rp[(size_t)q * k + p]});
+            for (int p = 0; p < c; ++p) {
+                const double d = dp[(size_t)q * k + p];
+                items.push_back({mir::merge_order_key(d, descending_scores), rp[(size_t)q * k + p], d});
+            }
         }
-        if (!descending_scores) {
-            std::sort(items.begin(), items.end(), [](const Item &a, const Item &c) {
-                const bool na = a.d != a.d, nc = c.d != c.d;
-                if (na || nc) return na == nc ? a.r < c.r : nc;
-                return a.d < c.d || (a.d == c.d && a.r < c.r);
-            });
-        } else {
-            std::sort(items.begin(), items.end(),
-                      [](const Item &a, const Item &c) { return a.d > c.d || (a.d == c.d && a.r > c.r); });
-        }
+        std::sort(items.begin(), items.end(), [descending_scores](const Item &a, const Item &c) {
+            return mir::merge_before(a.key, a.r, c.key, c.r, descending_scores);
+        });
         const int kout = (int)std::min<size_t>(items.size(), (size_t)k);
         for (int p = 0; p < kout; ++p) {
             out_dist[(size_t)q * k + p] = items[p].d;

@@ -33,6 +33,8 @@
 
 #include <type_traits>
 
+#include "merge_order.h"
+
 namespace mir {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -1267,7 +1269,7 @@ __global__ __launch_bounds__(256) void sample_threshold_kernel(const float *__re
 
 // ---------------------------------------------------------------- shard merge
 
-// One block of 64 threads per query: merge s lists of <= k (dist, row) into k.
+// One block of 64 threads per query: merge s lists of <= k (dist, row) into k, in the order of merge_order.h.
 // Shard sh's arrays start `sh * stride` bytes after the base pointers.
 __global__ __launch_bounds__(64) void merge_topk_global_kernel(const char *__restrict__ dist_b,
                                                         const char *__restrict__ row_b,
@@ -1284,12 +1286,13 @@ __global__ __launch_bounds__(64) void merge_topk_global_kernel(const char *__res
     int total = 0;
     for (int sh = 0; sh < s; ++sh) total += cnt(sh);
     const int kout = total < k ? total : k;
-    // rank by counting; s*k is small (<= 8*64)
+    // rank by counting, in the order of merge_order.h; every candidate is re-read from global memory (s*k > kMergeLds)
     for (int e = threadIdx.x; e < s * k; e += 64) {
         const int sh = e / k, p = e - sh * k;
         if (p >= cnt(sh)) continue;
         const double dm = dst(sh, p);
         const int64_t rm = rw(sh, p);
+        const uint64_t km = merge_order_key(dm, descending);
         int rank = 0;
         for (int s2 = 0; s2 < s; ++s2) {
             const int c2 = cnt(s2);
@@ -1297,15 +1300,7 @@ __global__ __launch_bounds__(64) void merge_topk_global_kernel(const char *__res
                 if (s2 == sh && p2 == p) continue;
                 const double d2 = dst(s2, p2);
                 const int64_t r2 = rw(s2, p2);
-                bool before;
-                if (!descending) {
-                    const bool n2 = d2 != d2, nm = dm != dm;
-                    if (n2 || nm) before = (n2 == nm) ? r2 < rm : nm;
-                    else before = d2 < dm || (d2 == dm && r2 < rm);
-                } else {
-                    before = d2 > dm || (d2 == dm && r2 > rm);
-                }
-                rank += before ? 1 : 0;
+                rank += merge_before(merge_order_key(d2, descending), r2, km, rm, descending) ? 1 : 0;
             }
         }
         if (rank < kout) {
@@ -1320,12 +1315,6 @@ __global__ __launch_bounds__(64) void merge_topk_global_kernel(const char *__res
 // candidate from global memory inside its rank loop - 2*s*k dependent loads per thread, 21 us at s = 8, k = 10,
 // on the critical path of every step of an 8-GPU search (after the all-gather).
 constexpr int kMergeLds = 1024;
-// float64 -> uint64 whose unsigned order is the reference's: numbers ascending (-0 = +0), NaN last
-__device__ __forceinline__ uint64_t merge_key(double d) {
-    if (d != d) return ~0ull;
-    const uint64_t u = (uint64_t)__double_as_longlong(d + 0.0);  // -0.0 + 0.0 = +0.0
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
 __global__ __launch_bounds__(256) void merge_topk_kernel(const char *__restrict__ dist_b, const char *__restrict__ row_b,
                                                          const char *__restrict__ count_b, int s, int64_t stride_d,
                                                          int64_t stride_r, int64_t stride_c, int b, int k, int descending,
@@ -1361,8 +1350,8 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(const char *__restrict_
             if (e < n) {
                 sd[e] = dv[u];
                 sr[e] = rv[u];
-                // descending scores (BM25; never NaN): larger first, ties to the LARGER row - invert both orders
-                skey[e] = descending ? ~merge_key(dv[u]) : merge_key(dv[u]);
+                // descending scores (BM25): NaN first, larger first, ties to the LARGER row - both orders inverted
+                skey[e] = merge_order_key(dv[u], descending);
             }
         }
     }
@@ -1382,8 +1371,7 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(const char *__restrict_
                 const int e2 = s2 * k + p2;
                 const uint64_t k2 = skey[e2];
                 const int64_t r2 = sr[e2];
-                const bool row_before = descending ? r2 > rm : r2 < rm;
-                rank += (k2 < km || (k2 == km && row_before)) ? 1 : 0;  // e2 == e: equal key, same row -> 0
+                rank += merge_before(k2, r2, km, rm, descending) ? 1 : 0;  // e2 == e: equal key, same row -> 0
             }
         }
         if (rank < kout) {

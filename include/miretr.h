@@ -263,9 +263,16 @@ int32_t mir_metric_eval(const void *docs_host, int64_t n, int32_t d, int32_t dty
  * shards' blocks in each of the three arrays (0 = densely packed: b*k*8,
  * b*k*8 and b*4 bytes) - an all-gather of one per-rank blob holding
  * {dist[b][k], row[b][k], count[b]} is merged in place by passing the three
- * base pointers of shard 0 and the blob size.  For BM25 pass descending_scores = 1: ordering becomes
- * (score descending, row DESCENDING), the reversed stable argsort of
- * bm25_retriever.py:84.
+ * base pointers of shard 0 and the blob size.  -0.0 and +0.0 are one value in
+ * both orders, ties - two NaNs included - go to the row, and the distances
+ * written are the stored ones, bit for bit.  For BM25 pass
+ * descending_scores = 1: the ordering becomes the exact reverse, (NaN FIRST,
+ * score descending, row DESCENDING), the reversed stable argsort of
+ * bm25_retriever.py:84; BM25 scores are NaN where rank-bm25 divides 0 by 0
+ * (k1 = 0, or b = 1 with empty chunks).  The rows of one query are distinct
+ * (shards are disjoint).  out_count[q] = min(k, sum of the counts); entries
+ * beyond it are not written.  The device and the host form rank by one
+ * definition of this order (csrc/merge_order.h).
  * ---------------------------------------------------------------------- */
 int32_t mir_topk_merge_device(const double *dist, const int64_t *row, const int32_t *count, int32_t s,
                               int64_t shard_stride_bytes, int32_t b, int32_t k, int32_t descending_scores,

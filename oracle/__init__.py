@@ -22,6 +22,11 @@ Pinning status ("Oracle"):
   of float range, builds the smallest corpus per search route and derives the
   float64 error bound of the metrics above; ``tests/test_oracle_query_range.py``
   proves that those inputs can be judged with identical ids.
+* shard merge     - ``merge.merge``: no such step upstream (single process); it is
+  the stable argsort above (reversed for BM25) applied across contiguous
+  shards, and ``tests/test_oracle_merge.py`` proves it equal to the unsharded
+  ``np.argsort(kind="stable")`` on NaNs, signed zeros, infinities and ties.
+  ``merge.case`` generates the inputs of the host and the device merge tests.
 * BM25            - parity unpinned upstream: arithmetic lives in third-party
   ``rank-bm25==0.2.2`` which is absent; restated from its published algorithm.
 * RRF fusion      - parity unpinned upstream: langchain 0.3.21
@@ -32,3 +37,5 @@ Pinning status ("Oracle"):
   rounding wherever the HIP kernels round (in float64 and float32), and the
   case models there give the attention kernels peaked scores to work on.
 """
+
+from . import merge  # noqa: E402,F401  (oracle.merge.merge: the cross-shard merge)

@@ -75,8 +75,12 @@ def test_merge_host_orderings(nat):
     assert list(oc) == [4, 2]
     assert list(orow[0]) == [3, 7, 40, 2] and list(od[0]) == [0.1, 0.1, 0.2, 0.5]
     assert list(orow[1, :2]) == [5, 6]
-    # BM25 ordering: score descending, ties to the HIGHER row
-    nat.check(nat.lib.mir_topk_merge_host(nat.ptr(dist), nat.ptr(row), nat.ptr(cnt), s, 0, 1, k, 1, nat.ptr(od), nat.ptr(orow), nat.ptr(oc)))
+    # BM25 ordering, the reversed stable argsort: NaN first, score descending, ties to the HIGHER row
+    od, orow, oc = np.zeros((b, k)), np.zeros((b, k), np.int64), np.zeros(b, np.int32)
+    nat.check(nat.lib.mir_topk_merge_host(nat.ptr(dist), nat.ptr(row), nat.ptr(cnt), s, 0, b, k, 1, nat.ptr(od), nat.ptr(orow), nat.ptr(oc)))
+    assert list(oc) == [4, 2]
+    assert list(orow[0]) == [9, 8, 2, 40] and np.isnan(od[0, 0]) and list(od[0, 1:]) == [0.5, 0.5, 0.2]
+    assert list(orow[1, :2]) == [6, 5] and list(od[1, :2]) == [2.0, 1.0]
 
 
 def test_rrf_fuse_matches_oracle(nat):
