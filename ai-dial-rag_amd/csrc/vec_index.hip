@@ -20,6 +20,7 @@
 #include "vec_kernels_i8.h"
 #include "vec_kernels_exact.h"
 #include "vec_kernels_scoped.h"
+#include "vec_kernels_shared.h"
 
 namespace mir {
 
@@ -1667,6 +1668,9 @@ struct ScopedBuffers {
     int64_t *seg_begin;   // host API: [nseg]
     int64_t *seg_end;     // host API: [nseg]
     mir_block_desc *table;  // host API of the block search: [nseg], in place of seg_begin / seg_end
+    int32_t *group_ptr;   // host API of the shared search: [n_groups + 1], in front of scope_ptr (then [n_groups + 1] too)
+    SharedSlab *slabs;    // the shared search: [max_slabs], written by shared_slabs_kernel, with
+    int32_t *n_slabs;     //   their number
     size_t in_span;       // host API: bytes from q to the end of seg_end / table (one copy in)
     double *q_sq, *q_norm;
     unsigned long long *arrive;  // [ceil(b / 2)] words = b counters, zeroed by the prep kernel
@@ -1676,20 +1680,31 @@ struct ScopedBuffers {
     SearchOut out;        // host API staging of outputs
 };
 
-static size_t carve_scoped(ScopedBuffers &sb, char *base, int b, int k, int d, int P, size_t nseg, bool host_api, bool blocks = false) {
+// The shared search (mir_blocks_search_shared): scope_ptr has one entry per GROUP, the arrival counters one per slab
+struct SharedShape {
+    int n_groups = -1;  // < 0: not the shared search
+    int max_slabs = 0;
+};
+
+static size_t carve_scoped(ScopedBuffers &sb, char *base, int b, int k, int d, int P, size_t nseg, bool host_api, bool blocks = false,
+                           const SharedShape &sh = SharedShape{}) {
     Carver c{base};
+    const bool shared = sh.n_groups >= 0;
     sb.q = host_api ? c.take<double>((size_t)b * d) : nullptr;
-    sb.scope_ptr = host_api ? c.take<int32_t>((size_t)b + 1) : nullptr;
+    sb.group_ptr = host_api && shared ? c.take<int32_t>((size_t)sh.n_groups + 1) : nullptr;
+    sb.scope_ptr = host_api ? c.take<int32_t>((size_t)(shared ? sh.n_groups : b) + 1) : nullptr;
     sb.seg_begin = host_api && !blocks ? c.take<int64_t>(nseg) : nullptr;
     sb.seg_end = host_api && !blocks ? c.take<int64_t>(nseg) : nullptr;
     sb.table = host_api && blocks ? c.take<mir_block_desc>(nseg) : nullptr;
     sb.in_span = c.off;
     sb.q_sq = c.take<double>(b);
     sb.q_norm = c.take<double>(b);
-    sb.arrive = c.take<unsigned long long>(((size_t)b + 1) / 2);
+    sb.arrive = c.take<unsigned long long>(((size_t)(shared ? sh.max_slabs : b) + 1) / 2);
     sb.bound_dist = c.take<double>(b);
     sb.bound_pos = c.take<uint32_t>(b);
     sb.part = c.take<uint64_t>(P > 1 ? (size_t)b * P * std::min(k, kExactRound) * 2 : 0);
+    sb.slabs = shared ? c.take<SharedSlab>((size_t)sh.max_slabs) : nullptr;
+    sb.n_slabs = shared ? c.take<int32_t>(1) : nullptr;
     sb.out = carve_out(c, b, k, host_api);
     return c.off + 256;
 }
@@ -1755,6 +1770,73 @@ static int32_t enqueue_scoped(mir_index *ix, const double *dq, int b, int k, int
     MIR_HIP(hipGetLastError());
     return MIR_OK;
 }
+
+// ---- the shared search (vec_kernels_shared.h): queries per slab and where the B fragments live, from d and k alone
+constexpr size_t kSharedLdsWide = 64 * 1024;  // a wider slab is taken while the workgroup's dynamic LDS stays below this (two workgroups per CU)
+constexpr size_t kSharedLdsMax = 144 * 1024;  // 16 queries' fragments and lists beyond this: the fragments are read through the caches
+
+struct SharedPlan {
+    int qs;       // queries per slab: 16, 32 or 64
+    bool qlds;    // B fragments in LDS
+    size_t lds;   // dynamic LDS of a workgroup
+};
+
+static SharedPlan shared_plan(int d, int k) {
+    const size_t kk = (size_t)std::min(k, kExactRound), dpad = ((size_t)d + 15) / 16 * 16;
+    auto bytes = [&](int qs, bool frag) { return (size_t)qs * ((frag ? dpad * 8 : 0) + (size_t)kScopedWaves * kk * 12); };
+    for (int qs : {64, 32})
+        if (bytes(qs, true) <= kSharedLdsWide) return SharedPlan{qs, true, bytes(qs, true)};
+    if (bytes(16, true) <= kSharedLdsMax) return SharedPlan{16, true, bytes(16, true)};
+    return SharedPlan{16, false, bytes(16, false)};
+}
+
+template <typename T>
+static int32_t launch_shared(const SharedArgs &a, const SharedPlan &pl, dim3 grid, hipStream_t stream) {
+    const dim3 block(kScopedThreads);
+    if (pl.qs == 64) return launch_dyn(shared_topk_kernel<T, 4, true>, grid, block, pl.lds, stream, a);
+    if (pl.qs == 32) return launch_dyn(shared_topk_kernel<T, 2, true>, grid, block, pl.lds, stream, a);
+    if (pl.qlds) return launch_dyn(shared_topk_kernel<T, 1, true>, grid, block, pl.lds, stream, a);
+    return launch_dyn(shared_topk_kernel<T, 1, false>, grid, block, pl.lds, stream, a);
+}
+
+static int32_t enqueue_shared(mir_index *ix, const double *dq, int b, int k, int metric, int P, const SharedPlan &pl, int n_groups,
+                              int max_slabs, const ScopedBuffers &sb, const int32_t *group_ptr, const int32_t *scope_ptr,
+                              const mir_block_desc *table, const SearchOut &out, hipStream_t stream) {
+    const int d = ix->d;
+    // per-query norms + the slabs' arrival counters zeroed; then the slab table
+    const int arrive_words = (max_slabs + 1) / 2;
+    prep_queries_kernel<<<dim3(std::max(b, (arrive_words + 63) / 64)), dim3(64), 0, stream>>>(dq, b, d, ix->ksteps, 0, nullptr, sb.q_sq,
+                                                                                                sb.q_norm, sb.arrive, arrive_words);
+    shared_slabs_kernel<<<dim3(1), dim3(kScopedThreads), 0, stream>>>(group_ptr, n_groups, pl.qs, max_slabs, sb.slabs, sb.n_slabs);
+    MIR_HIP(hipGetLastError());
+    SharedArgs sa;
+    ScopedArgs &a = sa.s;
+    a.docs = nullptr; a.docs16 = nullptr; a.doc_sq = nullptr; a.n_rows = 0; a.d = d; a.metric = metric;
+    a.q = dq; a.q_sq = sb.q_sq; a.q_norm = sb.q_norm; a.q0 = 0; a.scope_ptr = scope_ptr; a.seg_begin = nullptr; a.seg_end = nullptr; a.blocks = table;
+    a.k = k; a.list_stride = std::min(k, kExactRound); a.part = sb.part; a.arrive = reinterpret_cast<uint32_t *>(sb.arrive);
+    a.bound_dist = sb.bound_dist; a.bound_pos = sb.bound_pos; a.chunk_ids = nullptr; a.row_offset = 0;
+    a.out_doc = out.doc; a.out_chunk = out.chunk; a.out_row = out.row; a.out_dist = out.dist; a.out_count = out.count; a.out_flags = out.flags;
+    sa.group_ptr = group_ptr; sa.slabs = sb.slabs; sa.n_slabs = sb.n_slabs;
+    const dim3 grid((unsigned)max_slabs, (unsigned)P);
+    for (int round = 0; round * kExactRound < k; ++round) {
+        a.round = round;
+        const int32_t rc = ix->dtype == MIR_DTYPE_F16 ? launch_shared<_Float16>(sa, pl, grid, stream) : launch_shared<float>(sa, pl, grid, stream);
+        if (rc != MIR_OK) return rc;
+    }
+    return MIR_OK;
+}
+
+// Workgroups per slab: scoped_split's rule counted in slabs - about four workgroups per CU in all - with the shared kernel's own
+// limit on the lists it merges.  Where the caller can see the scopes a share is 512 positions at the least (eight tiles per
+// wave): every workgroup loads its slab's fragments first, and the last one merges P lists for each of up to 64 queries.
+static int shared_split(const mir_index *ix, int slabs, uint64_t max_rows) {
+    int want = (4 * std::max(ix->num_cus, 1) + slabs - 1) / std::max(slabs, 1);
+    if (max_rows) want = (int)std::min<uint64_t>((uint64_t)want, (max_rows + 511) / 512);
+    return std::min(std::max(want, 1), kSharedMaxP);
+}
+
+// slabs of a call at the most, from what both forms know: sum over groups of ceil(G / qs) <= ceil(b / qs) + n_groups
+static int shared_max_slabs(int b, int n_groups, int qs) { return (int)std::min<int64_t>(((int64_t)b + qs - 1) / qs + n_groups, 0x7fffffff); }
 
 }  // namespace mir
 
@@ -1922,6 +2004,95 @@ int32_t mir_blocks_search(mir_blocks *s_, const double *queries_host, int32_t b,
             seg.blocks = sb.table;
             return host_round_trip(w, s, in, nseg ? 3 : 2, sb.q, sb.in_span, sb.out, user, b, k, [&](const SearchOut &out) {
                 return enqueue_scoped(ix, sb.q, b, k, metric, P, sb, sb.scope_ptr, seg, out, s);
+            });
+        });
+}
+
+// ---- shared block search: the queries of a group search one scope, whose rows are read once per slab (vec_kernels_shared.h)
+
+int32_t mir_blocks_search_shared_device(mir_blocks *s_, const double *queries_device, int32_t b, int32_t k, int32_t metric, int32_t n_groups,
+                                        const int32_t *group_ptr_device, const int32_t *scope_ptr_device, const mir_block_desc *table_device,
+                                        int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
+                                        int32_t *out_flags, void *stream_) {
+    MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
+    mir_index *ix = s_->ix;
+    int32_t rc = check_scoped_args(ix, queries_device, b, k, metric, scope_ptr_device, out_count);
+    if (rc != MIR_OK) return rc;
+    MIR_REQUIRE(n_groups >= 0, "n_groups=%d is negative", n_groups);
+    if (b == 0) return MIR_OK;
+    MIR_REQUIRE(group_ptr_device != nullptr, "group_ptr is NULL");
+    rc = use_device(ix->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    const SharedPlan pl = shared_plan(ix->d, k);
+    const int max_slabs = shared_max_slabs(b, n_groups, pl.qs);
+    const int P = shared_split(ix, max_slabs, 0);
+    ScopedBuffers sb;
+    const SearchOut out{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    return with_workspace(
+        ix, static_cast<hipStream_t>(stream_), false,
+        [&](char *base) { return carve_scoped(sb, base, b, k, ix->d, P, 0, false, true, SharedShape{n_groups, max_slabs}); },
+        [&](Workspace *, hipStream_t s) {
+            return enqueue_shared(ix, queries_device, b, k, metric, P, pl, n_groups, max_slabs, sb, group_ptr_device, scope_ptr_device, table_device, out, s);
+        });
+}
+
+int32_t mir_blocks_search_shared(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, int32_t n_groups,
+                                 const int32_t *group_ptr_host, const int32_t *scope_ptr_host, const mir_rows *const *blocks_host,
+                                 int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
+                                 int32_t *out_flags) {
+    MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
+    mir_index *ix = s_->ix;
+    int32_t rc = check_scoped_args(ix, queries_host, b, k, metric, scope_ptr_host, out_count);
+    if (rc != MIR_OK) return rc;
+    MIR_REQUIRE(n_groups >= 0, "n_groups=%d is negative", n_groups);
+    if (b == 0) return MIR_OK;
+    // everything the device form trusts is checked here, before anything is launched
+    MIR_REQUIRE(group_ptr_host != nullptr, "group_ptr is NULL");
+    MIR_REQUIRE(group_ptr_host[0] == 0, "group_ptr[0]=%d must be 0", group_ptr_host[0]);
+    for (int g = 0; g < n_groups; ++g)
+        MIR_REQUIRE(group_ptr_host[g + 1] >= group_ptr_host[g], "group_ptr decreases at group %d", g);
+    MIR_REQUIRE(group_ptr_host[n_groups] == b, "group_ptr[n_groups]=%d must be b=%d", group_ptr_host[n_groups], b);
+    MIR_REQUIRE(scope_ptr_host[0] == 0, "scope_ptr[0]=%d must be 0", scope_ptr_host[0]);
+    for (int g = 0; g < n_groups; ++g)
+        MIR_REQUIRE(scope_ptr_host[g + 1] >= scope_ptr_host[g], "scope_ptr decreases at group %d", g);
+    const size_t nseg = (size_t)scope_ptr_host[n_groups];
+    MIR_REQUIRE(nseg == 0 || blocks_host != nullptr, "the block table is NULL");
+    const SharedPlan pl = shared_plan(ix->d, k);
+    std::vector<mir_block_desc> table(nseg);
+    uint64_t max_rows = 1;
+    int64_t slabs = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        uint64_t rows = 0;
+        for (int t = scope_ptr_host[g]; t < scope_ptr_host[g + 1]; ++t) {
+            const mir_rows *r = blocks_host[t];
+            MIR_REQUIRE(r != nullptr, "block %d of group %d is NULL", t - scope_ptr_host[g], g);
+            MIR_REQUIRE(r->d == ix->d && r->dtype == ix->dtype && r->device == ix->device,
+                        "block %d of group %d is %d-dimensional dtype %d on device %d, the searcher %d-dimensional dtype %d on device %d",
+                        t - scope_ptr_host[g], g, r->d, r->dtype, r->device, ix->d, ix->dtype, ix->device);
+            table[(size_t)t] = mir_block_desc{r->d_emb, r->d_docsq, r->d_chunk, r->n};
+            rows += (uint64_t)r->n;
+            MIR_REQUIRE(rows < (1ull << 32), "the scope of group %d holds 2^32 rows or more", g);
+        }
+        const int64_t queries = (int64_t)group_ptr_host[g + 1] - group_ptr_host[g];
+        if (queries > 0) max_rows = std::max(max_rows, rows);
+        slabs += (queries + pl.qs - 1) / pl.qs;
+    }
+    rc = use_device(ix->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    const int max_slabs = (int)slabs;  // (the host form can count them: no surplus workgroup)
+    const int P = shared_split(ix, max_slabs, max_rows);
+    ScopedBuffers sb;
+    const SearchOut user{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    return with_workspace(
+        ix, nullptr, true, [&](char *base) { return carve_scoped(sb, base, b, k, ix->d, P, nseg, true, true, SharedShape{n_groups, max_slabs}); },
+        [&](Workspace *w, hipStream_t s) {
+            // [q | group_ptr | scope_ptr | table] goes in as ONE copy of the span carved in that order
+            const HostPiece in[] = {{sb.q, queries_host, (size_t)b * ix->d * sizeof(double)},
+                                    {sb.group_ptr, group_ptr_host, ((size_t)n_groups + 1) * 4},
+                                    {sb.scope_ptr, scope_ptr_host, ((size_t)n_groups + 1) * 4},
+                                    {sb.table, table.data(), nseg * sizeof(mir_block_desc)}};
+            return host_round_trip(w, s, in, nseg ? 4 : 3, sb.q, sb.in_span, sb.out, user, b, k, [&](const SearchOut &out) {
+                return enqueue_shared(ix, sb.q, b, k, metric, P, pl, n_groups, max_slabs, sb, sb.group_ptr, sb.scope_ptr, sb.table, out, s);
             });
         });
 }

@@ -140,8 +140,8 @@ class BlockHybrid(CorpusHybrid):
     documents under the same keys.  ``find_many(query_vectors, query_ids, scopes, metric, k, weights, c)`` is
     ``CorpusHybrid``'s, with ``scopes`` listing keys."""
 
-    def __init__(self, device: int = 0):
-        super().__init__(BlockCorpus(device=device), BlockBM25(device=device))
+    def __init__(self, device: int = 0, share_scopes: bool = False):
+        super().__init__(BlockCorpus(device=device, share_scopes=share_scopes), BlockBM25(device=device))
         self._lock = threading.Lock()
 
     def add(self, doc_index, text_doc) -> int:

@@ -25,6 +25,13 @@ from .embeddings_metrics import Metric
 
 __all__ = ["BlockCorpus", "BlockView"]
 
+# Queries of one call that search the SAME scope go through ``BlockSearcher.search_shared`` from this many on
+# (``share_scopes=True``).  Measured (profiles/block_shared.md): the smallest group from which the shared
+# route's slowest call beats the per-query route's fastest is 1 on a scope of 1.25M rows and 256 on a scope of 10 000 rows
+# (below that the slab's per-query merge and result phases cost more than the rows it saves).  The corpus does not know
+# which case a call is, so the default is the larger of the two; pass a smaller ``min_group`` where scopes are large.
+DEFAULT_MIN_GROUP = 256
+
 
 class BlockView:
     """``CorpusView``'s surface over some documents of a ``BlockCorpus``: ``find(query)`` and ``find_batch``.
@@ -60,8 +67,10 @@ class BlockCorpus:
     """``add`` / ``remove`` / ``view`` / ``find_many`` may be called from any thread, also while searches run: a search
     works on the ``DeviceRows`` objects it took when it was submitted."""
 
-    def __init__(self, device: int = 0, max_batch: int = 256):
+    def __init__(self, device: int = 0, max_batch: int = 256, share_scopes: bool = False, min_group: int = DEFAULT_MIN_GROUP):
         self.device = device
+        self.share_scopes = bool(share_scopes)  # queries of a call with the same scope read its rows once (search_shared)
+        self.min_group = max(int(min_group), 1)
         self.d: Optional[int] = None      # fixed by the first non-empty document, with
         self.dtype: Optional[int] = None  # its storage type
         self._docs: Dict[int, Optional[DeviceRows]] = {}  # key -> block; None = a document without rows (any d)
@@ -117,6 +126,20 @@ class BlockCorpus:
         return sum(b.hbm_bytes() for b in blocks)
 
     # ---- the device search ------------------------------------------------------------------------------------
+    def _shared_groups(self, lists) -> List[List[int]]:
+        """share_scopes: the queries whose scopes are the same block OBJECTS in the same order form a group; the groups of
+        min_group queries or more (they read their rows once, ``search_shared``), each as its queries' positions.  Scopes
+        are sorted by (length, first block) first, so a call with nothing to share costs one small key per scope."""
+        coarse: Dict[tuple, List[int]] = {}
+        for i, s in enumerate(lists):
+            coarse.setdefault((len(s), id(s[0]) if s else 0), []).append(i)
+        groups: Dict[tuple, List[int]] = {}
+        for idx in coarse.values():
+            if len(idx) >= self.min_group:
+                for i in idx:
+                    groups.setdefault(tuple(map(id, lists[i])), []).append(i)
+        return [idx for idx in groups.values() if len(idx) >= self.min_group]
+
     def _search_blocks(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence[Optional[DeviceRows]]]):
         """(doc, chunk, dist, count); a scope lists blocks, None = a document without rows.  The one place that touches
         the GPU."""
@@ -129,8 +152,25 @@ class BlockCorpus:
         if searcher is None:  # no document with rows yet
             b = len(queries)
             return np.zeros((b, k), np.int32), np.zeros((b, k), np.int64), np.zeros((b, k)), np.zeros(b, np.int32)
-        doc, chunk, _row, dist, cnt, _flags = searcher.search(queries, k, metric, [[empty if blk is None else blk for blk in s] for s in scopes])
-        return doc, chunk, dist, cnt
+        lists = [[empty if blk is None else blk for blk in s] for s in scopes]
+        shared = self._shared_groups(lists) if self.share_scopes else []
+        if not shared:  # (the default; or nothing to share: the per-query route's call as it always was)
+            doc, chunk, _row, dist, cnt, _flags = searcher.search(queries, k, metric, lists)
+            return doc, chunk, dist, cnt
+        taken = {i for idx in shared for i in idx}
+        rest = [i for i in range(len(lists)) if i not in taken]
+        b = len(queries)
+        out = (np.zeros((b, k), np.int32), np.zeros((b, k), np.int64), np.zeros((b, k)), np.zeros(b, np.int32))
+        calls = []
+        if shared:
+            order = [i for idx in shared for i in idx]
+            calls.append((order, searcher.search_shared(queries[order], k, metric, [lists[idx[0]] for idx in shared], [len(idx) for idx in shared])))
+        if rest:
+            calls.append((rest, searcher.search(queries[rest], k, metric, [lists[i] for i in rest])))
+        for order, (doc, chunk, _row, dist, cnt, _flags) in calls:  # results go back to their queries
+            for dst, src in zip(out, (doc, chunk, dist, cnt)):
+                dst[order] = src
+        return out
 
     # ---- the public surface -----------------------------------------------------------------------------------
     def view(self, keys: Sequence[int], retrieval_type: RetrievalType, metric=Metric.SQEUCLIDEAN_DIST, limit: int = 1) -> BlockView:

@@ -155,6 +155,45 @@ class BlockSearcher:
                                                    out_chunk_ptr or None, out_row_ptr or None, out_dist_ptr or None, out_count_ptr,
                                                    out_flags_ptr or None, stream or None))
 
+    def search_shared(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence["DeviceRows"]],
+                      group_sizes: Sequence[int]) -> Tuple[np.ndarray, ...]:
+        """Queries that share a scope read its rows once (csrc/vec_kernels_shared.h).  Group g = the next
+        ``group_sizes[g]`` queries (0 is allowed); all of them search ``scopes[g]``.  Returns the six arrays of ``search``,
+        indexed by query: the same answer, its dot products summed in the matrix unit's order."""
+        q = nat.as_f64_queries(queries, self.d)
+        b = q.shape[0]
+        code = nat.METRIC_CODES[Metric(metric).value]
+        sizes = [int(g) for g in group_sizes]
+        if len(scopes) != len(sizes):
+            raise ValueError(f"{len(scopes)} scopes for {len(sizes)} groups")
+        if any(g < 0 for g in sizes) or sum(sizes) != b:
+            raise ValueError(f"group sizes {sizes} do not add up to {b} queries")
+        held = [blk for s in scopes for blk in s]  # (alive across the call)
+        gp = np.zeros(len(sizes) + 1, np.int32)
+        np.cumsum(sizes, out=gp[1:])
+        sp = np.zeros(len(sizes) + 1, np.int32)
+        np.cumsum([len(s) for s in scopes], out=sp[1:])
+        table = (C.c_void_p * max(len(held), 1))(*[blk.handle for blk in held])
+        doc = np.zeros((b, max(k, 0)), np.int32)
+        chunk = np.zeros((b, max(k, 0)), np.int64)
+        row = np.zeros((b, max(k, 0)), np.int64)
+        dist = np.zeros((b, max(k, 0)), np.float64)
+        cnt = np.zeros(b, np.int32)
+        flg = np.zeros(b, np.int32)
+        nat.check(nat.lib.mir_blocks_search_shared(self._h, nat.ptr(q), b, k, code, len(sizes), nat.ptr(gp), nat.ptr(sp), table, nat.ptr(doc),
+                                                   nat.ptr(chunk), nat.ptr(row), nat.ptr(dist), nat.ptr(cnt), nat.ptr(flg)))
+        return doc, chunk, row, dist, cnt, flg
+
+    def search_shared_device(self, q_ptr: int, b: int, k: int, metric, n_groups: int, group_ptr_ptr: int, scope_ptr_ptr: int, table_ptr: int,
+                             out_row_ptr: int, out_dist_ptr: int, out_count_ptr: int, out_flags_ptr: int = 0, out_doc_ptr: int = 0,
+                             out_chunk_ptr: int = 0, stream: int = 0) -> None:
+        """``search_shared`` with every buffer in HBM, asynchronous: ``search_device``'s rules, with ``group_ptr``
+        (int32[n_groups + 1]) and a ``scope_ptr`` per group.  Nothing in the arrays is validated."""
+        code = nat.METRIC_CODES[Metric(metric).value]
+        nat.check(nat.lib.mir_blocks_search_shared_device(self._h, q_ptr, b, k, code, n_groups, group_ptr_ptr or None, scope_ptr_ptr or None,
+                                                          table_ptr or None, out_doc_ptr or None, out_chunk_ptr or None, out_row_ptr or None,
+                                                          out_dist_ptr or None, out_count_ptr, out_flags_ptr or None, stream or None))
+
     def close(self):
         if self._h:
             nat.lib.mir_blocks_destroy(self._h)

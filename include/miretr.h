@@ -228,6 +228,36 @@ int32_t mir_blocks_search_device(mir_blocks *s, const double *queries_device, in
                                  int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
                                  int32_t *out_flags, void *stream);
 
+/* Shared block search (added within ABI 6): queries that share a scope read its rows once (csrc/vec_kernels_shared.h).
+ * Group g holds queries [group_ptr[g], group_ptr[g + 1]); all of them search scope g = blocks[scope_ptr[g] ..
+ * scope_ptr[g + 1]) in that order.  group_ptr: int32[n_groups + 1], group_ptr[0] = 0, non-decreasing, group_ptr[n_groups] = b
+ * (an empty group is allowed); scope_ptr: int32[n_groups + 1], as mir_blocks_search's per query.  Outputs are indexed by
+ * QUERY exactly as mir_blocks_search writes them ([b][k]; out_doc = ordinal of the block in the scope, out_chunk, out_row =
+ * the row inside its block, out_count[q] = min(k, L), out_flags 0; any of them but out_count may be NULL).
+ * The answer is mir_blocks_search's for every query: the first min(k, L) scope positions under (distance ascending, NaN
+ * last, position ascending), every distance the reference's float64 formula from the stored rows and the block's float32
+ * squared norms, for every row of the scope.  The ONE difference: the dot product is summed by v_mfma_f64_16x16x4_f64, one
+ * fused multiply-add per element in the matrix unit's order, where the per-query route adds 16 lanes' partial sums - a
+ * fourth float64 summation routine (gap 8).  Those values select and order the results; the k
+ * distances written to out_dist are evaluated once more by mir_blocks_search's routine and have its bits.  The order of
+ * rows whose distances tie to ~1e-16 may differ from mir_blocks_search (out_dist may then descend by those last bits);
+ * bit-identical rows tie exactly and go by position.
+ * Any k >= 1, float32 and float16 blocks, any d.  The host form returns MIR_ERR_INVALID, before anything is launched and
+ * with the outputs untouched, for everything mir_blocks_search refuses and for n_groups < 0, group_ptr[0] != 0, a decreasing
+ * group_ptr and group_ptr[n_groups] != b. */
+int32_t mir_blocks_search_shared(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                                 int32_t n_groups, const int32_t *group_ptr_host, const int32_t *scope_ptr_host,
+                                 const mir_rows *const *blocks_host, int32_t *out_doc, int64_t *out_chunk,
+                                 int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags);
+
+/* The same with every buffer in HBM, asynchronous on `stream`.  It trusts group_ptr, scope_ptr and the table as
+ * mir_blocks_search_device trusts its arrays; it sees none of them and sizes its launch from b, n_groups and k alone. */
+int32_t mir_blocks_search_shared_device(mir_blocks *s, const double *queries_device, int32_t b, int32_t k, int32_t metric,
+                                        int32_t n_groups, const int32_t *group_ptr_device, const int32_t *scope_ptr_device,
+                                        const mir_block_desc *table_device, int32_t *out_doc, int64_t *out_chunk,
+                                        int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags,
+                                        void *stream);
+
 /* Benchmark instrumentation: when enabled, every launch of the scan kernel (the
  * dominant, HBM-streaming kernel) is bracketed by HIP events on the stream it
  * is launched on.  mir_index_profile_read waits for those launches, returns

@@ -1,0 +1,507 @@
+"""GPU parity of the shared-scope block search (csrc/vec_kernels_shared.h): the queries of a group search one scope and
+read its rows once, every distance from v_mfma_f64_16x16x4_f64.  Expected answers: the oracle's `find` over the scope's
+documents by test_gpu_block_search.py's rules - (block ordinal, chunk id) pairs identical (cosine: up to ties within
+COS_NOISE), distances within 1e-9 (cosine 5e-7).  Where the per-query route runs too: doc, chunk, row and count equal,
+distances within the same tolerance."""
+
+import ctypes as C
+import threading
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+METRICS = ["cosine_sim", "euclidean_dist", "sqeuclidean_dist", "inner_product"]
+COS_NOISE = 2e-7
+
+
+def dist_tol(metric):
+    return 5e-7 if metric == "cosine_sim" else 1e-9
+
+
+@pytest.fixture(scope="module")
+def amd():
+    from aidial_rag_amd import _native
+    from aidial_rag_amd.index_record import RetrievalType
+    from aidial_rag_amd.retrievers import block_bm25 as bb
+    from aidial_rag_amd.retrievers import block_corpus as bc
+    from aidial_rag_amd.retrievers import embeddings_index as ei
+    from oracle import embeddings_index as oi
+
+    assert _native.device_count() >= 1, "no GPU visible: the product path has no CPU fallback"
+
+    class NS:
+        pass
+
+    ns = NS()
+    ns.nat, ns.ei, ns.bc, ns.bb, ns.oi, ns.RetrievalType = _native, ei, bc, bb, oi, RetrievalType
+    return ns
+
+
+def unit(x):
+    return (x / np.linalg.norm(x, axis=-1, keepdims=True)).astype(np.float32)
+
+
+def check_against_oracle(oi, metric, q, scope_docs, k, got_doc, got_chunk, got_dist, got_cnt, msg):
+    """test_gpu_block_search.py's rules; scope_docs: the oracle DocIndex objects of the scope, in its order"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        want, wdist = oi.find(q, scope_docs, metric, k)
+    m = int(got_cnt)
+    assert m == len(want), msg
+    got = [(int(a), int(b)) for a, b in zip(got_doc[:m], got_chunk[:m])]
+    if metric != "cosine_sim":
+        assert got == want, msg
+    else:
+        def dist_of(pair):
+            doc = scope_docs[pair[0]]
+            row = int(np.nonzero(doc.chunk_ids == pair[1])[0][0])
+            return float(oi.ENUM_TO_METRIC[oi.Metric(metric)](q, doc.embeddings[row : row + 1])[0])
+
+        for g, w in zip(got, want):
+            if g != w:
+                assert abs(dist_of(g) - dist_of(w)) <= COS_NOISE, f"{msg}: {g} vs {w}"
+    np.testing.assert_allclose(got_dist[:m], wdist, rtol=0, atol=dist_tol(metric), equal_nan=True, err_msg=msg)
+
+
+def make_blocks(amd, parts, chunks):
+    blocks = [amd.ei.DeviceRows.from_host(p, c) for p, c in zip(parts, chunks)]
+    docs = [amd.oi.DocIndex(c, p.astype(np.float32)) if len(p) else amd.oi.DocIndex() for c, p in zip(chunks, parts)]
+    return blocks, docs
+
+
+def searcher_for(amd, blocks):
+    return amd.ei.BlockSearcher(blocks[0].d, blocks[0].dtype)
+
+
+def run_groups(searcher, queries, k, metric, blocks, scope_lists, group_sizes):
+    return searcher.search_shared(queries, k, metric, [[blocks[j] for j in s] for s in scope_lists], group_sizes)
+
+
+def scope_of_query(scope_lists, group_sizes):
+    return [s for s, g in zip(scope_lists, group_sizes) for _ in range(g)]
+
+
+def check_groups(amd, metric, k, queries, docs, scope_lists, group_sizes, got, msg):
+    doc, chunk, row, dist, cnt, flags = got
+    assert (flags == 0).all(), msg
+    for i, s in enumerate(scope_of_query(scope_lists, group_sizes)):
+        check_against_oracle(amd.oi, metric, queries[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{msg} query {i} scope {s}")
+
+
+def assert_routes_agree(shared, per_query, metric, msg):
+    """doc, chunk, row and count equal; distances within the metric's tolerance, NaN equal to NaN"""
+    np.testing.assert_array_equal(shared[4], per_query[4], err_msg=msg)
+    for i, m in enumerate(shared[4]):
+        for a, b, what in zip(shared[:3], per_query[:3], ("doc", "chunk", "row")):
+            np.testing.assert_array_equal(a[i, :m], b[i, :m], err_msg=f"{msg} query {i}: {what}")
+        np.testing.assert_allclose(shared[3][i, :m], per_query[3][i, :m], rtol=0, atol=dist_tol(metric), equal_nan=True, err_msg=f"{msg} query {i}")
+        # more than the tolerance asks: a reported distance is evaluated by the per-query route's routine from the same row,
+        # query and doc_sq, so where the two routes report the same row they report the same bits
+        np.testing.assert_array_equal(shared[3][i, :m].view(np.uint64), per_query[3][i, :m].view(np.uint64), err_msg=f"{msg} query {i}: dist bits")
+
+
+# ---------------------------------------------------------------- 1. parity over ragged blocks
+
+RAGGED_SIZES = [0, 1, 15, 16, 17, 0, 33, 200, 5, 0]
+# all blocks; a reversed list; (an empty group); a block listed twice; only empty blocks; no block at all; a scope of 5 rows
+RAGGED_SCOPES = [list(range(10)), list(range(9, -1, -1)), [8], [7, 2, 7], [0, 5, 9], [], [8]]
+RAGGED_GROUPS = [33, 17, 0, 16, 15, 1, 2]
+
+
+@pytest.fixture(scope="module")
+def ragged(amd):
+    rng = np.random.default_rng(2025)
+    d = 384
+    parts = [unit(rng.standard_normal((m, d))) if m else np.zeros((0, d), np.float32) for m in RAGGED_SIZES]
+    chunks = [3 * np.arange(m, dtype=np.int64) + 1 for m in RAGGED_SIZES]  # chunk ids that are not rows
+    blocks, docs = make_blocks(amd, parts, chunks)
+    queries = rng.standard_normal((sum(RAGGED_GROUPS), d))
+    # one query of the all-blocks group is a copy of a stored row whose squared distance to itself is NEGATIVE in the
+    # reference's arithmetic (float32 doc_sq against the float64 dot): euclidean_dist's NaN, sorted last
+    emb = np.concatenate(parts)
+    with np.errstate(invalid="ignore"):
+        self_sq = np.array([amd.oi.ENUM_TO_METRIC[amd.oi.Metric("sqeuclidean_dist")](r.astype(np.float64), r[None])[0] for r in emb])
+    twin = int(np.argmin(self_sq))
+    assert self_sq[twin] < -1e-9
+    queries[5] = emb[twin].astype(np.float64)
+    twin_doc = int(np.searchsorted(np.cumsum(RAGGED_SIZES), twin, side="right"))
+    return blocks, docs, queries, twin_doc, searcher_for(amd, blocks)
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_parity_over_ragged_blocks(amd, ragged, metric):
+    blocks, docs, queries, twin_doc, searcher = ragged
+    first = np.concatenate([[0], np.cumsum(RAGGED_GROUPS)])
+    for k in (1, 7, 64):
+        got = run_groups(searcher, queries, k, metric, blocks, RAGGED_SCOPES, RAGGED_GROUPS)
+        check_groups(amd, metric, k, queries, docs, RAGGED_SCOPES, RAGGED_GROUPS, got, f"{metric} k={k}")
+        doc, chunk, row, dist, cnt, _ = got
+        assert (cnt[: first[2]] == k).all()
+        assert (cnt[first[4] : first[6]] == 0).all()         # only empty blocks; no block at all
+        assert (cnt[first[6] :] == min(k, 5)).all()            # a scope of 5 rows
+        for i in range(len(queries)):
+            np.testing.assert_array_equal(chunk[i, : cnt[i]], 3 * row[i, : cnt[i]] + 1)  # the row INSIDE its block
+        if metric == "euclidean_dist":
+            assert not np.isnan(dist[5]).any()  # NaN sorts last: never among the first k of 287 rows
+    if metric == "euclidean_dist":
+        # ... and it IS last where the scope is the twin's own block, searched to its last row
+        n = RAGGED_SIZES[twin_doc]
+        got = run_groups(searcher, queries[:16], n, metric, blocks, [[twin_doc]], [16])
+        assert got[4][5] == n and np.isnan(got[3][5, n - 1]) and not np.isnan(got[3][5, : n - 1]).any()
+        check_groups(amd, metric, n, queries[:16], docs, [[twin_doc]], [16], got, "NaN last")
+
+
+# ---------------------------------------------------------------- 2. ties and rounds
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_k_beyond_one_round_with_ties_across_blocks(amd, metric):
+    # test_gpu_block_search.py's construction: scaled basis vectors, each dot ONE product in any summation order, so the
+    # fifteen copies of a row - five per block - tie exactly; the tie on ranks 60 .. 74 lies across the first round's end
+    rng = np.random.default_rng(77)
+    d = 16
+    base = np.zeros((10, d), np.float32)
+    base[np.arange(10), np.arange(10)] = 1.0
+    order = rng.permutation(50) % 10
+    parts = [base[order].copy() for _ in range(3)]
+    chunks = [np.arange(50, dtype=np.int64) + 100 * i for i in range(3)]
+    blocks, docs = make_blocks(amd, parts, chunks)
+    qs = rng.standard_normal((20, d))
+    qs[11] = qs[3]  # two identical queries
+    k = 130
+    got = run_groups(searcher_for(amd, blocks), qs, k, metric, blocks, [[0, 1, 2]], [20])
+    doc, chunk, row, dist, cnt, _ = got
+    assert (cnt == k).all()
+    check_groups(amd, metric, k, qs, docs, [[0, 1, 2]], [20], got, f"{metric} k={k}")
+    for a in (doc, chunk, row, dist):
+        np.testing.assert_array_equal(a[11], a[3])
+    for i in range(20):
+        if metric != "cosine_sim":
+            assert (dist[i, 60:75] == dist[i, 60]).all() and dist[i, 59] < dist[i, 60] < dist[i, 75]
+        pos = 50 * doc[i].astype(np.int64) + row[i]
+        for g in range(0, 120, 15):
+            assert (np.diff(pos[g : g + 15]) > 0).all()  # inside a tie: scope position ascending, through all three blocks
+            assert set(doc[i, g : g + 15]) == {0, 1, 2}
+
+
+# ---------------------------------------------------------------- 3. storage
+
+STORAGE = {  # name: (dtype, d, rows per block, k)
+    "f16_d64": (np.float16, 64, (130, 0, 70), 7),
+    "f16_d6": (np.float16, 6, (90, 0, 61), 7),          # d % 4 != 0 and a tail of d
+    "f32_d100": (np.float32, 100, (150, 0, 77), 7),     # a tail of d
+    "f16_d1024": (np.float16, 1024, (100, 0, 57), 7),   # the slab shrinks to 16 queries
+    "f32_d1024": (np.float32, 1024, (100, 0, 57), 7),
+    "f32_d1024_k64": (np.float32, 1024, (100, 0, 57), 64),  # 16 queries' fragments and lists exceed LDS: fragments through the caches
+    "f32_d2052": (np.float32, 2052, (40, 0, 25), 7),        # the same at any k
+}
+
+
+@pytest.mark.parametrize("metric", METRICS)
+@pytest.mark.parametrize("shape", sorted(STORAGE))
+def test_storage(amd, metric, shape):
+    dtype, d, sizes, k = STORAGE[shape]
+    rng = np.random.default_rng(len(shape) + 31)
+    scale = 32.0 if dtype == np.float16 and d > 256 else 1.0
+    parts = [(rng.standard_normal((m, d)) / scale).astype(dtype) for m in sizes]
+    chunks = [2 * np.arange(m, dtype=np.int64) + i for i, m in enumerate(sizes)]
+    blocks, docs = make_blocks(amd, parts, chunks)
+    qs = rng.standard_normal((20, d))
+    got = run_groups(searcher_for(amd, blocks), qs, k, metric, blocks, [[0, 1, 2]], [20])
+    check_groups(amd, metric, k, qs, docs, [[0, 1, 2]], [20], got, f"{shape} {metric}")
+    np.testing.assert_array_equal(got[1], 2 * got[2] + got[0])
+
+
+# ---------------------------------------------------------------- 4. P > 1
+
+@pytest.fixture(scope="module")
+def one_big_block(amd):
+    rng = np.random.default_rng(43)
+    n, d, nq = 20000, 384, 40
+    emb = unit(rng.standard_normal((n, d)))
+    # every query's true best rows sit at positions 0, 15, 16, 19 999 and every 997th: the queries are one direction u with
+    # some noise each, the planted rows are u with some noise each (cosine ~0.6 against ~0.05 for a random row), so
+    # shares and tiles are crossed wherever the split falls
+    u = unit(rng.standard_normal(d)).astype(np.float64)
+    qs = u + 0.03 * rng.standard_normal((nq, d))
+    planted = np.array(sorted({0, 15, 16, n - 1} | set(range(997, n, 997))))
+    assert len(planted) == 24
+    emb[planted] = unit(u + 0.03 * rng.standard_normal((len(planted), d)))
+    chunk_ids = np.arange(n, dtype=np.int64)[::-1].copy()
+    blocks, docs = make_blocks(amd, [emb], [chunk_ids])
+    return blocks, docs, qs, planted, searcher_for(amd, blocks)
+
+
+@pytest.mark.parametrize("k", [10, 64])
+@pytest.mark.parametrize("metric", METRICS)
+def test_one_block_split_over_many_workgroups(amd, one_big_block, metric, k):
+    blocks, docs, qs, planted, searcher = one_big_block
+    got = run_groups(searcher, qs, k, metric, blocks, [[0]], [len(qs)])
+    doc, chunk, row, dist, cnt, _ = got
+    assert (cnt == k).all() and (doc == 0).all()
+    check_groups(amd, metric, k, qs, docs, [[0]], [len(qs)], got, f"{metric} k={k}")
+    np.testing.assert_array_equal(row, 19999 - chunk)
+    for i in range(len(qs)):  # the first 24 results are the planted rows
+        assert set(row[i, : min(k, 24)]) <= set(planted) and (k < 24 or set(row[i, :24]) == set(planted))
+
+
+# ---------------------------------------------------------------- 5. more queries than a slab, and than 256
+
+@pytest.mark.parametrize("metric", ["sqeuclidean_dist", "cosine_sim"])
+def test_a_group_of_300_queries_beside_a_group_of_one(amd, metric):
+    rng = np.random.default_rng(5)
+    sizes = [700, 0, 300, 450, 50, 999, 501]
+    parts = [unit(rng.standard_normal((m, 64))) if m else np.zeros((0, 64), np.float32) for m in sizes]
+    chunks = [np.arange(m, dtype=np.int64) + 1000 * i for i, m in enumerate(sizes)]
+    blocks, docs = make_blocks(amd, parts, chunks)
+    qs = rng.standard_normal((301, 64))
+    scope_lists, groups = [list(range(7)), [4, 2]], [300, 1]
+    searcher = searcher_for(amd, blocks)
+    got = run_groups(searcher, qs, 7, metric, blocks, scope_lists, groups)
+    check_groups(amd, metric, 7, qs, docs, scope_lists, groups, got, metric)
+    per_query = searcher.search(qs, 7, metric, [[blocks[j] for j in s] for s in scope_of_query(scope_lists, groups)])
+    assert_routes_agree(got, per_query, metric, metric)
+
+
+# ---------------------------------------------------------------- 6. special values
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_special_values_agree_with_the_per_query_route(amd, metric):
+    """The blocks and queries of test_block_route_equals_index_route_on_special_values, as groups of 3, against the
+    per-query route of the same call: doc, chunk, row and count equal, distances within 1e-9 (cosine 5e-7) absolute.
+
+    The 1e30 row is why the kernel REPORTS a result's distance from the per-query route's routine: the MFMA's dot product
+    with a random query is -6.138418e+30 there, 2.25e+15 (3.7e-16 relative, last bits) from the 16-lane sum, which no
+    absolute bound admits at that magnitude; the MFMA's values select and order, the reported ones have the other route's bits."""
+    rng = np.random.default_rng(3)
+    special = unit(rng.standard_normal((12, 384)))
+    special[2] = 0.0      # a zero row
+    special[5, 7] = np.nan  # a NaN row
+    special[9] = 1e30     # doc_sq overflows to +inf: the signal ref_row_norm tests
+    parts = [unit(rng.standard_normal((20, 384))), special, unit(rng.standard_normal((9, 384)))]
+    blocks = [amd.ei.DeviceRows.from_host(p, 5 * np.arange(len(p), dtype=np.int64)) for p in parts]
+    queries = rng.standard_normal((3, 384))
+    queries[1] = special[9].astype(np.float64) * 1e-30
+    searcher = searcher_for(amd, blocks)
+    for scope in ([1], [0, 1, 2], [2, 1]):
+        lists = [[blocks[j] for j in scope]]
+        for k in (12, 41):
+            shared = searcher.search_shared(queries, k, metric, lists, [3])
+            per_query = searcher.search(queries, k, metric, lists * 3)
+            assert_routes_agree(shared, per_query, metric, f"{metric} k={k} scope {scope}")
+
+
+# ---------------------------------------------------------------- 7. long lists
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_long_block_list(amd, metric):
+    rng = np.random.default_rng(41)
+    sizes = rng.integers(0, 4, 600)
+    sizes[[255, 256, 511]] = 0  # empties at the ends of the walk's steps of 256 segments
+    sizes[[0, 254, 257, 599]] = 3
+    parts = [unit(rng.standard_normal((m, 32))) if m else np.zeros((0, 32), np.float32) for m in sizes]
+    chunks = [np.arange(m, dtype=np.int64) + 7 * i for i, m in enumerate(sizes)]
+    blocks, docs = make_blocks(amd, parts, chunks)
+    qs = rng.standard_normal((18, 32))
+    got = run_groups(searcher_for(amd, blocks), qs, 10, metric, blocks, [list(range(600))], [18])
+    check_groups(amd, metric, 10, qs, docs, [list(range(600))], [18], got, metric)
+    np.testing.assert_array_equal(got[1], got[2] + 7 * got[0])
+
+
+# ---------------------------------------------------------------- 8. device entry
+
+def test_device_entry_matches_host_entry_on_a_side_stream(amd):
+    import torch
+
+    rng = np.random.default_rng(12)
+    sizes = (3000, 40, 0, 160)
+    parts = [unit(rng.standard_normal((m, 384))) if m else np.zeros((0, 384), np.float32) for m in sizes]
+    chunks = [np.arange(m, dtype=np.int64)[::-1].copy() for m in sizes]
+    blocks = [amd.ei.DeviceRows.from_host(p, c) for p, c in zip(parts, chunks)]
+    searcher = searcher_for(amd, blocks)
+    k = 70
+    scope_lists, groups = [[0], [1, 3], [], [2], [3, 1, 1]], [20, 3, 2, 0, 5]
+    b = sum(groups)
+    qs = rng.standard_normal((b, 384))
+    want = run_groups(searcher, qs, k, "sqeuclidean_dist", blocks, scope_lists, groups)
+    gp = np.zeros(len(groups) + 1, np.int32)
+    np.cumsum(groups, out=gp[1:])
+    sp = np.zeros(len(groups) + 1, np.int32)
+    np.cumsum([len(s) for s in scope_lists], out=sp[1:])
+    table = np.array([blocks[j].desc() for s in scope_lists for j in s], dtype=np.int64)  # [nseg][emb, doc_sq, chunk, n]
+    assert table.shape == (7, 4) and C.sizeof(amd.nat.BlockDesc) == 32
+    cuda = torch.device("cuda:0")
+    stream = torch.cuda.Stream(device=cuda)
+    with torch.cuda.stream(stream):
+        tq = torch.from_numpy(qs).to(cuda)
+        tgp, tsp, ttable = torch.from_numpy(gp).to(cuda), torch.from_numpy(sp).to(cuda), torch.from_numpy(table).to(cuda)
+        o_doc = torch.zeros((b, k), dtype=torch.int32, device=cuda)
+        o_chunk = torch.zeros((b, k), dtype=torch.int64, device=cuda)
+        o_row = torch.zeros((b, k), dtype=torch.int64, device=cuda)
+        o_dist = torch.zeros((b, k), dtype=torch.float64, device=cuda)
+        o_cnt = torch.full((b,), -1, dtype=torch.int32, device=cuda)
+        o_flg = torch.full((b,), -1, dtype=torch.int32, device=cuda)
+        searcher.search_shared_device(tq.data_ptr(), b, k, "sqeuclidean_dist", len(groups), tgp.data_ptr(), tsp.data_ptr(), ttable.data_ptr(),
+                                      o_row.data_ptr(), o_dist.data_ptr(), o_cnt.data_ptr(), o_flg.data_ptr(), o_doc.data_ptr(),
+                                      o_chunk.data_ptr(), stream=stream.cuda_stream)
+    stream.synchronize()
+    cnt = o_cnt.cpu().numpy()
+    np.testing.assert_array_equal(cnt, want[4])
+    assert list(cnt) == [70] * 23 + [0, 0] + [70] * 5 and (o_flg.cpu().numpy() == 0).all()
+    for got, host in zip((o_doc, o_chunk, o_row, o_dist), want[:4]):
+        g = got.cpu().numpy()
+        for i in range(b):
+            np.testing.assert_array_equal(g[i, : cnt[i]], host[i, : cnt[i]])  # (distances: the same bits)
+
+
+# ---------------------------------------------------------------- 9. what the host entry refuses
+
+def test_host_entry_refuses_and_leaves_the_outputs_untouched(amd):
+    nat = amd.nat
+    rng = np.random.default_rng(1)
+    good = [amd.ei.DeviceRows.from_host(unit(rng.standard_normal((50, 8)))) for _ in range(2)]
+    other_d = amd.ei.DeviceRows.from_host(unit(rng.standard_normal((50, 16))))
+    half = amd.ei.DeviceRows.from_host(unit(rng.standard_normal((50, 8))).astype(np.float16))
+    searcher = amd.ei.BlockSearcher(8, nat.DTYPE_F32)
+    q = np.zeros((3, 8))
+    ok = searcher.search_shared(q, 3, "inner_product", [[good[0]], [good[1]]], [2, 1])
+    assert list(ok[4]) == [3, 3, 3]
+
+    def table(*entries):
+        return (C.c_void_p * len(entries))(*[e.handle if e is not None else None for e in entries])
+
+    both = table(good[0], good[1])
+    bad = [  # what, n_groups, group_ptr, scope_ptr, table, k, metric
+        ("a NULL block", 2, [0, 2, 3], [0, 1, 2], table(good[0], None), 3, 3),
+        ("a block of another d", 2, [0, 2, 3], [0, 1, 2], table(good[0], other_d), 3, 3),
+        ("a float16 block", 2, [0, 2, 3], [0, 1, 2], table(half, good[1]), 3, 3),
+        ("scope_ptr[0] = 1", 2, [0, 2, 3], [1, 1, 2], both, 3, 3),
+        ("a decreasing scope_ptr", 2, [0, 2, 3], [0, 2, 1], both, 3, 3),
+        ("k = 0", 2, [0, 2, 3], [0, 1, 2], both, 0, 3),
+        ("an unknown metric", 2, [0, 2, 3], [0, 1, 2], both, 3, 9),
+        ("n_groups < 0", -1, [0, 2, 3], [0, 1, 2], both, 3, 3),
+        ("group_ptr[0] = 1", 2, [1, 2, 3], [0, 1, 2], both, 3, 3),
+        ("a decreasing group_ptr", 2, [0, 4, 3], [0, 1, 2], both, 3, 3),
+        ("group_ptr[n_groups] = 2, not b", 2, [0, 1, 2], [0, 1, 2], both, 3, 3),
+        ("group_ptr[n_groups] = 4, not b", 2, [0, 2, 4], [0, 1, 2], both, 3, 3),
+        ("no group for three queries", 0, [0], [0], both, 3, 3),
+    ]
+    for what, n_groups, gptr, sptr, tab, k, metric in bad:
+        gp, sp = np.array(gptr, np.int32), np.array(sptr, np.int32)
+        doc = np.full((3, 3), -7, np.int32)
+        chunk = np.full((3, 3), -7, np.int64)
+        row = np.full((3, 3), -7, np.int64)
+        dist = np.full((3, 3), -7.0)
+        cnt = np.full(3, -7, np.int32)
+        flg = np.full(3, -7, np.int32)
+        rc = nat.lib.mir_blocks_search_shared(searcher.handle, nat.ptr(q), 3, k, metric, n_groups, nat.ptr(gp), nat.ptr(sp), tab, nat.ptr(doc),
+                                              nat.ptr(chunk), nat.ptr(row), nat.ptr(dist), nat.ptr(cnt), nat.ptr(flg))
+        assert rc == nat.MIR_ERR_INVALID, what
+        with pytest.raises(ValueError):
+            nat.check(rc)
+        for a in (doc, chunk, row, dist, cnt, flg):
+            assert (a == -7).all(), what
+    with pytest.raises(ValueError):
+        searcher.search_shared(q, 3, "inner_product", [[good[0]]], [2, 1])  # one scope for two groups
+    with pytest.raises(ValueError):
+        searcher.search_shared(q, 3, "inner_product", [[good[0]], [good[1]]], [2, 2])  # four group members, three queries
+    with pytest.raises(ValueError):
+        searcher.search_shared(q, 3, "manhattan", [[good[0]], [good[1]]], [2, 1])
+
+
+# ---------------------------------------------------------------- 10. the Python surface
+
+@pytest.fixture(scope="module")
+def two_corpora(amd):
+    rng = np.random.default_rng(21)
+    sizes = [30, 0, 120, 45, 60, 200, 17]
+    parts = [unit(rng.standard_normal((m, 384))) if m else np.zeros((0, 384), np.float32) for m in sizes]
+    chunks = [3 * np.arange(m, dtype=np.int64) + 1 for m in sizes]
+    plain, sharing = amd.bc.BlockCorpus(), amd.bc.BlockCorpus(share_scopes=True, min_group=2)
+    for corpus in (plain, sharing):
+        assert [corpus.add(amd.ei.DocIndex(c, p) if len(p) else amd.ei.DocIndex()) for c, p in zip(chunks, parts)] == list(range(7))
+    return plain, sharing, rng.standard_normal((40, 384))
+
+
+def pairs(results):
+    return [[(d.metadata["doc_id"], d.metadata["chunk_id"]) for d in r] for r in results]
+
+
+def test_find_many_groups_equal_scopes(two_corpora):
+    plain, sharing, qs = two_corpora
+    A, B, Cc = [0, 2, 4], [5, 1, 3], [6]
+    scopes = [A, B, A, A, B, Cc]
+    for metric in ("sqeuclidean_dist", "cosine_sim"):
+        got = sharing.find_many(qs[:6], scopes, metric, 9)
+        want = plain.find_many(qs[:6], scopes, metric, 9)
+        np.testing.assert_array_equal(got[3], want[3])
+        assert list(got[3]) == [9] * 6
+        np.testing.assert_array_equal(got[0], want[0])
+        np.testing.assert_array_equal(got[1], want[1])
+        np.testing.assert_allclose(got[2], want[2], rtol=0, atol=dist_tol(metric))
+
+
+def test_find_batch_of_33_queries(amd, two_corpora):
+    plain, sharing, qs = two_corpora
+    views = [c.view([5, 1, 2], amd.RetrievalType.TEXT, "sqeuclidean_dist", 9) for c in (plain, sharing)]
+    want, got = (pairs(v.find_batch(qs[:33])) for v in views)
+    assert got == want and all(len(r) == 9 for r in got)
+
+
+def test_eight_threads_on_two_views_share_passes(amd, two_corpora):
+    plain, sharing, qs = two_corpora
+    key = sharing.add(amd.ei.DocIndex(np.arange(25, dtype=np.int64), unit(np.random.default_rng(2).standard_normal((25, 384)))))
+    assert plain.add(amd.ei.DocIndex(np.arange(25, dtype=np.int64), unit(np.random.default_rng(2).standard_normal((25, 384))))) == key
+    view_keys = [[0, 2, key], [5, 3]]
+    views = [sharing.view(s, amd.RetrievalType.TEXT, "sqeuclidean_dist", 7) for s in view_keys]
+    plain_views = [plain.view(s, amd.RetrievalType.TEXT, "sqeuclidean_dist", 7) for s in view_keys]
+    sharing.remove(key)  # a view made before a remove still answers
+    plain.remove(key)
+    rounds = 20
+    queries = np.random.default_rng(9).standard_normal((8, rounds, 384))
+    got = [[None] * rounds for _ in range(8)]
+    start = threading.Barrier(8)
+    calls0, passes0 = sharing._commit.calls, sharing._commit.passes
+
+    def worker(i):
+        start.wait()
+        for j in range(rounds):
+            got[i][j] = views[i % 2].find(queries[i, j])
+
+    threads = [threading.Thread(target=worker, args=(i,)) for i in range(8)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert sharing._commit.calls - calls0 == 8 * rounds and sharing._commit.passes - passes0 < 8 * rounds
+    for i in range(8):
+        assert pairs(got[i]) == pairs(plain_views[i % 2].find_batch(queries[i])), i
+    assert any(doc_id == 2 for r in got[0] for doc_id, _ in pairs([r])[0])  # the removed document still answers in its view
+
+
+def test_block_hybrid_with_shared_scopes_equals_the_default(amd):
+    rng = np.random.default_rng(66)
+    vocab, d, k = 200, 32, 4
+    per_doc = [12, 30, 7, 0, 25, 18]
+    hybrids = [amd.bb.BlockHybrid(), amd.bb.BlockHybrid(share_scopes=True)]
+    hybrids[1].vector.min_group = 2
+    text_all = []
+    for m in per_doc:
+        emb = rng.standard_normal((m, d)).astype(np.float32)
+        lens = rng.integers(1, 9, m)
+        text = (np.arange(m, dtype=np.int64), lens, ((rng.zipf(1.3, int(lens.sum())) - 1) % vocab).astype(np.int32))
+        text_all.append(text)
+        for h in hybrids:
+            h.add(amd.ei.DocIndex(np.arange(m, dtype=np.int64), emb) if m else amd.ei.DocIndex(), text)
+    doc_lists = [[1, 4, 0], [5], [1, 4, 0], [1, 4, 0], [0, 1, 2, 4, 5]]
+    qv = rng.standard_normal((5, d))
+    qt = [[int(t) for t in rng.choice(text_all[dl[0]][2], 3)] for dl in doc_lists]
+    for metric in ("sqeuclidean_dist", "cosine_sim"):
+        want = hybrids[0].find_many(qv, qt, doc_lists, metric, k)
+        got = hybrids[1].find_many(qv, qt, doc_lists, metric, k)
+        np.testing.assert_array_equal(got[3], want[3])
+        assert (got[3] > 0).all()
+        for i in range(5):
+            m = int(got[3][i])
+            np.testing.assert_array_equal(got[0][i, :m], want[0][i, :m])
+            np.testing.assert_array_equal(got[1][i, :m], want[1][i, :m])
