@@ -3,12 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/miretr.h"
+#include "mir_error.h"
 
 namespace mir {
-
-// thread-local error text behind mir_last_error()
-void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 
 #define MIR_HIP(call)                                                                              \
     do {                                                                                           \
@@ -17,14 +14,6 @@ void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
             ::mir::set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__,      \
                              __LINE__);                                                            \
             return MIR_ERR_HIP;                                                                    \
-        }                                                                                          \
-    } while (0)
-
-#define MIR_REQUIRE(cond, ...)                                                                     \
-    do {                                                                                           \
-        if (!(cond)) {                                                                             \
-            ::mir::set_error(__VA_ARGS__);                                                         \
-            return MIR_ERR_INVALID;                                                                \
         }                                                                                          \
     } while (0)
 

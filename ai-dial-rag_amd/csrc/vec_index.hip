@@ -21,6 +21,7 @@
 #include "vec_kernels_exact.h"
 #include "vec_kernels_scoped.h"
 #include "vec_kernels_shared.h"
+#include "vec_scoped_layout.h"
 
 namespace mir {
 
@@ -358,44 +359,6 @@ static int32_t check_create_args(int64_t n, int32_t d, int32_t dtype, mir_index 
         return MIR_ERR_UNSUPPORTED;
     }
     return MIR_OK;
-}
-
-
-// carve helper
-struct Carver {
-    char *base;
-    size_t off = 0;
-    template <typename T>
-    T *take(size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
-// The six result arrays of a search: the caller's, or their staging in a workspace
-struct SearchOut {
-    int32_t *doc;    // [b][k]
-    int64_t *chunk;
-    int64_t *row;
-    double *dist;
-    int32_t *count;  // [b]
-    int32_t *flags;  // [b]
-};
-
-// host API staging of outputs: one contiguous [doc .. flags] span (host_round_trip copies it back whole); all null otherwise
-static SearchOut carve_out(Carver &c, int b, int k, bool host_api) {
-    if (!host_api) return SearchOut{};
-    const size_t bk = (size_t)b * k;
-    SearchOut o;
-    o.doc = c.take<int32_t>(bk);
-    o.chunk = c.take<int64_t>(bk);
-    o.row = c.take<int64_t>(bk);
-    o.dist = c.take<double>(bk);
-    o.count = c.take<int32_t>(b);
-    o.flags = c.take<int32_t>(b);
-    return o;
 }
 
 struct SearchBuffers {
@@ -1658,66 +1621,28 @@ int32_t mir_index_search(mir_index *idx, const double *queries_host, int32_t b, 
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- scoped search (vec_kernels_scoped.h)
+// ---------------------------------------------------------------- scoped search (vec_kernels_scoped.h, vec_kernels_shared.h)
+// Six entries, one host path: an entry checks its arguments and fills a ScopedCall, run_scoped does the rest.
 
 namespace mir {
 
-struct ScopedBuffers {
-    double *q;            // host API: [b][d]
-    int32_t *scope_ptr;   // host API: [b + 1]
-    int64_t *seg_begin;   // host API: [nseg]
-    int64_t *seg_end;     // host API: [nseg]
-    mir_block_desc *table;  // host API of the block search: [nseg], in place of seg_begin / seg_end
-    int32_t *group_ptr;   // host API of the shared search: [n_groups + 1], in front of scope_ptr (then [n_groups + 1] too)
-    SharedSlab *slabs;    // the shared search: [max_slabs], written by shared_slabs_kernel, with
-    int32_t *n_slabs;     //   their number
-    size_t in_span;       // host API: bytes from q to the end of seg_end / table (one copy in)
-    double *q_sq, *q_norm;
-    unsigned long long *arrive;  // [ceil(b / 2)] words = b counters, zeroed by the prep kernel
-    double *bound_dist;
-    uint32_t *bound_pos;
-    uint64_t *part;       // [b][P][min(k, 64)][2]
-    SearchOut out;        // host API staging of outputs
-};
-
-// The shared search (mir_blocks_search_shared): scope_ptr has one entry per GROUP, the arrival counters one per slab
-struct SharedShape {
-    int n_groups = -1;  // < 0: not the shared search
+struct ScopedCall {
+    mir_index *ix;
+    const double *queries;
+    int b, k, metric;
+    const int32_t *scope_ptr;
+    const int64_t *seg_begin, *seg_end;  // the segments: row ranges of the index, or
+    const mir_block_desc *table;         //   row blocks, one descriptor each (may be null where no scope lists a block:
+    bool blocks;                         //   `blocks` says which search this is)
+    SearchOut out;                 // the caller's
+    hipStream_t stream = nullptr;  // the device forms: the caller's stream
+    bool host_api = false;         // the host forms: every array above is the host's, and walk_scopes has filled
+    ScopeRows rows{0, 0};          //   the segments of all scopes and the longest scope (0 = unknown)
+    int n_groups = -1;             // >= 0: the shared search, scope_ptr per group, with
+    const int32_t *group_ptr = nullptr;
+    SharedPlan plan{};
     int max_slabs = 0;
 };
-
-static size_t carve_scoped(ScopedBuffers &sb, char *base, int b, int k, int d, int P, size_t nseg, bool host_api, bool blocks = false,
-                           const SharedShape &sh = SharedShape{}) {
-    Carver c{base};
-    const bool shared = sh.n_groups >= 0;
-    sb.q = host_api ? c.take<double>((size_t)b * d) : nullptr;
-    sb.group_ptr = host_api && shared ? c.take<int32_t>((size_t)sh.n_groups + 1) : nullptr;
-    sb.scope_ptr = host_api ? c.take<int32_t>((size_t)(shared ? sh.n_groups : b) + 1) : nullptr;
-    sb.seg_begin = host_api && !blocks ? c.take<int64_t>(nseg) : nullptr;
-    sb.seg_end = host_api && !blocks ? c.take<int64_t>(nseg) : nullptr;
-    sb.table = host_api && blocks ? c.take<mir_block_desc>(nseg) : nullptr;
-    sb.in_span = c.off;
-    sb.q_sq = c.take<double>(b);
-    sb.q_norm = c.take<double>(b);
-    sb.arrive = c.take<unsigned long long>(((size_t)(shared ? sh.max_slabs : b) + 1) / 2);
-    sb.bound_dist = c.take<double>(b);
-    sb.bound_pos = c.take<uint32_t>(b);
-    sb.part = c.take<uint64_t>(P > 1 ? (size_t)b * P * std::min(k, kExactRound) * 2 : 0);
-    sb.slabs = shared ? c.take<SharedSlab>((size_t)sh.max_slabs) : nullptr;
-    sb.n_slabs = shared ? c.take<int32_t>(1) : nullptr;
-    sb.out = carve_out(c, b, k, host_api);
-    return c.off + 256;
-}
-
-// Workgroups per query: about four per CU in all, the kernel's merge takes up to kScopedMaxP lists.  One query over a
-// million rows gets 64 workgroups, 256 queries over a thousand rows each get four.
-// `max_rows`: the longest scope where the caller can see the scopes (the host form; 0 = unknown): a workgroup's share is 64
-// positions at the least, a document of a few hundred rows is not spread over 64 lists.
-static int scoped_split(const mir_index *ix, int b, uint64_t max_rows) {
-    int want = (4 * std::max(ix->num_cus, 1) + b - 1) / b;
-    if (max_rows) want = (int)std::min<uint64_t>((uint64_t)want, (max_rows + 63) / 64);
-    return std::min(std::max(want, 1), kScopedMaxP);
-}
 
 static int32_t check_scoped_args(const mir_index *ix, const void *queries, int32_t b, int32_t k, int32_t metric,
                                  const int32_t *scope_ptr, const int32_t *out_count) {
@@ -1727,11 +1652,44 @@ static int32_t check_scoped_args(const mir_index *ix, const void *queries, int32
     return MIR_OK;
 }
 
-// The segments of a scoped search: row ranges of the index (seg_begin / seg_end), or row blocks (a descriptor table)
-struct ScopedSegments {
-    const int64_t *seg_begin = nullptr, *seg_end = nullptr;
-    const mir_block_desc *blocks = nullptr;
-};
+// The block searches' host forms, everything their device forms trust: scope_ptr, and each listed block against the searcher
+// while it becomes its entry of the descriptor `table` the kernels read.  `unit`: what owns a scope, "query" or "group".
+static int32_t check_blocks(const mir_index *ix, const int32_t *scope_ptr, int n_scopes, const char *unit, const int32_t *group_ptr,
+                            const mir_rows *const *blocks, std::vector<mir_block_desc> &table, ScopeRows *rows) {
+    int32_t rc = check_ptr_array(scope_ptr, n_scopes, "scope_ptr", unit);
+    if (rc != MIR_OK) return rc;
+    MIR_REQUIRE(scope_ptr[n_scopes] == 0 || blocks != nullptr, "the block table is NULL");
+    table.resize((size_t)scope_ptr[n_scopes]);
+    return walk_scopes(scope_ptr, n_scopes, unit, group_ptr, [&](int t, int ordinal, int i, uint64_t *len) -> int32_t {
+        const mir_rows *r = blocks[t];
+        MIR_REQUIRE(r != nullptr, "block %d of %s %d is NULL", ordinal, unit, i);
+        MIR_REQUIRE(r->d == ix->d && r->dtype == ix->dtype && r->device == ix->device,
+                    "block %d of %s %d is %d-dimensional dtype %d on device %d, the searcher %d-dimensional dtype %d on device %d",
+                    ordinal, unit, i, r->d, r->dtype, r->device, ix->d, ix->dtype, ix->device);
+        table[(size_t)t] = mir_block_desc{r->d_emb, r->d_docsq, r->d_chunk, r->n};
+        *len = (uint64_t)r->n;
+        return MIR_OK;
+    }, rows);
+}
+
+// per-query norms (ngroups = 0: no fragments) + `counters` arrival counters zeroed
+static void launch_scoped_prep(const ScopedCall &c, const ScopedBuffers &sb, int counters, hipStream_t stream) {
+    const int arrive_words = (counters + 1) / 2;
+    prep_queries_kernel<<<dim3(std::max(c.b, (arrive_words + 63) / 64)), dim3(64), 0, stream>>>(c.queries, c.b, c.ix->d, c.ix->ksteps, 0, nullptr, sb.q_sq,
+                                                                                                  sb.q_norm, sb.arrive, arrive_words);
+}
+
+// The kernels' view of a call whose arrays are on the device (a block searcher's index holds no rows: null, 0)
+static ScopedArgs scoped_args(const ScopedCall &c, const ScopedBuffers &sb, const SearchOut &out) {
+    const mir_index *ix = c.ix;
+    ScopedArgs a;
+    a.docs = ix->d_orig; a.docs16 = ix->d_f16; a.doc_sq = ix->d_docsq; a.n_rows = (uint32_t)ix->n; a.d = ix->d; a.metric = c.metric;
+    a.q = c.queries; a.q_sq = sb.q_sq; a.q_norm = sb.q_norm; a.q0 = 0; a.scope_ptr = c.scope_ptr; a.seg_begin = c.seg_begin; a.seg_end = c.seg_end; a.blocks = c.table;
+    a.k = c.k; a.round = 0; a.list_stride = std::min(c.k, kExactRound); a.part = sb.part; a.arrive = reinterpret_cast<uint32_t *>(sb.arrive);
+    a.bound_dist = sb.bound_dist; a.bound_pos = sb.bound_pos; a.chunk_ids = ix->d_chunk; a.row_offset = ix->row_offset;
+    a.out_doc = out.doc; a.out_chunk = out.chunk; a.out_row = out.row; a.out_dist = out.dist; a.out_count = out.count; a.out_flags = out.flags;
+    return a;
+}
 
 template <typename T, bool BLOCKS>
 static void launch_scoped(const ScopedArgs &a, bool qlds, dim3 grid, size_t lds, hipStream_t stream) {
@@ -1739,20 +1697,12 @@ static void launch_scoped(const ScopedArgs &a, bool qlds, dim3 grid, size_t lds,
     else scoped_topk_kernel<T, false, BLOCKS><<<grid, dim3(kScopedThreads), lds, stream>>>(a);
 }
 
-static int32_t enqueue_scoped(mir_index *ix, const double *dq, int b, int k, int metric, int P, const ScopedBuffers &sb,
-                              const int32_t *scope_ptr, const ScopedSegments &seg, const SearchOut &out, hipStream_t stream) {
-    const int d = ix->d;
-    const bool f16 = seg.blocks ? ix->dtype == MIR_DTYPE_F16 : ix->d_f16 != nullptr;  // (blocks keep float16 as given at any d)
-    // per-query norms (ngroups = 0: no fragments) + the arrival counters zeroed
-    const int arrive_words = (b + 1) / 2;
-    prep_queries_kernel<<<dim3(std::max(b, (arrive_words + 63) / 64)), dim3(64), 0, stream>>>(dq, b, d, ix->ksteps, 0, nullptr, sb.q_sq,
-                                                                                                sb.q_norm, sb.arrive, arrive_words);
-    ScopedArgs a;
-    a.docs = ix->d_orig; a.docs16 = ix->d_f16; a.doc_sq = ix->d_docsq; a.n_rows = (uint32_t)ix->n; a.d = d; a.metric = metric;
-    a.q = dq; a.q_sq = sb.q_sq; a.q_norm = sb.q_norm; a.scope_ptr = scope_ptr; a.seg_begin = seg.seg_begin; a.seg_end = seg.seg_end; a.blocks = seg.blocks;
-    a.k = k; a.list_stride = std::min(k, kExactRound); a.part = sb.part; a.arrive = reinterpret_cast<uint32_t *>(sb.arrive);
-    a.bound_dist = sb.bound_dist; a.bound_pos = sb.bound_pos; a.chunk_ids = ix->d_chunk; a.row_offset = ix->row_offset;
-    a.out_doc = out.doc; a.out_chunk = out.chunk; a.out_row = out.row; a.out_dist = out.dist; a.out_count = out.count; a.out_flags = out.flags;
+static int32_t enqueue_scoped(const ScopedCall &c, int P, const ScopedBuffers &sb, const SearchOut &out, hipStream_t stream) {
+    const mir_index *ix = c.ix;
+    const int d = ix->d, b = c.b, k = c.k;
+    const bool f16 = c.table ? ix->dtype == MIR_DTYPE_F16 : ix->d_f16 != nullptr;  // (blocks keep float16 as given at any d)
+    launch_scoped_prep(c, sb, b, stream);
+    ScopedArgs a = scoped_args(c, sb, out);
     const bool qlds = d <= kScopedLdsDim;
     const size_t lds = qlds ? (size_t)d * sizeof(double) : 0;
     constexpr int kSlice = 32768;  // queries per launch (grid.y)
@@ -1761,33 +1711,14 @@ static int32_t enqueue_scoped(mir_index *ix, const double *dq, int b, int k, int
         for (int q0 = 0; q0 < b; q0 += kSlice) {
             a.q0 = q0;
             const dim3 grid((unsigned)P, (unsigned)std::min(kSlice, b - q0));
-            if (seg.blocks && f16) launch_scoped<_Float16, true>(a, qlds, grid, lds, stream);
-            else if (seg.blocks) launch_scoped<float, true>(a, qlds, grid, lds, stream);
+            if (c.table && f16) launch_scoped<_Float16, true>(a, qlds, grid, lds, stream);
+            else if (c.table) launch_scoped<float, true>(a, qlds, grid, lds, stream);
             else if (f16) launch_scoped<_Float16, false>(a, qlds, grid, lds, stream);
             else launch_scoped<float, false>(a, qlds, grid, lds, stream);
         }
     }
     MIR_HIP(hipGetLastError());
     return MIR_OK;
-}
-
-// ---- the shared search (vec_kernels_shared.h): queries per slab and where the B fragments live, from d and k alone
-constexpr size_t kSharedLdsWide = 64 * 1024;  // a wider slab is taken while the workgroup's dynamic LDS stays below this (two workgroups per CU)
-constexpr size_t kSharedLdsMax = 144 * 1024;  // 16 queries' fragments and lists beyond this: the fragments are read through the caches
-
-struct SharedPlan {
-    int qs;       // queries per slab: 16, 32 or 64
-    bool qlds;    // B fragments in LDS
-    size_t lds;   // dynamic LDS of a workgroup
-};
-
-static SharedPlan shared_plan(int d, int k) {
-    const size_t kk = (size_t)std::min(k, kExactRound), dpad = ((size_t)d + 15) / 16 * 16;
-    auto bytes = [&](int qs, bool frag) { return (size_t)qs * ((frag ? dpad * 8 : 0) + (size_t)kScopedWaves * kk * 12); };
-    for (int qs : {64, 32})
-        if (bytes(qs, true) <= kSharedLdsWide) return SharedPlan{qs, true, bytes(qs, true)};
-    if (bytes(16, true) <= kSharedLdsMax) return SharedPlan{16, true, bytes(16, true)};
-    return SharedPlan{16, false, bytes(16, false)};
 }
 
 template <typename T>
@@ -1799,44 +1730,53 @@ static int32_t launch_shared(const SharedArgs &a, const SharedPlan &pl, dim3 gri
     return launch_dyn(shared_topk_kernel<T, 1, false>, grid, block, pl.lds, stream, a);
 }
 
-static int32_t enqueue_shared(mir_index *ix, const double *dq, int b, int k, int metric, int P, const SharedPlan &pl, int n_groups,
-                              int max_slabs, const ScopedBuffers &sb, const int32_t *group_ptr, const int32_t *scope_ptr,
-                              const mir_block_desc *table, const SearchOut &out, hipStream_t stream) {
-    const int d = ix->d;
-    // per-query norms + the slabs' arrival counters zeroed; then the slab table
-    const int arrive_words = (max_slabs + 1) / 2;
-    prep_queries_kernel<<<dim3(std::max(b, (arrive_words + 63) / 64)), dim3(64), 0, stream>>>(dq, b, d, ix->ksteps, 0, nullptr, sb.q_sq,
-                                                                                                sb.q_norm, sb.arrive, arrive_words);
-    shared_slabs_kernel<<<dim3(1), dim3(kScopedThreads), 0, stream>>>(group_ptr, n_groups, pl.qs, max_slabs, sb.slabs, sb.n_slabs);
+static int32_t enqueue_shared(const ScopedCall &c, int P, const ScopedBuffers &sb, const SearchOut &out, hipStream_t stream) {
+    // the slabs' arrival counters; then the slab table
+    launch_scoped_prep(c, sb, c.max_slabs, stream);
+    shared_slabs_kernel<<<dim3(1), dim3(kScopedThreads), 0, stream>>>(c.group_ptr, c.n_groups, c.plan.qs, c.max_slabs, sb.slabs, sb.n_slabs);
     MIR_HIP(hipGetLastError());
-    SharedArgs sa;
-    ScopedArgs &a = sa.s;
-    a.docs = nullptr; a.docs16 = nullptr; a.doc_sq = nullptr; a.n_rows = 0; a.d = d; a.metric = metric;
-    a.q = dq; a.q_sq = sb.q_sq; a.q_norm = sb.q_norm; a.q0 = 0; a.scope_ptr = scope_ptr; a.seg_begin = nullptr; a.seg_end = nullptr; a.blocks = table;
-    a.k = k; a.list_stride = std::min(k, kExactRound); a.part = sb.part; a.arrive = reinterpret_cast<uint32_t *>(sb.arrive);
-    a.bound_dist = sb.bound_dist; a.bound_pos = sb.bound_pos; a.chunk_ids = nullptr; a.row_offset = 0;
-    a.out_doc = out.doc; a.out_chunk = out.chunk; a.out_row = out.row; a.out_dist = out.dist; a.out_count = out.count; a.out_flags = out.flags;
-    sa.group_ptr = group_ptr; sa.slabs = sb.slabs; sa.n_slabs = sb.n_slabs;
-    const dim3 grid((unsigned)max_slabs, (unsigned)P);
-    for (int round = 0; round * kExactRound < k; ++round) {
-        a.round = round;
-        const int32_t rc = ix->dtype == MIR_DTYPE_F16 ? launch_shared<_Float16>(sa, pl, grid, stream) : launch_shared<float>(sa, pl, grid, stream);
+    SharedArgs sa{scoped_args(c, sb, out), c.group_ptr, sb.slabs, sb.n_slabs};
+    const dim3 grid((unsigned)c.max_slabs, (unsigned)P);
+    for (int round = 0; round * kExactRound < c.k; ++round) {
+        sa.s.round = round;
+        const int32_t rc = c.ix->dtype == MIR_DTYPE_F16 ? launch_shared<_Float16>(sa, c.plan, grid, stream) : launch_shared<float>(sa, c.plan, grid, stream);
         if (rc != MIR_OK) return rc;
     }
     return MIR_OK;
 }
 
-// Workgroups per slab: scoped_split's rule counted in slabs - about four workgroups per CU in all - with the shared kernel's own
-// limit on the lists it merges.  Where the caller can see the scopes a share is 512 positions at the least (eight tiles per
-// wave): every workgroup loads its slab's fragments first, and the last one merges P lists for each of up to 64 queries.
-static int shared_split(const mir_index *ix, int slabs, uint64_t max_rows) {
-    int want = (4 * std::max(ix->num_cus, 1) + slabs - 1) / std::max(slabs, 1);
-    if (max_rows) want = (int)std::min<uint64_t>((uint64_t)want, (max_rows + 511) / 512);
-    return std::min(std::max(want, 1), kSharedMaxP);
+// Device, split, workspace, launches: a device form's on the caller's arrays and stream; a host form's on the workspace's copies, which
+// go in as ONE copy of the span carved in the order [q | group_ptr | scope_ptr | seg_begin | seg_end or table] (host_round_trip)
+static int32_t run_scoped(const ScopedCall &c) {
+    mir_index *ix = c.ix;
+    const int32_t rc = use_device(ix->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    const bool shared = c.n_groups >= 0;
+    const int n_scopes = shared ? c.n_groups : c.b;
+    const int P = shared ? shared_split(ix->num_cus, c.max_slabs, c.rows.max_rows, kSharedMaxP) : scoped_split(ix->num_cus, c.b, c.rows.max_rows, kScopedMaxP);
+    const size_t nseg = c.rows.nseg;
+    const ScopedShape shape{c.b, c.k, ix->d, P, nseg, c.host_api, c.blocks, c.n_groups, c.max_slabs};
+    ScopedBuffers sb;
+    auto enqueue = [&](const ScopedCall &on_device, const SearchOut &out, hipStream_t s) {
+        return shared ? enqueue_shared(on_device, P, sb, out, s) : enqueue_scoped(on_device, P, sb, out, s);
+    };
+    return with_workspace(
+        ix, c.stream, c.host_api, [&](char *base) { return carve_scoped(sb, base, shape, kExactRound); },
+        [&](Workspace *w, hipStream_t s) {
+            if (!c.host_api) return enqueue(c, c.out, s);
+            HostPiece in[5];
+            int n = 0;
+            in[n++] = {sb.q, c.queries, (size_t)c.b * ix->d * sizeof(double)};
+            if (shared) in[n++] = {sb.group_ptr, c.group_ptr, ((size_t)n_scopes + 1) * 4};
+            in[n++] = {sb.scope_ptr, c.scope_ptr, ((size_t)n_scopes + 1) * 4};
+            if (nseg) in[n++] = c.blocks ? HostPiece{sb.table, c.table, nseg * sizeof(mir_block_desc)} : HostPiece{sb.seg_begin, c.seg_begin, nseg * 8};
+            if (nseg && !c.blocks) in[n++] = {sb.seg_end, c.seg_end, nseg * 8};
+            ScopedCall dev = c;  // the call as the kernels see it
+            dev.queries = sb.q; dev.group_ptr = sb.group_ptr; dev.scope_ptr = sb.scope_ptr;
+            dev.seg_begin = sb.seg_begin; dev.seg_end = sb.seg_end; dev.table = sb.table;
+            return host_round_trip(w, s, in, n, sb.q, sb.in_span, sb.out, c.out, c.b, c.k, [&](const SearchOut &out) { return enqueue(dev, out, s); });
+        });
 }
-
-// slabs of a call at the most, from what both forms know: sum over groups of ceil(G / qs) <= ceil(b / qs) + n_groups
-static int shared_max_slabs(int b, int n_groups, int qs) { return (int)std::min<int64_t>(((int64_t)b + qs - 1) / qs + n_groups, 0x7fffffff); }
 
 }  // namespace mir
 
@@ -1847,18 +1787,10 @@ int32_t mir_index_search_scoped_device(mir_index *idx, const double *queries_dev
                                        const int64_t *seg_end_device, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row,
                                        double *out_dist, int32_t *out_count, int32_t *out_flags, void *stream_) {
     int32_t rc = check_scoped_args(idx, queries_device, b, k, metric, scope_ptr_device, out_count);
-    if (rc != MIR_OK) return rc;
-    if (b == 0) return MIR_OK;
-    rc = use_device(idx->device, nullptr);
-    if (rc != MIR_OK) return rc;
-    const int P = scoped_split(idx, b, 0);
-    ScopedBuffers sb;
-    const SearchOut out{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
-    return with_workspace(
-        idx, static_cast<hipStream_t>(stream_), false, [&](char *base) { return carve_scoped(sb, base, b, k, idx->d, P, 0, false); },
-        [&](Workspace *, hipStream_t s) {
-            return enqueue_scoped(idx, queries_device, b, k, metric, P, sb, scope_ptr_device, ScopedSegments{seg_begin_device, seg_end_device}, out, s);
-        });
+    if (rc != MIR_OK || b == 0) return rc;
+    ScopedCall c{idx, queries_device, b, k, metric, scope_ptr_device, seg_begin_device, seg_end_device, nullptr, false,
+                 {out_doc, out_chunk, out_row, out_dist, out_count, out_flags}, static_cast<hipStream_t>(stream_)};
+    return run_scoped(c);
 }
 
 int32_t mir_index_search_scoped(mir_index *idx, const double *queries_host, int32_t b, int32_t k, int32_t metric,
@@ -1866,43 +1798,16 @@ int32_t mir_index_search_scoped(mir_index *idx, const double *queries_host, int3
                                 int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
                                 int32_t *out_flags) {
     int32_t rc = check_scoped_args(idx, queries_host, b, k, metric, scope_ptr_host, out_count);
-    if (rc != MIR_OK) return rc;
-    if (b == 0) return MIR_OK;
+    if (rc != MIR_OK || b == 0) return rc;
     // everything the device form leaves to the kernel's clamping is refused here, before anything is launched
-    MIR_REQUIRE(scope_ptr_host[0] == 0, "scope_ptr[0]=%d must be 0", scope_ptr_host[0]);
-    for (int q = 0; q < b; ++q)
-        MIR_REQUIRE(scope_ptr_host[q + 1] >= scope_ptr_host[q], "scope_ptr decreases at query %d", q);
-    const size_t nseg = (size_t)scope_ptr_host[b];
-    MIR_REQUIRE(nseg == 0 || (seg_begin_host != nullptr && seg_end_host != nullptr), "segment arrays are NULL");
-    uint64_t max_rows = 1;
-    for (int q = 0; q < b; ++q) {
-        uint64_t rows = 0;
-        for (int s = scope_ptr_host[q]; s < scope_ptr_host[q + 1]; ++s) {
-            MIR_REQUIRE(seg_begin_host[s] >= 0 && seg_begin_host[s] <= seg_end_host[s] && seg_end_host[s] <= idx->n,
-                        "segment %d of query %d is [%lld, %lld): not inside 0 <= begin <= end <= n=%lld", s - scope_ptr_host[q], q,
-                        (long long)seg_begin_host[s], (long long)seg_end_host[s], (long long)idx->n);
-            rows += (uint64_t)(seg_end_host[s] - seg_begin_host[s]);
-            MIR_REQUIRE(rows < (1ull << 32), "the scope of query %d holds 2^32 rows or more", q);
-        }
-        max_rows = std::max(max_rows, rows);
-    }
-    rc = use_device(idx->device, nullptr);
+    rc = check_ptr_array(scope_ptr_host, b, "scope_ptr", "query");
     if (rc != MIR_OK) return rc;
-    const int P = scoped_split(idx, b, max_rows);
-    ScopedBuffers sb;
-    const SearchOut user{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
-    return with_workspace(
-        idx, nullptr, true, [&](char *base) { return carve_scoped(sb, base, b, k, idx->d, P, nseg, true); },
-        [&](Workspace *w, hipStream_t s) {
-            // [q | scope_ptr | seg_begin | seg_end] goes in as ONE copy of the span carved in that order
-            const HostPiece in[] = {{sb.q, queries_host, (size_t)b * idx->d * sizeof(double)},
-                                    {sb.scope_ptr, scope_ptr_host, ((size_t)b + 1) * 4},
-                                    {sb.seg_begin, seg_begin_host, nseg * 8},
-                                    {sb.seg_end, seg_end_host, nseg * 8}};
-            return host_round_trip(w, s, in, nseg ? 4 : 2, sb.q, sb.in_span, sb.out, user, b, k, [&](const SearchOut &out) {
-                return enqueue_scoped(idx, sb.q, b, k, metric, P, sb, sb.scope_ptr, ScopedSegments{sb.seg_begin, sb.seg_end}, out, s);
-            });
-        });
+    MIR_REQUIRE(scope_ptr_host[b] == 0 || (seg_begin_host != nullptr && seg_end_host != nullptr), "segment arrays are NULL");
+    ScopedCall c{idx, queries_host, b, k, metric, scope_ptr_host, seg_begin_host, seg_end_host, nullptr, false,
+                 {out_doc, out_chunk, out_row, out_dist, out_count, out_flags}};
+    c.host_api = true;
+    rc = walk_scopes(scope_ptr_host, b, "query", nullptr, range_rows(seg_begin_host, seg_end_host, idx->n), &c.rows);
+    return rc != MIR_OK ? rc : run_scoped(c);
 }
 
 // ---- block search: the scoped search over row blocks (a mir_blocks searcher holds no rows)
@@ -1942,70 +1847,26 @@ int32_t mir_blocks_search_device(mir_blocks *s_, const double *queries_device, i
                                  int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags,
                                  void *stream_) {
     MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
-    mir_index *ix = s_->ix;
-    int32_t rc = check_scoped_args(ix, queries_device, b, k, metric, scope_ptr_device, out_count);
-    if (rc != MIR_OK) return rc;
-    if (b == 0) return MIR_OK;
-    rc = use_device(ix->device, nullptr);
-    if (rc != MIR_OK) return rc;
-    const int P = scoped_split(ix, b, 0);
-    ScopedBuffers sb;
-    ScopedSegments seg;
-    seg.blocks = table_device;
-    const SearchOut out{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
-    return with_workspace(
-        ix, static_cast<hipStream_t>(stream_), false, [&](char *base) { return carve_scoped(sb, base, b, k, ix->d, P, 0, false, true); },
-        [&](Workspace *, hipStream_t s) { return enqueue_scoped(ix, queries_device, b, k, metric, P, sb, scope_ptr_device, seg, out, s); });
+    int32_t rc = check_scoped_args(s_->ix, queries_device, b, k, metric, scope_ptr_device, out_count);
+    if (rc != MIR_OK || b == 0) return rc;
+    ScopedCall c{s_->ix, queries_device, b, k, metric, scope_ptr_device, nullptr, nullptr, table_device, true,
+                 {out_doc, out_chunk, out_row, out_dist, out_count, out_flags}, static_cast<hipStream_t>(stream_)};
+    return run_scoped(c);
 }
 
 int32_t mir_blocks_search(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric,
                           const int32_t *scope_ptr_host, const mir_rows *const *blocks_host, int32_t *out_doc, int64_t *out_chunk,
                           int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags) {
     MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
-    mir_index *ix = s_->ix;
-    int32_t rc = check_scoped_args(ix, queries_host, b, k, metric, scope_ptr_host, out_count);
+    int32_t rc = check_scoped_args(s_->ix, queries_host, b, k, metric, scope_ptr_host, out_count);
+    if (rc != MIR_OK || b == 0) return rc;
+    std::vector<mir_block_desc> table;
+    ScopedCall c{s_->ix, queries_host, b, k, metric, scope_ptr_host, nullptr, nullptr, nullptr, true,
+                 {out_doc, out_chunk, out_row, out_dist, out_count, out_flags}};
+    rc = check_blocks(s_->ix, scope_ptr_host, b, "query", nullptr, blocks_host, table, &c.rows);
     if (rc != MIR_OK) return rc;
-    if (b == 0) return MIR_OK;
-    // everything the device form trusts is checked here, before anything is launched
-    MIR_REQUIRE(scope_ptr_host[0] == 0, "scope_ptr[0]=%d must be 0", scope_ptr_host[0]);
-    for (int q = 0; q < b; ++q)
-        MIR_REQUIRE(scope_ptr_host[q + 1] >= scope_ptr_host[q], "scope_ptr decreases at query %d", q);
-    const size_t nseg = (size_t)scope_ptr_host[b];
-    MIR_REQUIRE(nseg == 0 || blocks_host != nullptr, "the block table is NULL");
-    std::vector<mir_block_desc> table(nseg);
-    uint64_t max_rows = 1;
-    for (int q = 0; q < b; ++q) {
-        uint64_t rows = 0;
-        for (int t = scope_ptr_host[q]; t < scope_ptr_host[q + 1]; ++t) {
-            const mir_rows *r = blocks_host[t];
-            MIR_REQUIRE(r != nullptr, "block %d of query %d is NULL", t - scope_ptr_host[q], q);
-            MIR_REQUIRE(r->d == ix->d && r->dtype == ix->dtype && r->device == ix->device,
-                        "block %d of query %d is %d-dimensional dtype %d on device %d, the searcher %d-dimensional dtype %d on device %d",
-                        t - scope_ptr_host[q], q, r->d, r->dtype, r->device, ix->d, ix->dtype, ix->device);
-            table[(size_t)t] = mir_block_desc{r->d_emb, r->d_docsq, r->d_chunk, r->n};
-            rows += (uint64_t)r->n;
-            MIR_REQUIRE(rows < (1ull << 32), "the scope of query %d holds 2^32 rows or more", q);
-        }
-        max_rows = std::max(max_rows, rows);
-    }
-    rc = use_device(ix->device, nullptr);
-    if (rc != MIR_OK) return rc;
-    const int P = scoped_split(ix, b, max_rows);
-    ScopedBuffers sb;
-    const SearchOut user{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
-    return with_workspace(
-        ix, nullptr, true, [&](char *base) { return carve_scoped(sb, base, b, k, ix->d, P, nseg, true, true); },
-        [&](Workspace *w, hipStream_t s) {
-            // [q | scope_ptr | table] goes in as ONE copy of the span carved in that order
-            const HostPiece in[] = {{sb.q, queries_host, (size_t)b * ix->d * sizeof(double)},
-                                    {sb.scope_ptr, scope_ptr_host, ((size_t)b + 1) * 4},
-                                    {sb.table, table.data(), nseg * sizeof(mir_block_desc)}};
-            ScopedSegments seg;
-            seg.blocks = sb.table;
-            return host_round_trip(w, s, in, nseg ? 3 : 2, sb.q, sb.in_span, sb.out, user, b, k, [&](const SearchOut &out) {
-                return enqueue_scoped(ix, sb.q, b, k, metric, P, sb, sb.scope_ptr, seg, out, s);
-            });
-        });
+    c.host_api = true; c.table = table.data();
+    return run_scoped(c);
 }
 
 // ---- shared block search: the queries of a group search one scope, whose rows are read once per slab (vec_kernels_shared.h)
@@ -2015,25 +1876,17 @@ int32_t mir_blocks_search_shared_device(mir_blocks *s_, const double *queries_de
                                         int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
                                         int32_t *out_flags, void *stream_) {
     MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
-    mir_index *ix = s_->ix;
-    int32_t rc = check_scoped_args(ix, queries_device, b, k, metric, scope_ptr_device, out_count);
+    int32_t rc = check_scoped_args(s_->ix, queries_device, b, k, metric, scope_ptr_device, out_count);
     if (rc != MIR_OK) return rc;
     MIR_REQUIRE(n_groups >= 0, "n_groups=%d is negative", n_groups);
     if (b == 0) return MIR_OK;
     MIR_REQUIRE(group_ptr_device != nullptr, "group_ptr is NULL");
-    rc = use_device(ix->device, nullptr);
-    if (rc != MIR_OK) return rc;
-    const SharedPlan pl = shared_plan(ix->d, k);
-    const int max_slabs = shared_max_slabs(b, n_groups, pl.qs);
-    const int P = shared_split(ix, max_slabs, 0);
-    ScopedBuffers sb;
-    const SearchOut out{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
-    return with_workspace(
-        ix, static_cast<hipStream_t>(stream_), false,
-        [&](char *base) { return carve_scoped(sb, base, b, k, ix->d, P, 0, false, true, SharedShape{n_groups, max_slabs}); },
-        [&](Workspace *, hipStream_t s) {
-            return enqueue_shared(ix, queries_device, b, k, metric, P, pl, n_groups, max_slabs, sb, group_ptr_device, scope_ptr_device, table_device, out, s);
-        });
+    ScopedCall c{s_->ix, queries_device, b, k, metric, scope_ptr_device, nullptr, nullptr, table_device, true,
+                 {out_doc, out_chunk, out_row, out_dist, out_count, out_flags}, static_cast<hipStream_t>(stream_)};
+    c.n_groups = n_groups; c.group_ptr = group_ptr_device;
+    c.plan = shared_plan(s_->ix->d, k, kExactRound, kScopedWaves);
+    c.max_slabs = shared_max_slabs(b, n_groups, c.plan.qs);
+    return run_scoped(c);
 }
 
 int32_t mir_blocks_search_shared(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, int32_t n_groups,
@@ -2041,65 +1894,26 @@ int32_t mir_blocks_search_shared(mir_blocks *s_, const double *queries_host, int
                                  int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
                                  int32_t *out_flags) {
     MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
-    mir_index *ix = s_->ix;
-    int32_t rc = check_scoped_args(ix, queries_host, b, k, metric, scope_ptr_host, out_count);
+    int32_t rc = check_scoped_args(s_->ix, queries_host, b, k, metric, scope_ptr_host, out_count);
     if (rc != MIR_OK) return rc;
     MIR_REQUIRE(n_groups >= 0, "n_groups=%d is negative", n_groups);
     if (b == 0) return MIR_OK;
     // everything the device form trusts is checked here, before anything is launched
     MIR_REQUIRE(group_ptr_host != nullptr, "group_ptr is NULL");
-    MIR_REQUIRE(group_ptr_host[0] == 0, "group_ptr[0]=%d must be 0", group_ptr_host[0]);
-    for (int g = 0; g < n_groups; ++g)
-        MIR_REQUIRE(group_ptr_host[g + 1] >= group_ptr_host[g], "group_ptr decreases at group %d", g);
-    MIR_REQUIRE(group_ptr_host[n_groups] == b, "group_ptr[n_groups]=%d must be b=%d", group_ptr_host[n_groups], b);
-    MIR_REQUIRE(scope_ptr_host[0] == 0, "scope_ptr[0]=%d must be 0", scope_ptr_host[0]);
-    for (int g = 0; g < n_groups; ++g)
-        MIR_REQUIRE(scope_ptr_host[g + 1] >= scope_ptr_host[g], "scope_ptr decreases at group %d", g);
-    const size_t nseg = (size_t)scope_ptr_host[n_groups];
-    MIR_REQUIRE(nseg == 0 || blocks_host != nullptr, "the block table is NULL");
-    const SharedPlan pl = shared_plan(ix->d, k);
-    std::vector<mir_block_desc> table(nseg);
-    uint64_t max_rows = 1;
-    int64_t slabs = 0;
-    for (int g = 0; g < n_groups; ++g) {
-        uint64_t rows = 0;
-        for (int t = scope_ptr_host[g]; t < scope_ptr_host[g + 1]; ++t) {
-            const mir_rows *r = blocks_host[t];
-            MIR_REQUIRE(r != nullptr, "block %d of group %d is NULL", t - scope_ptr_host[g], g);
-            MIR_REQUIRE(r->d == ix->d && r->dtype == ix->dtype && r->device == ix->device,
-                        "block %d of group %d is %d-dimensional dtype %d on device %d, the searcher %d-dimensional dtype %d on device %d",
-                        t - scope_ptr_host[g], g, r->d, r->dtype, r->device, ix->d, ix->dtype, ix->device);
-            table[(size_t)t] = mir_block_desc{r->d_emb, r->d_docsq, r->d_chunk, r->n};
-            rows += (uint64_t)r->n;
-            MIR_REQUIRE(rows < (1ull << 32), "the scope of group %d holds 2^32 rows or more", g);
-        }
-        const int64_t queries = (int64_t)group_ptr_host[g + 1] - group_ptr_host[g];
-        if (queries > 0) max_rows = std::max(max_rows, rows);
-        slabs += (queries + pl.qs - 1) / pl.qs;
-    }
-    rc = use_device(ix->device, nullptr);
+    rc = check_ptr_array(group_ptr_host, n_groups, "group_ptr", "group");
     if (rc != MIR_OK) return rc;
-    const int max_slabs = (int)slabs;  // (the host form can count them: no surplus workgroup)
-    const int P = shared_split(ix, max_slabs, max_rows);
-    ScopedBuffers sb;
-    const SearchOut user{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
-    return with_workspace(
-        ix, nullptr, true, [&](char *base) { return carve_scoped(sb, base, b, k, ix->d, P, nseg, true, true, SharedShape{n_groups, max_slabs}); },
-        [&](Workspace *w, hipStream_t s) {
-            // [q | group_ptr | scope_ptr | table] goes in as ONE copy of the span carved in that order
-            const HostPiece in[] = {{sb.q, queries_host, (size_t)b * ix->d * sizeof(double)},
-                                    {sb.group_ptr, group_ptr_host, ((size_t)n_groups + 1) * 4},
-                                    {sb.scope_ptr, scope_ptr_host, ((size_t)n_groups + 1) * 4},
-                                    {sb.table, table.data(), nseg * sizeof(mir_block_desc)}};
-            return host_round_trip(w, s, in, nseg ? 4 : 3, sb.q, sb.in_span, sb.out, user, b, k, [&](const SearchOut &out) {
-                return enqueue_shared(ix, sb.q, b, k, metric, P, pl, n_groups, max_slabs, sb, sb.group_ptr, sb.scope_ptr, sb.table, out, s);
-            });
-        });
+    MIR_REQUIRE(group_ptr_host[n_groups] == b, "group_ptr[n_groups]=%d must be b=%d", group_ptr_host[n_groups], b);
+    std::vector<mir_block_desc> table;
+    ScopedCall c{s_->ix, queries_host, b, k, metric, scope_ptr_host, nullptr, nullptr, nullptr, true,
+                 {out_doc, out_chunk, out_row, out_dist, out_count, out_flags}};
+    rc = check_blocks(s_->ix, scope_ptr_host, n_groups, "group", group_ptr_host, blocks_host, table, &c.rows);
+    if (rc != MIR_OK) return rc;
+    c.host_api = true; c.table = table.data();
+    c.n_groups = n_groups; c.group_ptr = group_ptr_host;
+    c.plan = shared_plan(s_->ix->d, k, kExactRound, kScopedWaves);
+    c.max_slabs = shared_slab_count(group_ptr_host, n_groups, c.plan.qs);  // (no surplus workgroup, as the device form's bound leaves)
+    return run_scoped(c);
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int32_t mir_index_metric_eval(mir_index *idx, const double *query_host, int32_t metric, double *out_host) {
     MIR_REQUIRE(idx != nullptr, "index is NULL");

@@ -39,6 +39,7 @@
 //     every address is begin + offset with offset < length.
 #pragma once
 #include "vec_kernels_scoped.h"
+#include "vec_scoped_layout.h"  // SharedSlab
 
 namespace mir {
 
@@ -46,11 +47,6 @@ typedef double __attribute__((ext_vector_type(4))) shared_d4;
 
 constexpr int kSharedAhead = 8;   // steps of 16 columns whose row loads are issued before the first of their MFMAs (d = 384: three batches)
 constexpr int kSharedMaxP = 256;  // shares of a scope at the most: one slab alone still fills the chip; the merge reads P lists per query
-
-struct SharedSlab {
-    int32_t group;
-    int32_t q0;  // first query of the slab
-};
 
 struct SharedArgs {
     ScopedArgs s;               // blocks, q, q_sq, q_norm, part, bound_*, out_*; scope_ptr is indexed by GROUP; arrive by SLAB

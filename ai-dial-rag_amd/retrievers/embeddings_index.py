@@ -104,6 +104,23 @@ class DeviceRows:
             pass
 
 
+def _result_arrays(b: int, k: int) -> Tuple[np.ndarray, ...]:
+    """The six arrays every search returns: (doc i32, chunk i64, row i64, dist f64)[b, k], (count, flags) i32[b].
+    A negative k gives empty arrays, so it reaches the C check and is a ValueError like any other bad argument."""
+    bk = (b, max(k, 0))
+    return (np.zeros(bk, np.int32), np.zeros(bk, np.int64), np.zeros(bk, np.int64), np.zeros(bk, np.float64),
+            np.zeros(b, np.int32), np.zeros(b, np.int32))
+
+
+def _scope_table(scopes: Sequence[Sequence["DeviceRows"]]):
+    """-> (held, scope_ptr, table): the blocks of all scopes in order (whoever holds `held` keeps them alive), int32[len(scopes) + 1]
+    where each scope begins in that list, and the blocks' handles as the C array the block searches take."""
+    held = [blk for s in scopes for blk in s]
+    sp = np.zeros(len(scopes) + 1, np.int32)
+    np.cumsum([len(s) for s in scopes], out=sp[1:])
+    return held, sp, (C.c_void_p * max(len(held), 1))(*[blk.handle for blk in held])
+
+
 class BlockSearcher:
     """Owner of one ``mir_blocks`` handle: a searcher over ``DeviceRows`` blocks of one (d, dtype, device).  It holds
     workspaces only; the rows stay in their blocks, nothing is composed or copied (csrc/vec_kernels_scoped.h, BLOCKS)."""
@@ -126,23 +143,14 @@ class BlockSearcher:
         code = nat.METRIC_CODES[Metric(metric).value]
         if len(scopes) != b:
             raise ValueError(f"{len(scopes)} scopes for {b} queries")
-        held = [blk for s in scopes for blk in s]  # (alive across the call)
-        sp = np.zeros(b + 1, np.int32)
-        np.cumsum([len(s) for s in scopes], out=sp[1:])
-        table = (C.c_void_p * max(len(held), 1))(*[blk.handle for blk in held])
+        _held, sp, table = _scope_table(scopes)  # (the blocks: alive across the call)
         return self._search_raw(q, k, code, sp, table)
 
     def _search_raw(self, q: np.ndarray, k: int, code: int, sp: np.ndarray, table) -> Tuple[np.ndarray, ...]:
         b = q.shape[0]
-        doc = np.zeros((b, max(k, 0)), np.int32)
-        chunk = np.zeros((b, max(k, 0)), np.int64)
-        row = np.zeros((b, max(k, 0)), np.int64)
-        dist = np.zeros((b, max(k, 0)), np.float64)
-        cnt = np.zeros(b, np.int32)
-        flg = np.zeros(b, np.int32)
-        nat.check(nat.lib.mir_blocks_search(self._h, nat.ptr(q), b, k, code, nat.ptr(sp), table, nat.ptr(doc), nat.ptr(chunk), nat.ptr(row),
-                                            nat.ptr(dist), nat.ptr(cnt), nat.ptr(flg)))
-        return doc, chunk, row, dist, cnt, flg
+        out = _result_arrays(b, k)
+        nat.check(nat.lib.mir_blocks_search(self._h, nat.ptr(q), b, k, code, nat.ptr(sp), table, *map(nat.ptr, out)))
+        return out
 
     def search_device(self, q_ptr: int, b: int, k: int, metric, scope_ptr_ptr: int, table_ptr: int, out_row_ptr: int, out_dist_ptr: int,
                       out_count_ptr: int, out_flags_ptr: int = 0, out_doc_ptr: int = 0, out_chunk_ptr: int = 0, stream: int = 0) -> None:
@@ -168,21 +176,12 @@ class BlockSearcher:
             raise ValueError(f"{len(scopes)} scopes for {len(sizes)} groups")
         if any(g < 0 for g in sizes) or sum(sizes) != b:
             raise ValueError(f"group sizes {sizes} do not add up to {b} queries")
-        held = [blk for s in scopes for blk in s]  # (alive across the call)
+        _held, sp, table = _scope_table(scopes)  # (the blocks: alive across the call)
         gp = np.zeros(len(sizes) + 1, np.int32)
         np.cumsum(sizes, out=gp[1:])
-        sp = np.zeros(len(sizes) + 1, np.int32)
-        np.cumsum([len(s) for s in scopes], out=sp[1:])
-        table = (C.c_void_p * max(len(held), 1))(*[blk.handle for blk in held])
-        doc = np.zeros((b, max(k, 0)), np.int32)
-        chunk = np.zeros((b, max(k, 0)), np.int64)
-        row = np.zeros((b, max(k, 0)), np.int64)
-        dist = np.zeros((b, max(k, 0)), np.float64)
-        cnt = np.zeros(b, np.int32)
-        flg = np.zeros(b, np.int32)
-        nat.check(nat.lib.mir_blocks_search_shared(self._h, nat.ptr(q), b, k, code, len(sizes), nat.ptr(gp), nat.ptr(sp), table, nat.ptr(doc),
-                                                   nat.ptr(chunk), nat.ptr(row), nat.ptr(dist), nat.ptr(cnt), nat.ptr(flg)))
-        return doc, chunk, row, dist, cnt, flg
+        out = _result_arrays(b, k)
+        nat.check(nat.lib.mir_blocks_search_shared(self._h, nat.ptr(q), b, k, code, len(sizes), nat.ptr(gp), nat.ptr(sp), table, *map(nat.ptr, out)))
+        return out
 
     def search_shared_device(self, q_ptr: int, b: int, k: int, metric, n_groups: int, group_ptr_ptr: int, scope_ptr_ptr: int, table_ptr: int,
                              out_row_ptr: int, out_dist_ptr: int, out_count_ptr: int, out_flags_ptr: int = 0, out_doc_ptr: int = 0,
@@ -264,15 +263,9 @@ class DeviceIndex:
         q = nat.as_f64_queries(queries, self.d)
         b = q.shape[0]
         code = nat.METRIC_CODES[Metric(metric).value]
-        doc = np.zeros((b, k), np.int32)
-        chunk = np.zeros((b, k), np.int64)
-        row = np.zeros((b, k), np.int64)
-        dist = np.zeros((b, k), np.float64)
-        cnt = np.zeros(b, np.int32)
-        flg = np.zeros(b, np.int32)
-        nat.check(nat.lib.mir_index_search(self._h, nat.ptr(q), b, k, code, nat.ptr(doc), nat.ptr(chunk), nat.ptr(row),
-                                           nat.ptr(dist), nat.ptr(cnt), nat.ptr(flg)))
-        return doc, chunk, row, dist, cnt, flg
+        out = _result_arrays(b, k)
+        nat.check(nat.lib.mir_index_search(self._h, nat.ptr(q), b, k, code, *map(nat.ptr, out)))
+        return out
 
     def search_device(self, q_ptr: int, b: int, k: int, metric, out_row_ptr: int, out_dist_ptr: int, out_count_ptr: int,
                       out_flags_ptr: int = 0, out_doc_ptr: int = 0, out_chunk_ptr: int = 0, stream: int = 0) -> None:
@@ -296,15 +289,9 @@ class DeviceIndex:
             raise ValueError(f"scope_ptr has {len(sp)} entries for {b} queries (want b + 1)")
         if len(sb) != len(se) or int(sp.max()) > len(sb):
             raise ValueError(f"{len(sb)} segment begins, {len(se)} ends, scope_ptr up to {int(sp.max())}")
-        doc = np.zeros((b, k), np.int32)
-        chunk = np.zeros((b, k), np.int64)
-        row = np.zeros((b, k), np.int64)
-        dist = np.zeros((b, k), np.float64)
-        cnt = np.zeros(b, np.int32)
-        flg = np.zeros(b, np.int32)
-        nat.check(nat.lib.mir_index_search_scoped(self._h, nat.ptr(q), b, k, code, nat.ptr(sp), nat.ptr(sb), nat.ptr(se), nat.ptr(doc),
-                                                  nat.ptr(chunk), nat.ptr(row), nat.ptr(dist), nat.ptr(cnt), nat.ptr(flg)))
-        return doc, chunk, row, dist, cnt, flg
+        out = _result_arrays(b, k)
+        nat.check(nat.lib.mir_index_search_scoped(self._h, nat.ptr(q), b, k, code, nat.ptr(sp), nat.ptr(sb), nat.ptr(se), *map(nat.ptr, out)))
+        return out
 
     def search_scoped_device(self, q_ptr: int, b: int, k: int, metric, scope_ptr_ptr: int, seg_begin_ptr: int, seg_end_ptr: int,
                              out_row_ptr: int, out_dist_ptr: int, out_count_ptr: int, out_flags_ptr: int = 0, out_doc_ptr: int = 0,
