@@ -21,7 +21,9 @@
 #include "vec_kernels_exact.h"
 #include "vec_kernels_scoped.h"
 #include "vec_kernels_shared.h"
+#include "vec_kernels_pieces.h"
 #include "vec_scoped_layout.h"
+#include "vec_pieces_layout.h"
 
 namespace mir {
 
@@ -1913,6 +1915,89 @@ int32_t mir_blocks_search_shared(mir_blocks *s_, const double *queries_host, int
     c.plan = shared_plan(s_->ix->d, k, kExactRound, kScopedWaves);
     c.max_slabs = shared_slab_count(group_ptr_host, n_groups, c.plan.qs);  // (no surplus workgroup, as the device form's bound leaves)
     return run_scoped(c);
+}
+
+// ---- pieces search: scopes that overlap read their common blocks once (vec_pieces_layout.h, vec_kernels_pieces.h)
+
+int32_t mir_blocks_search_pieces(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, int32_t n_pieces,
+                                 const int32_t *piece_ptr_host, const mir_rows *const *blocks_host, const int32_t *rider_ptr_host,
+                                 const int32_t *rider_piece_host, int32_t min_riders, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row,
+                                 double *out_dist, int32_t *out_count, int32_t *out_flags) {
+    MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
+    mir_index *ix = s_->ix;
+    int32_t rc = check_search_args(ix, queries_host, b, k, metric, out_count);
+    if (rc != MIR_OK) return rc;
+    MIR_REQUIRE(n_pieces >= 0, "n_pieces=%d is negative", n_pieces);
+    MIR_REQUIRE(min_riders >= 1, "min_riders=%d must be >= 1", min_riders);
+    if (b == 0) return MIR_OK;
+    // everything the kernels trust is checked here, before anything is launched
+    rc = check_pieces_args(b, n_pieces, piece_ptr_host, rider_ptr_host, rider_piece_host, min_riders);
+    if (rc != MIR_OK) return rc;
+    std::vector<mir_block_desc> all;  // one descriptor per entry of blocks_host
+    ScopeRows piece_rows{0, 0};
+    if (n_pieces > 0) {
+        rc = check_blocks(ix, piece_ptr_host, n_pieces, "piece", nullptr, blocks_host, all, &piece_rows);
+        if (rc != MIR_OK) return rc;
+    }
+    PiecesPlan pl;
+    rc = plan_pieces(b, n_pieces, piece_ptr_host, rider_ptr_host, rider_piece_host, min_riders, [&](int t) { return (uint64_t)all[(size_t)t].n; }, &pl);
+    if (rc != MIR_OK) return rc;
+    const int n_occ = pl.n_occ(), n_groups = pl.n_groups(), d = ix->d;
+    MIR_REQUIRE((int64_t)n_occ * k < (1ll << 31), "%d occurrences of k=%d results are 2^31 list entries or more", n_occ, k);
+    const size_t nseg_shared = pl.shared_block.size(), nseg_solo = pl.solo_block.size();
+    std::vector<mir_block_desc> table(nseg_shared + nseg_solo);  // the groups' blocks, then the solo occurrences'
+    for (size_t i = 0; i < nseg_shared; ++i) table[i] = all[(size_t)pl.shared_block[i]];
+    for (size_t i = 0; i < nseg_solo; ++i) table[nseg_shared + i] = all[(size_t)pl.solo_block[i]];
+    rc = use_device(ix->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    const SharedPlan plan = shared_plan(d, k, kExactRound, kScopedWaves);
+    const int max_slabs = shared_slab_count(pl.group_ptr.data(), n_groups, plan.qs);
+    const int P_shared = shared_split(ix->num_cus, max_slabs, pl.shared_max_rows, kSharedMaxP);
+    const int P_solo = scoped_split(ix->num_cus, pl.n_solo, pl.solo_max_rows, kScopedMaxP);
+    const PiecesShape shape{b, k, d, pl.n_shared, pl.n_solo, n_groups, nseg_shared, nseg_solo, P_shared, P_solo, max_slabs};
+    PiecesBuffers pb;
+    const SearchOut user{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    return with_workspace(
+        ix, nullptr, true, [&](char *base) { return carve_pieces(pb, base, shape, kExactRound); },
+        [&](Workspace *w, hipStream_t s) {
+            HostPiece in[10];
+            int n = 0;
+            auto piece = [&](const void *dev, const void *host, size_t bytes) {
+                if (bytes) in[n++] = {dev, host, bytes};
+            };
+            piece(pb.q, queries_host, (size_t)b * d * sizeof(double));
+            piece(pb.occ_query, pl.occ_query.data(), (size_t)n_occ * 4);
+            piece(pb.group_ptr, pl.group_ptr.data(), ((size_t)n_groups + 1) * 4);
+            piece(pb.scope_ptr, pl.scope_ptr.data(), ((size_t)n_groups + 1) * 4);
+            piece(pb.solo_ptr, pl.solo_ptr.data(), ((size_t)pl.n_solo + 1) * 4);
+            piece(pb.table, table.data(), table.size() * sizeof(mir_block_desc));
+            piece(pb.occ_base, pl.occ_base.data(), (size_t)pl.n_shared * 4);
+            piece(pb.solo_ord, pl.solo_ord.data(), nseg_solo * 4);
+            piece(pb.q_occ_ptr, pl.q_occ_ptr.data(), ((size_t)b + 1) * 4);
+            piece(pb.q_occ, pl.q_occ.data(), (size_t)n_occ * 4);
+            return host_round_trip(w, s, in, n, pb.q, pb.in_span, pb.out, user, b, k, [&](const SearchOut &out) -> int32_t {
+                if (n_occ > 0) pieces_gather_kernel<<<dim3((unsigned)n_occ), dim3(64), 0, s>>>(pb.q, pb.occ_query, b, d, pb.q_by_occ);
+                MIR_HIP(hipGetLastError());
+                const size_t sk = (size_t)pl.n_shared * k;  // the solo occurrences' results lie behind the shared ones'
+                if (pl.n_shared > 0) {
+                    ScopedCall c{ix, pb.q_by_occ, pl.n_shared, k, metric, pb.scope_ptr, nullptr, nullptr, pb.table, true, SearchOut{}};
+                    c.n_groups = n_groups; c.group_ptr = pb.group_ptr; c.plan = plan; c.max_slabs = max_slabs;
+                    const int32_t rc2 = enqueue_shared(c, P_shared, pb.shared, pb.occ, s);
+                    if (rc2 != MIR_OK) return rc2;
+                }
+                if (pl.n_solo > 0) {
+                    ScopedCall c{ix, pb.q_by_occ + (size_t)pl.n_shared * d, pl.n_solo, k, metric, pb.solo_ptr, nullptr, nullptr, pb.table + nseg_shared, true, SearchOut{}};
+                    const SearchOut occ{pb.occ.doc + sk, pb.occ.chunk + sk, pb.occ.row + sk, pb.occ.dist + sk, pb.occ.count + pl.n_shared, pb.occ.flags + pl.n_shared};
+                    const int32_t rc2 = enqueue_scoped(c, P_solo, pb.solo, occ, s);
+                    if (rc2 != MIR_OK) return rc2;
+                }
+                const PiecesMergeArgs ma{pb.q_occ_ptr, pb.q_occ, pl.n_shared, pl.n_solo, pb.occ_base, pb.solo_ptr, pb.solo_ord, k, pb.occ,
+                                         pb.cand_key, pb.cand_row, pb.cand_src, out};
+                pieces_merge_kernel<<<dim3((unsigned)b), dim3(kPiecesThreads), 0, s>>>(ma);
+                MIR_HIP(hipGetLastError());
+                return MIR_OK;
+            });
+        });
 }
 
 int32_t mir_index_metric_eval(mir_index *idx, const double *query_host, int32_t metric, double *out_host) {

@@ -12,6 +12,7 @@ document's position, so a ``BlockCorpus`` stands where a ``CorpusIndex`` does (`
 """
 
 import threading
+from itertools import chain
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -30,6 +31,8 @@ __all__ = ["BlockCorpus", "BlockView"]
 # route's slowest call beats the per-query route's fastest is 1 on a scope of 1.25M rows and 256 on a scope of 10 000 rows
 # (below that the slab's per-query merge and result phases cost more than the rows it saves).  The corpus does not know
 # which case a call is, so the default is the larger of the two; pass a smaller ``min_group`` where scopes are large.
+# ``share_pieces=True`` uses the same number for the riders of a common run of blocks (``search_pieces``' ``min_riders``):
+# DESIGN.md 3.9 (a) / (b) measured the same two cases with private blocks beside the common ones, with the same outcome.
 DEFAULT_MIN_GROUP = 256
 
 
@@ -67,9 +70,11 @@ class BlockCorpus:
     """``add`` / ``remove`` / ``view`` / ``find_many`` may be called from any thread, also while searches run: a search
     works on the ``DeviceRows`` objects it took when it was submitted."""
 
-    def __init__(self, device: int = 0, max_batch: int = 256, share_scopes: bool = False, min_group: int = DEFAULT_MIN_GROUP):
+    def __init__(self, device: int = 0, max_batch: int = 256, share_scopes: bool = False, min_group: int = DEFAULT_MIN_GROUP,
+                 share_pieces: bool = False):
         self.device = device
         self.share_scopes = bool(share_scopes)  # queries of a call with the same scope read its rows once (search_shared)
+        self.share_pieces = bool(share_pieces)  # scopes that overlap read their common runs of blocks once (search_pieces); goes before share_scopes
         self.min_group = max(int(min_group), 1)
         self.d: Optional[int] = None      # fixed by the first non-empty document, with
         self.dtype: Optional[int] = None  # its storage type
@@ -140,6 +145,53 @@ class BlockCorpus:
                     groups.setdefault(tuple(map(id, lists[i])), []).append(i)
         return [idx for idx in groups.values() if len(idx) >= self.min_group]
 
+    def _pieces(self, lists):
+        """share_pieces: every scope cut into RUNS of blocks -> (pieces, scopes, riders): the distinct runs as block lists,
+        each scope as indices into them, and how often each piece is named in the call; None where no piece can be named
+        min_group times.  A block is COMMON when min_group scopes or more name it; a run ends where commonness changes or
+        where the set of scopes naming the block does, so [KB1, KB2] and [KB1] share KB1.  Equal runs (the same block
+        OBJECTS in the same order) are one piece.  One pass over the named blocks' ids."""
+        ids = np.fromiter(map(id, chain.from_iterable(lists)), np.int64)
+        if len(ids) < self.min_group:
+            return None
+        by_id = np.sort(ids)
+        last = np.append(np.flatnonzero(by_id[1:] != by_id[:-1]), len(ids) - 1)  # where each block's entries end in the sorted ids
+        if int(np.diff(last, prepend=-1).max()) < self.min_group:
+            return None  # no block is listed min_group times, and a piece rides no more often than its first block is listed
+        n_scopes = len(lists)
+        sizes = np.fromiter(map(len, lists), np.int64, n_scopes)
+        query = np.repeat(np.arange(n_scopes, dtype=np.int64), sizes)
+        blocks, block = np.unique(ids, return_inverse=True)  # block: 0 .. len(blocks) - 1 per named entry
+        pairs = np.unique(block * n_scopes + query)  # (block, scope) once each, sorted by block, then scope
+        pair_block, pair_query = pairs // n_scopes, pairs % n_scopes
+        named_by = np.bincount(pair_block, minlength=len(blocks))
+        ends = np.cumsum(named_by)
+        # the set of scopes naming a block, as a number: the scope itself where it is one, else n_scopes + a class of its own
+        sig = pair_query[ends - 1]
+        classes: Dict[bytes, int] = {}
+        for u in np.flatnonzero(named_by > 1).tolist():
+            sig[u] = n_scopes + classes.setdefault(pair_query[ends[u] - named_by[u]:ends[u]].tobytes(), len(classes))
+        common = named_by >= self.min_group
+        first = np.zeros(len(ids), bool)
+        first[(np.cumsum(sizes) - sizes)[sizes > 0]] = True  # a scope's first entry
+        e_sig, e_common = sig[block], common[block]
+        first[1:] |= (e_sig[1:] != e_sig[:-1]) | (e_common[1:] != e_common[:-1])
+        starts = np.flatnonzero(first)
+        stops = np.append(starts[1:], len(ids))
+        flat = list(chain.from_iterable(lists))
+        known: Dict[bytes, int] = {}
+        pieces: List[list] = []
+        run_piece = np.empty(len(starts), np.int64)
+        for r, (lo, hi) in enumerate(zip(starts.tolist(), stops.tolist())):  # equal runs are one piece
+            key = ids[lo:hi].tobytes()
+            p = known.get(key)
+            if p is None:
+                p = known[key] = len(pieces)
+                pieces.append(flat[lo:hi])
+            run_piece[r] = p
+        cuts = np.cumsum(np.bincount(query[starts], minlength=n_scopes))[:-1]
+        return pieces, [s.tolist() for s in np.split(run_piece, cuts)], np.bincount(run_piece, minlength=len(pieces))
+
     def _search_blocks(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence[Optional[DeviceRows]]]):
         """(doc, chunk, dist, count); a scope lists blocks, None = a document without rows.  The one place that touches
         the GPU."""
@@ -153,6 +205,13 @@ class BlockCorpus:
             b = len(queries)
             return np.zeros((b, k), np.int32), np.zeros((b, k), np.int64), np.zeros((b, k)), np.zeros(b, np.int32)
         lists = [[empty if blk is None else blk for blk in s] for s in scopes]
+        if self.share_pieces:
+            cut = self._pieces(lists)
+            if cut is not None and int(cut[2].max()) >= self.min_group:
+                doc, chunk, _row, dist, cnt, _flags = searcher.search_pieces(queries, k, metric, cut[0], cut[1], self.min_group)
+                return doc, chunk, dist, cnt
+            doc, chunk, _row, dist, cnt, _flags = searcher.search(queries, k, metric, lists)  # (nothing common: the default's call)
+            return doc, chunk, dist, cnt
         shared = self._shared_groups(lists) if self.share_scopes else []
         if not shared:  # (the default; or nothing to share: the per-query route's call as it always was)
             doc, chunk, _row, dist, cnt, _flags = searcher.search(queries, k, metric, lists)

@@ -183,6 +183,30 @@ class BlockSearcher:
         nat.check(nat.lib.mir_blocks_search_shared(self._h, nat.ptr(q), b, k, code, len(sizes), nat.ptr(gp), nat.ptr(sp), table, *map(nat.ptr, out)))
         return out
 
+    def search_pieces(self, queries: np.ndarray, k: int, metric, pieces: Sequence[Sequence["DeviceRows"]], scopes: Sequence[Sequence[int]],
+                      min_riders: int) -> Tuple[np.ndarray, ...]:
+        """Scopes that overlap read their common blocks once (csrc/vec_kernels_pieces.h).  ``pieces[p]`` is a list of
+        blocks; query q's scope is the blocks of the pieces ``scopes[q]`` (indices into ``pieces``) concatenated in that
+        order.  A piece named ``min_riders`` times or more in the call is read once per slab of its riders
+        (``search_shared``'s arithmetic), the others per query (``search``'s).  Returns the six arrays of ``search`` over
+        the flattened scopes: doc = the ordinal of the block in the flattened scope."""
+        q = nat.as_f64_queries(queries, self.d)
+        b = q.shape[0]
+        code = nat.METRIC_CODES[Metric(metric).value]
+        if len(scopes) != b:
+            raise ValueError(f"{len(scopes)} scopes for {b} queries")
+        _held, pp, table = _scope_table(pieces)  # (the blocks: alive across the call)
+        rp = np.zeros(b + 1, np.int32)
+        np.cumsum([len(s) for s in scopes], out=rp[1:])
+        riders = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int64).reshape(-1) for s in scopes] + [np.zeros(0, np.int64)]))
+        if len(riders) and (riders.min() < -2**31 or riders.max() >= 2**31):
+            raise ValueError("a piece index does not fit int32")
+        riders = riders.astype(np.int32)
+        out = _result_arrays(b, k)
+        nat.check(nat.lib.mir_blocks_search_pieces(self._h, nat.ptr(q), b, k, code, len(pieces), nat.ptr(pp), table, nat.ptr(rp), nat.ptr(riders),
+                                                   int(min_riders), *map(nat.ptr, out)))
+        return out
+
     def search_shared_device(self, q_ptr: int, b: int, k: int, metric, n_groups: int, group_ptr_ptr: int, scope_ptr_ptr: int, table_ptr: int,
                              out_row_ptr: int, out_dist_ptr: int, out_count_ptr: int, out_flags_ptr: int = 0, out_doc_ptr: int = 0,
                              out_chunk_ptr: int = 0, stream: int = 0) -> None:

@@ -258,6 +258,38 @@ int32_t mir_blocks_search_shared_device(mir_blocks *s, const double *queries_dev
                                         int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags,
                                         void *stream);
 
+/* Pieces search (added within ABI 6): scopes that overlap read their common blocks once (csrc/vec_pieces_layout.h,
+ * csrc/vec_kernels_pieces.h).  A PIECE is a list of blocks: piece p = blocks[piece_ptr[p] .. piece_ptr[p + 1]).  Query q's
+ * scope is a list of pieces, rider_piece[rider_ptr[q] .. rider_ptr[q + 1]), and stands for their blocks concatenated in
+ * that order: the FLATTENED scope.  piece_ptr: int32[n_pieces + 1], rider_ptr: int32[b + 1], both from 0 and non-decreasing.
+ * The answer is what mir_blocks_search gives for the flattened scope: the first out_count[q] = min(k, L_q) scope positions
+ * under (distance ascending, NaN last, position ascending); out_doc = the ordinal of the row's block in the FLATTENED
+ * scope, out_chunk = the block's chunk id of the row, out_row = the row inside its block, out_flags 0.  Any k >= 1; any
+ * output but out_count may be NULL.  A piece may be empty or hold empty blocks (each keeps its ordinal), may be named by no
+ * query, or twice by one query; a query may name no piece (count 0).
+ * Routing: a piece named by min_riders (query, occurrence) pairs of the call or more is read once per slab of its riders
+ * by mir_blocks_search_shared's arithmetic; all other pieces of a query are searched, concatenated in scope order, by
+ * mir_blocks_search's.  min_riders = 1 shares everything, INT32_MAX nothing.
+ * Bits and order: every distance written has mir_blocks_search's bits (the shared route evaluates its k reported
+ * distances once more by that routine).  Candidates are selected inside a piece (inside a query's unshared pieces as a
+ * whole) by that route; the final k are the first k of their union under (reported distance with -0 = +0, NaN last, then
+ * block ordinal, then row), csrc/merge_order.h's order with (ordinal << 32) | row as the row key - which is position order.
+ * With min_riders = INT32_MAX the result equals mir_blocks_search's bit for bit, order included.  With sharing, rows whose
+ * distances tie to ~1e-16 inside a shared piece may be selected by the matrix unit's values at the k-th place of that
+ * piece; reported rows are always in the order of their written distances.  Bit-identical rows tie exactly and go by
+ * (ordinal, row) everywhere.
+ * Returns MIR_ERR_INVALID, before anything is launched and with the outputs untouched, for everything mir_blocks_search
+ * refuses (each block is checked as block j of piece p; a PIECE of 2^32 rows or more is refused whether named or not) and for
+ * n_pieces < 0, a NULL piece_ptr with n_pieces > 0, piece_ptr[0] != 0, a decreasing piece_ptr, a NULL rider_ptr,
+ * rider_ptr[0] != 0, a decreasing rider_ptr, a rider_piece outside [0, n_pieces), min_riders < 1, a query whose flattened
+ * scope holds 2^32 rows or 2^31 blocks or more, and a call whose occurrences (one per ride of a shared piece, one per query
+ * with unshared pieces) times k reach 2^31.  Host form only: there is no _device form. */
+int32_t mir_blocks_search_pieces(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                                 int32_t n_pieces, const int32_t *piece_ptr_host, const mir_rows *const *blocks_host,
+                                 const int32_t *rider_ptr_host, const int32_t *rider_piece_host, int32_t min_riders,
+                                 int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist,
+                                 int32_t *out_count, int32_t *out_flags);
+
 /* Benchmark instrumentation: when enabled, every launch of the scan kernel (the
  * dominant, HBM-streaming kernel) is bracketed by HIP events on the stream it
  * is launched on.  mir_index_profile_read waits for those launches, returns
