@@ -8,7 +8,9 @@ or below 2^-126, one spike 2^20 above the rest - is where the two can part.  `ed
 `route_corpus` builds the smallest corpus that reaches each scan kernel, `error_bound` says how far two correct float64
 evaluations of one formula may lie apart.  tests/test_oracle_query_range.py proves on the CPU that every distance the GPU
 tests look at is either separated from its neighbour by more than twice that bound or bit-equal to it, which is what
-lets tests/test_gpu_query_range.py demand identical ids."""
+lets tests/test_gpu_query_range.py demand identical ids.  The second half does the same for the scoped and block searches
+(tests/test_gpu_scoped_query_range.py): `SCOPED_SHAPES`, `SCOPES`, the oracle over a scope, and `check`, which both GPU
+files judge with."""
 
 from typing import Dict, List, Tuple
 
@@ -259,3 +261,204 @@ def top(metric: str, q: np.ndarray, docs: np.ndarray, m: int) -> Tuple[np.ndarra
         alld = ENUM_TO_METRIC[Metric(metric)](q, docs)
         order = np.argsort(alld, kind="stable")[:m]
         return order, alld[order], error_bound(metric, q, docs, order)
+
+
+# ---- scoped and block searches: the same queries over scopes of row blocks ----------------------------------------------
+# The four scoped entries (mir_index_search_scoped, mir_blocks_search, mir_blocks_search_shared, mir_blocks_search_pieces)
+# answer over a SCOPE: a list of row blocks concatenated in the order listed.  A shape is the smallest that reaches one
+# kernel instance.  The shared search picks its instance from d and k alone (shared_plan in csrc/vec_scoped_layout.h),
+# restated here: with kk = min(k, 64) and dpad = d rounded up to 16, a slab of qs queries takes
+#     qs * (dpad * 8 + 4 * kk * 12) bytes of LDS with the B fragments in it, qs * 4 * kk * 12 without;
+# qs = 64 (QT = 4), else 32 (QT = 2), where that stays within 64 KiB; else qs = 16 (QT = 1) with the fragments in LDS
+# within 144 KiB; else qs = 16 with the fragments read through the caches (QLDS = false).  `shared_instance` is that
+# arithmetic; tests/test_oracle_query_range.py holds the table below against it.  The per-query kernel keeps its query in
+# LDS up to d = 4096 (kScopedLdsDim) and reads a wider one through the caches.
+# The split: the host forms give the shared route P = min(ceil(4 CUs / slabs), ceil(L / 512)) workgroups per slab and the
+# per-query routes P = min(ceil(4 CUs / b), ceil(L / 64)) per query, L the rows of the longest scope of the call: 1 300
+# rows are P = 3 and, for the 35 queries of a mixed batch on 256 CUs, P = 21.
+SCOPED_SIZES = (700, 0, 33, 562, 5)  # 1 300 rows, an empty block, a 5-row block; ZERO_ROW lies in block 0
+# name -> (dtype, d, rows per block)
+SCOPED_SHAPES = {
+    "f32_d64":   ("float32", 64, SCOPED_SIZES),     # k = 10: a 64-query slab (QT = 4); k = 20: QT = 2; k >= 64: QT = 1
+    "f32_d128":  ("float32", 128, SCOPED_SIZES),    # k = 10: QT = 2
+    "f32_d384":  ("float32", 384, SCOPED_SIZES),    # QT = 1, fragments in LDS: the product's shape
+    "f32_d1024": ("float32", 1024, SCOPED_SIZES),   # k = 64 / 100: fragments through the caches (QLDS = false of the shared kernel)
+    "f32_d100":  ("float32", 100, SCOPED_SIZES),    # a tail of d: the last step of 16 columns holds 4 (100 % 4 == 0: vector row loads still)
+    "f32_d102":  ("float32", 102, SCOPED_SIZES),    # d % 4 != 0: exact_metric_wave<T, 16, 8>, scalar row loads, a tail of d
+    "f16_d96":   ("float16", 96, SCOPED_SIZES),     # float16 blocks read directly; the index widens these
+    "f16_d1024": ("float16", 1024, SCOPED_SIZES),   # float16-native on both the index and the blocks
+    "f32_d4100": ("float32", 4100, (400, 0, 33, 162, 5)),  # the query does not fit LDS: scoped_topk_kernel<.., QLDS = false> (per-query routes only)
+}
+PER_QUERY_ONLY = ("f32_d4100",)
+SCOPED_KS = (10, 64, K_MAX)
+SCOPED_EXTRA_KS = {"f32_d64": (20,)}
+# what the table above claims of the shared search: shape -> {k: (queries per slab, fragments in LDS)}
+SHARED_INSTANCES = {
+    "f32_d64": {10: (64, True), 20: (32, True), 64: (16, True), 100: (16, True)},
+    "f32_d128": {10: (32, True)},
+    "f32_d384": {10: (16, True), 64: (16, True), 100: (16, True)},
+    "f32_d1024": {10: (16, True), 64: (16, False), 100: (16, False)},
+    "f16_d1024": {10: (16, True), 64: (16, False), 100: (16, False)},
+}
+SCOPES = {
+    "all": [0, 1, 2, 3, 4],
+    "reversed": [4, 3, 2, 1, 0],
+    "twice": [3, 0, 3],  # a block listed twice: every distance of block 3 is an exact tie across positions
+    "five": [4],         # the count is below k
+    "none": [],
+}
+# the pieces search: pieces are lists of blocks, a scope is a list of pieces
+PIECES = [[0, 1], [2], [3, 4]]
+PIECE_SCOPES = {
+    "all": [0, 1, 2],
+    "backwards": [2, 1, 0],
+    "twice": [2, 0, 2],
+    "short": [1],   # 33 rows: the count is below k = 64
+    "none": [],
+}
+
+
+def shared_instance(d: int, k: int) -> Tuple[int, bool]:
+    """-> (queries per slab, B fragments in LDS) of the shared search at this d and k: the arithmetic restated above."""
+    kk, dpad = min(k, 64), (d + 15) // 16 * 16
+    lists = 4 * kk * 12
+    for qs in (64, 32):
+        if qs * (dpad * 8 + lists) <= 64 * 1024:
+            return qs, True
+    return 16, 16 * (dpad * 8 + lists) <= 144 * 1024
+
+
+def flat_scope(piece_scope: List[int]) -> List[int]:
+    return [j for p in piece_scope for j in PIECES[p]]
+
+
+def scoped_corpus(name: str) -> Tuple[List[np.ndarray], np.ndarray]:
+    """-> (the blocks in their own dtype, the 12 ordinary queries).  The rows are made as `route_corpus` makes them - unit
+    norm x (1 +- NORM_SPREAD), cast, the zero planted - and cut into the shape's blocks."""
+    dtype, d, sizes = SCOPED_SHAPES[name]
+    n = sum(sizes)
+    rng = np.random.default_rng(4000 + sorted(SCOPED_SHAPES).index(name))
+    docs = rng.standard_normal((n, d), dtype=np.float32)
+    docs *= ((1.0 + rng.uniform(-NORM_SPREAD, NORM_SPREAD, n)) / np.linalg.norm(docs.astype(np.float64), axis=1)).astype(np.float32)[:, None]
+    docs = plant_zero(docs.astype(dtype))
+    qs = rng.standard_normal((N_ORDINARY, d))
+    qs /= np.linalg.norm(qs, axis=1, keepdims=True)
+    cuts = np.cumsum((0,) + tuple(sizes))
+    assert ZERO_ROW < sizes[0]
+    return [docs[a:b] for a, b in zip(cuts[:-1], cuts[1:])], qs
+
+
+def scope_matrix(parts: List[np.ndarray], scope: List[int]) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (the scope's rows in scope order as the oracle sees them (`oracle_rows`), int64 [L, 2]: the (ordinal inside the
+    scope, row inside the block) of every scope position)."""
+    d = parts[0].shape[1]
+    rows = [oracle_rows(parts[j]) for j in scope] + [np.zeros((0, d), np.float32)]
+    where = [np.stack([np.full(len(parts[j]), o, np.int64), np.arange(len(parts[j]), dtype=np.int64)], axis=1) for o, j in enumerate(scope)]
+    return np.concatenate(rows), np.concatenate(where + [np.zeros((0, 2), np.int64)])
+
+
+def scope_starts(parts: List[np.ndarray], scope: List[int]) -> np.ndarray:
+    """The scope position of the first row of every listed block: a result (ordinal, row) sits at starts[ordinal] + row."""
+    lengths = np.array([len(parts[j]) for j in scope], np.int64)
+    return np.cumsum(lengths) - lengths
+
+
+def scoped_queries(name: str, parts: List[np.ndarray]) -> Dict[str, np.ndarray]:
+    """The edge queries of a shape, drawn on the matrix of the scope `all`."""
+    _, d, _ = SCOPED_SHAPES[name]
+    return edge_queries(np.random.default_rng(5000 + sorted(SCOPED_SHAPES).index(name)), d, scope_matrix(parts, SCOPES["all"])[0])
+
+
+def scope_distances(metric: str, q: np.ndarray, blocks: Dict[int, np.ndarray], scope: List[int]) -> np.ndarray:
+    """The oracle's distances at every scope position, each listed block evaluated on its own as the reference does
+    (`find_in_doc`: one metric call per document, embeddings_index.py:51-60 upstream), an empty block skipped.
+
+    Per block, not one call on the concatenated matrix, because the scopes list a block twice: BLAS cuts a matrix-vector
+    product into row ranges per thread and sums a range's last rows by another routine, so ONE row's dot product differs in
+    its last bits with its position in the matrix and with the number of threads (measured: 2 to 28 of a 562-row block's
+    products differ between two positions of one matrix, d = 64 .. 4100).  Both occurrences of a block read here are one
+    call's arguments twice over, so they tie bit for bit on any machine - as they do in the reference and on the device."""
+    with np.errstate(all="ignore"):
+        per_block = {j: ENUM_TO_METRIC[Metric(metric)](q, blocks[j]) for j in set(scope) if len(blocks[j])}
+    return np.concatenate([per_block[j] for j in scope if len(blocks[j])] + [np.zeros(0)])
+
+
+def scope_top(metric: str, q: np.ndarray, parts: List[np.ndarray], scope: List[int], m: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`top` over a scope: the first m scope positions in the oracle's stable order, their distances, their error bounds."""
+    ref, _ = scope_matrix(parts, scope)
+    alld = scope_distances(metric, q, {j: oracle_rows(parts[j]) for j in set(scope)}, scope)
+    order = np.argsort(alld, kind="stable")[:m]
+    with np.errstate(all="ignore"):
+        return order, alld[order], error_bound(metric, q, ref, order)
+
+
+# ---- judging a search's answer against the oracle's -----------------------------------------------------------------------
+TOP = 128  # oracle rows kept per query on the large corpora (k <= 100 and room for a cosine swap)
+
+
+class Oracle:
+    """The oracle's answers for one corpus, computed once per (metric, query) and left unchanged."""
+
+    def __init__(self, ref):
+        self.ref = ref
+        self.keep = len(ref) if len(ref) <= 5000 else TOP
+        self.cache = {}
+
+    def top(self, metric, name, q):
+        key = (metric, name)
+        if key not in self.cache:
+            with np.errstate(all="ignore"):
+                alld = ENUM_TO_METRIC[Metric(metric)](q, self.ref)
+                order = np.argsort(alld, kind="stable")[: self.keep]
+            self.cache[key] = (order, alld[order], {int(r): float(v) for r, v in zip(order, alld[order])})
+        return self.cache[key]
+
+
+class ScopeOracle(Oracle):
+    """The oracle's answers over one scope of row blocks: `ref` is the scope's matrix (a "row" is a scope position), the
+    distances are `scope_distances`' - each block evaluated on its own, so a block listed twice ties exactly."""
+
+    def __init__(self, parts, scope):
+        super().__init__(scope_matrix(parts, scope)[0])
+        self.scope = list(scope)
+        self.blocks = {j: oracle_rows(parts[j]) for j in set(scope)}
+        assert self.keep == len(self.ref)
+
+    def top(self, metric, name, q):
+        key = (metric, name)
+        if key not in self.cache:
+            alld = scope_distances(metric, q, self.blocks, self.scope)
+            order = np.argsort(alld, kind="stable")
+            self.cache[key] = (order, alld[order], {int(r): float(v) for r, v in zip(order, alld[order])})
+        return self.cache[key]
+
+
+def same_value(got, want, bound):
+    """NaN equals NaN, an infinity the infinity of its sign, a number the number within the bound."""
+    with np.errstate(all="ignore"):
+        return (got == want) | (np.isnan(got) & np.isnan(want)) | (np.abs(got - want) <= bound)
+
+
+def check(oracle, metric, name, q, got, k, msg):
+    doc, chunk, row, dist, cnt, flag = got
+    order, _, value = oracle.top(metric, name, q)
+    want = order[:k]
+    assert cnt == min(k, len(oracle.ref)) == len(want), f"{msg}: count {cnt}"
+    g = row[:cnt]
+    assert len(set(g.tolist())) == cnt, f"{msg}: a row appears twice: {g}"
+    assert all(int(r) in value for r in g), f"{msg}: rows far from the oracle's first {len(order)}: {g} vs {want}"
+    gv = np.array([value[int(r)] for r in g])
+    if metric != "cosine_sim":
+        np.testing.assert_array_equal(g, want, err_msg=f"{msg} flag={flag}")
+    else:
+        noise = error_bound(metric, q, oracle.ref, want, ids=True)
+        wv = np.array([value[int(r)] for r in want])
+        with np.errstate(all="ignore"):
+            swap = (g == want) | (np.abs(gv - wv) <= noise)  # (NaN against NaN is no swap: ties come in row order)
+        assert swap.all(), f"{msg} flag={flag}: ranks {np.flatnonzero(~swap)}: {g[~swap]} vs {want[~swap]}"
+    ok = same_value(dist[:cnt], gv, error_bound(metric, q, oracle.ref, g))
+    assert ok.all(), f"{msg} flag={flag}: distances at ranks {np.flatnonzero(~ok)}: {dist[:cnt][~ok]} vs {gv[~ok]}"
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.int64) if a.dtype == np.float64 else a

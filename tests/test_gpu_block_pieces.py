@@ -255,6 +255,7 @@ def test_special_values_in_a_shared_and_a_solo_piece(amd, metric):
 # ---------------------------------------------------------------- 4. P > 1
 
 P_SEED = 43
+P_ROUNDS_SEED = 106  # the first seed from 100 on whose 20 queries have no near-tie among their first 131 rows under any metric
 
 
 def planted_case(seed):
@@ -288,6 +289,21 @@ def test_a_common_piece_split_over_many_workgroups(amd, metric):
         common_at = 3 if i % 2 else 0
         from_common = (doc[i] >= common_at) & (doc[i] < common_at + 4)
         assert from_common.sum() == 4 and set(doc[i]) == set(range(7))
+
+
+@pytest.mark.parametrize("k", [70, 130])
+@pytest.mark.parametrize("metric", METRICS)
+def test_rounds_over_a_common_piece_split_over_many_workgroups(amd, metric, k):
+    """The same case beyond one round: the common piece's shares and the rounds behind the bound cursor at once"""
+    parts, chunks, qs, piece_lists, scopes = planted_case(P_ROUNDS_SEED)
+    blocks = [amd.ei.DeviceRows.from_host(p, c) for p, c in zip(parts, chunks)]
+    docs = oracle_docs(amd.oi, parts, chunks)
+    doc, chunk, row, dist, cnt, _ = check_case(amd, amd.ei.BlockSearcher(64), metric, k, qs, blocks, docs, piece_lists, scopes, f"{metric} k={k}")
+    assert (cnt == k).all()
+    for i in range(len(qs)):  # the seven planted rows first, from the common piece and the private blocks
+        common_at = 3 if i % 2 else 0
+        from_common = (doc[i, :7] >= common_at) & (doc[i, :7] < common_at + 4)
+        assert from_common.sum() == 4 and set(doc[i, :7]) == set(range(7))
 
 
 # ---------------------------------------------------------------- 5. sizes of the merge

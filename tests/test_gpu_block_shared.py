@@ -245,6 +245,28 @@ def test_one_block_split_over_many_workgroups(amd, one_big_block, metric, k):
         assert set(row[i, : min(k, 24)]) <= set(planted) and (k < 24 or set(row[i, :24]) == set(planted))
 
 
+@pytest.mark.parametrize("k", [65, 130, 200])
+@pytest.mark.parametrize("metric", METRICS)
+def test_rounds_over_a_block_split_over_many_workgroups(amd, one_big_block, metric, k):
+    """k > 64 AND P > 1: every round's partial lists meet in HBM and are merged by the last workgroup to arrive, the rounds
+    behind the first select behind the bound cursor, and the slab's arrival counter serves every round in turn."""
+    blocks, docs, qs, planted, searcher = one_big_block
+    got = run_groups(searcher, qs, k, metric, blocks, [[0]], [len(qs)])
+    doc, chunk, row, dist, cnt, _ = got
+    assert (cnt == k).all() and (doc == 0).all()
+    check_groups(amd, metric, k, qs, docs, [[0]], [len(qs)], got, f"{metric} k={k}")
+    np.testing.assert_array_equal(row, 19999 - chunk)
+    for i in range(len(qs)):  # the first 24 results are the planted rows
+        assert set(row[i, :24]) == set(planted)
+    if metric != "cosine_sim":
+        per_query = searcher.search(qs, k, metric, [[blocks[0]]] * len(qs))
+        assert_routes_agree(got, per_query, metric, f"{metric} k={k}")
+    # a second call right after the first: the arrival counters were left at zero, the same bits come back
+    again = run_groups(searcher, qs, k, metric, blocks, [[0]], [len(qs)])
+    for a, b, what in zip(got, again, ("doc", "chunk", "row", "dist", "count", "flags")):
+        np.testing.assert_array_equal(a.view(np.uint64) if what == "dist" else a, b.view(np.uint64) if what == "dist" else b, err_msg=f"{metric} k={k} second call: {what}")
+
+
 # ---------------------------------------------------------------- 5. more queries than a slab, and than 256
 
 @pytest.mark.parametrize("metric", ["sqeuclidean_dist", "cosine_sim"])

@@ -21,11 +21,11 @@ import pytest
 from oracle import embeddings_index as oi
 from oracle import embeddings_metrics as om
 from oracle import query_range as qr
+from oracle.query_range import Oracle, bits, check, same_value  # (shared with tests/test_gpu_scoped_query_range.py)
 
 pytestmark = pytest.mark.gpu
 
 METRICS = qr.METRICS
-TOP = 128  # oracle rows kept per query on the large corpora (k <= 100 and room for a cosine swap)
 
 
 @pytest.fixture(scope="module")
@@ -41,55 +41,6 @@ def compute_units() -> int:
     import torch
 
     return int(torch.cuda.get_device_properties(0).multi_processor_count)
-
-
-class Oracle:
-    """The oracle's answers for one corpus, computed once per (metric, query) and left unchanged."""
-
-    def __init__(self, ref):
-        self.ref = ref
-        self.keep = len(ref) if len(ref) <= 5000 else TOP
-        self.cache = {}
-
-    def top(self, metric, name, q):
-        key = (metric, name)
-        if key not in self.cache:
-            with np.errstate(all="ignore"):
-                alld = om.ENUM_TO_METRIC[om.Metric(metric)](q, self.ref)
-                order = np.argsort(alld, kind="stable")[: self.keep]
-            self.cache[key] = (order, alld[order], {int(r): float(v) for r, v in zip(order, alld[order])})
-        return self.cache[key]
-
-
-def same_value(got, want, bound):
-    """NaN equals NaN, an infinity the infinity of its sign, a number the number within the bound."""
-    with np.errstate(all="ignore"):
-        return (got == want) | (np.isnan(got) & np.isnan(want)) | (np.abs(got - want) <= bound)
-
-
-def check(oracle, metric, name, q, got, k, msg):
-    doc, chunk, row, dist, cnt, flag = got
-    order, _, value = oracle.top(metric, name, q)
-    want = order[:k]
-    assert cnt == min(k, len(oracle.ref)) == len(want), f"{msg}: count {cnt}"
-    g = row[:cnt]
-    assert len(set(g.tolist())) == cnt, f"{msg}: a row appears twice: {g}"
-    assert all(int(r) in value for r in g), f"{msg}: rows far from the oracle's first {len(order)}: {g} vs {want}"
-    gv = np.array([value[int(r)] for r in g])
-    if metric != "cosine_sim":
-        np.testing.assert_array_equal(g, want, err_msg=f"{msg} flag={flag}")
-    else:
-        noise = qr.error_bound(metric, q, oracle.ref, want, ids=True)
-        wv = np.array([value[int(r)] for r in want])
-        with np.errstate(all="ignore"):
-            swap = (g == want) | (np.abs(gv - wv) <= noise)  # (NaN against NaN is no swap: ties come in row order)
-        assert swap.all(), f"{msg} flag={flag}: ranks {np.flatnonzero(~swap)}: {g[~swap]} vs {want[~swap]}"
-    ok = same_value(dist[:cnt], gv, qr.error_bound(metric, q, oracle.ref, g))
-    assert ok.all(), f"{msg} flag={flag}: distances at ranks {np.flatnonzero(~ok)}: {dist[:cnt][~ok]} vs {gv[~ok]}"
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64) if a.dtype == np.float64 else a
 
 
 class Route:

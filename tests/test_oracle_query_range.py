@@ -8,7 +8,11 @@ distances is either separated from the next by more than twice the formula's for
 or bit-equal to it (an exact tie, NaN = NaN, inf = inf of one sign: the absorbed regime, where squared L2 collapses to the
 query's square sum or to the float32 doc_sq, and the order is the row order whoever computes it).  No case may fall in
 between.  A corpus or a scale that misses the condition is changed (2^31 .. 2^59 are absent for that reason); the condition
-stays."""
+stays.
+
+The same holds for tests/test_gpu_scoped_query_range.py: the scoped and block searches answer over a scope of row blocks,
+and every (shape, scope, query) of that file is proven here on the scope's own distances - a block listed twice ties
+exactly with itself (`scope_distances`), everything else is separated."""
 
 import numpy as np
 import pytest
@@ -26,8 +30,9 @@ def route(request):
     return request.param, docs, ref, ordinary, qr.route_queries(request.param, docs)
 
 
-def assert_strict_or_tied(metric, q, ref, m, msg):
-    order, dist, bound = qr.top(metric, q, ref, m)
+def assert_strict_or_tied(metric, q, ref, m, msg, scope=None):
+    """`ref`: a matrix; with `scope`: the blocks that scope lists, judged on its positions"""
+    order, dist, bound = qr.top(metric, q, ref, m) if scope is None else qr.scope_top(metric, q, ref, scope, m)
     ok = qr.separated_or_tied(dist, bound)
     bad = np.flatnonzero(~ok)
     assert len(bad) == 0, (f"{msg}: ranks {bad[:5]} are neither separated nor tied: distances {dist[bad[:5]]} / {dist[bad[:5] + 1]}, "
@@ -101,6 +106,91 @@ def test_the_orders_the_issue_describes(route):
     assert np.array_equal(order[: len(neg)], neg) and np.isposinf(dist[: len(neg)]).all() and np.isnan(dist[len(neg) :]).all()
     order, dist, _ = qr.top("cosine_sim", q, ref, 10)
     assert np.array_equal(order, np.arange(10)) and np.isnan(dist).all()
+
+
+def test_the_orders_the_issue_describes_over_a_scope(scoped):
+    """The same orders on the `all` matrix of the product's shape, and on `twice`: a tie run spans both occurrences of block 3"""
+    name, parts, ordinary, edges = scoped("f32_d384")
+    ref, where = qr.scope_matrix(parts, qr.SCOPES["all"])
+    test_the_orders_the_issue_describes((name, None, ref, ordinary, edges))
+    assert len(ref) == 1300 and tuple(where[qr.ZERO_ROW]) == (0, qr.ZERO_ROW) and tuple(where[-1]) == (4, 4)
+    twice = qr.SCOPES["twice"]
+    ref2, where2 = qr.scope_matrix(parts, twice)
+    col = ref2[:, qr.INF_COLUMN]
+    order, dist, _ = qr.scope_top("inner_product", edges["nonfinite:+inf"], parts, twice, len(ref2))
+    pos = np.flatnonzero(col > 0)
+    assert np.array_equal(order[: len(pos)], pos) and np.isneginf(dist[: len(pos)]).all()
+    assert {0, 2} <= set(where2[pos, 0])  # the -inf run holds rows of both occurrences of block 3, in position order
+    neg = np.flatnonzero(col < 0)
+    assert np.array_equal(order[len(pos) : len(pos) + len(neg)], neg) and np.isposinf(dist[len(pos) : len(pos) + len(neg)]).all()
+    assert np.isnan(dist[len(pos) + len(neg) :]).all() and len(parts[3]) + qr.ZERO_ROW in order[len(pos) + len(neg) :]
+
+
+# ---- the scoped and block searches (tests/test_gpu_scoped_query_range.py) ----------------------------------------------
+@pytest.fixture(scope="module")
+def scoped():
+    made = {}
+
+    def get(name):
+        if name not in made:
+            parts, ordinary = qr.scoped_corpus(name)
+            made[name] = (name, parts, ordinary, qr.scoped_queries(name, parts))
+        return made[name]
+
+    return get
+
+
+PROVEN_SCOPES = [("scope", n, s) for n, s in qr.SCOPES.items() if s] + [("pieces", n, qr.flat_scope(s)) for n, s in qr.PIECE_SCOPES.items() if s]
+
+
+def test_scoped_shapes_are_what_the_table_says(scoped):
+    assert list(qr.SCOPES) == ["all", "reversed", "twice", "five", "none"] and [n for _, n, _ in PROVEN_SCOPES[:4]] == ["all", "reversed", "twice", "five"]
+    assert qr.flat_scope(qr.PIECE_SCOPES["all"]) == qr.SCOPES["all"]
+    for name, (dtype, d, sizes) in qr.SCOPED_SHAPES.items():
+        _, parts, ordinary, edges = scoped(name)
+        assert [len(p) for p in parts] == list(sizes) and all(p.dtype == np.dtype(dtype) and p.shape[1] == d for p in parts)
+        assert sizes[1] == 0 and sizes[4] == 5 and sizes[0] > qr.ZERO_ROW
+        rows = sum(sizes)
+        assert -(-rows // 512) > 1 and -(-rows // 64) > 1     # P > 1 on the shared and on the per-query routes
+        ref, where = qr.scope_matrix(parts, qr.SCOPES["all"])
+        assert ref.dtype == np.float32 and ref.shape == (rows, d) and qr.inf_column(ref) == qr.INF_COLUMN
+        norms = np.linalg.norm(ref.astype(np.float64), axis=1)
+        assert np.abs(norms - 1).max() < (2e-3 if dtype == "float16" else 2.5e-4)
+        starts = qr.scope_starts(parts, qr.SCOPES["twice"])
+        assert list(starts) == [0, sizes[3], sizes[3] + sizes[0]]
+        ref2, where2 = qr.scope_matrix(parts, qr.SCOPES["twice"])
+        assert np.array_equal(starts[where2[:, 0]] + where2[:, 1], np.arange(len(ref2)))
+        assert np.array_equal(ref2[: sizes[3]], ref2[sizes[3] + sizes[0] :])
+        assert len(qr.scope_matrix(parts, [])[0]) == 0
+        assert len(edges) == 23 and len(qr.mixed_batch(ordinary, edges)[0]) == 35
+    assert qr.SCOPED_SHAPES["f32_d4100"][1] > 4096   # beyond kScopedLdsDim
+    assert qr.SCOPED_SHAPES["f32_d100"][1] % 16 and qr.SCOPED_SHAPES["f32_d102"][1] % 4
+    for name, by_k in qr.SHARED_INSTANCES.items():  # the instances of the shared kernel the table names
+        for k, want in by_k.items():
+            assert qr.shared_instance(qr.SCOPED_SHAPES[name][1], k) == want, (name, k)
+
+
+@pytest.mark.parametrize("metric", NON_COSINE)
+@pytest.mark.parametrize("name", list(qr.SCOPED_SHAPES))
+def test_scoped_first_k_plus_one_distances_are_separated_or_tied(scoped, name, metric):
+    """Every shape, every scope the GPU tests search (the pieces search's flattened ones too), every edge and ordinary
+    query: none is left out."""
+    _, parts, ordinary, edges = scoped(name)
+    cases = 0
+    for kind, sn, scope in PROVEN_SCOPES:
+        m = min(qr.K_MAX + 1, sum(len(parts[j]) for j in scope))
+        for nm, q in list(edges.items()) + [(f"ord:{i}", q) for i, q in enumerate(ordinary)]:
+            assert_strict_or_tied(metric, q, parts, m, f"{name} {kind} {sn} {metric} {nm}", scope=scope)
+            cases += 1
+    assert cases == len(PROVEN_SCOPES) * (23 + qr.N_ORDINARY)
+
+
+@pytest.mark.parametrize("name", ["f32_d384", "f16_d96"])
+def test_scoped_whole_orders_are_separated_or_tied(scoped, name):
+    """k = L under inner_product with one +inf component: runs of -inf, +inf and NaN, whole (the zero behind an infinity)"""
+    _, parts, ordinary, edges = scoped(name)
+    for scope in (qr.SCOPES["all"], qr.SCOPES["twice"], qr.flat_scope(qr.PIECE_SCOPES["twice"])):
+        assert_strict_or_tied("inner_product", edges["nonfinite:+inf"], parts, sum(len(parts[j]) for j in scope), f"{name} {scope}", scope=scope)
 
 
 def test_cosine_clamp_shrinks_the_distances(route):
