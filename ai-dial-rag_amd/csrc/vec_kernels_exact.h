@@ -15,7 +15,7 @@
 //     per thread) before the current one is computed on.
 //   * a wave keeps its 8 queries' best `kk` <= 64 entries in registers, one entry per lane, sorted (exact_wave_insert);
 //     a block of 64 rows costs one vote per query unless a row actually enters a list.
-//   * per pass the workgroups' lists meet in HBM and the last workgroup to arrive merges them (as round 2's kernel).
+//   * per pass the workgroups' lists meet in HBM and the last workgroup to arrive merges them (vec_topk_lists.h).
 // float64 arithmetic: the reference's formulas (embeddings_metrics.py:14-50) with one fused multiply-add per element,
 // summed in ascending column order.  (exact_metric_wave sums lane-strided partials and a tree; both are the
 // reference's float64 formula to within its own rounding - numpy's BLAS order is not defined either - and every row
@@ -24,6 +24,7 @@
 // Device-gated: reads the number of flagged queries and exits at once when it is 0.
 #pragma once
 #include "vec_kernels.h"
+#include "vec_topk_lists.h"
 
 namespace mir {
 
@@ -73,7 +74,7 @@ struct ExactBatchArgs {
     int k;
     int round;
     int list_stride;           // min(k, kExactRound)
-    uint64_t *part;            // [b][grid][list_stride][2]: {dist bits, valid << 32 | row}
+    uint64_t *part;            // [b][grid][list_stride][2]: the workgroups' lists (vec_topk_lists.h), key = row
     uint32_t *arrive;          // [b], zero between launches
     double *bound_dist;        // [b] last result of the previous round
     uint32_t *bound_row;       // [b]
@@ -88,28 +89,102 @@ struct ExactBatchArgs {
     int32_t *out_flags;
 };
 
-// rank of this thread's entry among the workgroup's wave lists (WAVES lists of <= 64, sorted); -1: no entry
-template <int WAVES>
-__device__ __forceinline__ int xb_block_rank(double my_d, uint32_t my_r, int cnt, double *s_d, uint32_t *s_r, int *s_cnt, int tid,
-                                             int *total_out) {
-    const int lane = tid & 63, wave = tid >> 6;
-    __syncthreads();
-    s_d[tid] = my_d;
-    s_r[tid] = my_r;
-    if (lane == 0) s_cnt[wave] = cnt;
-    __syncthreads();
-    int total = 0, rank = 0;
-    const bool valid = lane < cnt;
-    for (int w = 0; w < WAVES; ++w) {
-        const int c = s_cnt[w];
-        total += c;
-        if (valid)
-            for (int l = 0; l < c; ++l) rank += dist_before(s_d[w * 64 + l], s_r[w * 64 + l], my_d, my_r) ? 1 : 0;
+// ---------------------------------------------------------------- the serial pass (one or two flagged queries)
+// The filter scan + completeness check PROVES its result for almost every query; the rest - more than klist - k rows
+// inside the scan's error band at the cut (near-duplicate chunks, boiler-plate pages), exact ties across the cut - and
+// every query whose k exceeds the scan's candidate lists take the exact pass, with no assumption on the data.
+//
+// grid = #CUs x 1024 threads; the flagged queries one after the other.  A wave walks rows wave, wave + #waves, ... in
+// ascending order, computes the reference formula for each (exact_metric_wave) and keeps its best `kk` <= 64 in
+// registers (exact_wave_insert).  Per workgroup the 16 wave lists are ranked in LDS and published; the last workgroup
+// to arrive merges the G lists and writes the query's results (vec_topk_lists.h).  k > 64 runs as ceil(k / 64) rounds;
+// round r only admits rows strictly after the last result of round r - 1 in the (distance, row) order.
+constexpr int kExactThreads = 1024;
+constexpr int kExactWaves = kExactThreads / 64;
+
+struct ExactArgs {
+    const float *docs;         // f32 [n][d], or null with
+    const _Float16 *docs16;    // f16 [n][d]
+    const float *doc_sq;
+    uint32_t n_rows;
+    int d;
+    int metric;
+    const double *q;           // [b][d]
+    const double *q_sq;
+    const double *q_norm;
+    const int32_t *nflag;
+    const int32_t *flagged;
+    int k;
+    int round;
+    int list_stride;           // min(k, kExactRound)
+    uint64_t *part;            // [b][grid][list_stride][2]: the workgroups' lists (vec_topk_lists.h), key = row
+    uint32_t *arrive;          // [b], zero between launches
+    double *bound_dist;        // [b] last result of the previous round
+    uint32_t *bound_row;       // [b]
+    const int64_t *chunk_ids;
+    const int32_t *doc_ids;
+    int64_t row_offset;
+    int32_t *out_doc;
+    int64_t *out_chunk;
+    int64_t *out_row;
+    double *out_dist;
+    int32_t *out_count;
+    int32_t *out_flags;
+};
+
+__device__ __forceinline__ void exact_topk_serial(const ExactArgs &a, const int nf) {
+    __shared__ double s_d[kExactThreads];
+    __shared__ uint32_t s_r[kExactThreads];
+    __shared__ int s_cnt[kExactWaves];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kk = min(kExactRound, a.k - kExactRound * a.round);
+    const uint32_t G = gridDim.x;
+    for (int f = 0; f < nf; ++f) {
+        const int qi = a.flagged[f];
+        const double *q = a.q + (size_t)qi * a.d;
+        const double q_sq = a.q_sq[qi], q_norm = a.q_norm[qi];
+        const bool bounded = a.round > 0;
+        const double b_d = bounded ? a.bound_dist[qi] : 0.0;
+        const uint32_t b_r = bounded ? a.bound_row[qi] : 0u;
+        double my_d = 0.0;
+        uint32_t my_r = 0;
+        int cnt = 0;
+        for (uint32_t row = blockIdx.x * kExactWaves + wave; row < a.n_rows; row += G * kExactWaves) {
+            double rv;
+            const double dist = a.docs16 ? exact_metric_wave(a.docs16 + (size_t)row * a.d, q, a.d, a.metric, a.doc_sq[row], q_sq, q_norm, lane, &rv)
+                                         : exact_metric_wave(a.docs + (size_t)row * a.d, q, a.d, a.metric, a.doc_sq[row], q_sq, q_norm, lane, &rv);
+            if (bounded && !dist_before(b_d, b_r, dist, row)) continue;
+            exact_wave_insert(dist, row, kk, lane, my_d, my_r, cnt);
+        }
+        int total;
+        int rank = block_rank<kExactWaves>(my_d, my_r, cnt, s_d, s_r, s_cnt, tid, &total);
+        uint64_t *lists = a.part + (size_t)f * G * a.list_stride * 2;
+        lists_publish(lists + (size_t)blockIdx.x * a.list_stride * 2, rank, total, kk, tid, my_d, my_r);
+        if (!lists_arrive(a.arrive + f, 1, G, &s_last, tid)) continue;  // uniform per workgroup
+        lists_merge<kExactWaves>(lists, G, a.list_stride, kk, wave, lane, my_d, my_r, cnt);
+        rank = block_rank<kExactWaves>(my_d, my_r, cnt, s_d, s_r, s_cnt, tid, &total);
+        const int kout = total < kk ? total : kk;
+        if (rank >= 0 && rank < kout) {
+            const size_t o = (size_t)qi * a.k + (size_t)kExactRound * a.round + rank;
+            if (a.out_row) a.out_row[o] = a.row_offset + (int64_t)my_r;
+            if (a.out_dist) a.out_dist[o] = my_d;
+            if (a.out_doc) a.out_doc[o] = a.doc_ids ? a.doc_ids[my_r] : 0;
+            if (a.out_chunk) a.out_chunk[o] = a.chunk_ids ? a.chunk_ids[my_r] : (int64_t)my_r;
+            if (rank == kout - 1) {
+                a.bound_dist[qi] = my_d;
+                a.bound_row[qi] = my_r;
+            }
+        }
+        lists_rearm(a.arrive + f, tid);
+        if (tid == 0 && a.round == 0) {
+            if (a.out_count) a.out_count[qi] = (int)((uint32_t)a.k < a.n_rows ? (uint32_t)a.k : a.n_rows);
+            if (a.out_flags) a.out_flags[qi] = MIR_FLAG_EXACT_PASS;
+        }
     }
-    *total_out = total;
-    return valid ? rank : -1;
 }
 
+// ---------------------------------------------------------------- the batched pass
 template <typename T, bool COS>
 __device__ __forceinline__ void exact_topk_batch(const ExactBatchArgs &a, const int nf) {
     __shared__ float tile[kXbRows * kXbStride];  // 49 408 B
@@ -265,39 +340,20 @@ __device__ __forceinline__ void exact_topk_batch(const ExactBatchArgs &a, const 
             for (int i = 0; i < kXbQW; ++i) {
                 if (!live[i]) continue;
                 const int f = p0 + wave * kXbQW + i;
-                uint64_t *out = a.part + ((size_t)f * G + blockIdx.x) * a.list_stride * 2;
-                if (lane < kk) {
-                    out[2 * lane] = lane < cnt[i] ? (uint64_t)__double_as_longlong(my_d[i]) : 0;
-                    out[2 * lane + 1] = lane < cnt[i] ? ((1ull << 32) | my_r[i]) : 0;
-                }
+                lists_publish_wave(a.part + ((size_t)f * G + blockIdx.x) * a.list_stride * 2, cnt[i], kk, lane, my_d[i], my_r[i]);
             }
         }
-        __threadfence();
-        __syncthreads();
-        if (tid < np) s_last[tid] = atomicAdd(&a.arrive[p0 + tid], 1u) == G - 1;
-        __syncthreads();
+        if (!lists_arrive(a.arrive + p0, np, G, s_last, tid)) continue;  // uniform per workgroup
         for (int c = 0; c < np; ++c) {
             if (!s_last[c]) continue;  // uniform per workgroup
-            __threadfence();
             const int f = p0 + c;
             const int qi = a.flagged[f];
-            double md = 0.0;
-            uint32_t mr = 0;
-            int mc = 0;
-            for (uint32_t g = wave; g < G; g += kXbWaves) {
-                const uint64_t *l = a.part + ((size_t)f * G + g) * a.list_stride * 2;
-                for (int j = 0; j < kk; ++j) {
-                    const uint64_t w1 = __hip_atomic_load(l + 2 * j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (!(w1 >> 32)) break;
-                    const double dj = __longlong_as_double((long long)__hip_atomic_load(l + 2 * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                    const double worst_d = __shfl(md, kk - 1, 64);
-                    const uint32_t worst_r = __shfl(mr, kk - 1, 64);
-                    if (mc == kk && !dist_before(dj, (uint32_t)w1, worst_d, worst_r)) break;  // the rest of this list is worse still
-                    exact_wave_insert(dj, (uint32_t)w1, kk, lane, md, mr, mc);
-                }
-            }
+            double md;
+            uint32_t mr;
+            int mc;
+            lists_merge<kXbWaves>(a.part + (size_t)f * G * a.list_stride * 2, G, a.list_stride, kk, wave, lane, md, mr, mc);
             int total;
-            const int rank = xb_block_rank<kXbWaves>(md, mr, mc, s_d, s_r, s_cnt, tid, &total);
+            const int rank = block_rank<kXbWaves>(md, mr, mc, s_d, s_r, s_cnt, tid, &total);
             const int kout = total < kk ? total : kk;
             if (rank >= 0 && rank < kout) {
                 const size_t o = (size_t)qi * a.k + (size_t)kExactRound * a.round + rank;
@@ -310,12 +366,10 @@ __device__ __forceinline__ void exact_topk_batch(const ExactBatchArgs &a, const 
                     a.bound_row[qi] = mr;
                 }
             }
-            if (tid == 0) {
-                a.arrive[f] = 0;
-                if (a.round == 0) {
-                    if (a.out_count) a.out_count[qi] = (int)((uint32_t)a.k < a.n_rows ? (uint32_t)a.k : a.n_rows);
-                    if (a.out_flags) a.out_flags[qi] = MIR_FLAG_EXACT_PASS;
-                }
+            lists_rearm(a.arrive + f, tid);
+            if (tid == 0 && a.round == 0) {
+                if (a.out_count) a.out_count[qi] = (int)((uint32_t)a.k < a.n_rows ? (uint32_t)a.k : a.n_rows);
+                if (a.out_flags) a.out_flags[qi] = MIR_FLAG_EXACT_PASS;
             }
             __syncthreads();
         }

@@ -11,10 +11,10 @@
 //     wave at a time, 16-byte loads (sieve_metric_g16; d % 4 != 0: exact_metric_wave<T, 16, 8>).  The query sits in LDS
 //     as float64 (kScopedLdsDim columns at the most; a wider query is read through the caches).
 //   * Selection: the exact pass's pieces with the scope position as the tie-break key: a wave keeps its best <= 64
-//     entries in registers (exact_wave_insert), the workgroup's 4 lists are ranked in LDS (xb_block_rank), k > 64 runs
+//     entries in registers (exact_wave_insert), the workgroup's 4 lists are ranked in LDS (block_rank), k > 64 runs
 //     in rounds of 64 behind a (distance, position) cursor.
 //   * Work split: grid (P, b).  Workgroup (p, q) takes the p-th share of q's scope positions; P > 1: the partial lists meet
-//     in HBM and the last workgroup of the query to arrive (device-scope fence + counter) merges them.
+//     in HBM and the last workgroup of the query to arrive merges them (vec_topk_lists.h).
 //   * The segment list is walked kScopedSegs segments at a time (a block-wide prefix sum of the clamped lengths in LDS; a
 //     position finds its segment by binary search there): any number of segments, nothing capped at an LDS size.
 //   * Safety: begin / end are clamped into [0, n] and end < begin is empty, so a row index is always begin + offset with
@@ -30,6 +30,7 @@
 #include "vec_kernels.h"
 #include "vec_kernels_sieve.h"
 #include "vec_kernels_exact.h"
+#include "vec_topk_lists.h"
 
 namespace mir {
 
@@ -57,7 +58,7 @@ struct ScopedArgs {
     int k;
     int round;
     int list_stride;           // min(k, kExactRound)
-    uint64_t *part;            // [b][P][list_stride][2]: {dist bits, valid << 32 | scope position}
+    uint64_t *part;            // [b][P][list_stride][2]: the workgroups' lists (vec_topk_lists.h), key = scope position
     uint32_t *arrive;          // [b], zero between launches
     double *bound_dist;        // [b] last result of the previous round
     uint32_t *bound_pos;       // [b]
@@ -84,12 +85,34 @@ struct ScopedWalk {
     const float **dsq;    // BLOCKS: [kScopedSegs] their float32 squared norms
 };
 
+// Block-wide (kScopedThreads threads, two barriers): the inclusive prefix sum of one value per thread; *total = the sum of all.
+// wsum: [kScopedWaves] in LDS.  The first barrier stands before wsum is written: whatever the previous call's readers read is consumed.
+template <typename V>
+__device__ __forceinline__ V scoped_block_scan(V x, V *wsum, int tid, V *total) {
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {  // inclusive prefix sum within the wave
+        const V y = __shfl_up(x, off, 64);
+        if (lane >= off) x += y;
+    }
+    __syncthreads();
+    if (lane == 63) wsum[wave] = x;
+    __syncthreads();
+    V before = 0, all = 0;
+    for (int i = 0; i < kScopedWaves; ++i) {
+        const V t = wsum[i];
+        if (i < wave) before += t;
+        all += t;
+    }
+    *total = all;
+    return before + x;
+}
+
 // Block-wide: segments [seg0, seg0 + kScopedSegs) of a list that ends at seg_hi -> their first positions and rows in LDS,
 // `base` = the position of segment seg0's first row.  Returns the position after the last of them.
 template <bool BLOCKS>
 __device__ __forceinline__ uint64_t scoped_load_segments(const ScopedArgs &a, int seg0, int seg_hi, uint64_t base, const ScopedWalk &w,
                                                          int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
     const int s = seg0 + tid;
     uint32_t begin = 0, len = 0;
     const void *emb = nullptr;
@@ -107,22 +130,8 @@ __device__ __forceinline__ uint64_t scoped_load_segments(const ScopedArgs &a, in
         begin = (uint32_t)b;
         len = e > b ? (uint32_t)(e - b) : 0u;
     }
-    uint64_t x = len;  // inclusive prefix sum within the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t y = __shfl_up(x, off, 64);
-        if (lane >= off) x += y;
-    }
-    __syncthreads();  // the previous step's arrays have been consumed
-    if (lane == 63) w.wsum[wave] = x;
-    __syncthreads();
-    uint64_t before = base, total = base;
-    for (int i = 0; i < kScopedWaves; ++i) {
-        const uint64_t t = w.wsum[i];
-        if (i < wave) before += t;
-        total += t;
-    }
-    w.start[tid] = before + x - len;
+    uint64_t total;
+    w.start[tid] = base + scoped_block_scan<uint64_t>(len, w.wsum, tid, &total) - len;  // (its first barrier: the previous step's arrays have been consumed)
     if constexpr (BLOCKS) {
         w.emb[tid] = emb;
         w.dsq[tid] = dsq;
@@ -130,7 +139,7 @@ __device__ __forceinline__ uint64_t scoped_load_segments(const ScopedArgs &a, in
         w.row0[tid] = begin;
     }
     __syncthreads();
-    return total;
+    return base + total;
 }
 
 // the segment (of the `cn` loaded ones) that holds position `pos`: the LAST one that starts at or before it (an empty
@@ -143,6 +152,14 @@ __device__ __forceinline__ int scoped_find_segment(const ScopedWalk &w, int cn, 
         if (t2 < cn && w.start[t2] <= pos) t = t2;
     }
     return t;
+}
+
+// BLOCKS: result slot `o` <- (block ordinal in the scope, chunk id, row in the block) of row `off` of the block table[seg]
+__device__ __forceinline__ void scoped_write_block_result(const ScopedArgs &a, size_t o, int ordinal, int seg, uint32_t off) {
+    if (a.out_doc) a.out_doc[o] = ordinal;
+    const int64_t *chunk = a.blocks[seg].chunk;
+    if (a.out_chunk) a.out_chunk[o] = chunk ? chunk[off] : (int64_t)off;
+    if (a.out_row) a.out_row[o] = (int64_t)off;
 }
 
 template <typename T, bool QLDS, bool BLOCKS = false>
@@ -227,41 +244,15 @@ __global__ __launch_bounds__(kScopedThreads) void scoped_topk_kernel(ScopedArgs 
     }
 
     int total;
-    int rank = xb_block_rank<kScopedWaves>(my_d, my_p, cnt, s_d, s_r, s_cnt, tid, &total);
+    int rank = block_rank<kScopedWaves>(my_d, my_p, cnt, s_d, s_r, s_cnt, tid, &total);
     if (P > 1) {
-        // ---- this workgroup's list -> HBM; the last workgroup of the query to arrive merges the P lists
-        uint64_t *mine = a.part + ((size_t)qi * P + p) * a.list_stride * 2;
-        if (rank >= 0 && rank < kk) {
-            mine[2 * rank] = (uint64_t)__double_as_longlong(my_d);
-            mine[2 * rank + 1] = (1ull << 32) | my_p;
-        }
-        if (tid < kk && tid >= total) {
-            mine[2 * tid] = 0;
-            mine[2 * tid + 1] = 0;
-        }
-        __threadfence();  // this workgroup's list is visible device-wide before its arrival is
-        __syncthreads();
-        if (tid == 0) s_last = atomicAdd(&a.arrive[qi], 1u) == P - 1;
-        __syncthreads();
-        if (!s_last) return;  // uniform per workgroup
-        __threadfence();
-        my_d = 0.0;
-        my_p = 0;
-        cnt = 0;
-        for (uint32_t g = wave; g < P; g += kScopedWaves) {
-            const uint64_t *l = a.part + ((size_t)qi * P + g) * a.list_stride * 2;
-            for (int j = 0; j < kk; ++j) {
-                const uint64_t w1 = __hip_atomic_load(l + 2 * j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (!(w1 >> 32)) break;
-                const double dj = __longlong_as_double((long long)__hip_atomic_load(l + 2 * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                const double worst_d = __shfl(my_d, kk - 1, 64);
-                const uint32_t worst_p = __shfl(my_p, kk - 1, 64);
-                if (cnt == kk && !dist_before(dj, (uint32_t)w1, worst_d, worst_p)) break;  // the rest of this list is worse still
-                exact_wave_insert(dj, (uint32_t)w1, kk, lane, my_d, my_p, cnt);
-            }
-        }
-        rank = xb_block_rank<kScopedWaves>(my_d, my_p, cnt, s_d, s_r, s_cnt, tid, &total);
-        if (tid == 0) a.arrive[qi] = 0;
+        // ---- this workgroup's list -> HBM; the last workgroup of the query to arrive merges the P lists (vec_topk_lists.h)
+        uint64_t *lists = a.part + (size_t)qi * P * a.list_stride * 2;
+        lists_publish(lists + (size_t)p * a.list_stride * 2, rank, total, kk, tid, my_d, my_p);
+        if (!lists_arrive(a.arrive + qi, 1, P, &s_last, tid)) return;  // uniform per workgroup
+        lists_merge<kScopedWaves>(lists, P, a.list_stride, kk, wave, lane, my_d, my_p, cnt);
+        rank = block_rank<kScopedWaves>(my_d, my_p, cnt, s_d, s_r, s_cnt, tid, &total);
+        lists_rearm(a.arrive + qi, tid);
     }
 
     // ---- results: a position goes back to (segment ordinal, row) by one more walk of the list
@@ -281,13 +272,10 @@ __global__ __launch_bounds__(kScopedThreads) void scoped_topk_kernel(ScopedArgs 
             const uint64_t end = scoped_load_segments<BLOCKS>(a, c, seg_hi, base, walk, tid);
             if (res && my_p >= base && my_p < end) {
                 const int t = scoped_find_segment(walk, min(kScopedSegs, seg_hi - c), my_p);
-                if (a.out_doc) a.out_doc[o] = c - seg_lo + t;
                 if constexpr (BLOCKS) {
-                    const uint32_t off = (uint32_t)(my_p - s_start[t]);
-                    const int64_t *chunk = a.blocks[c + t].chunk;
-                    if (a.out_chunk) a.out_chunk[o] = chunk ? chunk[off] : (int64_t)off;
-                    if (a.out_row) a.out_row[o] = (int64_t)off;
+                    scoped_write_block_result(a, o, c - seg_lo + t, c + t, (uint32_t)(my_p - s_start[t]));
                 } else {
+                    if (a.out_doc) a.out_doc[o] = c - seg_lo + t;
                     const uint32_t row = min(s_row0[t] + (uint32_t)(my_p - s_start[t]), a.n_rows - 1u);
                     if (a.out_chunk) a.out_chunk[o] = a.chunk_ids ? a.chunk_ids[row] : (int64_t)row;
                     if (a.out_row) a.out_row[o] = a.row_offset + (int64_t)row;

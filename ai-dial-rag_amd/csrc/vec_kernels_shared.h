@@ -32,9 +32,9 @@
 //   * Selection: after the d / 4 MFMAs of a query tile a lane holds four finished distances of query lane & 15.  Each is
 //     compared with that query's current worst of this wave and voted on; the rare path inserts with exact_wave_insert into
 //     the (wave, query) list, which lives in LDS between inserts.  Then per query the four wave lists are ranked
-//     (xb_block_rank); P > 1: the partial lists meet in HBM and the last workgroup of the SLAB to arrive (device-scope
-//     fence + counter, agent-scope loads) merges them per query, as scoped_topk_kernel does per query.  k > 64 runs in
-//     rounds of 64 behind the (distance, position) cursor.  One result walk per slab.
+//     (block_rank); P > 1: the partial lists meet in HBM and the last workgroup of the SLAB to arrive merges them per
+//     query (vec_topk_lists.h: one arrival per slab, one set of P lists per query).  k > 64 runs in rounds of 64 behind
+//     the (distance, position) cursor.  One result walk per slab.
 //   * Addressing: a row is emb[t] + (pos - start[t]) * d with pos inside segment t, as in scoped_topk_kernel<.., BLOCKS>:
 //     every address is begin + offset with offset < length.
 #pragma once
@@ -60,7 +60,7 @@ struct SharedArgs {
 __global__ __launch_bounds__(kScopedThreads) void shared_slabs_kernel(const int32_t *__restrict__ group_ptr, int n_groups, int qs, int cap,
                                                                       SharedSlab *__restrict__ slabs, int32_t *__restrict__ n_slabs) {
     __shared__ int s_w[kScopedWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     int base = 0;
     for (int g0 = 0; g0 < n_groups; g0 += kScopedThreads) {  // (block-uniform)
         const int g = g0 + tid;
@@ -70,23 +70,10 @@ __global__ __launch_bounds__(kScopedThreads) void shared_slabs_kernel(const int3
             n = max(group_ptr[g + 1] - lo, 0);
         }
         const int ns = (n + qs - 1) / qs;
-        int x = ns;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int y = __shfl_up(x, off, 64);
-            if (lane >= off) x += y;
-        }
-        __syncthreads();
-        if (lane == 63) s_w[wave] = x;
-        __syncthreads();
-        int before = base, total = base;
-        for (int i = 0; i < kScopedWaves; ++i) {
-            if (i < wave) before += s_w[i];
-            total += s_w[i];
-        }
-        const int at = before + x - ns;
+        int total;
+        const int at = base + scoped_block_scan<int>(ns, s_w, tid, &total) - ns;
         for (int i = 0; i < ns && at + i < cap; ++i) slabs[at + i] = SharedSlab{g, lo + i * qs};
-        base = total;
+        base += total;
     }
     if (tid == 0) *n_slabs = min(base, cap);
 }
@@ -304,57 +291,27 @@ __global__ __launch_bounds__(kScopedThreads) void shared_topk_kernel(SharedArgs 
             const double my_d = lane < cnt ? list_d[((size_t)wave * QS + n) * stride + lane] : 0.0;
             const uint32_t my_p = lane < cnt ? list_p[((size_t)wave * QS + n) * stride + lane] : 0u;
             int total;
-            const int rank = xb_block_rank<kScopedWaves>(my_d, my_p, cnt, s_d, s_r, s_cnt, tid, &total);
-            uint64_t *mine = a.part + ((size_t)(q0 + n) * P + p) * stride * 2;
-            if (rank >= 0 && rank < kk) {
-                mine[2 * rank] = (uint64_t)__double_as_longlong(my_d);
-                mine[2 * rank + 1] = (1ull << 32) | my_p;
-            }
-            if (tid < kk && tid >= total) {
-                mine[2 * tid] = 0;
-                mine[2 * tid + 1] = 0;
-            }
+            const int rank = block_rank<kScopedWaves>(my_d, my_p, cnt, s_d, s_r, s_cnt, tid, &total);
+            lists_publish(a.part + ((size_t)(q0 + n) * P + p) * stride * 2, rank, total, kk, tid, my_d, my_p);
         }
-        __threadfence();  // this workgroup's lists are visible device-wide before its arrival is
-        __syncthreads();
-        if (tid == 0) s_last = atomicAdd(&a.arrive[slab], 1u) == P - 1;
-        __syncthreads();
-        if (!s_last) return;  // uniform per workgroup
-        __threadfence();
+        if (!lists_arrive(a.arrive + slab, 1, P, &s_last, tid)) return;  // uniform per workgroup
     }
 
     // ---- per query: the ranked list, written over wave 0's list of the query (its entries are in registers by then)
     for (int n = 0; n < nq; ++n) {
         const int qi = q0 + n;
-        double my_d = 0.0;
-        uint32_t my_p = 0;
-        int cnt = 0;
+        double my_d;
+        uint32_t my_p;
+        int cnt;
         if (P > 1) {
-            for (uint32_t w = wave; w < P; w += kScopedWaves) {
-                const uint64_t *l = a.part + ((size_t)qi * P + w) * stride * 2;
-                // (the list's kk entries, one per lane, in ONE round trip to HBM: all of [0, kk) was written, zeros after its last entry)
-                unsigned long long e0 = 0, e1 = 0;
-                if (lane < kk) {
-                    e1 = __hip_atomic_load(l + 2 * lane + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    e0 = __hip_atomic_load(l + 2 * lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                for (int j = 0; j < kk; ++j) {
-                    const uint64_t w1 = __shfl(e1, j, 64);
-                    if (!(w1 >> 32)) break;
-                    const double dj = __longlong_as_double((long long)__shfl(e0, j, 64));
-                    const double worst_d = __shfl(my_d, kk - 1, 64);
-                    const uint32_t worst_p = __shfl(my_p, kk - 1, 64);
-                    if (cnt == kk && !dist_before(dj, (uint32_t)w1, worst_d, worst_p)) break;  // the rest of this list is worse still
-                    exact_wave_insert(dj, (uint32_t)w1, kk, lane, my_d, my_p, cnt);
-                }
-            }
+            lists_merge<kScopedWaves>(a.part + (size_t)qi * P * stride * 2, P, stride, kk, wave, lane, my_d, my_p, cnt);
         } else {
             cnt = s_lcnt[wave][n];
             my_d = lane < cnt ? list_d[((size_t)wave * QS + n) * stride + lane] : 0.0;
             my_p = lane < cnt ? list_p[((size_t)wave * QS + n) * stride + lane] : 0u;
         }
         int total;
-        const int rank = xb_block_rank<kScopedWaves>(my_d, my_p, cnt, s_d, s_r, s_cnt, tid, &total);
+        const int rank = block_rank<kScopedWaves>(my_d, my_p, cnt, s_d, s_r, s_cnt, tid, &total);
         const int kout = total < kk ? total : kk;
         if (rank >= 0 && rank < kout) {
             list_d[(size_t)n * stride + rank] = my_d;
@@ -366,7 +323,7 @@ __global__ __launch_bounds__(kScopedThreads) void shared_topk_kernel(SharedArgs 
         }
         if (tid == 0) s_kout[n] = kout;
     }
-    if (P > 1 && tid == 0) a.arrive[slab] = 0;
+    if (P > 1) lists_rearm(a.arrive + slab, tid);
     __syncthreads();
 
     // ---- results, one 16-lane group per (query, rank): a position goes back to (block ordinal, row) by one more walk of the
@@ -397,12 +354,7 @@ __global__ __launch_bounds__(kScopedThreads) void shared_topk_kernel(SharedArgs 
                                              : exact_metric_wave<T, 16, 8>(rowp, qrow, d, metric, s_dsq[t][off], s_qsq[n], q_norm, lg, &rv);
                     if (lg == 0) a.out_dist[o] = dist;
                 }
-                if (lg == 0) {
-                    if (a.out_doc) a.out_doc[o] = c - seg_lo + t;
-                    const int64_t *chunk = a.blocks[c + t].chunk;
-                    if (a.out_chunk) a.out_chunk[o] = chunk ? chunk[off] : (int64_t)off;
-                    if (a.out_row) a.out_row[o] = (int64_t)off;
-                }
+                if (lg == 0) scoped_write_block_result(a, o, c - seg_lo + t, c + t, off);
             }
             base = end;
         }

@@ -22,6 +22,10 @@ Pinning status ("Oracle"):
   of float range, builds the smallest corpus per search route and derives the
   float64 error bound of the metrics above; ``tests/test_oracle_query_range.py``
   proves that those inputs can be judged with identical ids.
+* scope rules     - ``scope_rules`` adds no formula either: it is how the scoped, block,
+  shared and pieces searches are judged against ``find`` over a scope (pairs, count,
+  tolerances, bit-equality of two routes) and the many-short-lists case of their GPU
+  tests; ``tests/test_scope_rules.py`` shows on the CPU that the rules bite.
 * shard merge     - ``merge.merge``: no such step upstream (single process); it is
   the stable argsort above (reversed for BM25) applied across contiguous
   shards, and ``tests/test_oracle_merge.py`` proves it equal to the unsharded

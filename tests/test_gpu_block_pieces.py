@@ -2,8 +2,7 @@
 pieces once, a query's partial answers are merged back into the reference's order.  Every case runs with min_riders 1
 (everything shared), 2 and INT32_MAX (nothing shared) and is checked against three references:
 
-  * the oracle's `find` over the flattened scope's documents, by test_gpu_block_shared.py's rules: (block ordinal, chunk
-    id) pairs identical (cosine: up to ties within COS_NOISE), distances within 1e-9 (cosine 5e-7);
+  * the oracle's `find` over the flattened scope's documents, by the rules of oracle/scope_rules.py;
   * BlockSearcher.search on the flattened scopes: doc, chunk, row and count equal, distance BITS equal;
   * with min_riders = INT32_MAX the whole answer equals `search`'s bit for bit.
 
@@ -16,16 +15,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from oracle.scope_rules import assert_routes_agree, check_against_oracle, dist_tol, oracle_docs, oracle_find, separated, unit
+
 pytestmark = pytest.mark.gpu
 
 METRICS = ["cosine_sim", "euclidean_dist", "sqeuclidean_dist", "inner_product"]
-COS_NOISE = 2e-7
 NEVER = 2**31 - 1
 MIN_RIDERS = (1, 2, NEVER)
-
-
-def dist_tol(metric):
-    return 5e-7 if metric == "cosine_sim" else 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -44,65 +40,6 @@ def amd():
     ns = NS()
     ns.nat, ns.ei, ns.bc, ns.oi, ns.RetrievalType = _native, ei, bc, oi, RetrievalType
     return ns
-
-
-def unit(x):
-    return (x / np.linalg.norm(x, axis=-1, keepdims=True)).astype(np.float32)
-
-
-def oracle_docs(oi, parts, chunks):
-    return [oi.DocIndex(c, p.astype(np.float32)) if len(p) else oi.DocIndex() for c, p in zip(chunks, parts)]
-
-
-def oracle_find(oi, metric, q, scope_docs, k):
-    with np.errstate(invalid="ignore", over="ignore"):
-        return oi.find(q, scope_docs, metric, k)
-
-
-def check_against_oracle(oi, metric, q, scope_docs, want, wdist, got_doc, got_chunk, got_dist, got_cnt, msg):
-    """test_gpu_block_shared.py's rules; scope_docs: the oracle DocIndex objects of the flattened scope, in its order;
-    (want, wdist) = oracle_find over them, computed once per case"""
-    m = int(got_cnt)
-    assert m == len(want), msg
-    got = [(int(a), int(b)) for a, b in zip(got_doc[:m], got_chunk[:m])]
-    if metric != "cosine_sim":
-        assert got == want, msg
-    else:
-        def dist_of(pair):
-            doc = scope_docs[pair[0]]
-            row = int(np.nonzero(doc.chunk_ids == pair[1])[0][0])
-            return float(oi.ENUM_TO_METRIC[oi.Metric(metric)](q, doc.embeddings[row : row + 1])[0])
-
-        for g, w in zip(got, want):
-            if g != w:
-                assert abs(dist_of(g) - dist_of(w)) <= COS_NOISE, f"{msg}: {g} vs {w}"
-    np.testing.assert_allclose(got_dist[:m], wdist, rtol=0, atol=dist_tol(metric), equal_nan=True, err_msg=msg)
-
-
-def assert_routes_agree(pieces, per_query, metric, msg):
-    """doc, chunk, row and count equal; distances within the metric's tolerance, NaN equal to NaN - and the same bits"""
-    np.testing.assert_array_equal(pieces[4], per_query[4], err_msg=msg)
-    for i, m in enumerate(pieces[4]):
-        for a, b, what in zip(pieces[:3], per_query[:3], ("doc", "chunk", "row")):
-            np.testing.assert_array_equal(a[i, :m], b[i, :m], err_msg=f"{msg} query {i}: {what}")
-        np.testing.assert_allclose(pieces[3][i, :m], per_query[3][i, :m], rtol=0, atol=dist_tol(metric), equal_nan=True, err_msg=f"{msg} query {i}")
-        np.testing.assert_array_equal(pieces[3][i, :m].view(np.uint64), per_query[3][i, :m].view(np.uint64), err_msg=f"{msg} query {i}: dist bits")
-
-
-def separated(oi, metric, q, scope_docs, k):
-    """No two of the first k + 1 rows of the scope under the oracle's float64 distances are within the tolerance of one
-    another, unless they are the same row bit for bit"""
-    rows = [d.embeddings for d in scope_docs if len(d.embeddings)]
-    if not rows:
-        return True
-    emb = np.concatenate(rows)
-    with np.errstate(invalid="ignore", over="ignore"):
-        dist = oi.ENUM_TO_METRIC[oi.Metric(metric)](q, emb)
-    top = np.argsort(dist, kind="stable")[: k + 1]
-    for a, b in zip(top[:-1], top[1:]):
-        if not dist[b] - dist[a] > dist_tol(metric) and emb[a].tobytes() != emb[b].tobytes():
-            return False
-    return True
 
 
 def flat_scopes(piece_lists, scopes):

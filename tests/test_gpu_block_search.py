@@ -1,7 +1,6 @@
 """GPU parity of the block search (csrc/vec_kernels_scoped.h, BLOCKS): every query of a batch searches its own list of row
 blocks, no index is built.  Expected answers: the oracle's `find` over just the documents of the scope, in the order of the
-scope - (block ordinal, chunk id) pairs identical (cosine: up to ties within COS_NOISE), distances within 1e-9 (cosine
-5e-7): test_gpu_scoped.py's rules.  Where the index route reads the same stored type, the two routes agree bit for bit."""
+scope, by the rules of oracle/scope_rules.py.  Where the index route reads the same stored type, the two routes agree bit for bit."""
 
 import ctypes as C
 import threading
@@ -9,14 +8,12 @@ import threading
 import numpy as np
 import pytest
 
+from oracle import scope_rules as sr
+from oracle.scope_rules import check_against_oracle_k, make_blocks, unit
+
 pytestmark = pytest.mark.gpu
 
 METRICS = ["cosine_sim", "euclidean_dist", "sqeuclidean_dist", "inner_product"]
-COS_NOISE = 2e-7
-
-
-def dist_tol(metric):
-    return 5e-7 if metric == "cosine_sim" else 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -37,38 +34,6 @@ def amd():
     ns = NS()
     ns.nat, ns.ei, ns.ci, ns.bc, ns.cb, ns.oi, ns.RetrievalType = _native, ei, ci, bc, cb, oi, RetrievalType
     return ns
-
-
-def unit(x):
-    return (x / np.linalg.norm(x, axis=-1, keepdims=True)).astype(np.float32)
-
-
-def check_against_oracle(oi, metric, q, scope_docs, k, got_doc, got_chunk, got_dist, got_cnt, msg):
-    """scope_docs: the oracle DocIndex objects of the scope, in its order"""
-    with np.errstate(invalid="ignore", over="ignore"):
-        want, wdist = oi.find(q, scope_docs, metric, k)
-    m = int(got_cnt)
-    assert m == len(want), msg
-    got = [(int(a), int(b)) for a, b in zip(got_doc[:m], got_chunk[:m])]
-    if metric != "cosine_sim":
-        assert got == want, msg
-    else:
-        def dist_of(pair):
-            doc = scope_docs[pair[0]]
-            row = int(np.nonzero(doc.chunk_ids == pair[1])[0][0])
-            return float(oi.ENUM_TO_METRIC[oi.Metric(metric)](q, doc.embeddings[row : row + 1])[0])
-
-        for g, w in zip(got, want):
-            if g != w:
-                assert abs(dist_of(g) - dist_of(w)) <= COS_NOISE, f"{msg}: {g} vs {w}"
-    np.testing.assert_allclose(got_dist[:m], wdist, rtol=0, atol=dist_tol(metric), equal_nan=True, err_msg=msg)
-
-
-def make_blocks(amd, parts, chunks):
-    """-> (DeviceRows per part, oracle DocIndex per part); float16 parts are stored as float16, the oracle sees them up-cast"""
-    blocks = [amd.ei.DeviceRows.from_host(p, c) for p, c in zip(parts, chunks)]
-    docs = [amd.oi.DocIndex(c, p.astype(np.float32)) if len(p) else amd.oi.DocIndex() for c, p in zip(chunks, parts)]
-    return blocks, docs
 
 
 def searcher_for(amd, blocks):
@@ -120,7 +85,7 @@ def test_parity_over_ragged_blocks(amd, ragged, metric):
         assert cnt[1] == 0 and cnt[2] == 0  # only an empty block; no block at all
         assert cnt[6] == min(k, 6)          # a scope of 6 rows
         for i, s in enumerate(SCOPES):
-            check_against_oracle(amd.oi, metric, queries[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{metric} k={k} scope {i}")
+            check_against_oracle_k(amd.oi, metric, queries[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{metric} k={k} scope {i}")
             m = int(cnt[i])
             np.testing.assert_array_equal(chunk[i, :m], 3 * row[i, :m] + 1)  # the row INSIDE its block
             assert all(0 <= row[i, j] < sizes[s[doc[i, j]]] for j in range(m))
@@ -136,12 +101,12 @@ def test_parity_over_ragged_blocks(amd, ragged, metric):
         n = int(sizes[twin_doc])
         doc, chunk, _, dist, cnt, _ = searcher.search(queries[3:4], n, metric, [[blocks[twin_doc]]])
         assert cnt[0] == n and np.isnan(dist[0, n - 1]) and not np.isnan(dist[0, : n - 1]).any()
-        check_against_oracle(amd.oi, metric, queries[3], [docs[twin_doc]], n, doc[0], chunk[0], dist[0], cnt[0], "NaN last")
+        check_against_oracle_k(amd.oi, metric, queries[3], [docs[twin_doc]], n, doc[0], chunk[0], dist[0], cnt[0], "NaN last")
 
 
 # ---------------------------------------------------------------- 2. the two routes agree bit for bit
 
-def assert_routes_agree(amd, blocks, sizes, scope_lists, queries, ks):
+def assert_block_route_equals_index_route(amd, blocks, sizes, scope_lists, queries, ks):
     """BlockSearcher.search against search_scoped on the index composed of the same blocks, over the matching segments"""
     live = [b for b in blocks if b.n > 0]
     dev = amd.ei.DeviceIndex.from_rows(live)
@@ -167,13 +132,13 @@ def assert_routes_agree(amd, blocks, sizes, scope_lists, queries, ks):
 
 def test_block_route_equals_index_route_float32(amd, ragged):
     sizes, parts, blocks, docs, queries, twin_doc, _ = ragged
-    assert_routes_agree(amd, blocks, sizes, SCOPES, queries, (7, 64))
+    assert_block_route_equals_index_route(amd, blocks, sizes, SCOPES, queries, (7, 64))
 
 
 def test_block_route_equals_index_route_float16_d1024(amd):
     sizes, parts, chunks, queries = ragged_parts(1024, np.float16)  # float16-native on the index route: both read the stored float16
     blocks = [amd.ei.DeviceRows.from_host(p, c) for p, c in zip(parts, chunks)]
-    assert_routes_agree(amd, blocks, sizes, SCOPES, queries, (7,))
+    assert_block_route_equals_index_route(amd, blocks, sizes, SCOPES, queries, (7,))
 
 
 def test_block_route_equals_index_route_on_special_values(amd):
@@ -186,7 +151,7 @@ def test_block_route_equals_index_route_on_special_values(amd):
     blocks = [amd.ei.DeviceRows.from_host(p, 5 * np.arange(len(p), dtype=np.int64)) for p in parts]
     queries = rng.standard_normal((3, 384))
     queries[1] = special[9].astype(np.float64) * 1e-30
-    assert_routes_agree(amd, blocks, [20, 12, 9], [[1], [0, 1, 2], [2, 1]], queries, (12, 41))
+    assert_block_route_equals_index_route(amd, blocks, [20, 12, 9], [[1], [0, 1, 2], [2, 1]], queries, (12, 41))
 
 
 # ---------------------------------------------------------------- 3. k beyond one round, ties across blocks
@@ -208,7 +173,7 @@ def test_k_beyond_one_round_with_ties_across_blocks(amd, metric):
     k = 130
     doc, chunk, row, dist, cnt, _ = searcher_for(amd, blocks).search(q[None], k, metric, [blocks])
     assert cnt[0] == k
-    check_against_oracle(amd.oi, metric, q, docs, k, doc[0], chunk[0], dist[0], cnt[0], f"{metric} k={k}")
+    check_against_oracle_k(amd.oi, metric, q, docs, k, doc[0], chunk[0], dist[0], cnt[0], f"{metric} k={k}")
     if metric != "cosine_sim":  # (a unit row's cosine is one product and one division: exact ties there too, but the rule allows noise)
         assert (dist[0, 60:75] == dist[0, 60]).all() and dist[0, 59] < dist[0, 60] < dist[0, 75]
     pos = 50 * doc[0].astype(np.int64) + row[0]
@@ -232,7 +197,7 @@ def test_long_block_list(amd, metric):
     qs = rng.standard_normal((2, 32))
     doc, chunk, row, dist, cnt, _ = searcher_for(amd, blocks).search(qs, 10, metric, [[blocks[j] for j in s] for s in scope_lists])
     for i, s in enumerate(scope_lists):
-        check_against_oracle(amd.oi, metric, qs[i], [docs[j] for j in s], 10, doc[i], chunk[i], dist[i], cnt[i], f"{metric} scope {i}")
+        check_against_oracle_k(amd.oi, metric, qs[i], [docs[j] for j in s], 10, doc[i], chunk[i], dist[i], cnt[i], f"{metric} scope {i}")
         np.testing.assert_array_equal(chunk[i], row[i] + 7 * np.asarray(s)[doc[i]])
 
 
@@ -246,7 +211,7 @@ def test_one_block_split_over_many_workgroups(amd, metric):
     q = rng.standard_normal(384)
     doc, chunk, row, dist, cnt, _ = searcher_for(amd, blocks).search(q[None], 64, metric, [blocks])
     assert cnt[0] == 64 and (doc[0] == 0).all()
-    check_against_oracle(amd.oi, metric, q, docs, 64, doc[0], chunk[0], dist[0], cnt[0], metric)
+    check_against_oracle_k(amd.oi, metric, q, docs, 64, doc[0], chunk[0], dist[0], cnt[0], metric)
     np.testing.assert_array_equal(row[0], 4999 - chunk[0])
 
 
@@ -276,7 +241,7 @@ def test_other_storage(amd, metric, shape):
     qs = rng.standard_normal((len(scope_lists), d))
     doc, chunk, row, dist, cnt, _ = searcher_for(amd, blocks).search(qs, 5, metric, [[blocks[j] for j in s] for s in scope_lists])
     for i, s in enumerate(scope_lists):
-        check_against_oracle(amd.oi, metric, qs[i], [docs[j] for j in s], 5, doc[i], chunk[i], dist[i], cnt[i], f"{shape} {metric} scope {s}")
+        check_against_oracle_k(amd.oi, metric, qs[i], [docs[j] for j in s], 5, doc[i], chunk[i], dist[i], cnt[i], f"{shape} {metric} scope {s}")
         np.testing.assert_array_equal(chunk[i], 2 * row[i] + np.asarray(s)[doc[i]])
 
 
@@ -322,6 +287,48 @@ def test_device_entry_matches_host_entry_on_a_side_stream(amd):
         g = got.cpu().numpy()
         for i in range(b):
             np.testing.assert_array_equal(g[i, : cnt[i]], host[i, : cnt[i]])
+
+
+def device_search(searcher, qs, k, metric, blocks, scope_lists):
+    """search's six arrays through the device entry, which does not see the scopes on the host"""
+    import torch
+
+    cuda, b = torch.device("cuda:0"), len(qs)
+    ptr = np.zeros(b + 1, np.int32)
+    np.cumsum([len(s) for s in scope_lists], out=ptr[1:])
+    table = np.array([blocks[j].desc() for s in scope_lists for j in s], dtype=np.int64).reshape(-1, 4)  # [nseg][emb, doc_sq, chunk, n]
+    tq, tptr, ttable = (torch.from_numpy(np.ascontiguousarray(a)).to(cuda) for a in (qs, ptr, table))
+    o_doc = torch.zeros((b, k), dtype=torch.int32, device=cuda)
+    o_chunk, o_row = (torch.zeros((b, k), dtype=torch.int64, device=cuda) for _ in range(2))
+    o_dist = torch.zeros((b, k), dtype=torch.float64, device=cuda)
+    o_cnt, o_flg = (torch.full((b,), -1, dtype=torch.int32, device=cuda) for _ in range(2))
+    searcher.search_device(tq.data_ptr(), b, k, metric, tptr.data_ptr(), ttable.data_ptr(), o_row.data_ptr(), o_dist.data_ptr(), o_cnt.data_ptr(),
+                           o_flg.data_ptr(), o_doc.data_ptr(), o_chunk.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in (o_doc, o_chunk, o_row, o_dist, o_cnt, o_flg))
+
+
+@pytest.mark.parametrize("metric", METRICS)
+@pytest.mark.parametrize("dtype", ["float32", "float16"])
+def test_many_short_lists_through_the_device_entry(amd, dtype, metric):
+    """oracle/scope_rules.py, "many short lists": scopes of 0, 1, 70 and 200 rows split over 64 workgroups each.  The
+    oracle's answer by the shared rules; doc, chunk, row, count and distance bits equal to the host entry's (<= 4 shares)."""
+    parts, chunks, queries = sr.short_lists_case(np.dtype(dtype).type)
+    qs = queries[:3]
+    blocks, docs = make_blocks(amd, parts, chunks)
+    searcher = searcher_for(amd, blocks)
+    for k in sr.SHORT_KS:
+        for turn in range(len(sr.SHORT_SCOPES)):  # every query on every scope: query i takes scope i + turn
+            scopes = [sr.SHORT_SCOPES[(i + turn) % len(sr.SHORT_SCOPES)] for i in range(len(qs))]
+            got = device_search(searcher, qs, k, metric, blocks, scopes)
+            host = searcher.search(qs, k, metric, [[blocks[j] for j in s] for s in scopes])
+            assert (got[5] == 0).all()
+            for i, s in enumerate(scopes):
+                msg = f"{dtype} {metric} k={k} query {i} scope {s}"
+                assert got[4][i] == min(k, sum(sr.SHORT_SIZES[j] for j in s)), msg
+                check_against_oracle_k(amd.oi, metric, qs[i], [docs[j] for j in s], k, got[0][i], got[1][i], got[3][i], got[4][i], msg)
+                np.testing.assert_array_equal(got[1][i, : got[4][i]], 3 * got[2][i, : got[4][i]] + 1)  # the row INSIDE its block
+            sr.assert_routes_agree(got, host, metric, f"{dtype} {metric} k={k} turn {turn}")
 
 
 # ---------------------------------------------------------------- 7. what the host entry refuses
@@ -403,7 +410,7 @@ def test_a_corpus_that_changes(amd):
     for metric in METRICS:
         keys = [5, 1, 0, 4]
         doc, chunk, dist, cnt = corpus.find_many(qs[:1], [keys], metric, 7)
-        check_against_oracle(amd.oi, metric, qs[0], [oracle_docs[j] for j in keys], 7, doc[0], chunk[0], dist[0], cnt[0], f"{metric} after add")
+        check_against_oracle_k(amd.oi, metric, qs[0], [oracle_docs[j] for j in keys], 7, doc[0], chunk[0], dist[0], cnt[0], f"{metric} after add")
         got = pairs([corpus.view(keys, amd.RetrievalType.TEXT, metric, 7).find(qs[0])])[0]
         assert got == [(int(a), int(b)) for a, b in zip(doc[0, : cnt[0]], chunk[0, : cnt[0]])]
     # two different scopes in one call = the two single calls

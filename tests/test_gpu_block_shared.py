@@ -1,8 +1,7 @@
 """GPU parity of the shared-scope block search (csrc/vec_kernels_shared.h): the queries of a group search one scope and
 read its rows once, every distance from v_mfma_f64_16x16x4_f64.  Expected answers: the oracle's `find` over the scope's
-documents by test_gpu_block_search.py's rules - (block ordinal, chunk id) pairs identical (cosine: up to ties within
-COS_NOISE), distances within 1e-9 (cosine 5e-7).  Where the per-query route runs too: doc, chunk, row and count equal,
-distances within the same tolerance."""
+documents by the rules of oracle/scope_rules.py.  Where the per-query route runs too: doc, chunk, row and count equal,
+distances within the same tolerance and the same bits (assert_routes_agree there)."""
 
 import ctypes as C
 import threading
@@ -10,14 +9,12 @@ import threading
 import numpy as np
 import pytest
 
+from oracle import scope_rules as sr
+from oracle.scope_rules import assert_routes_agree, check_against_oracle_k, dist_tol, make_blocks, unit
+
 pytestmark = pytest.mark.gpu
 
 METRICS = ["cosine_sim", "euclidean_dist", "sqeuclidean_dist", "inner_product"]
-COS_NOISE = 2e-7
-
-
-def dist_tol(metric):
-    return 5e-7 if metric == "cosine_sim" else 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -39,37 +36,6 @@ def amd():
     return ns
 
 
-def unit(x):
-    return (x / np.linalg.norm(x, axis=-1, keepdims=True)).astype(np.float32)
-
-
-def check_against_oracle(oi, metric, q, scope_docs, k, got_doc, got_chunk, got_dist, got_cnt, msg):
-    """test_gpu_block_search.py's rules; scope_docs: the oracle DocIndex objects of the scope, in its order"""
-    with np.errstate(invalid="ignore", over="ignore"):
-        want, wdist = oi.find(q, scope_docs, metric, k)
-    m = int(got_cnt)
-    assert m == len(want), msg
-    got = [(int(a), int(b)) for a, b in zip(got_doc[:m], got_chunk[:m])]
-    if metric != "cosine_sim":
-        assert got == want, msg
-    else:
-        def dist_of(pair):
-            doc = scope_docs[pair[0]]
-            row = int(np.nonzero(doc.chunk_ids == pair[1])[0][0])
-            return float(oi.ENUM_TO_METRIC[oi.Metric(metric)](q, doc.embeddings[row : row + 1])[0])
-
-        for g, w in zip(got, want):
-            if g != w:
-                assert abs(dist_of(g) - dist_of(w)) <= COS_NOISE, f"{msg}: {g} vs {w}"
-    np.testing.assert_allclose(got_dist[:m], wdist, rtol=0, atol=dist_tol(metric), equal_nan=True, err_msg=msg)
-
-
-def make_blocks(amd, parts, chunks):
-    blocks = [amd.ei.DeviceRows.from_host(p, c) for p, c in zip(parts, chunks)]
-    docs = [amd.oi.DocIndex(c, p.astype(np.float32)) if len(p) else amd.oi.DocIndex() for c, p in zip(chunks, parts)]
-    return blocks, docs
-
-
 def searcher_for(amd, blocks):
     return amd.ei.BlockSearcher(blocks[0].d, blocks[0].dtype)
 
@@ -86,19 +52,7 @@ def check_groups(amd, metric, k, queries, docs, scope_lists, group_sizes, got, m
     doc, chunk, row, dist, cnt, flags = got
     assert (flags == 0).all(), msg
     for i, s in enumerate(scope_of_query(scope_lists, group_sizes)):
-        check_against_oracle(amd.oi, metric, queries[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{msg} query {i} scope {s}")
-
-
-def assert_routes_agree(shared, per_query, metric, msg):
-    """doc, chunk, row and count equal; distances within the metric's tolerance, NaN equal to NaN"""
-    np.testing.assert_array_equal(shared[4], per_query[4], err_msg=msg)
-    for i, m in enumerate(shared[4]):
-        for a, b, what in zip(shared[:3], per_query[:3], ("doc", "chunk", "row")):
-            np.testing.assert_array_equal(a[i, :m], b[i, :m], err_msg=f"{msg} query {i}: {what}")
-        np.testing.assert_allclose(shared[3][i, :m], per_query[3][i, :m], rtol=0, atol=dist_tol(metric), equal_nan=True, err_msg=f"{msg} query {i}")
-        # more than the tolerance asks: a reported distance is evaluated by the per-query route's routine from the same row,
-        # query and doc_sq, so where the two routes report the same row they report the same bits
-        np.testing.assert_array_equal(shared[3][i, :m].view(np.uint64), per_query[3][i, :m].view(np.uint64), err_msg=f"{msg} query {i}: dist bits")
+        check_against_oracle_k(amd.oi, metric, queries[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{msg} query {i} scope {s}")
 
 
 # ---------------------------------------------------------------- 1. parity over ragged blocks
@@ -374,6 +328,45 @@ def test_device_entry_matches_host_entry_on_a_side_stream(amd):
         g = got.cpu().numpy()
         for i in range(b):
             np.testing.assert_array_equal(g[i, : cnt[i]], host[i, : cnt[i]])  # (distances: the same bits)
+
+
+def device_search_shared(searcher, qs, k, metric, blocks, scope_lists, groups):
+    """search_shared's six arrays through the device entry, which sees neither the groups nor the scopes on the host"""
+    import torch
+
+    cuda, b = torch.device("cuda:0"), len(qs)
+    gp, sp = np.zeros(len(groups) + 1, np.int32), np.zeros(len(groups) + 1, np.int32)
+    np.cumsum(groups, out=gp[1:])
+    np.cumsum([len(s) for s in scope_lists], out=sp[1:])
+    table = np.array([blocks[j].desc() for s in scope_lists for j in s], dtype=np.int64).reshape(-1, 4)  # [nseg][emb, doc_sq, chunk, n]
+    tq, tgp, tsp, ttable = (torch.from_numpy(np.ascontiguousarray(a)).to(cuda) for a in (qs, gp, sp, table))
+    o_doc = torch.zeros((b, k), dtype=torch.int32, device=cuda)
+    o_chunk, o_row = (torch.zeros((b, k), dtype=torch.int64, device=cuda) for _ in range(2))
+    o_dist = torch.zeros((b, k), dtype=torch.float64, device=cuda)
+    o_cnt, o_flg = (torch.full((b,), -1, dtype=torch.int32, device=cuda) for _ in range(2))
+    searcher.search_shared_device(tq.data_ptr(), b, k, metric, len(groups), tgp.data_ptr(), tsp.data_ptr(), ttable.data_ptr(), o_row.data_ptr(),
+                                  o_dist.data_ptr(), o_cnt.data_ptr(), o_flg.data_ptr(), o_doc.data_ptr(), o_chunk.data_ptr(),
+                                  stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in (o_doc, o_chunk, o_row, o_dist, o_cnt, o_flg))
+
+
+@pytest.mark.parametrize("metric", METRICS)
+@pytest.mark.parametrize("dtype", ["float32", "float16"])
+def test_many_short_lists_through_the_device_entry(amd, dtype, metric):
+    """oracle/scope_rules.py, "many short lists": groups of 1, 17 and 33 queries over scopes of 0, 1, 70 and 200 rows, each
+    scope split over up to 256 workgroups: a share is one row or none.  The oracle's answer; equal to the host entry's."""
+    parts, chunks, queries = sr.short_lists_case(np.dtype(dtype).type)
+    blocks, docs = make_blocks(amd, parts, chunks)
+    searcher = searcher_for(amd, blocks)
+    groups = [1, 17, 33]
+    empty, one, seventy, two_hundred = sr.SHORT_SCOPES
+    for k in sr.SHORT_KS:
+        for scope_lists in ([empty, two_hundred, seventy], [two_hundred, one, empty], [seventy, empty, two_hundred]):
+            msg = f"{dtype} {metric} k={k} scopes {[len(s) for s in scope_lists]}"
+            got = device_search_shared(searcher, queries, k, metric, blocks, scope_lists, groups)
+            check_groups(amd, metric, k, queries, docs, scope_lists, groups, got, msg)
+            assert_routes_agree(got, run_groups(searcher, queries, k, metric, blocks, scope_lists, groups), metric, msg)
 
 
 # ---------------------------------------------------------------- 9. what the host entry refuses

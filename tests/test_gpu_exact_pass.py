@@ -189,6 +189,54 @@ def test_any_limit(ei, metric, kind):
             np.testing.assert_allclose(dist[i, : cnt[i]], wdist, rtol=1e-9, atol=2e-7, equal_nan=True)
 
 
+@pytest.mark.parametrize("metric", METRICS)
+@pytest.mark.parametrize("kind", ["f32", "f16"])
+def test_short_and_empty_workgroup_lists(ei, metric, kind):
+    """The smallest index the exact pass splits: 65 rows, two workgroups (one per 64-row block, so n < 16 G cannot be had
+    with G > 1).  The batched pass gives the second workgroup ONE row: its list is shorter than every k, and empty in the
+    rounds after the one that takes that row; the serial pass gives each workgroup 32 or 33 rows, fewer than k = 64.  One,
+    two (serial) and five (batched) flagged queries.  k = 64 and 130 are beyond the filter's lists; at k = 5 the queries
+    are flagged by 19 bit-identical nearest rows, more ties at the cut than the lists hold.  Ties go by row.  (The lone row
+    of the second workgroup is a near copy, not a copy: the oracle's matrix product sums the last row of an odd matrix in
+    another order, and a copy there is not a tie for the oracle.)"""
+    from oracle import embeddings_index as oi
+
+    rng = np.random.default_rng(19)
+    n, d = 65, (24 if kind == "f32" else 320)
+    docs = unit(rng.standard_normal((n, d)))
+    if kind == "f16":
+        docs = docs.astype(np.float16)
+    twins = np.sort(rng.choice(64, 19, replace=False))
+    docs[twins] = docs[twins[0]]
+    docs[64] = unit(docs[twins[0]].astype(np.float32) + 0.05 * rng.standard_normal(d) / np.sqrt(d))  # the second workgroup's only row: among the nearest
+    odocs = docs.astype(np.float32)
+    for b in (1, 2, 5):
+        qs = odocs[twins[0]].astype(np.float64) + 0.1 * rng.standard_normal((b, d)) / np.sqrt(d)
+        for k in (5, 64, 130):
+            _, chunk, rows, dist, cnt, flags = dev_search(ei, docs, qs, k, metric)
+            assert (flags == FLAG_EXACT_PASS).all(), f"{metric} {kind} b={b} k={k}: flags {flags}"
+            for i, q in enumerate(qs):
+                with np.errstate(invalid="ignore"):
+                    want, wdist = oi.find_flat(q, odocs, metric, k)
+                    alld = oi.ENUM_TO_METRIC[oi.Metric(metric)](q, odocs)
+                order = np.argsort(alld, kind="stable")
+                gaps, same = np.diff(alld[order]), [odocs[x].tobytes() == odocs[y].tobytes() for x, y in zip(order[:-1], order[1:])]
+                assert all(g > 1e-6 or (g == 0 and t) for g, t in zip(gaps, same)), "near-ties that are not exact ties of copies: draw another seed"
+                assert set(order[:20]) == set(twins) | {64}
+                assert cnt[i] == min(k, n) == len(want)
+                check_ids(metric, rows[i, : cnt[i]], want, alld, f"{metric} {kind} b={b} k={k} q={i}")
+                np.testing.assert_array_equal(chunk[i, : cnt[i]], rows[i, : cnt[i]])
+                np.testing.assert_allclose(dist[i, : cnt[i]], wdist, rtol=1e-9, atol=2e-7, equal_nan=True)
+
+
+def dev_search(ei, docs, qs, k, metric, cache={}):
+    key = docs.tobytes()
+    if key not in cache:
+        cache.clear()
+        cache[key] = ei.DeviceIndex.from_host(docs)
+    return cache[key].search(qs, k, metric)
+
+
 def test_any_limit_through_the_retriever_surface(ei):
     """EmbeddingsIndex(limit=100).find over ragged documents == the reference's two-level stable argsort."""
     from aidial_rag_amd.index_record import RetrievalType

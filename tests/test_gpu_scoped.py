@@ -1,21 +1,18 @@
 """GPU parity of the scoped search (csrc/vec_kernels_scoped.h): every query of a batch searches its own row ranges of one
-shared index.  Expected answers: the oracle's `find` over just the documents of the scope, in the order of the scope -
-(segment ordinal, chunk id) pairs identical (cosine: up to ties within COS_NOISE, as test_gpu_vector.py), distances
-within 1e-9 (cosine 5e-7), the exact pass's tolerances."""
+shared index.  Expected answers: the oracle's `find` over just the documents of the scope, in the order of the scope, by
+the rules of oracle/scope_rules.py."""
 
 import threading
 
 import numpy as np
 import pytest
 
+from oracle import scope_rules as sr
+from oracle.scope_rules import COS_NOISE, check_against_oracle_k, dist_tol, unit
+
 pytestmark = pytest.mark.gpu
 
 METRICS = ["cosine_sim", "euclidean_dist", "sqeuclidean_dist", "inner_product"]
-COS_NOISE = 2e-7
-
-
-def dist_tol(metric):
-    return 5e-7 if metric == "cosine_sim" else 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -36,10 +33,6 @@ def amd():
     return ns
 
 
-def unit(x):
-    return (x / np.linalg.norm(x, axis=-1, keepdims=True)).astype(np.float32)
-
-
 def flatten(parts, chunks):
     live = [i for i, p in enumerate(parts) if len(p)]
     return np.concatenate([parts[i] for i in live]), np.concatenate([chunks[i] for i in live])
@@ -52,27 +45,6 @@ def csr(segment_lists):
     begin = np.concatenate([np.asarray(b, np.int64) for b, _ in segment_lists] + [np.zeros(0, np.int64)])
     end = np.concatenate([np.asarray(e, np.int64) for _, e in segment_lists] + [np.zeros(0, np.int64)])
     return ptr, begin, end
-
-
-def check_against_oracle(oi, metric, q, scope_docs, k, got_doc, got_chunk, got_dist, got_cnt, msg):
-    """scope_docs: the oracle DocIndex objects of the scope, in its order"""
-    with np.errstate(invalid="ignore"):
-        want, wdist = oi.find(q, scope_docs, metric, k)
-    m = int(got_cnt)
-    assert m == len(want), msg
-    got = [(int(a), int(b)) for a, b in zip(got_doc[:m], got_chunk[:m])]
-    if metric != "cosine_sim":
-        assert got == want, msg
-    else:
-        def dist_of(pair):
-            doc = scope_docs[pair[0]]
-            row = int(np.nonzero(doc.chunk_ids == pair[1])[0][0])
-            return float(oi.ENUM_TO_METRIC[oi.Metric(metric)](q, doc.embeddings[row : row + 1])[0])
-
-        for g, w in zip(got, want):
-            if g != w:
-                assert abs(dist_of(g) - dist_of(w)) <= COS_NOISE, f"{msg}: {g} vs {w}"
-    np.testing.assert_allclose(got_dist[:m], wdist, rtol=0, atol=dist_tol(metric), equal_nan=True, err_msg=msg)
 
 
 # ---------------------------------------------------------------- 1. parity
@@ -113,7 +85,7 @@ def test_parity_over_ragged_documents(amd, ragged, metric):
         assert cnt[1] == 0 and cnt[2] == 0  # only an empty document; no segment at all
         assert cnt[6] == min(k, 6)          # a scope of 6 rows
         for i, s in enumerate(scopes):
-            check_against_oracle(amd.oi, metric, queries[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{metric} k={k} scope {i}")
+            check_against_oracle_k(amd.oi, metric, queries[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{metric} k={k} scope {i}")
             # the B = 1 call is the same computation
             p1, b1, e1 = csr([segs[i]])
             one = dev.search_scoped(queries[i : i + 1], k, metric, p1, b1, e1)
@@ -141,7 +113,7 @@ def test_parity_over_ragged_documents(amd, ragged, metric):
         p1, b1, e1 = csr([(b, e)])
         doc, chunk, _, dist, cnt, _ = dev.search_scoped(queries[3:4], n, metric, p1, b1, e1)
         assert cnt[0] == n and np.isnan(dist[0, n - 1]) and not np.isnan(dist[0, : n - 1]).any()
-        check_against_oracle(amd.oi, metric, queries[3], [docs[twin_doc]], n, doc[0], chunk[0], dist[0], cnt[0], "NaN last")
+        check_against_oracle_k(amd.oi, metric, queries[3], [docs[twin_doc]], n, doc[0], chunk[0], dist[0], cnt[0], "NaN last")
 
 
 # ---------------------------------------------------------------- 2. order
@@ -164,7 +136,7 @@ def test_ties_follow_the_scope_order_and_row_offset_shifts_rows(amd, metric):
     ptr, begin, end = csr([amd.ei.scope_segments(sizes, s) for s in scopes])
     doc, chunk_o, row, dist, cnt, _ = dev.search_scoped(queries, 3, metric, ptr, begin, end)
     for i, s in enumerate(scopes):
-        check_against_oracle(amd.oi, metric, queries[i], [docs[j] for j in s], 3, doc[i], chunk_o[i], dist[i], cnt[i], f"{metric} scope {s}")
+        check_against_oracle_k(amd.oi, metric, queries[i], [docs[j] for j in s], 3, doc[i], chunk_o[i], dist[i], cnt[i], f"{metric} scope {s}")
     if metric != "euclidean_dist":  # (there the copies are the NaN-last rows or near-zero values; the oracle check above covers it)
         assert [(doc[0, j], chunk_o[0, j]) for j in range(2)] == [(0, 5), (1, 3)]  # scope [B, A]: B's copy first
         assert [(doc[1, j], chunk_o[1, j]) for j in range(2)] == [(0, 3), (1, 5)]  # scope [A, B]: A's
@@ -209,7 +181,7 @@ def test_k_beyond_one_round_with_ties_across_position_64(amd, metric):
         doc, chunk_o, _, dist, cnt, _ = dev.search_scoped(qs, k, metric, ptr, begin, end)
         assert list(cnt) == [k, 90]
         for i, s in enumerate(scopes):
-            check_against_oracle(amd.oi, metric, qs[i], [docs[j] for j in s], k, doc[i], chunk_o[i], dist[i], cnt[i], f"{metric} k={k} scope {s}")
+            check_against_oracle_k(amd.oi, metric, qs[i], [docs[j] for j in s], k, doc[i], chunk_o[i], dist[i], cnt[i], f"{metric} k={k} scope {s}")
             assert (dist[i, 60:70] == dist[i, 60]).all()  # one value ...
             np.testing.assert_array_equal(chunk_o[i, 60:70], tied[i])  # ... rows ascending
 
@@ -284,7 +256,7 @@ def test_other_storage(amd, metric, shape):
         doc, chunk, row, dist, cnt, _ = dev.search_scoped(qs, k, metric, ptr, begin, end)
         np.testing.assert_array_equal(chunk, row)
         for i, s in enumerate(scopes):
-            check_against_oracle(amd.oi, metric, qs[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{shape} {metric} k={k} scope {s}")
+            check_against_oracle_k(amd.oi, metric, qs[i], [docs[j] for j in s], k, doc[i], chunk[i], dist[i], cnt[i], f"{shape} {metric} k={k} scope {s}")
 
 
 # ---------------------------------------------------------------- 6. device entry, and what the host entry refuses
@@ -322,6 +294,46 @@ def test_device_entry_matches_host_entry_on_a_side_stream(amd):
         g = got.cpu().numpy()
         for i in range(b):
             np.testing.assert_array_equal(g[i, : cnt[i]], host[i, : cnt[i]])
+
+
+def device_scoped(dev, qs, k, metric, ptr, begin, end):
+    """search_scoped's six arrays through the device entry, which does not see the scopes on the host"""
+    import torch
+
+    cuda, b = torch.device("cuda:0"), len(qs)
+    tq, tptr, tb, te = (torch.from_numpy(np.ascontiguousarray(a)).to(cuda) for a in (qs, ptr, begin, end))
+    o_doc = torch.zeros((b, k), dtype=torch.int32, device=cuda)
+    o_chunk, o_row = (torch.zeros((b, k), dtype=torch.int64, device=cuda) for _ in range(2))
+    o_dist = torch.zeros((b, k), dtype=torch.float64, device=cuda)
+    o_cnt, o_flg = (torch.full((b,), -1, dtype=torch.int32, device=cuda) for _ in range(2))
+    dev.search_scoped_device(tq.data_ptr(), b, k, metric, tptr.data_ptr(), tb.data_ptr(), te.data_ptr(), o_row.data_ptr(), o_dist.data_ptr(),
+                             o_cnt.data_ptr(), o_flg.data_ptr(), o_doc.data_ptr(), o_chunk.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return tuple(t.cpu().numpy() for t in (o_doc, o_chunk, o_row, o_dist, o_cnt, o_flg))
+
+
+@pytest.mark.parametrize("metric", METRICS)
+@pytest.mark.parametrize("dtype", ["float32", "float16"])
+def test_many_short_lists_through_the_device_entry(amd, dtype, metric):
+    """oracle/scope_rules.py, "many short lists": scopes of 0, 1, 70 and 200 rows split over 64 workgroups each.  The
+    oracle's answer by the shared rules; doc, chunk, row, count and distance bits equal to the host entry's (<= 4 shares)."""
+    parts, chunks, queries = sr.short_lists_case(np.dtype(dtype).type)
+    qs = queries[:3]
+    docs = sr.oracle_docs(amd.oi, parts, chunks)
+    emb, chunk_ids = flatten(parts, chunks)
+    dev = amd.ei.DeviceIndex.from_host(emb, chunk_ids)
+    for k in sr.SHORT_KS:
+        for turn in range(len(sr.SHORT_SCOPES)):  # every query on every scope: query i takes scope i + turn
+            scopes = [sr.SHORT_SCOPES[(i + turn) % len(sr.SHORT_SCOPES)] for i in range(len(qs))]
+            ptr, begin, end = csr([amd.ei.scope_segments(sr.SHORT_SIZES, s) for s in scopes])
+            got = device_scoped(dev, qs, k, metric, ptr, begin, end)
+            host = dev.search_scoped(qs, k, metric, ptr, begin, end)
+            assert (got[5] == 0).all()
+            for i, s in enumerate(scopes):
+                msg = f"{dtype} {metric} k={k} query {i} scope {s}"
+                assert got[4][i] == min(k, sum(sr.SHORT_SIZES[j] for j in s)), msg
+                check_against_oracle_k(amd.oi, metric, qs[i], [docs[j] for j in s], k, got[0][i], got[1][i], got[3][i], got[4][i], msg)
+            sr.assert_routes_agree(got, host, metric, f"{dtype} {metric} k={k} turn {turn}")
 
 
 def test_host_entry_refuses_malformed_scopes(amd):
