@@ -78,6 +78,7 @@ def _load():
         "mir_blocks_search_shared": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_blocks_search_shared_device": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_blocks_search_pieces": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
+        "mir_blocks_search_pieces_indexed": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
         "mir_index_profile": ([vp, i32], i32),
         "mir_index_profile_read": ([vp, i32, vp, vp], i32),
         "mir_index_scan_stats": ([vp, i32, vp], i32),

@@ -24,6 +24,7 @@
 #include "vec_kernels_pieces.h"
 #include "vec_scoped_layout.h"
 #include "vec_pieces_layout.h"
+#include "vec_frozen_layout.h"
 
 namespace mir {
 
@@ -1919,13 +1920,13 @@ int32_t mir_blocks_search_shared(mir_blocks *s_, const double *queries_host, int
 
 // ---- pieces search: scopes that overlap read their common blocks once (vec_pieces_layout.h, vec_kernels_pieces.h)
 
-int32_t mir_blocks_search_pieces(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, int32_t n_pieces,
-                                 const int32_t *piece_ptr_host, const mir_rows *const *blocks_host, const int32_t *rider_ptr_host,
-                                 const int32_t *rider_piece_host, int32_t min_riders, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row,
-                                 double *out_dist, int32_t *out_count, int32_t *out_flags) {
+// The two pieces entries' one host path.  piece_index: NULL, or per piece NULL / the index composed of that piece's rows
+static int32_t run_pieces(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, int32_t n_pieces,
+                          const int32_t *piece_ptr_host, const mir_rows *const *blocks_host, const int32_t *rider_ptr_host,
+                          const int32_t *rider_piece_host, int32_t min_riders, const mir_index *const *piece_index, const SearchOut &user) {
     MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
     mir_index *ix = s_->ix;
-    int32_t rc = check_search_args(ix, queries_host, b, k, metric, out_count);
+    int32_t rc = check_search_args(ix, queries_host, b, k, metric, user.count);
     if (rc != MIR_OK) return rc;
     MIR_REQUIRE(n_pieces >= 0, "n_pieces=%d is negative", n_pieces);
     MIR_REQUIRE(min_riders >= 1, "min_riders=%d must be >= 1", min_riders);
@@ -1939,10 +1940,26 @@ int32_t mir_blocks_search_pieces(mir_blocks *s_, const double *queries_host, int
         rc = check_blocks(ix, piece_ptr_host, n_pieces, "piece", nullptr, blocks_host, all, &piece_rows);
         if (rc != MIR_OK) return rc;
     }
-    PiecesPlan pl;
-    rc = plan_pieces(b, n_pieces, piece_ptr_host, rider_ptr_host, rider_piece_host, min_riders, [&](int t) { return (uint64_t)all[(size_t)t].n; }, &pl);
+    auto index_of = [&](int p) { return piece_index ? const_cast<mir_index *>(piece_index[p]) : nullptr; };
+    for (int p = 0; p < n_pieces; ++p) {
+        const mir_index *px = index_of(p);
+        if (!px) continue;
+        MIR_REQUIRE(px->d == ix->d && px->dtype == ix->dtype && px->device == ix->device,
+                    "the index of piece %d is %d-dimensional dtype %d on device %d, the searcher %d-dimensional dtype %d on device %d", p,
+                    px->d, px->dtype, px->device, ix->d, ix->dtype, ix->device);
+        MIR_REQUIRE(px->row_offset == 0, "the index of piece %d has row_offset %lld: must be 0", p, (long long)px->row_offset);
+        MIR_REQUIRE(px->n > 0, "the index of piece %d holds no row", p);
+        int64_t rows = 0;
+        for (int t = piece_ptr_host[p]; t < piece_ptr_host[p + 1]; ++t) rows += all[(size_t)t].n;
+        MIR_REQUIRE(px->n == rows, "the index of piece %d holds %lld rows, its blocks %lld", p, (long long)px->n, (long long)rows);
+    }
+    IndexedPlan ip;
+    rc = plan_pieces_indexed(b, n_pieces, piece_ptr_host, rider_ptr_host, rider_piece_host, min_riders, [&](int p) { return index_of(p) != nullptr; },
+                             [&](int t) { return (uint64_t)all[(size_t)t].n; }, &ip);
     if (rc != MIR_OK) return rc;
+    const PiecesPlan &pl = ip.pl;
     const int n_occ = pl.n_occ(), n_groups = pl.n_groups(), d = ix->d;
+    const int gs = ip.n_shared_groups(), n_shared = ip.n_shared_occ();  // what the shared search sees: the index groups and their rides lie behind
     MIR_REQUIRE((int64_t)n_occ * k < (1ll << 31), "%d occurrences of k=%d results are 2^31 list entries or more", n_occ, k);
     const size_t nseg_shared = pl.shared_block.size(), nseg_solo = pl.solo_block.size();
     std::vector<mir_block_desc> table(nseg_shared + nseg_solo);  // the groups' blocks, then the solo occurrences'
@@ -1951,16 +1968,17 @@ int32_t mir_blocks_search_pieces(mir_blocks *s_, const double *queries_host, int
     rc = use_device(ix->device, nullptr);
     if (rc != MIR_OK) return rc;
     const SharedPlan plan = shared_plan(d, k, kExactRound, kScopedWaves);
-    const int max_slabs = shared_slab_count(pl.group_ptr.data(), n_groups, plan.qs);
+    const int max_slabs = shared_slab_count(pl.group_ptr.data(), gs, plan.qs);
     const int P_shared = shared_split(ix->num_cus, max_slabs, pl.shared_max_rows, kSharedMaxP);
     const int P_solo = scoped_split(ix->num_cus, pl.n_solo, pl.solo_max_rows, kScopedMaxP);
     const PiecesShape shape{b, k, d, pl.n_shared, pl.n_solo, n_groups, nseg_shared, nseg_solo, P_shared, P_solo, max_slabs};
+    const IndexedShape xshape{ip.n_index_groups, ip.n_index_occ, ip.prefix.size()};
     PiecesBuffers pb;
-    const SearchOut user{out_doc, out_chunk, out_row, out_dist, out_count, out_flags};
+    IndexedBuffers xb;
     return with_workspace(
-        ix, nullptr, true, [&](char *base) { return carve_pieces(pb, base, shape, kExactRound); },
+        ix, nullptr, true, [&](char *base) { return carve_pieces_indexed(pb, xb, base, shape, xshape, kExactRound); },
         [&](Workspace *w, hipStream_t s) {
-            HostPiece in[10];
+            HostPiece in[11];
             int n = 0;
             auto piece = [&](const void *dev, const void *host, size_t bytes) {
                 if (bytes) in[n++] = {dev, host, bytes};
@@ -1975,13 +1993,14 @@ int32_t mir_blocks_search_pieces(mir_blocks *s_, const double *queries_host, int
             piece(pb.solo_ord, pl.solo_ord.data(), nseg_solo * 4);
             piece(pb.q_occ_ptr, pl.q_occ_ptr.data(), ((size_t)b + 1) * 4);
             piece(pb.q_occ, pl.q_occ.data(), (size_t)n_occ * 4);
+            piece(xb.prefix, ip.prefix.data(), ip.prefix.size() * 8);
             return host_round_trip(w, s, in, n, pb.q, pb.in_span, pb.out, user, b, k, [&](const SearchOut &out) -> int32_t {
                 if (n_occ > 0) pieces_gather_kernel<<<dim3((unsigned)n_occ), dim3(64), 0, s>>>(pb.q, pb.occ_query, b, d, pb.q_by_occ);
                 MIR_HIP(hipGetLastError());
-                const size_t sk = (size_t)pl.n_shared * k;  // the solo occurrences' results lie behind the shared ones'
-                if (pl.n_shared > 0) {
-                    ScopedCall c{ix, pb.q_by_occ, pl.n_shared, k, metric, pb.scope_ptr, nullptr, nullptr, pb.table, true, SearchOut{}};
-                    c.n_groups = n_groups; c.group_ptr = pb.group_ptr; c.plan = plan; c.max_slabs = max_slabs;
+                const size_t sk = (size_t)pl.n_shared * k;  // the solo occurrences' results lie behind the shared and the index ones'
+                if (n_shared > 0) {
+                    ScopedCall c{ix, pb.q_by_occ, n_shared, k, metric, pb.scope_ptr, nullptr, nullptr, pb.table, true, SearchOut{}};
+                    c.n_groups = gs; c.group_ptr = pb.group_ptr; c.plan = plan; c.max_slabs = max_slabs;
                     const int32_t rc2 = enqueue_shared(c, P_shared, pb.shared, pb.occ, s);
                     if (rc2 != MIR_OK) return rc2;
                 }
@@ -1991,6 +2010,27 @@ int32_t mir_blocks_search_pieces(mir_blocks *s_, const double *queries_host, int
                     const int32_t rc2 = enqueue_scoped(c, P_solo, pb.solo, occ, s);
                     if (rc2 != MIR_OK) return rc2;
                 }
+                if (ip.n_index_occ > 0) {  // the gathered queries' norms, for the rescore kernel
+                    prep_queries_kernel<<<dim3((unsigned)ip.n_index_occ), dim3(64), 0, s>>>(pb.q_by_occ + (size_t)n_shared * d, ip.n_index_occ, d, 0, 0, nullptr,
+                                                                                             xb.q_sq, xb.q_norm, nullptr, 0);
+                    MIR_HIP(hipGetLastError());
+                }
+                for (int gx = 0; gx < ip.n_index_groups; ++gx) {
+                    // One batched search of the piece's index over its rides, on this call's stream: the index takes a workspace
+                    // of its own and gives it back pending on `s` (mir_index_search_device); no mutex of either handle is held here.
+                    const int g = gs + gx, o0 = pl.group_ptr[(size_t)g], nq = pl.group_ptr[(size_t)g + 1] - o0;
+                    const size_t r0 = (size_t)o0 * k;
+                    const int32_t rc2 = mir_index_search_device(index_of(pl.group_piece[(size_t)g]), pb.q_by_occ + (size_t)o0 * d, nq, k, metric, pb.occ.doc + r0,
+                                                                pb.occ.chunk + r0, pb.occ.row + r0, pb.occ.dist + r0, pb.occ.count + o0, pb.occ.flags + o0, s);
+                    if (rc2 != MIR_OK) return rc2;
+                    const int t0 = pl.scope_ptr[(size_t)g], x0 = o0 - n_shared;
+                    const PiecesRescoreArgs ra{pb.q_by_occ + (size_t)o0 * d, xb.q_sq + x0, xb.q_norm + x0, pb.table + t0, xb.prefix + ip.prefix_ptr[(size_t)gx],
+                                               pl.scope_ptr[(size_t)g + 1] - t0, d, metric, k, pb.occ.count + o0, pb.occ.doc + r0, pb.occ.chunk + r0,
+                                               pb.occ.row + r0, pb.occ.dist + r0};
+                    if (ix->dtype == MIR_DTYPE_F16) pieces_rescore_kernel<_Float16><<<dim3((unsigned)nq), dim3(kPiecesThreads), 0, s>>>(ra);
+                    else pieces_rescore_kernel<float><<<dim3((unsigned)nq), dim3(kPiecesThreads), 0, s>>>(ra);
+                    MIR_HIP(hipGetLastError());
+                }
                 const PiecesMergeArgs ma{pb.q_occ_ptr, pb.q_occ, pl.n_shared, pl.n_solo, pb.occ_base, pb.solo_ptr, pb.solo_ord, k, pb.occ,
                                          pb.cand_key, pb.cand_row, pb.cand_src, out};
                 pieces_merge_kernel<<<dim3((unsigned)b), dim3(kPiecesThreads), 0, s>>>(ma);
@@ -1998,6 +2038,24 @@ int32_t mir_blocks_search_pieces(mir_blocks *s_, const double *queries_host, int
                 return MIR_OK;
             });
         });
+}
+
+int32_t mir_blocks_search_pieces(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, int32_t n_pieces,
+                                 const int32_t *piece_ptr_host, const mir_rows *const *blocks_host, const int32_t *rider_ptr_host,
+                                 const int32_t *rider_piece_host, int32_t min_riders, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row,
+                                 double *out_dist, int32_t *out_count, int32_t *out_flags) {
+    return run_pieces(s_, queries_host, b, k, metric, n_pieces, piece_ptr_host, blocks_host, rider_ptr_host, rider_piece_host, min_riders, nullptr,
+                      SearchOut{out_doc, out_chunk, out_row, out_dist, out_count, out_flags});
+}
+
+// ---- the same with frozen runs: a piece that comes with an index is searched through it (vec_frozen_layout.h)
+
+int32_t mir_blocks_search_pieces_indexed(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, int32_t n_pieces,
+                                         const int32_t *piece_ptr_host, const mir_rows *const *blocks_host, const mir_index *const *piece_index_host,
+                                         const int32_t *rider_ptr_host, const int32_t *rider_piece_host, int32_t min_riders, int32_t *out_doc,
+                                         int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags) {
+    return run_pieces(s_, queries_host, b, k, metric, n_pieces, piece_ptr_host, blocks_host, rider_ptr_host, rider_piece_host, min_riders, piece_index_host,
+                      SearchOut{out_doc, out_chunk, out_row, out_dist, out_count, out_flags});
 }
 
 int32_t mir_index_metric_eval(mir_index *idx, const double *query_host, int32_t metric, double *out_host) {

@@ -18,10 +18,17 @@
 //     against tile by tile through LDS: any number of occurrences, any k, no list capped at an LDS size.
 //   * Every index is clamped where it is read: a count into [0, k], a doc into its occurrence's blocks.
 //   * Stream order is the only synchronisation: the search kernels' results are complete at their kernels' ends.
+//
+// Index occurrences (mir_blocks_search_pieces_indexed, vec_frozen_layout.h): the rides of a piece that
+// comes with an index are answered by ONE batched search of that index, and pieces_rescore_kernel then rewrites each of
+// their reported results in place into what a shared occurrence holds - (block inside the piece, chunk, row inside the
+// block, distance by the per-query routine from the BLOCK's rows) - so the merge reads them as it reads shared ones:
+// ordinal = occ_base + block inside the piece.
 #pragma once
 #include "merge_order.h"
 #include "vec_kernels_scoped.h"
-#include "vec_pieces_layout.h"  // pieces_row_key
+#include "vec_kernels_sieve.h"   // sieve_metric_g16
+#include "vec_frozen_layout.h"  // pieces_row_key, piece_block_of
 
 namespace mir {
 
@@ -36,10 +43,59 @@ __global__ __launch_bounds__(64) void pieces_gather_kernel(const double *__restr
     for (int j = threadIdx.x; j < d; j += 64) q_by_occ[(size_t)o * d + j] = queries[(size_t)q * d + j];
 }
 
+// One index piece's rides: occurrence o = blockIdx.x of the group, its results at [o][k] of the arrays given
+struct PiecesRescoreArgs {
+    const double *q;                // [nq][d] the group's gathered queries
+    const double *q_sq, *q_norm;    // [nq] prep_queries_kernel's
+    const mir_block_desc *blocks;   // [nb] the piece's blocks
+    const int64_t *prefix;          // [nb + 1] their row prefix
+    int nb, d, metric, k;
+    const int32_t *count;           // [nq] the index search's
+    int32_t *doc;                   // [nq][k] in: the index's doc id; out: the block inside the piece
+    int64_t *chunk;                 //         out: the block's chunk id of the row
+    int64_t *row;                   //         in: the index row; out: the row inside its block
+    double *dist;                   //         out: the per-query routine's value
+};
+
+// A 16-lane group per reported result, as the per-query kernel evaluates a row (scoped_topk_kernel: sieve_metric_g16, or
+// exact_metric_wave<T, 16, 8> where d % 4 != 0), from the block's rows and squared norms: mir_blocks_search's bits,
+// whichever route the index took.  Every index read is clamped: the count into [0, k], the row into the piece, the block
+// into the piece's list, the row into its block.
+template <typename T>
+__global__ __launch_bounds__(kPiecesThreads) void pieces_rescore_kernel(PiecesRescoreArgs a) {
+    const int o = blockIdx.x, tid = threadIdx.x, lg = tid & 15, grp = tid >> 4;
+    const int d = a.d, k = a.k;
+    const int cnt = min(max(a.count[o], 0), k);
+    const int64_t total = a.prefix[a.nb];
+    if (a.nb <= 0 || total <= 0) return;
+    const double *qv = a.q + (size_t)o * d;
+    const double q_sq = a.q_sq[o], q_norm = a.q_norm[o];
+    const bool vec4 = (d & 3) == 0;
+    for (int e = grp; e < cnt; e += kPiecesThreads / 16) {  // (e, and all below, uniform within a 16-lane group)
+        const size_t src = (size_t)o * k + e;
+        const int64_t r = min(max(a.row[src], (int64_t)0), total - 1);
+        const int j = piece_block_of(a.prefix, a.nb, r);
+        const mir_block_desc blk = a.blocks[j];
+        if (blk.n <= 0 || blk.emb == nullptr) continue;  // (a row of the piece lies in a block that has rows)
+        const int64_t off = min(r - a.prefix[j], blk.n - 1);
+        const T *rowp = static_cast<const T *>(blk.emb) + (size_t)off * d;
+        const float row_sq = blk.doc_sq[off];
+        double rv;
+        const double dist = vec4 ? sieve_metric_g16<T>(rowp, qv, d, a.metric, row_sq, q_sq, q_norm, lg, &rv)
+                                 : exact_metric_wave<T, 16, 8>(rowp, qv, d, a.metric, row_sq, q_sq, q_norm, lg, &rv);
+        if (lg == 0) {
+            a.doc[src] = j;
+            a.chunk[src] = blk.chunk ? blk.chunk[off] : off;
+            a.row[src] = off;
+            a.dist[src] = dist;
+        }
+    }
+}
+
 struct PiecesMergeArgs {
     const int32_t *q_occ_ptr;  // [b + 1]
     const int32_t *q_occ;      // a query's occurrences
-    int n_shared, n_solo;      // occurrence o < n_shared is shared, else solo occurrence o - n_shared
+    int n_shared, n_solo;      // occurrence o < n_shared is shared or, rescored, an index one; else solo occurrence o - n_shared
     const int32_t *occ_base;   // [n_shared]
     const int32_t *solo_ptr;   // [n_solo + 1]
     const int32_t *solo_ord;

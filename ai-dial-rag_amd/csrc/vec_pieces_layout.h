@@ -65,9 +65,11 @@ struct PiecesPlan {
 // The plan of a call that check_pieces_args has passed.  `rows(t)`: the rows of blocks_host[t], a block that has been checked.
 // Refused: a query whose flattened scope holds 2^32 rows or more (the kernels count positions in 32 bits), or lists 2^31
 // blocks or more (ordinals are int32, as mir_blocks_search's scope_ptr makes them).
-template <typename Rows>
-inline int32_t plan_pieces(int32_t b, int32_t n_pieces, const int32_t *piece_ptr, const int32_t *rider_ptr, const int32_t *rider_piece,
-                           int32_t min_riders, Rows rows, PiecesPlan *out) {
+//
+// plan_pieces_by: the same with the threshold per piece, `min_riders_of(p)` (vec_frozen_layout.h gives an index piece 1).
+template <typename MinRiders, typename Rows>
+inline int32_t plan_pieces_by(int32_t b, int32_t n_pieces, const int32_t *piece_ptr, const int32_t *rider_ptr, const int32_t *rider_piece,
+                              MinRiders min_riders_of, Rows rows, PiecesPlan *out) {
     PiecesPlan &pl = *out;
     pl = PiecesPlan{};
     constexpr uint64_t kLimit = 1ull << 32;
@@ -79,7 +81,7 @@ inline int32_t plan_pieces(int32_t b, int32_t n_pieces, const int32_t *piece_ptr
     pl.group_ptr.push_back(0);
     pl.scope_ptr.push_back(0);
     for (int p = 0; p < n_pieces; ++p) {
-        if (riders[(size_t)p] == 0 || riders[(size_t)p] < min_riders) continue;
+        if (riders[(size_t)p] == 0 || riders[(size_t)p] < min_riders_of(p)) continue;
         group_of[(size_t)p] = pl.n_groups();
         pl.group_piece.push_back(p);
         pl.group_ptr.push_back(pl.group_ptr.back() + riders[(size_t)p]);
@@ -133,6 +135,12 @@ inline int32_t plan_pieces(int32_t b, int32_t n_pieces, const int32_t *piece_ptr
     return MIR_OK;
 }
 
+template <typename Rows>
+inline int32_t plan_pieces(int32_t b, int32_t n_pieces, const int32_t *piece_ptr, const int32_t *rider_ptr, const int32_t *rider_piece,
+                           int32_t min_riders, Rows rows, PiecesPlan *out) {
+    return plan_pieces_by(b, n_pieces, piece_ptr, rider_ptr, rider_piece, [=](int) { return min_riders; }, rows, out);
+}
+
 // ---- the workspace of a call
 struct PiecesShape {
     int b, k, d;
@@ -166,8 +174,22 @@ struct PiecesBuffers {
     SearchOut out;          // staging of the caller's outputs: one contiguous [doc .. flags] span
 };
 
-// Lays a call's buffers out from `base` (null: sizes the slab only) and returns the bytes the slab needs.  `round`: kExactRound
-inline size_t carve_pieces(PiecesBuffers &pb, char *base, const PiecesShape &s, int round) {
+// The index occurrences of a call (mir_blocks_search_pieces_indexed, vec_frozen_layout.h), beside the two
+// structs above: the LAST n_groups of PiecesShape's n_groups are index pieces and the LAST n_occ of its n_shared their
+// rides, which the shared search does not see.
+struct IndexedShape {
+    int n_groups = 0, n_occ = 0;
+    size_t n_prefix = 0;  // entries of the index pieces' row prefixes: per piece its blocks + 1
+};
+
+struct IndexedBuffers {
+    int64_t *prefix;     // [n_prefix], the last array of the input span
+    double *q_sq, *q_norm;  // [n_occ]: the rescore kernel's, of the gathered queries
+};
+
+// Lays a call's buffers out from `base` (null: sizes the slab only) and returns the bytes the slab needs.  `round`: kExactRound.
+// A call without index pieces (carve_pieces) has no byte more or elsewhere than it had before there were any.
+inline size_t carve_pieces_indexed(PiecesBuffers &pb, IndexedBuffers &xb, char *base, const PiecesShape &s, const IndexedShape &xs, int round) {
     Carver c{base};
     const size_t n_occ = (size_t)s.n_shared + s.n_solo, ok = n_occ * s.k;
     pb.q = c.take<double>((size_t)s.b * s.d);
@@ -180,13 +202,16 @@ inline size_t carve_pieces(PiecesBuffers &pb, char *base, const PiecesShape &s, 
     pb.solo_ord = c.take<int32_t>(s.nseg_solo);
     pb.q_occ_ptr = c.take<int32_t>((size_t)s.b + 1);
     pb.q_occ = c.take<int32_t>(n_occ);
+    xb.prefix = xs.n_prefix ? c.take<int64_t>(xs.n_prefix) : nullptr;
     pb.in_span = c.off;
+    xb.q_sq = xs.n_occ ? c.take<double>((size_t)xs.n_occ) : nullptr;
+    xb.q_norm = xs.n_occ ? c.take<double>((size_t)xs.n_occ) : nullptr;
     pb.q_by_occ = c.take<double>(n_occ * s.d);
     auto nested = [&](ScopedBuffers &sb, const ScopedShape &shape) {  // carve_scoped from the next 256-byte boundary on
         c.take<char>(0);
         c.off += carve_scoped(sb, base ? base + c.off : nullptr, shape, round);
     };
-    nested(pb.shared, ScopedShape{s.n_shared, s.k, s.d, s.P_shared, 0, false, true, s.n_groups, s.max_slabs});
+    nested(pb.shared, ScopedShape{s.n_shared - xs.n_occ, s.k, s.d, s.P_shared, 0, false, true, s.n_groups - xs.n_groups, s.max_slabs});
     nested(pb.solo, ScopedShape{s.n_solo, s.k, s.d, s.P_solo, 0, false, true});
     pb.occ = SearchOut{c.take<int32_t>(ok), c.take<int64_t>(ok), c.take<int64_t>(ok), c.take<double>(ok), c.take<int32_t>(n_occ), c.take<int32_t>(n_occ)};
     pb.cand_key = c.take<uint64_t>(ok);
@@ -194,6 +219,11 @@ inline size_t carve_pieces(PiecesBuffers &pb, char *base, const PiecesShape &s, 
     pb.cand_src = c.take<uint32_t>(ok);
     pb.out = carve_out(c, s.b, s.k, true);
     return c.off + 256;
+}
+
+inline size_t carve_pieces(PiecesBuffers &pb, char *base, const PiecesShape &s, int round) {
+    IndexedBuffers none;
+    return carve_pieces_indexed(pb, none, base, s, IndexedShape{}, round);
 }
 
 // ---- the merge's rule: candidate (distance, ordinal, row) by merge_order.h's ascending order with this as the row key

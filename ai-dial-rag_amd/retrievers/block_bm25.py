@@ -161,5 +161,12 @@ class BlockHybrid(CorpusHybrid):
         with self._lock:
             if int(key) not in self.vector or int(key) not in self.keywords:
                 raise KeyError(key)
-            self.vector.remove(key)
+            self.vector.remove(key)  # (thaws a frozen run that holds the key)
             self.keywords.remove(key)
+
+    def freeze(self, keys: Sequence[int]) -> int:
+        """``BlockCorpus.freeze`` of the vector leg: scopes that contain ``keys`` search that stretch through an index."""
+        return self.vector.freeze(keys)
+
+    def thaw(self, token: int) -> None:
+        self.vector.thaw(token)

@@ -9,11 +9,15 @@ position of the document in the request, row), doc ids numbered by position in t
 
 Documents are named by KEYS that count up from 0 and are never reused; while nothing has been removed a key is the
 document's position, so a ``BlockCorpus`` stands where a ``CorpusIndex`` does (``CorpusHybrid``).
+
+A run of documents that is large AND stable - the knowledge base every request sees - can be FROZEN (``freeze``): an index
+is composed of its rows, and every scope that contains the run searches that stretch through the index and the rest
+through the blocks, with the same answer.
 """
 
 import threading
 from itertools import chain
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -21,7 +25,7 @@ from .. import _native as nat
 from ..index_record import Document, RetrievalType, to_metadata_doc
 from ._group_commit import _GroupCommit
 from .corpus_index import check_pass_item, run_grouped_pass
-from .embeddings_index import BlockSearcher, DeviceRows, DocIndex
+from .embeddings_index import BlockSearcher, DeviceIndex, DeviceRows, DocIndex
 from .embeddings_metrics import Metric
 
 __all__ = ["BlockCorpus", "BlockView"]
@@ -34,6 +38,16 @@ __all__ = ["BlockCorpus", "BlockView"]
 # ``share_pieces=True`` uses the same number for the riders of a common run of blocks (``search_pieces``' ``min_riders``):
 # DESIGN.md 3.9 (a) / (b) measured the same two cases with private blocks beside the common ones, with the same outcome.
 DEFAULT_MIN_GROUP = 256
+NEVER_SHARED = 2**31 - 1  # ``search_pieces``' min_riders that shares nothing
+
+
+class FrozenRun(NamedTuple):
+    """A frozen run (``BlockCorpus.freeze``): documents in order, and the index composed of exactly their rows."""
+
+    token: int
+    keys: tuple
+    blocks: tuple  # the block OBJECTS in order, None = a document without rows: an ordinal without rows in the run
+    index: DeviceIndex
 
 
 class BlockView:
@@ -83,6 +97,8 @@ class BlockCorpus:
         self._lock = threading.Lock()
         self._searcher: Optional[BlockSearcher] = None
         self._empty: Optional[DeviceRows] = None  # what an empty document is to the device search: a block of 0 rows
+        self._frozen: Dict[int, FrozenRun] = {}  # token -> run; tokens count up from 0 and are never reused
+        self._next_token = 0
         self._commit = _GroupCommit(self._run_pass, max_batch=max_batch, validate=lambda item: check_pass_item(item, self.d))
 
     # ---- documents --------------------------------------------------------------------------------------------
@@ -109,9 +125,42 @@ class BlockCorpus:
             return key
 
     def remove(self, key: int) -> None:
-        """The corpus forgets the block; its HBM goes with the last view or running search that holds it."""
+        """The corpus forgets the block; its HBM goes with the last view or running search that holds it.  A frozen run
+        that holds the key is thawed: no new scope can name the run."""
         with self._lock:
             del self._docs[int(key)]  # KeyError: unknown or removed
+            for token in [t for t, run in self._frozen.items() if int(key) in run.keys]:
+                del self._frozen[token]
+
+    # ---- frozen runs (DESIGN.md 3.10) ----------------------------------------------------------------------------
+    def freeze(self, keys: Sequence[int]) -> int:
+        """The documents ``keys``, in this order, become a FROZEN RUN -> its token.  An index is composed of their rows
+        (``DeviceIndex.from_rows`` over the blocks that hold rows; a document without rows stays in the run as an ordinal
+        without rows), and from now on every scope that contains ``keys`` as a consecutive sub-list, in this order, is
+        searched through that index for that stretch and through its blocks for the rest: the same answer, the same
+        bits.  For a set that is large AND stable; the blocks stay where they are, so the run's rows are held twice."""
+        keys = tuple(int(k) for k in keys)
+        blocks = tuple(self._blocks_of(keys))  # KeyError for a removed key
+        parts = [b for b in blocks if b is not None]
+        if not parts:
+            raise ValueError("the run holds no row")
+        index = DeviceIndex.from_rows(parts, device=self.device)  # (outside the lock: searches go on meanwhile)
+        with self._lock:
+            if any(self._docs.get(k, self) is not b for k, b in zip(keys, blocks)):
+                raise KeyError("a document of the run was removed while it was frozen")
+            token = self._next_token
+            self._next_token += 1
+            self._frozen[token] = FrozenRun(token, keys, blocks, index)
+            return token
+
+    def thaw(self, token: int) -> None:
+        """The corpus forgets the run's index; its HBM goes with the last running search that holds it."""
+        with self._lock:
+            del self._frozen[int(token)]  # KeyError: unknown or thawed
+
+    def frozen(self) -> List[int]:
+        with self._lock:
+            return list(self._frozen)
 
     def _blocks_of(self, keys: Sequence[int]) -> List[Optional[DeviceRows]]:
         with self._lock:
@@ -126,9 +175,12 @@ class BlockCorpus:
             return key in self._docs
 
     def hbm_bytes(self) -> int:
+        """The blocks and the frozen runs' indexes.  An index is a SECOND copy of its run's rows plus the images its
+        searches scan (``DeviceIndex.hbm_bytes``): freezing trades HBM for time."""
         with self._lock:
             blocks = [b for b in self._docs.values() if b is not None]
-        return sum(b.hbm_bytes() for b in blocks)
+            indexes = [run.index for run in self._frozen.values()]
+        return sum(b.hbm_bytes() for b in blocks) + sum(ix.hbm_bytes() for ix in indexes)
 
     # ---- the device search ------------------------------------------------------------------------------------
     def _shared_groups(self, lists) -> List[List[int]]:
@@ -192,6 +244,59 @@ class BlockCorpus:
         cuts = np.cumsum(np.bincount(query[starts], minlength=n_scopes))[:-1]
         return pieces, [s.tolist() for s in np.split(run_piece, cuts)], np.bincount(run_piece, minlength=len(pieces))
 
+    def _cut_frozen(self, lists, runs: Sequence[FrozenRun], empty):
+        """Frozen runs: every scope cut where it contains a run as a consecutive sub-list in the run's order ->
+        (pieces, piece_indexes, scopes, min_riders) for ``search_pieces_indexed``, or None where no scope contains a run.
+        The runs take their places in the order (more blocks first, then older token), each from left to right every
+        occurrence none of whose entries an earlier match has taken.  What lies between the matches (the GAPS) is cut
+        as the corpus cuts scopes: with ``share_pieces`` by ``_pieces`` over the gaps, else one unshared piece per gap."""
+        order = sorted(runs, key=lambda r: (-len(r.blocks), r.token))
+        run_blocks = [[empty if blk is None else blk for blk in run.blocks] for run in order]
+        run_piece: Dict[int, int] = {}  # token -> its number among the run pieces
+        run_list: List[FrozenRun] = []
+        gaps: List[list] = []
+        shape: List[list] = []  # per scope: (True, run piece) / (False, gap)
+        for s in lists:
+            found = []  # (start, stop, run): the matches in this scope, none overlapping another
+            for run, blocks in zip(order, run_blocks):
+                m, start = len(blocks), 0
+                while start + m <= len(s):  # (list.index and the slice comparison go by identity first, at C speed)
+                    try:
+                        c = s.index(blocks[0], start, len(s) - m + 1)
+                    except ValueError:
+                        break
+                    if s[c:c + m] == blocks and not any(lo < c + m and c < hi for lo, hi, _ in found):
+                        found.append((c, c + m, run))
+                        start = c + m
+                    else:
+                        start = c + 1
+            parts, pos = [], 0
+            for lo, hi, run in sorted(found, key=lambda f: f[0]):
+                if lo > pos:
+                    parts.append((False, len(gaps)))
+                    gaps.append(s[pos:lo])
+                if run.token not in run_piece:
+                    run_piece[run.token] = len(run_list)
+                    run_list.append(run)
+                parts.append((True, run_piece[run.token]))
+                pos = hi
+            if len(s) > pos:
+                parts.append((False, len(gaps)))
+                gaps.append(s[pos:])
+            shape.append(parts)
+        if not run_list:
+            return None
+        cut = self._pieces(gaps) if self.share_pieces and gaps else None
+        if cut is not None and int(cut[2].max()) >= self.min_group:
+            pieces, gap_pieces, min_riders = list(cut[0]), cut[1], self.min_group
+        else:
+            pieces, gap_pieces, min_riders = gaps, [[g] for g in range(len(gaps))], NEVER_SHARED
+        n_plain = len(pieces)
+        pieces = pieces + [[empty if blk is None else blk for blk in run.blocks] for run in run_list]
+        piece_indexes = [None] * n_plain + [run.index for run in run_list]
+        scopes = [[p for is_run, i in parts for p in ([n_plain + i] if is_run else gap_pieces[i])] for parts in shape]
+        return pieces, piece_indexes, scopes, min_riders
+
     def _search_blocks(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence[Optional[DeviceRows]]]):
         """(doc, chunk, dist, count); a scope lists blocks, None = a document without rows.  The one place that touches
         the GPU."""
@@ -201,10 +306,16 @@ class BlockCorpus:
                 self._searcher = BlockSearcher(d, dtype, self.device)
                 self._empty = DeviceRows.from_host(np.zeros((0, d), np.float16 if dtype == nat.DTYPE_F16 else np.float32), None, self.device)
             searcher, empty = self._searcher, self._empty
+            runs = list(self._frozen.values())  # (the runs, their indexes with them: alive across the call)
         if searcher is None:  # no document with rows yet
             b = len(queries)
             return np.zeros((b, k), np.int32), np.zeros((b, k), np.int64), np.zeros((b, k)), np.zeros(b, np.int32)
         lists = [[empty if blk is None else blk for blk in s] for s in scopes]
+        if runs:  # (a corpus without frozen runs makes the calls it always made)
+            cut = self._cut_frozen(lists, runs, empty)
+            if cut is not None:
+                doc, chunk, _row, dist, cnt, _flags = searcher.search_pieces_indexed(queries, k, metric, *cut[:2], cut[2], cut[3])
+                return doc, chunk, dist, cnt
         if self.share_pieces:
             cut = self._pieces(lists)
             if cut is not None and int(cut[2].max()) >= self.min_group:

@@ -190,6 +190,16 @@ class BlockSearcher:
         order.  A piece named ``min_riders`` times or more in the call is read once per slab of its riders
         (``search_shared``'s arithmetic), the others per query (``search``'s).  Returns the six arrays of ``search`` over
         the flattened scopes: doc = the ordinal of the block in the flattened scope."""
+        return self.search_pieces_indexed(queries, k, metric, pieces, None, scopes, min_riders)
+
+    def search_pieces_indexed(self, queries: np.ndarray, k: int, metric, pieces: Sequence[Sequence["DeviceRows"]],
+                              piece_indexes: Optional[Sequence[Optional["DeviceIndex"]]], scopes: Sequence[Sequence[int]],
+                              min_riders: int) -> Tuple[np.ndarray, ...]:
+        """``search_pieces`` where a piece may be a FROZEN RUN: ``piece_indexes[p]`` is None or the ``DeviceIndex`` composed
+        (``from_rows``) of exactly ``pieces[p]``'s blocks that hold rows, in their order.  All rides of such a piece are
+        answered by one batched search of its index, whatever ``min_riders`` says; the answer, its distances' bits
+        included, stays ``search``'s over the flattened scopes.  That the index was composed of these
+        very blocks is TRUSTED (``BlockCorpus.freeze`` makes it so).  ``piece_indexes=None``: ``search_pieces``' call."""
         q = nat.as_f64_queries(queries, self.d)
         b = q.shape[0]
         code = nat.METRIC_CODES[Metric(metric).value]
@@ -203,8 +213,15 @@ class BlockSearcher:
             raise ValueError("a piece index does not fit int32")
         riders = riders.astype(np.int32)
         out = _result_arrays(b, k)
-        nat.check(nat.lib.mir_blocks_search_pieces(self._h, nat.ptr(q), b, k, code, len(pieces), nat.ptr(pp), table, nat.ptr(rp), nat.ptr(riders),
-                                                   int(min_riders), *map(nat.ptr, out)))
+        if piece_indexes is None:
+            nat.check(nat.lib.mir_blocks_search_pieces(self._h, nat.ptr(q), b, k, code, len(pieces), nat.ptr(pp), table, nat.ptr(rp), nat.ptr(riders),
+                                                       int(min_riders), *map(nat.ptr, out)))
+            return out
+        if len(piece_indexes) != len(pieces):
+            raise ValueError(f"{len(piece_indexes)} indexes for {len(pieces)} pieces")
+        indexes = (C.c_void_p * max(len(pieces), 1))(*[None if ix is None else ix.handle for ix in piece_indexes])  # (piece_indexes: alive across the call)
+        nat.check(nat.lib.mir_blocks_search_pieces_indexed(self._h, nat.ptr(q), b, k, code, len(pieces), nat.ptr(pp), table, indexes, nat.ptr(rp),
+                                                           nat.ptr(riders), int(min_riders), *map(nat.ptr, out)))
         return out
 
     def search_shared_device(self, q_ptr: int, b: int, k: int, metric, n_groups: int, group_ptr_ptr: int, scope_ptr_ptr: int, table_ptr: int,

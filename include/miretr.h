@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: BM25 route report, ADDED without a new number (a test hook; nothing of ABI 6 changed): mir_bm25_last_routes;
+#define MIR_ABI_VERSION 6 /* 6: frozen runs, ADDED without a new number (nothing of ABI 6 changed): mir_blocks_search_pieces_indexed;
+                            6: BM25 route report, ADDED without a new number (a test hook; nothing of ABI 6 changed): mir_bm25_last_routes;
                             6: block BM25, ADDED without a new number (nothing of ABI 6 changed): mir_bm25_doc_create / _info / _destroy,
                                mir_bm25_blocks_create / _destroy / _scope_create / _scope_info / _scope_idf / _scope_destroy /
                                _scores / _search;
@@ -289,6 +290,38 @@ int32_t mir_blocks_search_pieces(mir_blocks *s, const double *queries_host, int3
                                  const int32_t *rider_ptr_host, const int32_t *rider_piece_host, int32_t min_riders,
                                  int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist,
                                  int32_t *out_count, int32_t *out_flags);
+
+/* Pieces search with frozen runs (added within ABI 6): a piece that is large AND stable is searched through an index
+ * (csrc/vec_frozen_layout.h, csrc/vec_kernels_pieces.h).  A FROZEN RUN is an ordered list of blocks together
+ * with a mir_index composed of exactly those blocks' rows in that order (mir_index_create_from_rows over the blocks that
+ * hold rows, row_offset 0).  piece_index_host: mir_index*[n_pieces]; entry p is NULL - an ordinary piece - or the index of
+ * the frozen run that piece p's blocks are.  A NULL array is all entries NULL, and then the call IS
+ * mir_blocks_search_pieces: the same host path, the same result bit for bit.
+ * The answer is unchanged - what mir_blocks_search returns for the flattened scope: out_doc = the block's ordinal in the
+ * flattened scope, out_chunk, out_row = the row inside its block, out_count[q] = min(k, L_q), out_flags 0, any k >= 1.
+ * Only the route differs: ALL rides of an index piece in the call are answered by ONE batched search of its index (the
+ * sieve, the int8 or bf16 filter, a small index's scan, the exact pass: whatever mir_index_search would take for that many
+ * queries and that k), enqueued on the call's stream.  Index pieces ignore min_riders: one with a ride or more is always
+ * searched through its index, one with none is not searched.
+ * Bits and order: every (ride, result) the index reports is evaluated once more by mir_blocks_search's routine from the
+ * BLOCK's rows and squared norms, so every distance written has mir_blocks_search's bits whichever route the index took,
+ * and bit-identical rows in an index piece and in a block tie exactly and go by (ordinal, row).  The caveat is the shared
+ * route's: selection inside an index piece is by the index route's values, so rows whose distances tie to the last bits
+ * at the k-th place of that piece may be chosen differently than mir_blocks_search would choose them; reported rows are
+ * always in the order of their written distances.
+ * Returns MIR_ERR_INVALID, before anything is launched and with the outputs untouched, for everything
+ * mir_blocks_search_pieces refuses and for an index whose d, dtype or device differs from the searcher's, whose row count
+ * differs from the sum of its piece's blocks' rows, whose row_offset is not 0, or that holds no row.  The entry CANNOT
+ * verify that the index was composed of these very blocks: that is TRUSTED, as the _device forms trust their tables
+ * (an index of other rows of the same count gives wrong rows, never a read outside the blocks: every row it reports is
+ * clamped into the piece).  The caller keeps the indexes and the blocks alive until the call returns; other searches of
+ * the same index may run meanwhile.  Host form only. */
+int32_t mir_blocks_search_pieces_indexed(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                                         int32_t n_pieces, const int32_t *piece_ptr_host, const mir_rows *const *blocks_host,
+                                         const mir_index *const *piece_index_host, const int32_t *rider_ptr_host,
+                                         const int32_t *rider_piece_host, int32_t min_riders, int32_t *out_doc,
+                                         int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
+                                         int32_t *out_flags);
 
 /* Benchmark instrumentation: when enabled, every launch of the scan kernel (the
  * dominant, HBM-streaming kernel) is bracketed by HIP events on the stream it
