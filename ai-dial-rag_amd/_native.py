@@ -79,6 +79,12 @@ def _load():
         "mir_blocks_search_shared_device": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_blocks_search_pieces": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
         "mir_blocks_search_pieces_indexed": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
+        "mir_fanout_create": ([i64, vp, vp, vp, i32, vp], i32),
+        "mir_fanout_info": ([vp, vp, vp, vp, vp], i32),
+        "mir_fanout_destroy": ([vp], i32),
+        "mir_fanout_get_desc": ([vp, vp], i32),
+        "mir_blocks_search_expanded": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "mir_blocks_search_expanded_device": ([vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_index_profile": ([vp, i32], i32),
         "mir_index_profile_read": ([vp, i32, vp, vp], i32),
         "mir_index_scan_stats": ([vp, i32, vp], i32),
@@ -152,6 +158,13 @@ class BlockDesc(C.Structure):
     """mir_block_desc: one row block as the device form of the block search reads it (device pointers)."""
 
     _fields_ = [("emb", C.c_void_p), ("doc_sq", C.c_void_p), ("chunk", C.c_void_p), ("n", C.c_int64)]
+
+
+class FanoutDesc(C.Structure):
+    """mir_fanout_desc: one block's fan-out as the device form of the expanded block search reads it (device pointers);
+    all null = the block has no fan-out."""
+
+    _fields_ = [("rep_ptr", C.c_void_p), ("rep_chunk", C.c_void_p), ("rep_pos", C.c_void_p), ("n", C.c_int64)]
 
 
 def last_error() -> str:

@@ -22,9 +22,11 @@
 #include "vec_kernels_scoped.h"
 #include "vec_kernels_shared.h"
 #include "vec_kernels_pieces.h"
+#include "vec_kernels_expand.h"
 #include "vec_scoped_layout.h"
 #include "vec_pieces_layout.h"
 #include "vec_frozen_layout.h"
+#include "vec_fanout_layout.h"
 
 namespace mir {
 
@@ -147,6 +149,18 @@ struct mir_rows {
     void *d_emb = nullptr;       // n x d, as given (float32 or float16)
     int64_t *d_chunk = nullptr;  // n
     float *d_docsq = nullptr;    // n: float32 squared norms, bit for bit an index's d_docsq of these rows (mir_blocks_search)
+    int64_t hbm_bytes = 0;
+};
+
+// The fan-out of one row block resident in HBM (mir_fanout_create; vec_fanout_layout.h): stored row r stands for the expanded
+// rows at positions d_pos[d_ptr[r] .. d_ptr[r + 1]) with the chunk ids d_chunk[...] there.
+struct mir_fanout {
+    int device = 0;
+    int64_t n = 0;               // stored rows
+    int64_t R = 0;               // replicas = rows of the expanded block
+    int64_t *d_ptr = nullptr;    // n + 1 (one entry, 0, for an empty block: a fan-out's rep_ptr is never null)
+    int64_t *d_chunk = nullptr;  // R
+    int64_t *d_pos = nullptr;    // R
     int64_t hbm_bytes = 0;
 };
 
@@ -1625,7 +1639,7 @@ int32_t mir_index_search(mir_index *idx, const double *queries_host, int32_t b, 
 }  // extern "C"
 
 // ---------------------------------------------------------------- scoped search (vec_kernels_scoped.h, vec_kernels_shared.h)
-// Six entries, one host path: an entry checks its arguments and fills a ScopedCall, run_scoped does the rest.
+// Eight entries, one host path: an entry checks its arguments and fills a ScopedCall, run_scoped does the rest.
 
 namespace mir {
 
@@ -1645,6 +1659,8 @@ struct ScopedCall {
     const int32_t *group_ptr = nullptr;
     SharedPlan plan{};
     int max_slabs = 0;
+    bool expanded = false;         // the expanded block search: `out` takes the expansion of the stream kernel's lists through
+    const mir_fanout_desc *fan_table = nullptr;  // the fan-outs, one descriptor per block of `table` (null: none has one)
 };
 
 static int32_t check_scoped_args(const mir_index *ix, const void *queries, int32_t b, int32_t k, int32_t metric,
@@ -1749,7 +1765,7 @@ static int32_t enqueue_shared(const ScopedCall &c, int P, const ScopedBuffers &s
 }
 
 // Device, split, workspace, launches: a device form's on the caller's arrays and stream; a host form's on the workspace's copies, which
-// go in as ONE copy of the span carved in the order [q | group_ptr | scope_ptr | seg_begin | seg_end or table] (host_round_trip)
+// go in as ONE copy of the span carved in the order [q | group_ptr | scope_ptr | seg_begin | seg_end or table | fan-out table] (host_round_trip)
 static int32_t run_scoped(const ScopedCall &c) {
     mir_index *ix = c.ix;
     const int32_t rc = use_device(ix->device, nullptr);
@@ -1758,25 +1774,36 @@ static int32_t run_scoped(const ScopedCall &c) {
     const int n_scopes = shared ? c.n_groups : c.b;
     const int P = shared ? shared_split(ix->num_cus, c.max_slabs, c.rows.max_rows, kSharedMaxP) : scoped_split(ix->num_cus, c.b, c.rows.max_rows, kScopedMaxP);
     const size_t nseg = c.rows.nseg;
-    const ScopedShape shape{c.b, c.k, ix->d, P, nseg, c.host_api, c.blocks, c.n_groups, c.max_slabs};
+    const ScopedShape shape{c.b, c.k, ix->d, P, nseg, c.host_api, c.blocks, c.n_groups, c.max_slabs, c.expanded};
     ScopedBuffers sb;
-    auto enqueue = [&](const ScopedCall &on_device, const SearchOut &out, hipStream_t s) {
-        return shared ? enqueue_shared(on_device, P, sb, out, s) : enqueue_scoped(on_device, P, sb, out, s);
+    SearchOut stored{};  // the expanded search: the stream kernel's lists of stored rows, in the workspace
+    auto enqueue = [&](const ScopedCall &on_device, const SearchOut &out, hipStream_t s) -> int32_t {
+        if (shared) return enqueue_shared(on_device, P, sb, out, s);
+        if (!c.expanded) return enqueue_scoped(on_device, P, sb, out, s);
+        const int32_t rc2 = enqueue_scoped(on_device, P, sb, stored, s);
+        if (rc2 != MIR_OK) return rc2;
+        const ExpandArgs ea{on_device.scope_ptr, on_device.table, on_device.fan_table, c.k, stored.doc, stored.row, stored.dist, stored.count,
+                            out.doc, out.chunk, out.row, out.dist, out.count, out.flags};
+        expand_topk_kernel<<<dim3((unsigned)c.b), dim3(kExpandThreads), 0, s>>>(ea);
+        MIR_HIP(hipGetLastError());
+        return MIR_OK;
     };
     return with_workspace(
-        ix, c.stream, c.host_api, [&](char *base) { return carve_scoped(sb, base, shape, kExactRound); },
+        ix, c.stream, c.host_api,
+        [&](char *base) { return c.expanded ? carve_expanded(sb, stored, base, shape, kExactRound) : carve_scoped(sb, base, shape, kExactRound); },
         [&](Workspace *w, hipStream_t s) {
             if (!c.host_api) return enqueue(c, c.out, s);
-            HostPiece in[5];
+            HostPiece in[6];
             int n = 0;
             in[n++] = {sb.q, c.queries, (size_t)c.b * ix->d * sizeof(double)};
             if (shared) in[n++] = {sb.group_ptr, c.group_ptr, ((size_t)n_scopes + 1) * 4};
             in[n++] = {sb.scope_ptr, c.scope_ptr, ((size_t)n_scopes + 1) * 4};
             if (nseg) in[n++] = c.blocks ? HostPiece{sb.table, c.table, nseg * sizeof(mir_block_desc)} : HostPiece{sb.seg_begin, c.seg_begin, nseg * 8};
             if (nseg && !c.blocks) in[n++] = {sb.seg_end, c.seg_end, nseg * 8};
+            if (nseg && c.expanded) in[n++] = {sb.fan_table, c.fan_table, nseg * sizeof(mir_fanout_desc)};
             ScopedCall dev = c;  // the call as the kernels see it
             dev.queries = sb.q; dev.group_ptr = sb.group_ptr; dev.scope_ptr = sb.scope_ptr;
-            dev.seg_begin = sb.seg_begin; dev.seg_end = sb.seg_end; dev.table = sb.table;
+            dev.seg_begin = sb.seg_begin; dev.seg_end = sb.seg_end; dev.table = sb.table; dev.fan_table = sb.fan_table;
             return host_round_trip(w, s, in, n, sb.q, sb.in_span, sb.out, c.out, c.b, c.k, [&](const SearchOut &out) { return enqueue(dev, out, s); });
         });
 }
@@ -1869,6 +1896,111 @@ int32_t mir_blocks_search(mir_blocks *s_, const double *queries_host, int32_t b,
     rc = check_blocks(s_->ix, scope_ptr_host, b, "query", nullptr, blocks_host, table, &c.rows);
     if (rc != MIR_OK) return rc;
     c.host_api = true; c.table = table.data();
+    return run_scoped(c);
+}
+
+// ---- expanded block search: rows stored once, hits expanded to the rows they stand for (vec_fanout_layout.h, vec_kernels_expand.h)
+
+int32_t mir_fanout_create(int64_t n_rows, const int64_t *rep_ptr_host, const int64_t *rep_chunk_host, const int64_t *rep_pos_host,
+                          int32_t device, mir_fanout **out) {
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    int32_t rc = check_fanout(n_rows, rep_ptr_host, rep_chunk_host, rep_pos_host);
+    if (rc != MIR_OK) return rc;
+    rc = use_device(device, nullptr);
+    if (rc != MIR_OK) return rc;
+    mir_fanout *f = new (std::nothrow) mir_fanout();
+    MIR_REQUIRE(f != nullptr, "out of host memory");
+    f->device = device; f->n = n_rows; f->R = rep_ptr_host[n_rows];
+    const size_t pb = ((size_t)n_rows + 1) * 8, rb = (size_t)f->R * 8;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&f->d_ptr), pb);
+    if (e == hipSuccess) e = hipMemcpy(f->d_ptr, rep_ptr_host, pb, hipMemcpyHostToDevice);
+    if (f->R > 0) {
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&f->d_chunk), rb);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&f->d_pos), rb);
+        if (e == hipSuccess) e = hipMemcpy(f->d_chunk, rep_chunk_host, rb, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(f->d_pos, rep_pos_host, rb, hipMemcpyHostToDevice);
+    }
+    f->hbm_bytes = (int64_t)(pb + 2 * rb);
+    if (e != hipSuccess) {
+        set_error("mir_fanout_create: %s", hipGetErrorString(e));
+        mir_fanout_destroy(f);
+        return MIR_ERR_HIP;
+    }
+    *out = f;
+    return MIR_OK;
+}
+
+int32_t mir_fanout_info(const mir_fanout *f, int64_t *n_rows, int64_t *n_replicas, int32_t *device, int64_t *hbm_bytes) {
+    MIR_REQUIRE(f != nullptr, "handle is NULL");
+    if (n_rows) *n_rows = f->n;
+    if (n_replicas) *n_replicas = f->R;
+    if (device) *device = f->device;
+    if (hbm_bytes) *hbm_bytes = f->hbm_bytes;
+    return MIR_OK;
+}
+
+int32_t mir_fanout_get_desc(const mir_fanout *f, mir_fanout_desc *out) {
+    MIR_REQUIRE(f != nullptr, "handle is NULL");
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = mir_fanout_desc{f->d_ptr, f->d_chunk, f->d_pos, f->n};
+    return MIR_OK;
+}
+
+int32_t mir_fanout_destroy(mir_fanout *f) {
+    if (!f) return MIR_OK;
+    (void)hipSetDevice(f->device);
+    (void)hipFree(f->d_ptr);
+    (void)hipFree(f->d_chunk);
+    (void)hipFree(f->d_pos);
+    delete f;
+    return MIR_OK;
+}
+
+int32_t mir_blocks_search_expanded_device(mir_blocks *s_, const double *queries_device, int32_t b, int32_t k, int32_t metric,
+                                          const int32_t *scope_ptr_device, const mir_block_desc *table_device,
+                                          const mir_fanout_desc *fanout_table_device, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row,
+                                          double *out_dist, int32_t *out_count, int32_t *out_flags, void *stream_) {
+    MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
+    int32_t rc = check_scoped_args(s_->ix, queries_device, b, k, metric, scope_ptr_device, out_count);
+    if (rc != MIR_OK || b == 0) return rc;
+    ScopedCall c{s_->ix, queries_device, b, k, metric, scope_ptr_device, nullptr, nullptr, table_device, true,
+                 {out_doc, out_chunk, out_row, out_dist, out_count, out_flags}, static_cast<hipStream_t>(stream_)};
+    c.expanded = true; c.fan_table = fanout_table_device;
+    return run_scoped(c);
+}
+
+int32_t mir_blocks_search_expanded(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                                   const int32_t *scope_ptr_host, const mir_rows *const *blocks_host, const mir_fanout *const *fanouts_host,
+                                   int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
+                                   int32_t *out_flags) {
+    MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
+    int32_t rc = check_scoped_args(s_->ix, queries_host, b, k, metric, scope_ptr_host, out_count);
+    if (rc != MIR_OK || b == 0) return rc;
+    std::vector<mir_block_desc> table;
+    ScopedCall c{s_->ix, queries_host, b, k, metric, scope_ptr_host, nullptr, nullptr, nullptr, true,
+                 {out_doc, out_chunk, out_row, out_dist, out_count, out_flags}};
+    rc = check_blocks(s_->ix, scope_ptr_host, b, "query", nullptr, blocks_host, table, &c.rows);
+    if (rc != MIR_OK) return rc;
+    // the fan-outs against their blocks, while they become the descriptor table the expansion reads; the expanded scopes' rows
+    std::vector<mir_fanout_desc> fan_table(table.size(), mir_fanout_desc{nullptr, nullptr, nullptr, 0});
+    for (int i = 0; i < b; ++i) {
+        uint64_t rows = 0;
+        for (int t = scope_ptr_host[i]; t < scope_ptr_host[i + 1]; ++t) {
+            const mir_fanout *f = fanouts_host ? fanouts_host[t] : nullptr;
+            const int ordinal = t - scope_ptr_host[i];
+            if (f) {
+                MIR_REQUIRE(f->n == blocks_host[t]->n && f->device == blocks_host[t]->device,
+                            "the fan-out of block %d of query %d is of %lld stored rows on device %d, the block holds %lld on device %d", ordinal, i,
+                            (long long)f->n, f->device, (long long)blocks_host[t]->n, blocks_host[t]->device);
+                fan_table[(size_t)t] = mir_fanout_desc{f->d_ptr, f->d_chunk, f->d_pos, f->n};
+            }
+            rows += (uint64_t)(f ? f->R : blocks_host[t]->n);
+            MIR_REQUIRE(rows < (1ull << 32), "the expanded scope of query %d holds 2^32 rows or more", i);
+        }
+    }
+    c.host_api = true; c.table = table.data();
+    c.expanded = true; c.fan_table = fan_table.data();
     return run_scoped(c);
 }
 

@@ -142,10 +142,11 @@ struct ScopedBuffers {
     int64_t *seg_begin;   // host API: [nseg]
     int64_t *seg_end;     // host API: [nseg]
     mir_block_desc *table;  // host API of the block search: [nseg], in place of seg_begin / seg_end
+    mir_fanout_desc *fan_table;  // host API of the expanded block search: [nseg] behind table (vec_fanout_layout.h)
     int32_t *group_ptr;   // host API of the shared search: [n_groups + 1], in front of scope_ptr (then [n_groups + 1] too)
     SharedSlab *slabs;    // the shared search: [max_slabs], written by shared_slabs_kernel, with
     int32_t *n_slabs;     //   their number
-    size_t in_span;       // host API: bytes from q to the end of seg_end / table (one copy in)
+    size_t in_span;       // host API: bytes from q to the end of seg_end / table / fan_table (one copy in)
     double *q_sq, *q_norm;
     unsigned long long *arrive;  // [ceil(b / 2)] words = b counters, zeroed by the prep kernel
     double *bound_dist;
@@ -161,6 +162,7 @@ struct ScopedShape {
     size_t nseg;     // host API: segments of all scopes
     bool host_api, blocks;  // blocks: a descriptor table in place of seg_begin / seg_end
     int n_groups = -1, max_slabs = 0;
+    bool fanout = false;  // the expanded block search: a fan-out descriptor table behind the block table
 };
 
 // Lays a call's buffers out from `base` (null: sizes the slab only) and returns the bytes the slab needs.  `round`: kExactRound
@@ -173,6 +175,7 @@ inline size_t carve_scoped(ScopedBuffers &sb, char *base, const ScopedShape &s, 
     sb.seg_begin = s.host_api && !s.blocks ? c.take<int64_t>(s.nseg) : nullptr;
     sb.seg_end = s.host_api && !s.blocks ? c.take<int64_t>(s.nseg) : nullptr;
     sb.table = s.host_api && s.blocks ? c.take<mir_block_desc>(s.nseg) : nullptr;
+    sb.fan_table = s.host_api && s.fanout ? c.take<mir_fanout_desc>(s.nseg) : nullptr;
     sb.in_span = c.off;
     sb.q_sq = c.take<double>(s.b);
     sb.q_norm = c.take<double>(s.b);

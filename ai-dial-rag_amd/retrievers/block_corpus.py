@@ -13,6 +13,12 @@ document's position, so a ``BlockCorpus`` stands where a ``CorpusIndex`` does (`
 A run of documents that is large AND stable - the knowledge base every request sees - can be FROZEN (``freeze``): an index
 is composed of its rows, and every scope that contains the run searches that stretch through the index and the rest
 through the blocks, with the same answer.
+
+A by-page document can be held PAGED (``add(PagedDocIndex)``): every page row once, with the fan-out that says which rows of
+the by-page index it stands for.  Callers see the by-page index's answer (``chunk_id`` = the replica's); a call that lists a
+paged block takes ``BlockSearcher.search_expanded`` for all its queries.  The shared, pieces and frozen
+routes do not take fanned-out blocks yet: such a call goes per query whatever ``share_scopes`` / ``share_pieces`` say, and
+``freeze`` refuses a paged document.
 """
 
 import threading
@@ -25,7 +31,7 @@ from .. import _native as nat
 from ..index_record import Document, RetrievalType, to_metadata_doc
 from ._group_commit import _GroupCommit
 from .corpus_index import check_pass_item, run_grouped_pass
-from .embeddings_index import BlockSearcher, DeviceIndex, DeviceRows, DocIndex
+from .embeddings_index import BlockSearcher, DeviceFanout, DeviceIndex, DeviceRows, DocIndex, PagedDocIndex
 from .embeddings_metrics import Metric
 
 __all__ = ["BlockCorpus", "BlockView"]
@@ -105,9 +111,27 @@ class BlockCorpus:
     def _upload(self, doc: DocIndex) -> DeviceRows:
         return DeviceRows.from_host(np.asarray(doc.embeddings), np.asarray(doc.chunk_ids, dtype=np.int64), self.device)
 
+    def _upload_paged(self, doc: PagedDocIndex) -> DeviceRows:
+        fanout = DeviceFanout.from_host(doc.rep_ptr, doc.rep_chunk, doc.rep_pos, self.device)  # (ValueError before anything is uploaded)
+        block = DeviceRows.from_host(np.asarray(doc.embeddings), None, self.device)
+        block.fanout = fanout
+        return block
+
     def add(self, doc) -> int:
-        """``doc``: a ``DocIndex`` (uploaded once as a block) or a ``DeviceRows`` (adopted, not copied) -> its key."""
-        if isinstance(doc, DeviceRows):
+        """``doc``: a ``DocIndex`` (uploaded once as a block), a ``DeviceRows`` (adopted, not copied), a ``PagedDocIndex``
+        (its stored rows uploaded once, with their fan-out) or a ``(DeviceRows, DeviceFanout)`` pair to adopt -> its key.
+        A block and its fan-out are held and dropped together: the block carries it (``DeviceRows.fanout``)."""
+        if isinstance(doc, tuple):
+            block, fanout = doc
+            if fanout.n != block.n or fanout.device != block.device:
+                raise ValueError(f"the fan-out is of {fanout.n} stored rows on device {fanout.device}, the block holds {block.n} on device {block.device}")
+            if block.fanout is not None and block.fanout is not fanout:
+                raise ValueError("the block already carries another fan-out")
+            block.fanout = fanout
+            block = block if block.n > 0 else None
+        elif isinstance(doc, PagedDocIndex):
+            block = self._upload_paged(doc) if len(doc.embeddings) > 0 else None
+        elif isinstance(doc, DeviceRows):
             block = doc if doc.n > 0 else None
         else:
             block = self._upload(doc) if len(doc.embeddings) > 0 else None
@@ -141,6 +165,9 @@ class BlockCorpus:
         bits.  For a set that is large AND stable; the blocks stay where they are, so the run's rows are held twice."""
         keys = tuple(int(k) for k in keys)
         blocks = tuple(self._blocks_of(keys))  # KeyError for a removed key
+        paged = [k for k, b in zip(keys, blocks) if getattr(b, "fanout", None) is not None]
+        if paged:  # (an index holds rows, not fan-outs: DESIGN.md 3.11)
+            raise ValueError(f"documents {paged} are paged (their blocks have a fan-out): a frozen run cannot hold them")
         parts = [b for b in blocks if b is not None]
         if not parts:
             raise ValueError("the run holds no row")
@@ -175,12 +202,13 @@ class BlockCorpus:
             return key in self._docs
 
     def hbm_bytes(self) -> int:
-        """The blocks and the frozen runs' indexes.  An index is a SECOND copy of its run's rows plus the images its
+        """The blocks, their fan-outs and the frozen runs' indexes.  An index is a SECOND copy of its run's rows plus the images its
         searches scan (``DeviceIndex.hbm_bytes``): freezing trades HBM for time."""
         with self._lock:
             blocks = [b for b in self._docs.values() if b is not None]
             indexes = [run.index for run in self._frozen.values()]
-        return sum(b.hbm_bytes() for b in blocks) + sum(ix.hbm_bytes() for ix in indexes)
+        fanouts = [f for f in (getattr(b, "fanout", None) for b in blocks) if f is not None]
+        return sum(b.hbm_bytes() for b in blocks) + sum(f.hbm_bytes() for f in fanouts) + sum(ix.hbm_bytes() for ix in indexes)
 
     # ---- the device search ------------------------------------------------------------------------------------
     def _shared_groups(self, lists) -> List[List[int]]:
@@ -311,6 +339,10 @@ class BlockCorpus:
             b = len(queries)
             return np.zeros((b, k), np.int32), np.zeros((b, k), np.int64), np.zeros((b, k)), np.zeros(b, np.int32)
         lists = [[empty if blk is None else blk for blk in s] for s in scopes]
+        fanouts = [[getattr(blk, "fanout", None) for blk in s] for s in lists]
+        if any(f is not None for fs in fanouts for f in fs):  # a paged block: the expanded route for the whole call
+            doc, chunk, _row, dist, cnt, _flags = searcher.search_expanded(queries, k, metric, lists, fanouts)
+            return doc, chunk, dist, cnt
         if runs:  # (a corpus without frozen runs makes the calls it always made)
             cut = self._cut_frozen(lists, runs, empty)
             if cut is not None:

@@ -60,6 +60,7 @@ class DeviceRows:
 
     def __init__(self, handle: C.c_void_p, n: int, d: int, device: int, dtype: int = nat.DTYPE_F32):
         self._h, self.n, self.d, self.device, self.dtype = handle, n, d, device, dtype
+        self.fanout: Optional["DeviceFanout"] = None  # set where the block's rows are stored once (``BlockCorpus.add``): held and dropped with it
 
     @classmethod
     def from_host(cls, emb: np.ndarray, chunk_ids=None, device: int = 0):
@@ -95,6 +96,57 @@ class DeviceRows:
     def close(self):
         if self._h:
             nat.lib.mir_rows_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceFanout:
+    """Owner of one ``mir_fanout`` handle: the fan-out of one ``DeviceRows`` block resident in HBM (csrc/vec_fanout_layout.h).
+    Stored row r stands for the rows of the EXPANDED block at positions ``rep_pos[rep_ptr[r]:rep_ptr[r + 1]]``, with the chunk
+    ids ``rep_chunk[...]`` there."""
+
+    def __init__(self, handle: C.c_void_p, n: int, replicas: int, device: int):
+        self._h, self.n, self.replicas, self.device = handle, n, replicas, device
+
+    @classmethod
+    def from_host(cls, rep_ptr, rep_chunk, rep_pos, device: int = 0):
+        """ValueError, before the device is touched, for a map that is no valid fan-out (``check_fanout``)."""
+        ptr = np.ascontiguousarray(rep_ptr, dtype=np.int64).reshape(-1)
+        chunk = np.ascontiguousarray(rep_chunk, dtype=np.int64).reshape(-1)
+        pos = np.ascontiguousarray(rep_pos, dtype=np.int64).reshape(-1)
+        if len(ptr) < 1:
+            raise ValueError("rep_ptr holds no entry (want n + 1)")
+        n = len(ptr) - 1
+        if len(chunk) != len(pos) or int(ptr[n]) != len(pos):
+            raise ValueError(f"{len(chunk)} replica chunk ids, {len(pos)} positions, rep_ptr ends at {int(ptr[n])}")
+        h = C.c_void_p()
+        nat.check(nat.lib.mir_fanout_create(n, nat.ptr(ptr), nat.ptr(chunk), nat.ptr(pos), device, C.byref(h)))
+        return cls(h, n, len(pos), device)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def hbm_bytes(self) -> int:
+        b = C.c_int64(0)
+        nat.check(nat.lib.mir_fanout_info(self._h, None, None, None, C.byref(b)))
+        return int(b.value)
+
+    def desc(self) -> Tuple[int, int, int, int]:
+        """(rep_ptr, rep_chunk, rep_pos, n): the device pointers as ints and the stored rows - one entry of the fan-out table
+        ``BlockSearcher.search_expanded_device`` reads (32 bytes: three pointers and an int64, in this order)."""
+        out = nat.FanoutDesc()
+        nat.check(nat.lib.mir_fanout_get_desc(self._h, C.byref(out)))
+        return int(out.rep_ptr or 0), int(out.rep_chunk or 0), int(out.rep_pos or 0), int(out.n)
+
+    def close(self):
+        if self._h:
+            nat.lib.mir_fanout_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -162,6 +214,44 @@ class BlockSearcher:
         nat.check(nat.lib.mir_blocks_search_device(self._h, q_ptr, b, k, code, scope_ptr_ptr or None, table_ptr or None, out_doc_ptr or None,
                                                    out_chunk_ptr or None, out_row_ptr or None, out_dist_ptr or None, out_count_ptr,
                                                    out_flags_ptr or None, stream or None))
+
+    def search_expanded(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence["DeviceRows"]],
+                        fanouts: Optional[Sequence[Sequence[Optional["DeviceFanout"]]]]) -> Tuple[np.ndarray, ...]:
+        """``search`` over the EXPANDED blocks while only the stored rows are read (csrc/vec_kernels_expand.h).
+        ``fanouts[q][j]``: the fan-out of ``scopes[q][j]``, or None where that block is its own expanded block; ``fanouts=None``:
+        no block has one.  Returns the six arrays of ``search``: chunk = the replica's chunk id, row = its position inside the
+        expanded block, count[q] = min(k, expanded rows of the scope).  Blocks and fan-outs are held until the call returns."""
+        q = nat.as_f64_queries(queries, self.d)
+        b = q.shape[0]
+        code = nat.METRIC_CODES[Metric(metric).value]
+        if len(scopes) != b:
+            raise ValueError(f"{len(scopes)} scopes for {b} queries")
+        _held, sp, table = _scope_table(scopes)  # (the blocks: alive across the call)
+        fan_table = None
+        if fanouts is not None:
+            if [len(f) for f in fanouts] != [len(s) for s in scopes]:
+                raise ValueError("fanouts must list one entry (a DeviceFanout or None) per listed block")
+            fans = [f for fs in fanouts for f in fs]  # (alive across the call)
+            fan_table = (C.c_void_p * max(len(fans), 1))(*[None if f is None else f.handle for f in fans])
+        return self._search_expanded_raw(q, k, code, sp, table, fan_table)
+
+    def _search_expanded_raw(self, q: np.ndarray, k: int, code: int, sp: np.ndarray, table, fan_table) -> Tuple[np.ndarray, ...]:
+        b = q.shape[0]
+        out = _result_arrays(b, k)
+        nat.check(nat.lib.mir_blocks_search_expanded(self._h, nat.ptr(q), b, k, code, nat.ptr(sp), table, fan_table, *map(nat.ptr, out)))
+        return out
+
+    def search_expanded_device(self, q_ptr: int, b: int, k: int, metric, scope_ptr_ptr: int, table_ptr: int, fanout_table_ptr: int,
+                               out_row_ptr: int, out_dist_ptr: int, out_count_ptr: int, out_flags_ptr: int = 0, out_doc_ptr: int = 0,
+                               out_chunk_ptr: int = 0, stream: int = 0) -> None:
+        """``search_expanded`` with every buffer in HBM, asynchronous: ``search_device``'s rules, with ``fanout_table_ptr``: one
+        32-byte descriptor (``DeviceFanout.desc()``, all zero = no fan-out) per listed block, parallel to the block table; 0:
+        no block has one.  Nothing in the arrays is validated."""
+        code = nat.METRIC_CODES[Metric(metric).value]
+        nat.check(nat.lib.mir_blocks_search_expanded_device(self._h, q_ptr, b, k, code, scope_ptr_ptr or None, table_ptr or None,
+                                                            fanout_table_ptr or None, out_doc_ptr or None, out_chunk_ptr or None,
+                                                            out_row_ptr or None, out_dist_ptr or None, out_count_ptr, out_flags_ptr or None,
+                                                            stream or None))
 
     def search_shared(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence["DeviceRows"]],
                       group_sizes: Sequence[int]) -> Tuple[np.ndarray, ...]:
@@ -550,6 +640,59 @@ def create_index_by_page(chunks: Sequence, pages_embeddings: Optional[Sequence])
         ids.extend([i] * len(emb))
         rows.extend(emb)
     return DocIndex(chunk_ids=np.array(ids, dtype=np.int64), embeddings=np.array(rows, dtype=np.float32))
+
+
+class PagedDocIndex:
+    """A by-page index with every page row stored ONCE: ``embeddings[n, d]`` and the fan-out (``rep_ptr`` int64[n + 1],
+    ``rep_chunk`` and ``rep_pos`` int64[R]) that says which rows of ``create_index_by_page``'s index each stored row stands
+    for (csrc/vec_fanout_layout.h).  ``expand()`` is that index."""
+
+    def __init__(self, embeddings: Optional[np.ndarray] = None, rep_ptr=None, rep_chunk=None, rep_pos=None):
+        self.embeddings = embeddings if embeddings is not None else np.zeros((0, 0), dtype=np.float32)
+        self.rep_ptr = np.ascontiguousarray(rep_ptr if rep_ptr is not None else [0], dtype=np.int64)
+        self.rep_chunk = np.ascontiguousarray(rep_chunk if rep_chunk is not None else [], dtype=np.int64)
+        self.rep_pos = np.ascontiguousarray(rep_pos if rep_pos is not None else [], dtype=np.int64)
+
+    def expand(self) -> DocIndex:
+        """The index with the copies: row ``rep_pos[e]`` is stored row r's, with chunk id ``rep_chunk[e]``, for e in r's range."""
+        total = len(self.rep_pos)
+        if total == 0:
+            return DocIndex(chunk_ids=np.array([], dtype=np.int64), embeddings=np.array([], dtype=np.float32))
+        stored = np.repeat(np.arange(len(self.rep_ptr) - 1, dtype=np.int64), np.diff(self.rep_ptr))
+        row_of = np.empty(total, np.int64)
+        row_of[self.rep_pos] = stored
+        chunk_ids = np.empty(total, np.int64)
+        chunk_ids[self.rep_pos] = self.rep_chunk
+        return DocIndex(chunk_ids=chunk_ids, embeddings=np.ascontiguousarray(np.asarray(self.embeddings)[row_of]))
+
+
+def create_paged_index_by_page(chunks: Sequence, pages_embeddings: Optional[Sequence]) -> PagedDocIndex:
+    """``create_index_by_page`` without the copies: each (page, embedding j) that a chunk names is stored once, in the order of
+    its first use; a page no chunk names is dropped.  ``create_paged_index_by_page(c, p).expand()`` equals
+    ``create_index_by_page(c, p)`` array for array."""
+    if pages_embeddings is None:
+        return PagedDocIndex()
+    stored: dict = {}  # (page, j) -> stored row
+    rows: List[np.ndarray] = []
+    replicas: List[List[Tuple[int, int]]] = []  # per stored row its (chunk, position) pairs, positions ascending
+    pos = 0
+    for i, chunk in enumerate(chunks):
+        page = _get_page_index(chunk)
+        emb = _item_rows(pages_embeddings[page])
+        for j in range(len(emb)):
+            r = stored.get((page, j))
+            if r is None:
+                r = stored[(page, j)] = len(rows)
+                rows.append(emb[j])
+                replicas.append([])
+            replicas[r].append((i, pos))
+            pos += 1
+    if not rows:
+        return PagedDocIndex()
+    rep_ptr = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(r) for r in replicas], out=rep_ptr[1:])
+    flat = np.array([pair for r in replicas for pair in r], dtype=np.int64).reshape(-1, 2)
+    return PagedDocIndex(np.array(rows, dtype=np.float32), rep_ptr, flat[:, 0], flat[:, 1])
 
 
 def create_index_by_chunk(chunks_embeddings: Optional[Sequence]) -> DocIndex:

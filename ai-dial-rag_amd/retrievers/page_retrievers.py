@@ -15,8 +15,20 @@ import numpy as np
 
 from ..embeddings import embeddings as emb
 from ..index_record import Document, RetrievalType
-from .embeddings_index import EmbeddingsIndex, create_index_by_page
+from .embeddings_index import EmbeddingsIndex, PagedDocIndex, create_index_by_page, create_paged_index_by_page
 from .embeddings_metrics import Metric
+
+
+def multimodal_paged_indexes(document_records) -> List[PagedDocIndex]:
+    """The multimodal leg's by-page indexes with every page row stored once, one per record in order: what a caller hands
+    to ``BlockCorpus.add`` to serve this leg from resident blocks.  ``MultimodalRetriever`` itself is
+    not rewired."""
+    return [create_paged_index_by_page(doc.chunks, doc.multimodal_embeddings_index) for doc in document_records]
+
+
+def description_paged_indexes(document_records) -> List[PagedDocIndex]:
+    """The same for the description leg (``DescriptionRetriever``'s rows)."""
+    return [create_paged_index_by_page(doc.chunks, doc.description_embeddings_index) for doc in document_records]
 
 
 class MultimodalRetriever:

@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: frozen runs, ADDED without a new number (nothing of ABI 6 changed): mir_blocks_search_pieces_indexed;
+#define MIR_ABI_VERSION 6 /* 6: expanded block search, ADDED without a new number (nothing of ABI 6 changed): mir_fanout_create / _info /
+                               _get_desc / _destroy, mir_blocks_search_expanded, mir_blocks_search_expanded_device;
+                            6: frozen runs, ADDED without a new number (nothing of ABI 6 changed): mir_blocks_search_pieces_indexed;
                             6: BM25 route report, ADDED without a new number (a test hook; nothing of ABI 6 changed): mir_bm25_last_routes;
                             6: block BM25, ADDED without a new number (nothing of ABI 6 changed): mir_bm25_doc_create / _info / _destroy,
                                mir_bm25_blocks_create / _destroy / _scope_create / _scope_info / _scope_idf / _scope_destroy /
@@ -322,6 +324,57 @@ int32_t mir_blocks_search_pieces_indexed(mir_blocks *s, const double *queries_ho
                                          const int32_t *rider_piece_host, int32_t min_riders, int32_t *out_doc,
                                          int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count,
                                          int32_t *out_flags);
+
+/* Expanded block search (added within ABI 6): a block's rows are stored once and stand for several rows of the EXPANDED
+ * block the caller means (csrc/vec_fanout_layout.h, csrc/vec_kernels_expand.h) - a by-page index repeats a
+ * page's row once per chunk on the page, a fanned-out block holds it once.
+ * A FAN-OUT of a block of n_rows stored rows is a CSR map: rep_ptr int64[n_rows + 1] from 0, rep_chunk and rep_pos
+ * int64[R], R = rep_ptr[n_rows].  Stored row r stands for the expanded rows at block-local positions
+ * rep_pos[rep_ptr[r] .. rep_ptr[r + 1]), with the chunk ids rep_chunk[...] there.  It must satisfy: rep_pos is a permutation
+ * of [0, R); every stored row has a replica; a row's replicas ascend in position; stored rows are ordered by their first
+ * replica's position.  mir_fanout_create checks all of it BEFORE the device is touched (MIR_ERR_INVALID names the first
+ * offender, on a machine without a GPU too) and copies the three arrays to `device`; n_rows = 0 is the fan-out of an empty
+ * block.  mir_fanout_info: any out pointer may be NULL.  mir_fanout_destroy(NULL) is OK. */
+typedef struct mir_fanout mir_fanout;
+int32_t mir_fanout_create(int64_t n_rows, const int64_t *rep_ptr_host, const int64_t *rep_chunk_host,
+                          const int64_t *rep_pos_host, int32_t device, mir_fanout **out);
+int32_t mir_fanout_info(const mir_fanout *f, int64_t *n_rows, int64_t *n_replicas, int32_t *device, int64_t *hbm_bytes);
+int32_t mir_fanout_destroy(mir_fanout *f);
+
+/* One entry of the device form's fan-out table: DEVICE pointers and the stored rows; all null (n = 0) = the block has no
+ * fan-out.  (A type and a function cannot share a name in C: the getter is mir_fanout_get_desc.) */
+typedef struct { const int64_t *rep_ptr; const int64_t *rep_chunk; const int64_t *rep_pos; int64_t n; } mir_fanout_desc;
+int32_t mir_fanout_get_desc(const mir_fanout *f, mir_fanout_desc *out);
+
+/* mir_blocks_search over the EXPANDED blocks, bit for bit, while only the stored rows are read.  fanouts_host:
+ * mir_fanout*[scope_ptr[b]] parallel to blocks_host; a NULL entry = that block is its own expanded block (position = row,
+ * chunk id = the block's), a NULL array = all entries NULL.  With R_t the expanded rows of listed block t:
+ *   out_doc   : the ORDINAL of the block inside the query's scope     out_chunk : the replica's chunk id
+ *   out_row   : the replica's position inside its EXPANDED block      out_dist  : the stored row's distance, with
+ *   out_count : min(k, sum of R_t over the scope)                                 mir_blocks_search's bits
+ *   out_flags : 0
+ * in the order (distance ascending with -0 = +0, NaN last, then ordinal, then expanded position): csrc/merge_order.h's key
+ * on the distance.  Only the first out_count[q] entries of a query are written; any output but out_count may be NULL; any
+ * k >= 1.  Route: mir_blocks_search's stream kernel, unchanged, selects min(k, stored rows) STORED rows per query into the
+ * workspace; expand_topk_kernel writes the answer from them (the first k stored rows under (distance, stored position) hold
+ * every row of the first k expanded ones: DESIGN.md 3.11).
+ * Returns MIR_ERR_INVALID, before anything is launched and with the outputs untouched, for everything mir_blocks_search
+ * refuses, for a fan-out whose n_rows or device differs from its block's, and for a query whose expanded scope holds 2^32
+ * rows or more.  The caller keeps blocks and fan-outs alive until the call returns. */
+int32_t mir_blocks_search_expanded(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                                   const int32_t *scope_ptr_host, const mir_rows *const *blocks_host,
+                                   const mir_fanout *const *fanouts_host, int32_t *out_doc, int64_t *out_chunk,
+                                   int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags);
+
+/* The same with every buffer in HBM, asynchronous on `stream`.  fanout_table_device: one mir_fanout_desc per listed block,
+ * parallel to table_device (NULL: no block has a fan-out).  It trusts scope_ptr and both tables as mir_blocks_search_device
+ * trusts its arrays.  The expansion kernel clamps what it takes from them - a stored row below n, a replica range inside
+ * [0, rep_ptr[n]] - so a fan-out descriptor that lies gives wrong rows, never a read outside the arrays it names. */
+int32_t mir_blocks_search_expanded_device(mir_blocks *s, const double *queries_device, int32_t b, int32_t k, int32_t metric,
+                                          const int32_t *scope_ptr_device, const mir_block_desc *table_device,
+                                          const mir_fanout_desc *fanout_table_device, int32_t *out_doc, int64_t *out_chunk,
+                                          int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags,
+                                          void *stream);
 
 /* Benchmark instrumentation: when enabled, every launch of the scan kernel (the
  * dominant, HBM-streaming kernel) is bracketed by HIP events on the stream it
