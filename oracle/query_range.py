@@ -10,9 +10,12 @@ evaluations of one formula may lie apart.  tests/test_oracle_query_range.py prov
 tests look at is either separated from its neighbour by more than twice that bound or bit-equal to it, which is what
 lets tests/test_gpu_query_range.py demand identical ids.  The second half does the same for the scoped and block searches
 (tests/test_gpu_scoped_query_range.py): `SCOPED_SHAPES`, `SCOPES`, the oracle over a scope, and `check`, which both GPU
-files judge with."""
+files judge with.  The same file's two later entries have their inputs here too: `scoped_fanouts` stores the scoped corpora
+once with a fan-out per block (the expanded search; the oracle of an EXPANDED scope evaluates every stored row once and
+gathers, `scope_distances`), `frozen_sieve_corpus` is a frozen run of sieve size between two own blocks (the pieces search
+through an index)."""
 
-from typing import Dict, List, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -328,6 +331,14 @@ def shared_instance(d: int, k: int) -> Tuple[int, bool]:
     return 16, 16 * (dpad * 8 + lists) <= 144 * 1024
 
 
+# the two later entries (tests/test_gpu_scoped_query_range.py: blocks_expanded, blocks_frozen) and the shapes they run on
+EXPANDED_SHAPES = ("f32_d384", "f16_d96", "f32_d102")  # the stream kernel under the expansion is covered at every shape by
+#                                                        `blocks`, the expansion kernel does not see d: the product's shape,
+#                                                        float16, and the d % 4 != 0 routine
+FROZEN_SHAPES = ("f32_d64", "f32_d384", "f32_d1024", "f32_d102", "f16_d96", "f16_d1024")  # one per index route / re-score routine
+FREEZE_PATTERNS = {"piece0": (0,), "piece2": (2,), "all": (0, 1, 2)}  # the pieces of PIECES that come with an index
+
+
 def flat_scope(piece_scope: List[int]) -> List[int]:
     return [j for p in piece_scope for j in PIECES[p]]
 
@@ -369,7 +380,7 @@ def scoped_queries(name: str, parts: List[np.ndarray]) -> Dict[str, np.ndarray]:
     return edge_queries(np.random.default_rng(5000 + sorted(SCOPED_SHAPES).index(name)), d, scope_matrix(parts, SCOPES["all"])[0])
 
 
-def scope_distances(metric: str, q: np.ndarray, blocks: Dict[int, np.ndarray], scope: List[int]) -> np.ndarray:
+def scope_distances(metric: str, q: np.ndarray, blocks: Dict[int, np.ndarray], scope: List[int], seqs: Optional[Dict[int, np.ndarray]] = None) -> np.ndarray:
     """The oracle's distances at every scope position, each listed block evaluated on its own as the reference does
     (`find_in_doc`: one metric call per document, embeddings_index.py:51-60 upstream), an empty block skipped.
 
@@ -377,19 +388,156 @@ def scope_distances(metric: str, q: np.ndarray, blocks: Dict[int, np.ndarray], s
     product into row ranges per thread and sums a range's last rows by another routine, so ONE row's dot product differs in
     its last bits with its position in the matrix and with the number of threads (measured: 2 to 28 of a 562-row block's
     products differ between two positions of one matrix, d = 64 .. 4100).  Both occurrences of a block read here are one
-    call's arguments twice over, so they tie bit for bit on any machine - as they do in the reference and on the device."""
+    call's arguments twice over, so they tie bit for bit on any machine - as they do in the reference and on the device.
+
+    `seqs` (an EXPANDED scope, `scoped_fanouts`): `blocks` hold the STORED rows, `seqs[j]` the stored row at every position
+    of block j's expanded block (absent or None: the block is its own expanded block).  The metric is evaluated ONCE per
+    stored row and gathered through `seqs[j]` to the expanded positions; it is never evaluated on the expanded matrix, for
+    the same reason: there the replicas of one row lie at different positions of one BLAS call and would differ in their
+    last bits, while the product DEFINES that the replicas of a stored row tie bit for bit (they are one evaluation)."""
     with np.errstate(all="ignore"):
         per_block = {j: ENUM_TO_METRIC[Metric(metric)](q, blocks[j]) for j in set(scope) if len(blocks[j])}
+    if seqs:
+        per_block = {j: v[seqs[j]] if seqs.get(j) is not None else v for j, v in per_block.items()}
     return np.concatenate([per_block[j] for j in scope if len(blocks[j])] + [np.zeros(0)])
 
 
-def scope_top(metric: str, q: np.ndarray, parts: List[np.ndarray], scope: List[int], m: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """`top` over a scope: the first m scope positions in the oracle's stable order, their distances, their error bounds."""
-    ref, _ = scope_matrix(parts, scope)
-    alld = scope_distances(metric, q, {j: oracle_rows(parts[j]) for j in set(scope)}, scope)
+def scope_top(metric: str, q: np.ndarray, parts: List[np.ndarray], scope: List[int], m: int, fans=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`top` over a scope: the first m scope positions in the oracle's stable order, their distances, their error bounds.
+    `fans` (`scoped_fanouts`): the positions are those of the EXPANDED scope, `parts` the stored blocks."""
+    ref, _ = scope_matrix(expanded_parts(parts, fans) if fans else parts, scope)
+    alld = scope_distances(metric, q, {j: oracle_rows(parts[j]) for j in set(scope)}, scope, fanout_seqs(fans))
     order = np.argsort(alld, kind="stable")[:m]
     with np.errstate(all="ignore"):
         return order, alld[order], error_bound(metric, q, ref, order)
+
+
+# ---- the expanded block search (mir_blocks_search_expanded): the scoped corpora with their rows stored once ---------------
+MANY_REPLICAS = 70   # one stored row of block 0 stands for this many rows: more than the 64 replicas of one step of the
+#                      expansion kernel, within the bound that keeps its worst case (k^3 log k on one wave) at milliseconds
+PLAIN_BLOCK = 2      # the block without a fan-out: its own expanded block, in the same scopes
+
+
+class Fanout(NamedTuple):
+    """The fan-out of one block (csrc/vec_fanout_layout.h) and `seq`: the stored row at every position of the expanded block"""
+    rep_ptr: np.ndarray
+    rep_chunk: np.ndarray
+    rep_pos: np.ndarray
+    seq: np.ndarray
+
+
+def check_fanout(n: int, rep_ptr: np.ndarray, rep_pos: np.ndarray) -> None:
+    """The four conditions of a valid fan-out (csrc/vec_fanout_layout.h: check_fanout), restated in numpy"""
+    assert len(rep_ptr) == n + 1 and rep_ptr[0] == 0 and len(rep_pos) == rep_ptr[n]
+    assert np.array_equal(np.sort(rep_pos), np.arange(rep_ptr[n])), "1. rep_pos is a permutation of [0, R)"
+    assert (np.diff(rep_ptr) > 0).all(), "2. every stored row has a replica"
+    inside = np.ones(len(rep_pos), bool)
+    inside[rep_ptr[:-1]] = False  # (an entry that is not its row's first one)
+    assert (np.diff(rep_pos)[inside[1:]] > 0).all(), "3. a row's replicas ascend in position"
+    assert (np.diff(rep_pos[rep_ptr[:-1]]) > 0).all(), "4. stored rows are ordered by their first replica's position"
+
+
+def many_replicas_row(block: np.ndarray) -> int:
+    """The stored row of block 0 that gets MANY_REPLICAS replicas: the first whose infinite-column value is > 0, so that under
+    inner_product with a +inf component it lies in the -inf run, at its head (and at the head of an all-NaN order)"""
+    return int(np.flatnonzero(oracle_rows(block)[:, INF_COLUMN] > 0)[0])
+
+
+def make_fanout(rng, n: int, chunk_base: int, counts_at_least: Dict[int, int], most: int = 4) -> Fanout:
+    """1 to `most` replicas per stored row, the multiset of (row, replica) shuffled over the WHOLE block - replicas of neighbouring
+    rows interleave, as the chunks of pages that alternate do, and the first hundred positions name nearly a hundred stored
+    rows - then relabelled by first appearance, which IS condition 4.  `counts_at_least`: rows that get further replicas, each
+    put at a drawn position behind the row's first one (the order of first appearances stays)."""
+    counts = rng.integers(1, most + 1, n)
+    labels = rng.permutation(np.repeat(np.arange(n), counts))
+    _, first = np.unique(labels, return_index=True)
+    new = np.empty(n, np.int64)
+    new[np.argsort(first)] = np.arange(n)
+    seq = list(new[labels]) if n else []
+    for row, want in counts_at_least.items():
+        for _ in range(max(want - seq.count(row), 0)):
+            seq.insert(int(rng.integers(seq.index(row) + 1, len(seq) + 1)), row)
+    seq = np.array(seq, np.int64)
+    rep_pos = np.argsort(seq, kind="stable").astype(np.int64)  # the positions of row 0 ascending, then row 1's, ...
+    rep_ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(seq, minlength=n), out=rep_ptr[1:])
+    rep_chunk = 7 * rep_pos + 2 + chunk_base  # chunk ids that are neither positions nor stored rows
+    check_fanout(n, rep_ptr, rep_pos)
+    return Fanout(rep_ptr, rep_chunk, rep_pos, seq)
+
+
+def scoped_fanouts(name: str) -> List[Optional[Fanout]]:
+    """Per block of `scoped_corpus(name)` its fan-out, deterministic; None for PLAIN_BLOCK.  Every stored row has 1 to 4
+    replicas, but `many_replicas_row` of block 0, which has MANY_REPLICAS, and ZERO_ROW of block 0, which has at least 2; the
+    empty block has an empty map.  All four validity conditions are asserted (`check_fanout`)."""
+    parts, _ = scoped_corpus(name)
+    rng = np.random.default_rng(6000 + sorted(SCOPED_SHAPES).index(name))
+    out: List[Optional[Fanout]] = []
+    for j, p in enumerate(parts):
+        if j == PLAIN_BLOCK:
+            out.append(None)
+            continue
+        more = {many_replicas_row(p): MANY_REPLICAS, ZERO_ROW: 2} if j == 0 else {}
+        out.append(make_fanout(rng, len(p), 100_000 * j, more))
+    f0 = out[0]
+    m = np.diff(f0.rep_ptr)
+    assert m[many_replicas_row(parts[0])] == MANY_REPLICAS and 2 <= m[ZERO_ROW] <= 4 and np.sort(m)[-2] <= 4 and len(out[1].rep_pos) == 0
+    return out
+
+
+def fanout_seqs(fans) -> Optional[Dict[int, np.ndarray]]:
+    return {j: f.seq for j, f in enumerate(fans) if f is not None} if fans else None
+
+
+def expanded_parts(parts: List[np.ndarray], fans: List[Optional[Fanout]]) -> List[np.ndarray]:
+    """The expanded blocks: what a by-page index with its copies holds (rows gathered through `seq`; a block without a fan-out
+    as it is)"""
+    return [p if f is None else p[f.seq] for p, f in zip(parts, fans)]
+
+
+def expanded_chunks(chunks: List[np.ndarray], fans: List[Optional[Fanout]]) -> List[np.ndarray]:
+    """The chunk id at every position of the expanded blocks (`chunks`: the plain blocks' own ids)"""
+    out = []
+    for c, f in zip(chunks, fans):
+        if f is None:
+            out.append(np.asarray(c, np.int64))
+        else:
+            by_pos = np.zeros(len(f.rep_pos), np.int64)
+            by_pos[f.rep_pos] = f.rep_chunk
+            out.append(by_pos)
+    return out
+
+
+# ---- a frozen run of sieve size (mir_blocks_search_pieces_indexed) -------------------------------------------------------
+FROZEN_RUN_SIZES = (15_000, 0, 20_000, 5_000)  # route_corpus("sieve_i8") cut into blocks: unit rows, the int8 image
+FROZEN_OWN_SIZES = (33, 5)
+FROZEN_PIECES = [[0, 1, 2, 3], [4], [5]]       # piece 0: the run; 1: own33; 2: own5
+FROZEN_SCOPES = {
+    "around": [1, 0, 2],   # [own33, RUN, own5]: ZERO_ROW lies in own33
+    "run": [0],
+    "own": [2, 1],         # names no run: not searched through the index
+}
+
+
+def frozen_flat(piece_scope: List[int]) -> List[int]:
+    return [j for p in piece_scope for j in FROZEN_PIECES[p]]
+
+
+def frozen_sieve_corpus() -> Tuple[List[np.ndarray], np.ndarray, Dict[str, np.ndarray]]:
+    """-> (blocks 0 .. 3: the run, the rows of route_corpus("sieve_i8") cut at FROZEN_RUN_SIZES; blocks 4 and 5: own blocks of
+    33 and 5 rows made as `scoped_corpus` makes rows, a seed of their own; the 12 ordinary queries of the route; the edge
+    queries, every direction drawn until it is strictly judged on the matrix of scope `around`)."""
+    run, ordinary = route_corpus("sieve_i8")
+    assert len(run) == sum(FROZEN_RUN_SIZES)
+    rng = np.random.default_rng(7000)
+    n, d = sum(FROZEN_OWN_SIZES), run.shape[1]
+    own = rng.standard_normal((n, d), dtype=np.float32)
+    own *= ((1.0 + rng.uniform(-NORM_SPREAD, NORM_SPREAD, n)) / np.linalg.norm(own.astype(np.float64), axis=1)).astype(np.float32)[:, None]
+    own = plant_zero(own)
+    cuts = np.cumsum((0,) + FROZEN_RUN_SIZES)
+    parts = [run[a:b] for a, b in zip(cuts[:-1], cuts[1:])] + [own[: FROZEN_OWN_SIZES[0]], own[FROZEN_OWN_SIZES[0] :]]
+    edges = edge_queries(np.random.default_rng(7001), d, scope_matrix(parts, frozen_flat(FROZEN_SCOPES["around"]))[0])
+    return parts, ordinary, edges
 
 
 # ---- judging a search's answer against the oracle's -----------------------------------------------------------------------
@@ -416,19 +564,23 @@ class Oracle:
 
 class ScopeOracle(Oracle):
     """The oracle's answers over one scope of row blocks: `ref` is the scope's matrix (a "row" is a scope position), the
-    distances are `scope_distances`' - each block evaluated on its own, so a block listed twice ties exactly."""
+    distances are `scope_distances`' - each block evaluated on its own, so a block listed twice ties exactly.  A scope of up
+    to 5 000 positions is kept whole, a longer one (the frozen run of sieve size) to its first TOP positions, as `Oracle`
+    keeps a corpus.  `fans` (`scoped_fanouts`): the EXPANDED scope - `parts` are the stored blocks, `ref` and the positions
+    are the expanded scope's, every distance is its stored row's (`scope_distances`: one evaluation per stored row)."""
 
-    def __init__(self, parts, scope):
-        super().__init__(scope_matrix(parts, scope)[0])
+    def __init__(self, parts, scope, fans=None):
+        super().__init__(scope_matrix(expanded_parts(parts, fans) if fans else parts, scope)[0])
         self.scope = list(scope)
         self.blocks = {j: oracle_rows(parts[j]) for j in set(scope)}
-        assert self.keep == len(self.ref)
+        self.seqs = fanout_seqs(fans)
 
     def top(self, metric, name, q):
         key = (metric, name)
         if key not in self.cache:
-            alld = scope_distances(metric, q, self.blocks, self.scope)
-            order = np.argsort(alld, kind="stable")
+            alld = scope_distances(metric, q, self.blocks, self.scope, self.seqs)
+            assert len(alld) == len(self.ref)
+            order = np.argsort(alld, kind="stable")[: self.keep]
             self.cache[key] = (order, alld[order], {int(r): float(v) for r, v in zip(order, alld[order])})
         return self.cache[key]
 

@@ -221,6 +221,110 @@ def test_one_row_with_a_hundred_replicas(amd, metric):
     assert got[4][0] == 130
 
 
+# ---------------------------------------------------------------- 4b. long runs: the expansion kernel's run handling
+
+# Stored rows are bit-identical copies of four group vectors A .. D (rows of one group tie in their distances' bits) and a
+# group of NaN rows.  (stored rows of A, B, C, D, NaN) per block; the scopes list block 1 twice, so a query's sorted stored-row
+# list has runs of 60, 10, 3, 67 and 6 entries: [0, 60), [60, 70), [70, 73), [73, 140), [140, 146) where A ranks first - a run
+# across entry 63 / 64 (expand_topk_kernel walks 64 entries at a step: the walk back through `carry`), a run that ends at
+# entry 69, a short one, one over three steps (73 .. 139), NaN last - and, where D ranks first, [0, 67), [67, 70), [70, 80),
+# [80, 140).  Block 4 is plain.  One row of group B in block 0 has 70 replicas: an entry inside a run that alone fills more
+# than one 64-replica pass.  The block listed twice meets itself at an equal ordinal (expand_before) and at a smaller one (m_j).
+LONG_GROUPS = [(14, 2, 1, 15, 2), (10, 2, 1, 11, 1), (12, 1, 0, 14, 0), (6, 1, 0, 7, 1), (8, 2, 0, 9, 1)]
+LONG_SCOPES = [[0, 1, 4, 1, 2, 3], [3, 1, 2, 4, 0, 1]]
+LONG_RUNS = (60, 10, 3, 67, 6)
+LONG_KS = (1, 59, 60, 61, 63, 64, 65, 69, 70, 100, 130, 200)
+LONG_MANY = 70
+
+
+@pytest.fixture(scope="module")
+def long_runs(amd):
+    from oracle import query_range as qr
+
+    rng = np.random.default_rng(77)
+    d = 96
+    u = unit(rng.standard_normal((1, d)))[0].astype(np.float64)
+    groups = np.stack([(a * u + 0.05 * unit(rng.standard_normal((1, d)))[0]) for a in (1.0, 0.9, 0.8, 0.7)] + [u]).astype(np.float32)
+    groups[4, 5] = np.nan
+    queries = np.stack([u, 0.6 * u])  # squared L2 ranks A, B, C, D for the first and D, C, B, A for the second; inner product A first for both
+    blocks = []
+    for j, sizes in enumerate(LONG_GROUPS):
+        label = rng.permutation(np.repeat(np.arange(5), sizes))  # the group of every stored row, the groups interleaved
+        rows = groups[label]
+        if j == 4:
+            chunk = 3 * np.arange(len(rows), dtype=np.int64) + 1
+            fan, seq = None, np.arange(len(rows))
+            by_pos = chunk
+        else:
+            many = {int(np.flatnonzero(label == 1)[0]): LONG_MANY} if j == 0 else {}
+            f = qr.make_fanout(rng, len(rows), 100_000 * j, many, most=5)
+            fan, seq = amd.ei.DeviceFanout.from_host(f.rep_ptr, f.rep_chunk, f.rep_pos), f.seq
+            by_pos = np.zeros(len(seq), np.int64)
+            by_pos[f.rep_pos] = f.rep_chunk
+            assert 1 <= np.diff(f.rep_ptr).min() and np.diff(f.rep_ptr).max() <= (LONG_MANY if j == 0 else 5) and (j != 0 or np.diff(f.rep_ptr).max() == LONG_MANY)
+        blocks.append({"stored": amd.ei.DeviceRows.from_host(rows, None if fan is not None else by_pos), "fanout": fan,
+                       "expanded": amd.ei.DeviceRows.from_host(rows[seq], by_pos), "group": label[seq], "chunk": by_pos,
+                       "stored_group": label, "m": np.bincount(seq, minlength=len(rows))})
+    for s in LONG_SCOPES:  # the runs of the stored-row list are the ones the comment names
+        assert tuple(np.sum([LONG_GROUPS[j] for j in s], axis=0)) == LONG_RUNS
+    return d, groups, queries, blocks, amd.ei.BlockSearcher(d)
+
+
+@pytest.mark.parametrize("metric", ["sqeuclidean_dist", "inner_product"])
+def test_long_runs_across_the_steps_of_the_expansion(amd, long_runs, metric):
+    d, groups, queries, blocks, searcher = long_runs
+    total = [sum(len(blocks[j]["group"]) for j in s) for s in LONG_SCOPES]
+    assert total[0] == total[1] > 200
+    with np.errstate(all="ignore"):
+        gd = np.stack([amd.oi.ENUM_TO_METRIC[amd.oi.Metric(metric)](q, groups) for q in queries])  # the groups' distances: far apart, NaN last
+    assert np.isnan(gd[:, 4]).all() and (np.diff(np.sort(gd[:, :4], axis=1), axis=1) > 5e-3).all()
+    grank = np.argsort(np.argsort(gd, axis=1, kind="stable"), axis=1)
+    assert grank[0].tolist() == [0, 1, 2, 3, 4] and grank[1].tolist() == ([3, 2, 1, 0, 4] if metric == "sqeuclidean_dist" else [0, 1, 2, 3, 4])
+    want = []
+    for i, s in enumerate(LONG_SCOPES):  # yardstick (B): the stable sort of the expanded scope by (group rank, ordinal, position)
+        o = np.concatenate([np.full(len(blocks[j]["group"]), n) for n, j in enumerate(s)])
+        p = np.concatenate([np.arange(len(blocks[j]["group"])) for j in s])
+        g = np.concatenate([grank[i][blocks[j]["group"]] for j in s])
+        c = np.concatenate([blocks[j]["chunk"] for j in s])
+        order = np.lexsort((p, o, g))
+        want.append((o[order], c[order], p[order], g[order]))
+    scopes = [[blocks[j]["stored"] for j in s] for s in LONG_SCOPES]
+    fans = [[blocks[j]["fanout"] for j in s] for s in LONG_SCOPES]
+    wide = [[blocks[j]["expanded"] for j in s] for s in LONG_SCOPES]
+    # An entry stands for several replicas, so the k of the list above reaches entry 64 only from about 200 on.  The same cuts in
+    # REPLICAS: with before[e] = the replicas of the entries in front of entry e of a query's stored-row list (sorted by group
+    # rank, ordinal, stored row), k around before[64] and before[128] (the first replica written by the second and third step)
+    # and around the ends of the runs.
+    around = set()
+    for i, s in enumerate(LONG_SCOPES):
+        g = np.concatenate([grank[i][blocks[j]["stored_group"]] for j in s])
+        m = np.concatenate([blocks[j]["m"] for j in s])
+        before = np.concatenate([[0], np.cumsum(m[np.argsort(g, kind="stable")])])  # (ordinal and stored row ascend within a scope)
+        assert len(before) == sum(LONG_RUNS) + 1 and before[-1] == total[i]
+        ends = np.cumsum(np.bincount(g, minlength=5))
+        assert sorted(np.diff(np.concatenate([[0], ends])).tolist()) == sorted(LONG_RUNS)
+        for e in (64, 128, *ends[:4].tolist()):
+            around |= {int(before[e]) + x for x in (-1, 0, 1, 7)}
+    assert len(around) <= 48 and max(around) < total[0] + 8
+    for k in LONG_KS + tuple(sorted(around - set(LONG_KS))) + (total[0] + 5,):
+        msg = f"long runs {metric} k={k}"
+        got = searcher.search_expanded(queries, k, metric, scopes, fans)
+        same_bits(got, searcher.search(queries, k, metric, wide), msg)  # yardstick (A)
+        for i in range(2):
+            m = min(k, total[i])
+            assert got[4][i] == m, msg
+            wo, wc, wp, wg = (a[:m] for a in want[i])
+            for x, y, what in ((got[0][i, :m], wo, "doc"), (got[1][i, :m], wc, "chunk"), (got[2][i, :m], wp, "row")):
+                np.testing.assert_array_equal(x, y, err_msg=f"{msg} query {i}: {what}")
+            dist = got[3][i, :m]
+            assert np.isnan(dist[wg == 4]).all() and not np.isnan(dist[wg != 4]).any(), msg
+            for r in range(4):  # one group, one distance, bit for bit; the groups where the oracle has them
+                mine = dist[wg == r]
+                assert len(set(mine.view(np.uint64).tolist())) <= 1, f"{msg} query {i}: group of rank {r}"
+                if len(mine):
+                    assert abs(mine[0] - np.sort(gd[i, :4])[r]) < 1e-6, f"{msg} query {i}: group of rank {r}"
+
+
 # ---------------------------------------------------------------- 5. rounds
 
 @pytest.mark.parametrize("k", [70, 130])

@@ -12,7 +12,10 @@ stays.
 
 The same holds for tests/test_gpu_scoped_query_range.py: the scoped and block searches answer over a scope of row blocks,
 and every (shape, scope, query) of that file is proven here on the scope's own distances - a block listed twice ties
-exactly with itself (`scope_distances`), everything else is separated."""
+exactly with itself (`scope_distances`), everything else is separated.  Its expanded and frozen entries rest on the proofs at
+the end: the fan-outs are valid and what they are meant to be, the expanded scopes are separated or tied (replicas tie bit
+for bit: one evaluation per stored row) and really hold the long runs the expansion kernel is to be driven through, and
+the frozen corpus of sieve size is separated on its three scopes."""
 
 import numpy as np
 import pytest
@@ -191,6 +194,206 @@ def test_scoped_whole_orders_are_separated_or_tied(scoped, name):
     _, parts, ordinary, edges = scoped(name)
     for scope in (qr.SCOPES["all"], qr.SCOPES["twice"], qr.flat_scope(qr.PIECE_SCOPES["twice"])):
         assert_strict_or_tied("inner_product", edges["nonfinite:+inf"], parts, sum(len(parts[j]) for j in scope), f"{name} {scope}", scope=scope)
+
+
+# ---- the expanded and the frozen entries of tests/test_gpu_scoped_query_range.py -----------------------------------------
+EXPANDED_SCOPES = [(n, s) for n, s in qr.SCOPES.items() if s]
+RUN_QUERIES = ("nonfinite:+inf", "nonfinite:nan", "nonfinite:all_nan")
+
+
+@pytest.fixture(scope="module")
+def fanned():
+    made = {}
+
+    def get(name):
+        if name not in made:
+            made[name] = qr.scoped_fanouts(name)
+        return made[name]
+
+    return get
+
+
+@pytest.mark.parametrize("name", qr.EXPANDED_SHAPES)
+def test_scoped_fanouts_are_what_the_issue_asks_for(scoped, fanned, name):
+    _, parts, _, _ = scoped(name)
+    fans = fanned(name)
+    again = qr.scoped_fanouts(name)
+    assert fans[qr.PLAIN_BLOCK] is None and [f is None for f in fans] == [j == qr.PLAIN_BLOCK for j in range(len(parts))]
+    for j, (p, f, g) in enumerate(zip(parts, fans, again)):
+        if f is None:
+            continue
+        assert all(np.array_equal(a, b) and a.dtype == np.int64 for a, b in zip(f, g))  # deterministic
+        qr.check_fanout(len(p), f.rep_ptr, f.rep_pos)
+        # the same four conditions once more, entry by entry as the C check walks them
+        R, seen, firsts = int(f.rep_ptr[-1]), set(), []
+        for r in range(len(p)):
+            mine = f.rep_pos[f.rep_ptr[r] : f.rep_ptr[r + 1]].tolist()
+            assert len(mine) >= 1 and mine == sorted(mine) and not seen & set(mine) and all(0 <= x < R for x in mine)
+            assert (f.seq[mine] == r).all()
+            seen |= set(mine)
+            firsts.append(mine[0])
+        assert len(seen) == R == len(f.seq) and firsts == sorted(firsts)
+        m = np.diff(f.rep_ptr)
+        if len(p):
+            assert (f.rep_chunk != f.rep_pos).all() and len(set(f.rep_chunk.tolist())) == R  # no chunk id is its position
+        if j == 0:
+            x = qr.many_replicas_row(p)
+            assert m[x] == qr.MANY_REPLICAS == 70 and p[x, qr.INF_COLUMN] > 0 and 2 <= m[qr.ZERO_ROW] <= 4
+            assert ((m >= 1) & (m <= 4))[np.arange(len(p)) != x].all()
+        else:
+            assert ((m >= 1) & (m <= 4)).all() if len(p) else R == 0
+        if len(p) > 30:
+            # neighbouring rows interleave: most stored rows have a replica of the NEXT row between their first and last replica
+            last = f.rep_pos[f.rep_ptr[1:] - 1]
+            between = [(f.rep_pos[f.rep_ptr[r + 1]] < last[r]) for r in range(len(p) - 1) if m[r] > 1]
+            assert np.mean(between) > 0.9
+    assert len(fans[1].rep_ptr) == 1 and len(fans[1].seq) == 0
+    wide = qr.expanded_parts(parts, fans)
+    assert wide[qr.PLAIN_BLOCK] is parts[qr.PLAIN_BLOCK] and [len(w) for w in wide] == [len(p) if f is None else len(f.seq) for p, f in zip(parts, fans)]
+    assert np.array_equal(wide[0][fans[0].rep_pos[fans[0].rep_ptr[qr.ZERO_ROW]]], parts[0][qr.ZERO_ROW])
+    chunks = qr.expanded_chunks([np.arange(len(p)) + 5 for p in parts], fans)
+    assert np.array_equal(chunks[0][fans[0].rep_pos], fans[0].rep_chunk) and np.array_equal(chunks[qr.PLAIN_BLOCK], np.arange(len(parts[qr.PLAIN_BLOCK])) + 5)
+
+
+def test_the_expanded_oracle_ties_replicas_bit_for_bit(scoped, fanned):
+    """One evaluation per stored row, gathered: every replica has its stored row's bits, under every metric and query"""
+    _, parts, ordinary, edges = scoped("f32_d384")
+    fans = fanned("f32_d384")
+    scope = qr.SCOPES["twice"]
+    oracle = qr.ScopeOracle(parts, scope, fans)
+    stored = qr.ScopeOracle(parts, scope)
+    assert oracle.keep == len(oracle.ref) == sum(len(qr.expanded_parts(parts, fans)[j]) for j in scope)
+    starts = qr.scope_starts(parts, scope)
+    seq_of_pos = np.concatenate([starts[o] + fans[j].seq for o, j in enumerate(scope)])  # expanded position -> stored position
+    for metric in qr.METRICS:
+        for nm, q in [("scale:20", edges["scale:20"]), ("ord:0", ordinary[0]), ("nonfinite:+inf", edges["nonfinite:+inf"])]:
+            order, dist, _ = oracle.top(metric, nm, q)
+            _, _, value = stored.top(metric, nm, q)
+            want = np.array([value[int(seq_of_pos[p])] for p in order])
+            assert np.array_equal(qr.bits(dist), qr.bits(want)), (metric, nm)
+            # the stable order of the expanded scope: (distance, position)
+            same = qr.bits(dist[1:]) == qr.bits(dist[:-1])
+            assert (np.diff(order)[same] > 0).all()
+
+
+@pytest.mark.parametrize("metric", NON_COSINE)
+@pytest.mark.parametrize("name", qr.EXPANDED_SHAPES)
+def test_expanded_first_k_plus_one_distances_are_separated_or_tied(scoped, fanned, name, metric):
+    """The flat SCOPES over the expanded parts, every edge and ordinary query: none is left out"""
+    _, parts, ordinary, edges = scoped(name)
+    fans = fanned(name)
+    wide = qr.expanded_parts(parts, fans)
+    cases = 0
+    for sn, scope in EXPANDED_SCOPES:
+        m = min(qr.K_MAX + 1, sum(len(wide[j]) for j in scope))
+        for nm, q in list(edges.items()) + [(f"ord:{i}", q) for i, q in enumerate(ordinary)]:
+            order, dist, bound = qr.scope_top(metric, q, parts, scope, m, fans)
+            bad = np.flatnonzero(~qr.separated_or_tied(dist, bound))
+            assert len(order) == m and len(bad) == 0, f"expanded {name} {sn} {metric} {nm}: ranks {bad[:5]} are neither separated nor tied"
+            cases += 1
+    assert cases == 4 * (23 + qr.N_ORDINARY) and [n for n, _ in EXPANDED_SCOPES] == ["all", "reversed", "twice", "five"]
+
+
+@pytest.mark.parametrize("name", qr.EXPANDED_SHAPES)
+def test_expanded_scopes_have_the_long_runs(scoped, fanned, name):
+    """What the GPU test is written for: on `all` and `twice`, for a query with one +inf or NaN component and the all-NaN query,
+    the oracle's first 100 expanded positions lie in ONE run of equal merge_key (-inf under inner_product, +inf under the L2
+    metrics of the +inf query, NaN otherwise) that names more than 64 stored rows - the expansion kernel walks a run across its
+    64-entry step.  The run as a whole holds every replica of the 70-replica row wherever that row's distance is the run's
+    (-inf: its column value is > 0; NaN); on `all`, where block 0 leads the scope, its replicas are among the first 100
+    positions themselves.  On `twice` block 3 leads and the 70-replica row is reached by the whole-order case (k = L)."""
+    _, parts, ordinary, edges = scoped(name)
+    fans = fanned(name)
+    x = qr.many_replicas_row(parts[0])
+    cases = 0
+    for sn in ("all", "twice"):
+        scope = qr.SCOPES[sn]
+        oracle = qr.ScopeOracle(parts, scope, fans)
+        stored_starts = qr.scope_starts(parts, scope)
+        wide_starts = qr.scope_starts(qr.expanded_parts(parts, fans), scope)
+        stored_of = np.concatenate([stored_starts[o] + (fans[j].seq if fans[j] is not None else np.arange(len(parts[j]))) for o, j in enumerate(scope)])
+        o0 = scope.index(0)
+        x_positions = wide_starts[o0] + fans[0].rep_pos[fans[0].rep_ptr[x] : fans[0].rep_ptr[x + 1]]
+        assert len(x_positions) == 70
+        for nm in RUN_QUERIES:
+            for metric in qr.METRICS:
+                order, dist, _ = oracle.top(metric, nm, edges[nm])
+                key = qr.bits(np.where(np.isnan(dist), np.nan, dist))  # (one NaN: merge_key's)
+                run = np.flatnonzero(key == key[0])
+                assert len(run) == run[-1] + 1 >= 100, f"{name} {sn} {nm} {metric}: the first run has {len(run)} positions"
+                assert len(set(stored_of[order[:100]].tolist())) > 64, f"{name} {sn} {nm} {metric}"
+                first = dist[0]
+                assert np.isnan(first) or np.isinf(first)
+                x_dist = dist[np.flatnonzero(order == x_positions[0])[0]]
+                holds = set(x_positions.tolist()) <= set(order[run].tolist())
+                assert holds == (np.isnan(first) and np.isnan(x_dist) or first == x_dist), f"{name} {sn} {nm} {metric}"
+                if nm == "nonfinite:+inf" and metric == "inner_product":
+                    assert np.isneginf(first) and holds
+                if nm != "nonfinite:+inf" or metric == "cosine_sim":
+                    assert np.isnan(first) and holds
+                if holds and sn == "all":
+                    assert len(set(x_positions.tolist()) & set(order[:100].tolist())) >= 2, f"{name} {sn} {nm} {metric}"
+                cases += 1
+    assert cases == 2 * 3 * 4
+
+
+@pytest.mark.parametrize("name", ["f32_d384", "f16_d96"])
+def test_expanded_whole_orders_are_separated_or_tied(scoped, fanned, name):
+    """k = the expanded L under inner_product with one +inf component, on the expanded `all` and `twice`"""
+    _, parts, ordinary, edges = scoped(name)
+    fans = fanned(name)
+    wide = qr.expanded_parts(parts, fans)
+    for sn in ("all", "twice"):
+        scope = qr.SCOPES[sn]
+        L = sum(len(wide[j]) for j in scope)
+        order, dist, bound = qr.scope_top("inner_product", edges["nonfinite:+inf"], parts, scope, L, fans)
+        assert len(order) == L > sum(len(parts[j]) for j in scope) and qr.separated_or_tied(dist, bound).all(), f"{name} {sn}"
+
+
+def test_frozen_small_runs_reuse_the_proven_scopes():
+    """The frozen entry searches PIECES / PIECE_SCOPES of the shapes FROZEN_SHAPES: the scopes
+    test_scoped_first_k_plus_one_distances_are_separated_or_tied proves, at shapes it proves"""
+    proven = [s for kind, _, s in PROVEN_SCOPES if kind == "pieces"]
+    assert proven == [qr.flat_scope(s) for s in qr.PIECE_SCOPES.values() if s] and len(proven) == 4
+    assert set(qr.FROZEN_SHAPES) <= set(qr.SCOPED_SHAPES) - set(qr.PER_QUERY_ONLY) and set(qr.EXPANDED_SHAPES) <= set(qr.SCOPED_SHAPES)
+    assert all(set(p) <= set(range(len(qr.PIECES))) for p in qr.FREEZE_PATTERNS.values()) and qr.PIECES == [[0, 1], [2], [3, 4]]
+    assert [qr.SCOPED_SHAPES[n][1] % 4 for n in qr.FROZEN_SHAPES] == [0, 0, 0, 2, 0, 0]  # f32_d102: exact_metric_wave in the re-score
+
+
+@pytest.fixture(scope="module")
+def frozen_sieve():
+    return qr.frozen_sieve_corpus()
+
+
+def test_frozen_sieve_corpus_is_what_the_issue_asks_for(frozen_sieve):
+    parts, ordinary, edges = frozen_sieve
+    run, _ = qr.route_corpus("sieve_i8")
+    assert [len(p) for p in parts] == [15_000, 0, 20_000, 5_000, 33, 5] and all(p.dtype == np.float32 and p.shape[1] == 384 for p in parts)
+    assert np.array_equal(np.concatenate(parts[:4]), run) and qr.FROZEN_PIECES[0] == [0, 1, 2, 3]
+    norms = np.linalg.norm(np.concatenate(parts).astype(np.float64), axis=1)
+    assert np.abs(norms - 1).max() < 2.5e-4  # unit rows: the run qualifies for the int8 image
+    assert {n: qr.frozen_flat(s) for n, s in qr.FROZEN_SCOPES.items()} == {"around": [4, 0, 1, 2, 3, 5], "run": [0, 1, 2, 3], "own": [5, 4]}
+    ref, where = qr.scope_matrix(parts, qr.frozen_flat(qr.FROZEN_SCOPES["around"]))
+    assert qr.inf_column(ref) == qr.INF_COLUMN and tuple(where[qr.ZERO_ROW]) == (0, qr.ZERO_ROW) and len(ref) == 40_038
+    assert len(edges) == 23 and len(ordinary) == qr.N_ORDINARY
+    big = qr.ScopeOracle(parts, qr.frozen_flat(qr.FROZEN_SCOPES["around"]))
+    small = qr.ScopeOracle(parts, qr.frozen_flat(qr.FROZEN_SCOPES["own"]))
+    assert big.keep == qr.TOP and small.keep == 38 == len(small.ref)
+    order, dist, value = big.top("sqeuclidean_dist", "ord:0", ordinary[0])
+    assert len(order) == qr.TOP == len(value) and (np.diff(dist) >= 0).all()
+
+
+@pytest.mark.parametrize("metric", NON_COSINE)
+def test_frozen_sieve_first_k_plus_one_distances_are_separated_or_tied(frozen_sieve, metric):
+    parts, ordinary, edges = frozen_sieve
+    cases = 0
+    for sn, ps in qr.FROZEN_SCOPES.items():
+        scope = qr.frozen_flat(ps)
+        m = min(qr.K_MAX + 1, sum(len(parts[j]) for j in scope))
+        for nm, q in list(edges.items()) + [(f"ord:{i}", q) for i, q in enumerate(ordinary)]:
+            assert_strict_or_tied(metric, q, parts, m, f"frozen sieve {sn} {metric} {nm}", scope=scope)
+            cases += 1
+    assert cases == 3 * (23 + qr.N_ORDINARY)
 
 
 def test_cosine_clamp_shrinks_the_distances(route):
