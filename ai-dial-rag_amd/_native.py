@@ -79,6 +79,7 @@ def _load():
         "mir_blocks_search_shared_device": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_blocks_search_pieces": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
         "mir_blocks_search_pieces_indexed": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
+        "mir_blocks_search_pieces_expanded": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
         "mir_fanout_create": ([i64, vp, vp, vp, i32, vp], i32),
         "mir_fanout_info": ([vp, vp, vp, vp, vp], i32),
         "mir_fanout_destroy": ([vp], i32),

@@ -1782,9 +1782,9 @@ static int32_t run_scoped(const ScopedCall &c) {
         if (!c.expanded) return enqueue_scoped(on_device, P, sb, out, s);
         const int32_t rc2 = enqueue_scoped(on_device, P, sb, stored, s);
         if (rc2 != MIR_OK) return rc2;
-        const ExpandArgs ea{on_device.scope_ptr, on_device.table, on_device.fan_table, c.k, stored.doc, stored.row, stored.dist, stored.count,
+        const ExpandArgs ea{on_device.table, on_device.fan_table, c.k, stored.doc, stored.row, stored.dist, stored.count,
                             out.doc, out.chunk, out.row, out.dist, out.count, out.flags};
-        expand_topk_kernel<<<dim3((unsigned)c.b), dim3(kExpandThreads), 0, s>>>(ea);
+        expand_topk_kernel<<<dim3((unsigned)c.b), dim3(kExpandThreads), 0, s>>>(ea, ExpandFlatScope{on_device.scope_ptr});
         MIR_HIP(hipGetLastError());
         return MIR_OK;
     };
@@ -2052,10 +2052,13 @@ int32_t mir_blocks_search_shared(mir_blocks *s_, const double *queries_host, int
 
 // ---- pieces search: scopes that overlap read their common blocks once (vec_pieces_layout.h, vec_kernels_pieces.h)
 
-// The two pieces entries' one host path.  piece_index: NULL, or per piece NULL / the index composed of that piece's rows
+// The three pieces entries' one host path.  piece_index: NULL, or per piece NULL / the index composed of that piece's rows.
+// fanouts: NULL, or per entry of blocks_host NULL / that block's fan-out; where one is given the merge leaves the stored rows'
+// lists in the workspace and expand_topk_kernel<ExpandPiecesScope> writes the answer (vec_pieces_expanded_layout.h)
 static int32_t run_pieces(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, int32_t n_pieces,
                           const int32_t *piece_ptr_host, const mir_rows *const *blocks_host, const int32_t *rider_ptr_host,
-                          const int32_t *rider_piece_host, int32_t min_riders, const mir_index *const *piece_index, const SearchOut &user) {
+                          const int32_t *rider_piece_host, int32_t min_riders, const mir_index *const *piece_index,
+                          const mir_fanout *const *fanouts, const SearchOut &user) {
     MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
     mir_index *ix = s_->ix;
     int32_t rc = check_search_args(ix, queries_host, b, k, metric, user.count);
@@ -2089,6 +2092,28 @@ static int32_t run_pieces(mir_blocks *s_, const double *queries_host, int32_t b,
     rc = plan_pieces_indexed(b, n_pieces, piece_ptr_host, rider_ptr_host, rider_piece_host, min_riders, [&](int p) { return index_of(p) != nullptr; },
                              [&](int t) { return (uint64_t)all[(size_t)t].n; }, &ip);
     if (rc != MIR_OK) return rc;
+    // the fan-outs against their blocks, while they become the descriptor table the expansion reads; the expanded scopes' rows
+    const size_t n_blocks = all.size();
+    std::vector<mir_fanout_desc> fan_table;
+    ExpandedPiecesPlan ep;
+    ExpandedPiecesShape eshape;
+    for (size_t t = 0; fanouts && t < n_blocks && !eshape.on; ++t) eshape.on = fanouts[t] != nullptr;
+    if (eshape.on) {
+        fan_table.assign(n_blocks, mir_fanout_desc{nullptr, nullptr, nullptr, 0});
+        for (int p = 0; p < n_pieces; ++p)
+            for (int t = piece_ptr_host[p]; t < piece_ptr_host[p + 1]; ++t) {
+                const mir_fanout *f = fanouts[t];
+                if (!f) continue;
+                MIR_REQUIRE(f->n == blocks_host[t]->n && f->device == blocks_host[t]->device,
+                            "the fan-out of block %d of piece %d is of %lld stored rows on device %d, the block holds %lld on device %d",
+                            t - piece_ptr_host[p], p, (long long)f->n, f->device, (long long)blocks_host[t]->n, blocks_host[t]->device);
+                fan_table[(size_t)t] = mir_fanout_desc{f->d_ptr, f->d_chunk, f->d_pos, f->n};
+            }
+        rc = plan_pieces_expanded(b, n_pieces, piece_ptr_host, rider_ptr_host, rider_piece_host,
+                                  [&](int t) { return (uint64_t)(fanouts[t] ? fanouts[t]->R : all[(size_t)t].n); }, &ep);
+        if (rc != MIR_OK) return rc;
+        eshape.n_blocks = n_blocks; eshape.n_riders = (size_t)rider_ptr_host[b]; eshape.n_pieces = n_pieces;
+    }
     const PiecesPlan &pl = ip.pl;
     const int n_occ = pl.n_occ(), n_groups = pl.n_groups(), d = ix->d;
     const int gs = ip.n_shared_groups(), n_shared = ip.n_shared_occ();  // what the shared search sees: the index groups and their rides lie behind
@@ -2107,10 +2132,11 @@ static int32_t run_pieces(mir_blocks *s_, const double *queries_host, int32_t b,
     const IndexedShape xshape{ip.n_index_groups, ip.n_index_occ, ip.prefix.size()};
     PiecesBuffers pb;
     IndexedBuffers xb;
+    ExpandedPiecesBuffers eb;
     return with_workspace(
-        ix, nullptr, true, [&](char *base) { return carve_pieces_indexed(pb, xb, base, shape, xshape, kExactRound); },
+        ix, nullptr, true, [&](char *base) { return carve_pieces_expanded(pb, xb, eb, base, shape, xshape, eshape, kExactRound); },
         [&](Workspace *w, hipStream_t s) {
-            HostPiece in[11];
+            HostPiece in[18];
             int n = 0;
             auto piece = [&](const void *dev, const void *host, size_t bytes) {
                 if (bytes) in[n++] = {dev, host, bytes};
@@ -2126,6 +2152,15 @@ static int32_t run_pieces(mir_blocks *s_, const double *queries_host, int32_t b,
             piece(pb.q_occ_ptr, pl.q_occ_ptr.data(), ((size_t)b + 1) * 4);
             piece(pb.q_occ, pl.q_occ.data(), (size_t)n_occ * 4);
             piece(xb.prefix, ip.prefix.data(), ip.prefix.size() * 8);
+            if (eshape.on) {
+                piece(eb.all_table, all.data(), n_blocks * sizeof(mir_block_desc));
+                piece(eb.fan_table, fan_table.data(), n_blocks * sizeof(mir_fanout_desc));
+                piece(eb.piece_ptr, piece_ptr_host, ((size_t)n_pieces + 1) * 4);
+                piece(eb.rider_ptr, rider_ptr_host, ((size_t)b + 1) * 4);
+                piece(eb.rider_piece, rider_piece_host, eshape.n_riders * 4);
+                piece(eb.rider_base, ep.rider_base.data(), eshape.n_riders * 4);
+                piece(eb.piece_rows, ep.piece_rows.data(), (size_t)n_pieces * 8);
+            }
             return host_round_trip(w, s, in, n, pb.q, pb.in_span, pb.out, user, b, k, [&](const SearchOut &out) -> int32_t {
                 if (n_occ > 0) pieces_gather_kernel<<<dim3((unsigned)n_occ), dim3(64), 0, s>>>(pb.q, pb.occ_query, b, d, pb.q_by_occ);
                 MIR_HIP(hipGetLastError());
@@ -2164,9 +2199,17 @@ static int32_t run_pieces(mir_blocks *s_, const double *queries_host, int32_t b,
                     MIR_HIP(hipGetLastError());
                 }
                 const PiecesMergeArgs ma{pb.q_occ_ptr, pb.q_occ, pl.n_shared, pl.n_solo, pb.occ_base, pb.solo_ptr, pb.solo_ord, k, pb.occ,
-                                         pb.cand_key, pb.cand_row, pb.cand_src, out};
+                                         pb.cand_key, pb.cand_row, pb.cand_src, eshape.on ? eb.stored : out};
                 pieces_merge_kernel<<<dim3((unsigned)b), dim3(kPiecesThreads), 0, s>>>(ma);
                 MIR_HIP(hipGetLastError());
+                if (eshape.on) {  // the stored rows' lists -> the first k rows of the expanded flattened scopes
+                    const ExpandArgs ea{eb.all_table, eb.fan_table, k, eb.stored.doc, eb.stored.row, eb.stored.dist, eb.stored.count,
+                                        out.doc, out.chunk, out.row, out.dist, out.count, out.flags};
+                    const ExpandPiecesScope scope{PiecesScopes{eb.piece_ptr, eb.rider_ptr, eb.rider_piece, eb.rider_base, eb.piece_rows, n_pieces,
+                                                               (int32_t)eshape.n_riders, (int32_t)n_blocks}};
+                    expand_topk_kernel<<<dim3((unsigned)b), dim3(kExpandThreads), 0, s>>>(ea, scope);
+                    MIR_HIP(hipGetLastError());
+                }
                 return MIR_OK;
             });
         });
@@ -2177,7 +2220,7 @@ int32_t mir_blocks_search_pieces(mir_blocks *s_, const double *queries_host, int
                                  const int32_t *rider_piece_host, int32_t min_riders, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row,
                                  double *out_dist, int32_t *out_count, int32_t *out_flags) {
     return run_pieces(s_, queries_host, b, k, metric, n_pieces, piece_ptr_host, blocks_host, rider_ptr_host, rider_piece_host, min_riders, nullptr,
-                      SearchOut{out_doc, out_chunk, out_row, out_dist, out_count, out_flags});
+                      nullptr, SearchOut{out_doc, out_chunk, out_row, out_dist, out_count, out_flags});
 }
 
 // ---- the same with frozen runs: a piece that comes with an index is searched through it (vec_frozen_layout.h)
@@ -2187,7 +2230,18 @@ int32_t mir_blocks_search_pieces_indexed(mir_blocks *s_, const double *queries_h
                                          const int32_t *rider_ptr_host, const int32_t *rider_piece_host, int32_t min_riders, int32_t *out_doc,
                                          int64_t *out_chunk, int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags) {
     return run_pieces(s_, queries_host, b, k, metric, n_pieces, piece_ptr_host, blocks_host, rider_ptr_host, rider_piece_host, min_riders, piece_index_host,
-                      SearchOut{out_doc, out_chunk, out_row, out_dist, out_count, out_flags});
+                      nullptr, SearchOut{out_doc, out_chunk, out_row, out_dist, out_count, out_flags});
+}
+
+// ---- the same over paged blocks: the routes select stored rows, the hits are expanded on device (vec_pieces_expanded_layout.h)
+
+int32_t mir_blocks_search_pieces_expanded(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, int32_t n_pieces,
+                                          const int32_t *piece_ptr_host, const mir_rows *const *blocks_host, const mir_fanout *const *fanouts_host,
+                                          const mir_index *const *piece_index_host, const int32_t *rider_ptr_host, const int32_t *rider_piece_host,
+                                          int32_t min_riders, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist,
+                                          int32_t *out_count, int32_t *out_flags) {
+    return run_pieces(s_, queries_host, b, k, metric, n_pieces, piece_ptr_host, blocks_host, rider_ptr_host, rider_piece_host, min_riders, piece_index_host,
+                      fanouts_host, SearchOut{out_doc, out_chunk, out_row, out_dist, out_count, out_flags});
 }
 
 int32_t mir_index_metric_eval(mir_index *idx, const double *query_host, int32_t metric, double *out_host) {

@@ -20,17 +20,22 @@
 //     of the run with a binary search each, O(k^3 log k) steps on one wave, to write k results.
 //   * Safety: the ordinal is clamped into the scope, the stored row below min(block n, fan-out n), the replica range into
 //     [0, R] with R = rep_ptr[n]: whatever the tables hold, nothing outside the arrays they name is read.
+//   * Where a query's scope comes from is a POLICY (the kernel's template argument); everything above is shared.
+//     ExpandFlatScope: scope_ptr and tables parallel to it, one entry per listed block (mir_blocks_search_expanded[_device]).
+//     ExpandPiecesScope: the rides of a pieces search (mir_blocks_search_pieces_expanded) - the tables hold
+//     one entry per block of the CALL, an ordinal finds its block by a binary search over the query's rider_base
+//     (pieces_block_of_ordinal, vec_pieces_expanded_layout.h: ride, piece and block clamped), out_count sums the per-piece totals.
 #pragma once
 #include "vec_kernels.h"
 #include "merge_order.h"
+#include "vec_pieces_expanded_layout.h"
 
 namespace mir {
 
 constexpr int kExpandThreads = 64;  // one wave per query
 
 struct ExpandArgs {
-    const int32_t *scope_ptr;        // [b + 1]
-    const mir_block_desc *blocks;    // one per listed block
+    const mir_block_desc *blocks;    // one per listed block (flat) / per block of the call (pieces)
     const mir_fanout_desc *fanouts;  // parallel to blocks; null: no block has a fan-out
     int k;
     const int32_t *in_doc;           // [b][k] the stored rows' lists
@@ -64,10 +69,49 @@ __device__ __forceinline__ uint64_t expand_block_rows(const ExpandArgs &a, int s
     return (uint64_t)expand_clamp(f.rep_ptr[f.n > 0 ? f.n : 0], 0, 0xffffffffll);
 }
 
-__device__ __forceinline__ ExpandRow expand_row(const ExpandArgs &a, int seg_lo, int nseg, int ord, int64_t row) {
+// ---- the scope policies: rows(a, lane) = this lane's share of the scope's expanded rows; nseg = the blocks the scope lists;
+// block(ord) = the entry of a.blocks / a.fanouts that ordinal `ord` stands for, -1: none
+
+struct ExpandFlatScope {
+    const int32_t *scope_ptr;  // [b + 1]
+    struct Query {
+        int seg_lo, nseg;
+        __device__ __forceinline__ uint64_t rows(const ExpandArgs &a, int lane) const {
+            uint64_t total = 0;
+            for (int s = lane; s < nseg; s += 64) total += expand_block_rows(a, seg_lo + s);
+            return total;
+        }
+        __device__ __forceinline__ int block(int ord) const { return nseg <= 0 ? -1 : seg_lo + (int)expand_clamp(ord, 0, nseg - 1); }
+    };
+    __device__ __forceinline__ Query open(int q) const {
+        const int seg_lo = max(scope_ptr[q], 0);
+        return Query{seg_lo, scope_ptr[q + 1] - seg_lo};
+    }
+};
+
+struct ExpandPiecesScope {
+    PiecesScopes sc;
+    struct Query {
+        PiecesScopes sc;
+        PiecesQueryScope qs;
+        int nseg;
+        __device__ __forceinline__ uint64_t rows(const ExpandArgs &, int lane) const {
+            uint64_t total = 0;
+            for (int r = lane; r < qs.n; r += 64) total += pieces_ride_rows(sc, qs.lo + r);
+            return total;
+        }
+        __device__ __forceinline__ int block(int ord) const { return pieces_block_of_ordinal(sc, qs, ord); }
+    };
+    __device__ __forceinline__ Query open(int q) const {
+        const PiecesQueryScope qs = pieces_query_scope(sc, q);
+        return Query{sc, qs, qs.nseg};
+    }
+};
+
+// the replicas of stored row `row` of the block at entry `seg` of the tables (-1: none)
+__device__ __forceinline__ ExpandRow expand_row(const ExpandArgs &a, int seg, int64_t row) {
     ExpandRow r{nullptr, nullptr, 0, 0};
-    if (nseg <= 0) return r;
-    const int seg = seg_lo + (int)expand_clamp(ord, 0, nseg - 1);
+    if (seg < 0) return r;
     const mir_block_desc bd = a.blocks[seg];
     int64_t n = bd.n;
     mir_fanout_desc f{nullptr, nullptr, nullptr, 0};
@@ -116,14 +160,15 @@ __device__ __forceinline__ int64_t expand_wave_scan(int64_t x, int lane) {
     return x;
 }
 
-__global__ __launch_bounds__(kExpandThreads) void expand_topk_kernel(ExpandArgs a) {
+template <typename Scope>
+__global__ __launch_bounds__(kExpandThreads) void expand_topk_kernel(ExpandArgs a, Scope scope) {
     const int q = blockIdx.x, lane = threadIdx.x;
     const int64_t k = a.k;
-    const int seg_lo = max(a.scope_ptr[q], 0), nseg = a.scope_ptr[q + 1] - seg_lo;
+    const typename Scope::Query sq = scope.open(q);
+    const int nseg = sq.nseg;
 
     // ---- out_count = min(k, expanded rows of the scope)
-    uint64_t total = 0;
-    for (int s = lane; s < nseg; s += 64) total += expand_block_rows(a, seg_lo + s);
+    uint64_t total = sq.rows(a, lane);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) total += (uint64_t)__shfl_xor((long long)total, off, 64);
     if (lane == 0) {
@@ -145,7 +190,7 @@ __global__ __launch_bounds__(kExpandThreads) void expand_topk_kernel(ExpandArgs 
         int m = 0;
         if (live) {
             key = merge_key(in_dist[i]);
-            m = expand_row(a, seg_lo, nseg, in_doc[i], in_row[i]).m;
+            m = expand_row(a, sq.block(in_doc[i]), in_row[i]).m;
         }
         const int64_t incl = expand_wave_scan(m, lane);
         int64_t base = carry + incl - m;  // off_i, then off of the run's first entry
@@ -154,7 +199,7 @@ __global__ __launch_bounds__(kExpandThreads) void expand_topk_kernel(ExpandArgs 
         const bool single = starts && (i + 1 >= cnt || merge_key(in_dist[i + 1]) != key);
         if (!starts)
             for (int j = i - 1; j >= 0 && merge_key(in_dist[j]) == key; --j) {
-                base -= expand_row(a, seg_lo, nseg, in_doc[j], in_row[j]).m;
+                base -= expand_row(a, sq.block(in_doc[j]), in_row[j]).m;
                 run_lo = j;
             }
         // every later entry's run begins at or behind the run of this step's first entry: its ranks start at that `base` or beyond
@@ -179,7 +224,7 @@ __global__ __launch_bounds__(kExpandThreads) void expand_topk_kernel(ExpandArgs 
                 const int ei = c0 + e, t = (int)(w - (e_incl - e_g));
                 const int ord = in_doc[ei];
                 const double dist = in_dist[ei];
-                const ExpandRow r = expand_row(a, seg_lo, nseg, ord, in_row[ei]);
+                const ExpandRow r = expand_row(a, sq.block(ord), in_row[ei]);
                 const int64_t pos = expand_pos(r, t);
                 int64_t rank = e_base;
                 if (e_single) {
@@ -193,7 +238,7 @@ __global__ __launch_bounds__(kExpandThreads) void expand_topk_kernel(ExpandArgs 
                         }
                         const int oj = in_doc[j];
                         if (oj > ord) continue;
-                        const ExpandRow rj = expand_row(a, seg_lo, nseg, oj, in_row[j]);
+                        const ExpandRow rj = expand_row(a, sq.block(oj), in_row[j]);
                         rank += oj < ord ? rj.m : expand_before(rj, pos);
                     }
                 }

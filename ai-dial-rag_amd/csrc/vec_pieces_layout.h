@@ -189,7 +189,11 @@ struct IndexedBuffers {
 
 // Lays a call's buffers out from `base` (null: sizes the slab only) and returns the bytes the slab needs.  `round`: kExactRound.
 // A call without index pieces (carve_pieces) has no byte more or elsewhere than it had before there were any.
-inline size_t carve_pieces_indexed(PiecesBuffers &pb, IndexedBuffers &xb, char *base, const PiecesShape &s, const IndexedShape &xs, int round) {
+// `more_in(c)` carves what a caller adds at the END of the input span, `more_lists(c)` what it adds in front of the staging
+// (vec_pieces_expanded_layout.h); one that carves nothing changes no byte.
+template <typename MoreIn, typename MoreLists>
+inline size_t carve_pieces_with(PiecesBuffers &pb, IndexedBuffers &xb, char *base, const PiecesShape &s, const IndexedShape &xs, int round,
+                                MoreIn more_in, MoreLists more_lists) {
     Carver c{base};
     const size_t n_occ = (size_t)s.n_shared + s.n_solo, ok = n_occ * s.k;
     pb.q = c.take<double>((size_t)s.b * s.d);
@@ -203,6 +207,7 @@ inline size_t carve_pieces_indexed(PiecesBuffers &pb, IndexedBuffers &xb, char *
     pb.q_occ_ptr = c.take<int32_t>((size_t)s.b + 1);
     pb.q_occ = c.take<int32_t>(n_occ);
     xb.prefix = xs.n_prefix ? c.take<int64_t>(xs.n_prefix) : nullptr;
+    more_in(c);
     pb.in_span = c.off;
     xb.q_sq = xs.n_occ ? c.take<double>((size_t)xs.n_occ) : nullptr;
     xb.q_norm = xs.n_occ ? c.take<double>((size_t)xs.n_occ) : nullptr;
@@ -217,8 +222,13 @@ inline size_t carve_pieces_indexed(PiecesBuffers &pb, IndexedBuffers &xb, char *
     pb.cand_key = c.take<uint64_t>(ok);
     pb.cand_row = c.take<uint64_t>(ok);
     pb.cand_src = c.take<uint32_t>(ok);
+    more_lists(c);
     pb.out = carve_out(c, s.b, s.k, true);
     return c.off + 256;
+}
+
+inline size_t carve_pieces_indexed(PiecesBuffers &pb, IndexedBuffers &xb, char *base, const PiecesShape &s, const IndexedShape &xs, int round) {
+    return carve_pieces_with(pb, xb, base, s, xs, round, [](Carver &) {}, [](Carver &) {});
 }
 
 inline size_t carve_pieces(PiecesBuffers &pb, char *base, const PiecesShape &s, int round) {

@@ -140,9 +140,11 @@ class BlockHybrid(CorpusHybrid):
     documents under the same keys.  ``find_many(query_vectors, query_ids, scopes, metric, k, weights, c)`` is
     ``CorpusHybrid``'s, with ``scopes`` listing keys."""
 
-    def __init__(self, device: int = 0, share_scopes: bool = False, share_pieces: bool = False, min_group: Optional[int] = None):
+    def __init__(self, device: int = 0, share_scopes: bool = False, share_pieces: bool = False, min_group: Optional[int] = None,
+                 share_paged: bool = False):
         options = {} if min_group is None else {"min_group": min_group}
-        super().__init__(BlockCorpus(device=device, share_scopes=share_scopes, share_pieces=share_pieces, **options), BlockBM25(device=device))
+        super().__init__(BlockCorpus(device=device, share_scopes=share_scopes, share_pieces=share_pieces, share_paged=share_paged, **options),
+                         BlockBM25(device=device))
         self._lock = threading.Lock()
 
     def add(self, doc_index, text_doc) -> int:

@@ -16,9 +16,11 @@ through the blocks, with the same answer.
 
 A by-page document can be held PAGED (``add(PagedDocIndex)``): every page row once, with the fan-out that says which rows of
 the by-page index it stands for.  Callers see the by-page index's answer (``chunk_id`` = the replica's); a call that lists a
-paged block takes ``BlockSearcher.search_expanded`` for all its queries.  The shared, pieces and frozen
-routes do not take fanned-out blocks yet: such a call goes per query whatever ``share_scopes`` / ``share_pieces`` say, and
-``freeze`` refuses a paged document.
+paged block takes ``BlockSearcher.search_expanded`` for all its queries, whatever ``share_scopes`` /
+``share_pieces`` say, and ``freeze`` refuses a paged document - unless the corpus was made with ``share_paged=True``: then a
+call that lists a paged block is cut exactly as one without (frozen runs, then common runs, then equal scopes) and goes to
+``BlockSearcher.search_pieces_expanded`` where the cut finds something to share, and ``freeze`` composes a run's index of
+its blocks' stored rows.
 """
 
 import threading
@@ -91,10 +93,11 @@ class BlockCorpus:
     works on the ``DeviceRows`` objects it took when it was submitted."""
 
     def __init__(self, device: int = 0, max_batch: int = 256, share_scopes: bool = False, min_group: int = DEFAULT_MIN_GROUP,
-                 share_pieces: bool = False):
+                 share_pieces: bool = False, share_paged: bool = False):
         self.device = device
         self.share_scopes = bool(share_scopes)  # queries of a call with the same scope read its rows once (search_shared)
         self.share_pieces = bool(share_pieces)  # scopes that overlap read their common runs of blocks once (search_pieces); goes before share_scopes
+        self.share_paged = bool(share_paged)  # a call that lists a paged block shares and takes frozen runs as one without does (search_pieces_expanded)
         self.min_group = max(int(min_group), 1)
         self.d: Optional[int] = None      # fixed by the first non-empty document, with
         self.dtype: Optional[int] = None  # its storage type
@@ -162,11 +165,13 @@ class BlockCorpus:
         (``DeviceIndex.from_rows`` over the blocks that hold rows; a document without rows stays in the run as an ordinal
         without rows), and from now on every scope that contains ``keys`` as a consecutive sub-list, in this order, is
         searched through that index for that stretch and through its blocks for the rest: the same answer, the same
-        bits.  For a set that is large AND stable; the blocks stay where they are, so the run's rows are held twice."""
+        bits.  For a set that is large AND stable; the blocks stay where they are, so the run's rows are held twice.
+        A paged document is refused unless the corpus shares paged calls (``share_paged=True``): then the index is
+        composed of its STORED rows, and the hits in it are expanded like any other."""
         keys = tuple(int(k) for k in keys)
         blocks = tuple(self._blocks_of(keys))  # KeyError for a removed key
         paged = [k for k, b in zip(keys, blocks) if getattr(b, "fanout", None) is not None]
-        if paged:  # (an index holds rows, not fan-outs: DESIGN.md 3.11)
+        if paged and not self.share_paged:  # (an index holds rows, not fan-outs: DESIGN.md 3.11; only search_pieces_expanded expands its hits)
             raise ValueError(f"documents {paged} are paged (their blocks have a fan-out): a frozen run cannot hold them")
         parts = [b for b in blocks if b is not None]
         if not parts:
@@ -325,6 +330,35 @@ class BlockCorpus:
         scopes = [[p for is_run, i in parts for p in ([n_plain + i] if is_run else gap_pieces[i])] for parts in shape]
         return pieces, piece_indexes, scopes, min_riders
 
+    def _cut_paged(self, lists, runs: Sequence[FrozenRun], empty):
+        """share_paged: a call that lists a paged block, cut as a call without one is -> (pieces, piece_indexes or None,
+        scopes, min_riders) for ``search_pieces_expanded``, or None where the cut finds nothing to share and no frozen run.
+        Frozen runs first (``_cut_frozen``, the gaps by ``_pieces`` under ``share_pieces``); then ``_pieces`` under
+        ``share_pieces``; then, under ``share_scopes``, every group of min_group equal scopes or more is one piece and
+        every other scope a piece of its own."""
+        if runs:
+            cut = self._cut_frozen(lists, runs, empty)
+            if cut is not None:
+                return cut
+        if self.share_pieces:
+            cut = self._pieces(lists)
+            if cut is not None and int(cut[2].max()) >= self.min_group:
+                return cut[0], None, cut[1], self.min_group
+            return None
+        shared = self._shared_groups(lists) if self.share_scopes else []
+        if not shared:
+            return None
+        pieces = [lists[idx[0]] for idx in shared]
+        scopes: List[list] = [[] for _ in lists]
+        for p, idx in enumerate(shared):
+            for i in idx:
+                scopes[i] = [p]
+        for i, s in enumerate(lists):
+            if not scopes[i]:
+                scopes[i] = [len(pieces)]
+                pieces.append(s)
+        return pieces, None, scopes, self.min_group
+
     def _search_blocks(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence[Optional[DeviceRows]]]):
         """(doc, chunk, dist, count); a scope lists blocks, None = a document without rows.  The one place that touches
         the GPU."""
@@ -341,6 +375,11 @@ class BlockCorpus:
         lists = [[empty if blk is None else blk for blk in s] for s in scopes]
         fanouts = [[getattr(blk, "fanout", None) for blk in s] for s in lists]
         if any(f is not None for fs in fanouts for f in fs):  # a paged block: the expanded route for the whole call
+            cut = self._cut_paged(lists, runs, empty) if self.share_paged else None
+            if cut is not None:  # 
+                piece_fanouts = [[getattr(blk, "fanout", None) for blk in p] for p in cut[0]]
+                doc, chunk, _row, dist, cnt, _flags = searcher.search_pieces_expanded(queries, k, metric, cut[0], piece_fanouts, cut[1], cut[2], cut[3])
+                return doc, chunk, dist, cnt
             doc, chunk, _row, dist, cnt, _flags = searcher.search_expanded(queries, k, metric, lists, fanouts)
             return doc, chunk, dist, cnt
         if runs:  # (a corpus without frozen runs makes the calls it always made)

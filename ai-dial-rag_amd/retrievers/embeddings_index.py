@@ -314,6 +314,44 @@ class BlockSearcher:
                                                            nat.ptr(riders), int(min_riders), *map(nat.ptr, out)))
         return out
 
+    def search_pieces_expanded(self, queries: np.ndarray, k: int, metric, pieces: Sequence[Sequence["DeviceRows"]],
+                               piece_fanouts: Optional[Sequence[Sequence[Optional["DeviceFanout"]]]],
+                               piece_indexes: Optional[Sequence[Optional["DeviceIndex"]]], scopes: Sequence[Sequence[int]],
+                               min_riders: int) -> Tuple[np.ndarray, ...]:
+        """``search_pieces_indexed`` over PAGED blocks: ``piece_fanouts[p][j]`` is the fan-out of ``pieces[p][j]``, or None
+        where that block is its own expanded block.  The routes select stored rows as they do without fan-outs - a frozen
+        run's index is composed of its blocks' STORED rows - and one launch expands the hits (csrc/vec_kernels_expand.h,
+        DESIGN.md 3.12).  Returns ``search_expanded``'s six arrays over the flattened scopes: doc = the ordinal of the
+        block in the flattened scope, chunk = the replica's chunk id, row = its position inside the expanded block,
+        count[q] = min(k, expanded rows).  ``piece_fanouts=None``: ``search_pieces_indexed``'s call."""
+        if piece_fanouts is None:
+            return self.search_pieces_indexed(queries, k, metric, pieces, piece_indexes, scopes, min_riders)
+        q = nat.as_f64_queries(queries, self.d)
+        b = q.shape[0]
+        code = nat.METRIC_CODES[Metric(metric).value]
+        if len(scopes) != b:
+            raise ValueError(f"{len(scopes)} scopes for {b} queries")
+        if [len(f) for f in piece_fanouts] != [len(p) for p in pieces]:
+            raise ValueError("piece_fanouts must list one entry (a DeviceFanout or None) per block of every piece")
+        if piece_indexes is not None and len(piece_indexes) != len(pieces):
+            raise ValueError(f"{len(piece_indexes)} indexes for {len(pieces)} pieces")
+        _held, pp, table = _scope_table(pieces)  # (the blocks: alive across the call)
+        fans = [f for fs in piece_fanouts for f in fs]  # (alive across the call)
+        fan_table = (C.c_void_p * max(len(fans), 1))(*[None if f is None else f.handle for f in fans])
+        indexes = None
+        if piece_indexes is not None:  # (piece_indexes: alive across the call)
+            indexes = (C.c_void_p * max(len(pieces), 1))(*[None if ix is None else ix.handle for ix in piece_indexes])
+        rp = np.zeros(b + 1, np.int32)
+        np.cumsum([len(s) for s in scopes], out=rp[1:])
+        riders = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int64).reshape(-1) for s in scopes] + [np.zeros(0, np.int64)]))
+        if len(riders) and (riders.min() < -2**31 or riders.max() >= 2**31):
+            raise ValueError("a piece index does not fit int32")
+        riders = riders.astype(np.int32)
+        out = _result_arrays(b, k)
+        nat.check(nat.lib.mir_blocks_search_pieces_expanded(self._h, nat.ptr(q), b, k, code, len(pieces), nat.ptr(pp), table, fan_table, indexes,
+                                                            nat.ptr(rp), nat.ptr(riders), int(min_riders), *map(nat.ptr, out)))
+        return out
+
     def search_shared_device(self, q_ptr: int, b: int, k: int, metric, n_groups: int, group_ptr_ptr: int, scope_ptr_ptr: int, table_ptr: int,
                              out_row_ptr: int, out_dist_ptr: int, out_count_ptr: int, out_flags_ptr: int = 0, out_doc_ptr: int = 0,
                              out_chunk_ptr: int = 0, stream: int = 0) -> None:

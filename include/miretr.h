@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: expanded block search, ADDED without a new number (nothing of ABI 6 changed): mir_fanout_create / _info /
+#define MIR_ABI_VERSION 6 /* 6: pieces search over paged blocks, ADDED without a new number (nothing of ABI 6 changed):
+                               mir_blocks_search_pieces_expanded;
+                            6: expanded block search, ADDED without a new number (nothing of ABI 6 changed): mir_fanout_create / _info /
                                _get_desc / _destroy, mir_blocks_search_expanded, mir_blocks_search_expanded_device;
                             6: frozen runs, ADDED without a new number (nothing of ABI 6 changed): mir_blocks_search_pieces_indexed;
                             6: BM25 route report, ADDED without a new number (a test hook; nothing of ABI 6 changed): mir_bm25_last_routes;
@@ -375,6 +377,39 @@ int32_t mir_blocks_search_expanded_device(mir_blocks *s, const double *queries_d
                                           const mir_fanout_desc *fanout_table_device, int32_t *out_doc, int64_t *out_chunk,
                                           int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags,
                                           void *stream);
+
+/* Pieces search over paged blocks (added within ABI 6): the shared, index and per-query routes of
+ * mir_blocks_search_pieces_indexed take fanned-out blocks (csrc/vec_pieces_expanded_layout.h, csrc/vec_kernels_expand.h;
+ * DESIGN.md 3.12).  fanouts_host: mir_fanout*[piece_ptr[n_pieces]] parallel to blocks_host; a NULL entry = that block is its
+ * own expanded block, a NULL array = all entries NULL.  piece_index_host, the rider arrays and min_riders: as for
+ * mir_blocks_search_pieces_indexed.  The index of a frozen run that holds paged blocks is composed of the blocks' STORED
+ * rows (mir_index_create_from_rows never sees a fan-out); its row count is checked against the sum of the stored rows.
+ * The answer is what mir_blocks_search_expanded gives for the flattened scope: out_doc = the block's ordinal in the
+ * flattened scope, out_chunk = the replica's chunk id, out_row = the replica's position inside its expanded block, out_dist
+ * = the stored row's distance with mir_blocks_search's bits, out_count[q] = min(k, expanded rows of the flattened scope),
+ * out_flags 0, in the order (distance ascending with -0 = +0, NaN last, then ordinal, then expanded position); any k >= 1;
+ * only the first out_count[q] entries of a query are written; any output but out_count may be NULL.
+ * Route: mir_blocks_search_pieces_indexed's, unchanged, over the STORED rows - pieces with min_riders rides or more are read
+ * once per slab, index pieces go through one batched search of their index and the rescore, the rest goes per query, the
+ * merge puts a query's occurrences into one list sorted by written distance - and then ONE launch of the expansion kernel
+ * writes the answer from those lists.  It finds the block of a flattened ordinal by a binary search over the query's rides
+ * (no flat per-query table is built or copied).
+ * The caveat is mir_blocks_search_pieces_indexed's: inside a shared or index piece the selection at that piece's k-th place
+ * is by that route's values, so rows whose distances tie to the last bits there may be chosen differently than the per-query
+ * route would choose them; bit-identical rows tie exactly, and the replicas of one stored row always do.
+ * With min_riders = INT32_MAX and no index the result equals mir_blocks_search_expanded's on the flattened scope bit for
+ * bit, order included.  With fanouts_host NULL (or every entry NULL) the call IS mir_blocks_search_pieces_indexed: the
+ * same host path, the same workspace bytes, no expansion launch, the same result bit for bit.
+ * Returns MIR_ERR_INVALID, before anything is launched and with the outputs untouched, for everything
+ * mir_blocks_search_pieces_indexed refuses, for a fan-out whose n_rows or device differs from its block's, and for a query
+ * whose expanded flattened scope holds 2^32 rows or more.  The caller keeps blocks, fan-outs and indexes alive until the
+ * call returns.  Host form only. */
+int32_t mir_blocks_search_pieces_expanded(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                                          int32_t n_pieces, const int32_t *piece_ptr_host, const mir_rows *const *blocks_host,
+                                          const mir_fanout *const *fanouts_host, const mir_index *const *piece_index_host,
+                                          const int32_t *rider_ptr_host, const int32_t *rider_piece_host, int32_t min_riders,
+                                          int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist,
+                                          int32_t *out_count, int32_t *out_flags);
 
 /* Benchmark instrumentation: when enabled, every launch of the scan kernel (the
  * dominant, HBM-streaming kernel) is bracketed by HIP events on the stream it
