@@ -129,6 +129,8 @@ def _load():
         "mir_bm25_blocks_scope_info": ([vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "mir_bm25_blocks_scope_idf": ([vp, vp], i32),
         "mir_bm25_blocks_scope_destroy": ([vp], i32),
+        "mir_bm25_blocks_scopes_create": ([vp, vp, vp, i32, vp, vp], i32),
+        "mir_bm25_blocks_scope_tune": ([vp, i64, i64], i32),
         "mir_bm25_blocks_scores": ([vp, vp, vp, i32, vp], i32),
         "mir_bm25_blocks_search": ([vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp], i32),
         "mir_encoder_create": ([i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp], i32),

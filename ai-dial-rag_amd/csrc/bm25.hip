@@ -44,6 +44,8 @@
 #include <new>
 #include <vector>
 
+#include <hipcub/hipcub.hpp>
+
 #include "bm25_build.h"
 #include <cstdint>
 #include "common.h"
@@ -1291,7 +1293,9 @@ __global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const doubl
 
 #include "bm25_scoped.h"
 #include "bm25_blocks.h"
+#include "bm25_scopes_build.h"
 #include "bm25_host.h"
+#include "bm25_scope_batch_layout.h"
 
 using namespace mir;
 
@@ -2018,10 +2022,15 @@ struct mir_bm25_doc {
 struct mir_bm25_blocks {
     int device = 0;
     double k1 = 1.5, b = 0.75, epsilon = 0.25;
-    std::mutex mu;  // serialises use of the scratch below
+    std::mutex mu;  // serialises use of everything below
     DevScratch scratch;
     hipStream_t stream = nullptr;
     int32_t take_scratch(size_t need) { return scratch.ensure(need); }
+    // mir_bm25_blocks_scopes_create: its caps, the radix sort's storage, and ln_half[i] = log(i + 0.5)
+    int64_t scope_workspace_bytes = kBm25ScopeWorkspaceDefault, scope_table_chunks = kBm25ScopeTableDefault;
+    DevScratch sort_tmp;
+    double *ln_half = nullptr;
+    int64_t ln_half_n = 0;
 };
 
 // A scope of a searcher (mir_bm25_blocks_scope_create): immutable once built, shared by any number of searches.
@@ -2031,11 +2040,15 @@ struct mir_bm25_blocks_scope {
     int32_t n_blk = 0, n_terms = 0, vocab = 0;
     int64_t n_pos = 0, total_tokens = 0;
     double avgdl = 0.0, average_idf = 0.0;
-    std::vector<double> h_idf;
+    mutable std::vector<double> h_idf;
     Bm25BlockDev *blk = nullptr;  // [n_blk] in HBM
     int64_t *pos = nullptr;       // [n_blk + 1]
     double *idf = nullptr;        // [vocab]
     int64_t hbm_bytes = 0;
+    // built on the device: blk, pos and idf lie in ONE allocation, and h_idf is fetched when first asked for
+    void *slab = nullptr;
+    mutable std::mutex idf_mu;
+    mutable bool idf_on_host = true;
 };
 
 static void free_doc(mir_bm25_doc *d) {
@@ -2054,9 +2067,13 @@ static void free_doc(mir_bm25_doc *d) {
 static void free_blocks_scope(mir_bm25_blocks_scope *sc) {
     if (!sc) return;
     (void)hipSetDevice(sc->device);
-    (void)hipFree(sc->blk);
-    (void)hipFree(sc->pos);
-    (void)hipFree(sc->idf);
+    if (sc->slab) {
+        (void)hipFree(sc->slab);
+    } else {
+        (void)hipFree(sc->blk);
+        (void)hipFree(sc->pos);
+        (void)hipFree(sc->idf);
+    }
     delete sc;
 }
 
@@ -2133,8 +2150,39 @@ int32_t mir_bm25_blocks_destroy(mir_bm25_blocks *h) {
     if (!h) return MIR_OK;
     (void)hipSetDevice(h->device);
     h->scratch.release();
+    h->sort_tmp.release();
+    (void)hipFree(h->ln_half);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
+    return MIR_OK;
+}
+
+// A document list as both scope creators read it: the descriptor table, and the prefixes of the blocks' chunks, tokens
+// and distinct terms.
+struct BlockListHost {
+    std::vector<Bm25BlockDev> table;
+    std::vector<int64_t> pos, tok, upre;
+    int32_t max_term = -1;
+};
+
+// the host check of a document list: nothing is allocated or launched for a malformed scope
+static int32_t block_list_host(const mir_bm25_blocks *h, const mir_bm25_doc *const *docs, int32_t n, BlockListHost *out) {
+    MIR_REQUIRE(n >= 0 && (n == 0 || docs != nullptr), "bad document list (n=%d)", n);
+    out->table.resize((size_t)n);
+    out->pos.assign((size_t)n + 1, 0); out->tok.assign((size_t)n + 1, 0); out->upre.assign((size_t)n + 1, 0);
+    for (int32_t s = 0; s < n; ++s) {
+        const mir_bm25_doc *d = docs[s];
+        MIR_REQUIRE(d != nullptr, "document block %d is NULL", s);
+        MIR_REQUIRE(d->device == h->device, "document block %d lives on device %d, the searcher on %d", s, d->device, h->device);
+        Bm25BlockDev &t = out->table[s];
+        t.terms = d->d.terms; t.t_ptr = d->d.t_ptr; t.first = d->d.first; t.p_chunk = d->d.p_chunk; t.p_tf = d->d.p_tf;
+        t.doc_len = d->d.doc_len; t.chunk = d->d.chunk; t.U = (int32_t)d->U; t.n_chunks = (int32_t)d->n_chunks;
+        out->pos[s + 1] = out->pos[s] + d->n_chunks;
+        out->tok[s + 1] = out->tok[s] + d->n_tokens;
+        out->upre[s + 1] = out->upre[s] + d->U;
+        out->max_term = std::max(out->max_term, d->max_term);
+    }
+    MIR_REQUIRE(out->pos[n] < ((int64_t)1 << 31), "scope of %lld chunks: 2^31 or more", (long long)out->pos[n]);
     return MIR_OK;
 }
 
@@ -2142,30 +2190,18 @@ int32_t mir_bm25_blocks_scope_create(mir_bm25_blocks *h, const mir_bm25_doc *con
     MIR_REQUIRE(out != nullptr, "out is NULL");
     *out = nullptr;
     MIR_REQUIRE(h != nullptr, "searcher is NULL");
-    MIR_REQUIRE(n >= 0 && (n == 0 || docs != nullptr), "bad document list (n=%d)", n);
-    // host check first: nothing is launched for a malformed scope
-    std::vector<Bm25BlockDev> table((size_t)n);
-    std::vector<int64_t> pos((size_t)n + 1, 0), tok((size_t)n + 1, 0), upre((size_t)n + 1, 0);
-    int32_t max_term = -1;
-    for (int32_t s = 0; s < n; ++s) {
-        const mir_bm25_doc *d = docs[s];
-        MIR_REQUIRE(d != nullptr, "document block %d is NULL", s);
-        MIR_REQUIRE(d->device == h->device, "document block %d lives on device %d, the searcher on %d", s, d->device, h->device);
-        Bm25BlockDev &t = table[s];
-        t.terms = d->d.terms; t.t_ptr = d->d.t_ptr; t.first = d->d.first; t.p_chunk = d->d.p_chunk; t.p_tf = d->d.p_tf;
-        t.doc_len = d->d.doc_len; t.chunk = d->d.chunk; t.U = (int32_t)d->U; t.n_chunks = (int32_t)d->n_chunks;
-        pos[s + 1] = pos[s] + d->n_chunks;
-        tok[s + 1] = tok[s] + d->n_tokens;
-        upre[s + 1] = upre[s] + d->U;
-        max_term = std::max(max_term, d->max_term);
-    }
+    BlockListHost list;
+    int32_t rc = block_list_host(h, docs, n, &list);
+    if (rc != MIR_OK) return rc;
+    const std::vector<Bm25BlockDev> &table = list.table;
+    const std::vector<int64_t> &pos = list.pos, &tok = list.tok, &upre = list.upre;
+    const int32_t max_term = list.max_term;
     const int64_t L = pos[n], total = tok[n], total_u = upre[n];
-    MIR_REQUIRE(L < ((int64_t)1 << 31), "scope of %lld chunks: 2^31 or more", (long long)L);
     if (total == 0) {
         set_error("Text index is empty.");  // bm25_retriever.py:75-76 on the request's own documents
         return MIR_ERR_EMPTY;
     }
-    int32_t rc = use_device(h->device, nullptr);
+    rc = use_device(h->device, nullptr);
     if (rc != MIR_OK) return rc;
     mir_bm25_blocks_scope *sc = new (std::nothrow) mir_bm25_blocks_scope();
     MIR_REQUIRE(sc != nullptr, "out of host memory");
@@ -2226,7 +2262,238 @@ int32_t mir_bm25_blocks_scope_info(const mir_bm25_blocks_scope *scope, int64_t *
 
 int32_t mir_bm25_blocks_scope_idf(const mir_bm25_blocks_scope *scope, double *out_idf_host) {
     MIR_REQUIRE(scope != nullptr && out_idf_host != nullptr, "NULL argument");
+    {
+        std::lock_guard<std::mutex> lk(scope->idf_mu);  // a device-built scope: fetched by the first caller, kept
+        if (!scope->idf_on_host) {
+            MIR_HIP(hipSetDevice(scope->device));
+            std::vector<double> got((size_t)scope->vocab);
+            MIR_HIP(hipMemcpy(got.data(), scope->idf, sizeof(double) * got.size(), hipMemcpyDeviceToHost));
+            scope->h_idf.swap(got);
+            scope->idf_on_host = true;
+        }
+    }
     std::memcpy(out_idf_host, scope->h_idf.data(), sizeof(double) * scope->h_idf.size());
+    return MIR_OK;
+}
+
+// ---- scopes built on the device (bm25_scopes_build.h) -------------------------------------------------
+
+static_assert(sizeof(Bm25ScopeBuildDev) == kBm25ScopeDescBytes && sizeof(Bm25ScopeResult) == kBm25ScopeResultBytes,
+              "bm25_scope_batch_layout.h sizes the arrays");
+
+int32_t mir_bm25_blocks_scope_tune(mir_bm25_blocks *h, int64_t workspace_bytes, int64_t table_chunks) {
+    MIR_REQUIRE(h != nullptr, "searcher is NULL");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->scope_workspace_bytes = workspace_bytes > 0 ? workspace_bytes : kBm25ScopeWorkspaceDefault;
+    h->scope_table_chunks = table_chunks > 0 ? table_chunks : kBm25ScopeTableDefault;
+    return MIR_OK;
+}
+
+// What a call keeps until its one synchronisation: host arrays whose uploads are queued, and log tables that grew out of use.
+struct ScopesCallHold {
+    std::vector<std::vector<char>> host;
+    std::vector<double> fresh_logs;
+    std::vector<void *> retired;
+    void release() {  // (after the stream has passed their last use)
+        for (void *p : retired) (void)hipFree(p);
+        retired.clear();
+    }
+};
+
+// ln_half[0, need) on the device, under the searcher's mutex: only the new entries are computed (libm's log, the routine of
+// mir_bm25_idf_from_stats) and uploaded; the old entries are copied on the stream, and the old table goes to `hold`.
+static int32_t grow_log_table(mir_bm25_blocks *h, int64_t need, ScopesCallHold *hold) {
+    if (need <= h->ln_half_n) return MIR_OK;
+    const int64_t old_n = h->ln_half_n;
+    hold->fresh_logs.resize((size_t)(need - old_n));
+    for (int64_t i = old_n; i < need; ++i) hold->fresh_logs[(size_t)(i - old_n)] = std::log((double)i + 0.5);
+    double *grown = nullptr;
+    MIR_HIP(hipMalloc((void **)&grown, (size_t)need * 8));
+    hipError_t e = hipSuccess;
+    if (old_n) e = hipMemcpyAsync(grown, h->ln_half, (size_t)old_n * 8, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(grown + old_n, hold->fresh_logs.data(), (size_t)(need - old_n) * 8, hipMemcpyHostToDevice, h->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipFree(grown);
+        set_error("growing the log table failed: %s", hipGetErrorString(e));
+        return MIR_ERR_HIP;
+    }
+    if (h->ln_half) hold->retired.push_back(h->ln_half);
+    h->ln_half = grown;
+    h->ln_half_n = need;
+    return MIR_OK;
+}
+
+// The device route of one call, under the searcher's mutex: every scope with route 1 is allocated and its table uploaded,
+// then the sub-batches are queued one after the other on the stream, and the results are read once.  made[i] holds the
+// scopes as they come into being; the caller destroys them if this fails.
+static int32_t scopes_build_device(mir_bm25_blocks *h, const std::vector<BlockListHost> &lists, const Bm25ScopeBatchPlan &plan,
+                                   std::vector<mir_bm25_blocks_scope *> &made, ScopesCallHold *hold) {
+    hipStream_t s = h->stream;
+    for (size_t i = 0; i < lists.size(); ++i) {
+        if (!plan.route[i]) continue;
+        const BlockListHost &l = lists[i];
+        const size_t n = l.table.size();
+        mir_bm25_blocks_scope *sc = new (std::nothrow) mir_bm25_blocks_scope();
+        MIR_REQUIRE(sc != nullptr, "out of host memory");
+        made[i] = sc;
+        const int32_t V = l.max_term + 1;  // >= 1: there is a token
+        sc->searcher = h; sc->device = h->device; sc->n_blk = (int32_t)n; sc->vocab = V; sc->n_pos = l.pos[n]; sc->total_tokens = l.tok[n];
+        sc->avgdl = (double)l.tok[n] / (double)l.pos[n];
+        sc->idf_on_host = false;
+        const size_t head = n * sizeof(Bm25BlockDev) + (n + 1) * 8, bytes = head + (size_t)V * 8;  // [Bm25BlockDev[n] | pos[n + 1] | idf[V]]
+        MIR_HIP(hipMalloc(&sc->slab, bytes));
+        sc->hbm_bytes = (int64_t)bytes;
+        char *base = static_cast<char *>(sc->slab);
+        sc->blk = reinterpret_cast<Bm25BlockDev *>(base);
+        sc->pos = reinterpret_cast<int64_t *>(base + n * sizeof(Bm25BlockDev));
+        sc->idf = reinterpret_cast<double *>(base + head);
+        hold->host.emplace_back(head);
+        char *up = hold->host.back().data();
+        std::memcpy(up, l.table.data(), n * sizeof(Bm25BlockDev));
+        std::memcpy(up + n * sizeof(Bm25BlockDev), l.pos.data(), (n + 1) * 8);
+        MIR_HIP(hipMemcpyAsync(base, up, head, hipMemcpyHostToDevice, s));
+    }
+    int32_t rc = grow_log_table(h, plan.max_L + 1, hold);
+    if (rc != MIR_OK) return rc;
+    rc = h->take_scratch(plan.total);
+    if (rc != MIR_OK) return rc;
+    char *ws = static_cast<char *>(h->scratch.ptr);
+    Bm25ScopeResult *d_result = reinterpret_cast<Bm25ScopeResult *>(ws + plan.workspace);
+    auto buffers = [&](const Bm25ScopeSubBatch &sb, hipcub::DoubleBuffer<unsigned long long> *keys, hipcub::DoubleBuffer<int32_t> *vals) {
+        *keys = hipcub::DoubleBuffer<unsigned long long>(reinterpret_cast<unsigned long long *>(ws + sb.keys[0]),
+                                                         reinterpret_cast<unsigned long long *>(ws + sb.keys[1]));
+        *vals = hipcub::DoubleBuffer<int32_t>(reinterpret_cast<int32_t *>(ws + sb.vals[0]), reinterpret_cast<int32_t *>(ws + sb.vals[1]));
+    };
+    size_t sort_bytes = 256;
+    for (const Bm25ScopeSubBatch &sb : plan.sub) {
+        hipcub::DoubleBuffer<unsigned long long> keys;
+        hipcub::DoubleBuffer<int32_t> vals;
+        buffers(sb, &keys, &vals);
+        size_t want = 0;
+        MIR_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, want, keys, vals, (int)sb.cap, 0, sb.scope_bits + sb.pos_bits, s));
+        sort_bytes = std::max(sort_bytes, want);
+    }
+    rc = h->sort_tmp.ensure(sort_bytes);
+    if (rc != MIR_OK) return rc;
+    auto grid_for = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1 << 16))); };
+    for (const Bm25ScopeSubBatch &sb : plan.sub) {
+        const int32_t S = (int32_t)sb.scopes.size();
+        hold->host.emplace_back(sb.meta_bytes);
+        char *meta = hold->host.back().data();
+        Bm25ScopeBuildDev *desc = reinterpret_cast<Bm25ScopeBuildDev *>(meta + sb.desc);
+        int64_t *u_prefix = reinterpret_cast<int64_t *>(meta + sb.u_prefix), *tok_prefix = reinterpret_cast<int64_t *>(meta + sb.tok_prefix);
+        int32_t *blk_scope = reinterpret_cast<int32_t *>(meta + sb.blk_scope);
+        int64_t *v_off = reinterpret_cast<int64_t *>(meta + sb.v_off);
+        int64_t g = 0, u = 0, v = 0;
+        for (int32_t j = 0; j < S; ++j) {
+            const size_t i = (size_t)sb.scopes[(size_t)j];
+            const BlockListHost &l = lists[i];
+            const mir_bm25_blocks_scope *sc = made[i];
+            Bm25ScopeBuildDev d = {};
+            d.blk = sc->blk; d.df = reinterpret_cast<unsigned long long *>(sc->idf); d.v_off = v; d.L = sc->n_pos; d.blk0 = (int32_t)g; d.n_blk = sc->n_blk;
+            d.V = sc->vocab;
+            desc[j] = d;
+            v_off[j] = v;
+            for (size_t k = 0; k < l.table.size(); ++k, ++g) {
+                u_prefix[g] = u + l.upre[k];
+                tok_prefix[g] = l.tok[k];
+                blk_scope[g] = j;
+            }
+            u += l.upre[l.table.size()];
+            v += sc->vocab;
+        }
+        u_prefix[g] = u;
+        v_off[S] = v;
+        MIR_REQUIRE(g == sb.n_blk && u == sb.sum_u && v == sb.sum_v, "the plan and the lists disagree");
+        MIR_HIP(hipMemcpyAsync(ws, meta, sb.meta_bytes, hipMemcpyHostToDevice, s));
+        const Bm25ScopeBuildDev *d_desc = reinterpret_cast<const Bm25ScopeBuildDev *>(ws + sb.desc);
+        const int64_t *d_v_off = reinterpret_cast<const int64_t *>(ws + sb.v_off);
+        unsigned long long *d_first = reinterpret_cast<unsigned long long *>(ws + sb.first);
+        uint32_t *d_cursor = reinterpret_cast<uint32_t *>(ws + sb.cursor);
+        hipcub::DoubleBuffer<unsigned long long> keys;
+        hipcub::DoubleBuffer<int32_t> vals;
+        buffers(sb, &keys, &vals);
+        const int bits = sb.scope_bits + sb.pos_bits;
+        const unsigned long long tail_key = (unsigned long long)S << sb.pos_bits;  // above every scope's keys, inside `bits`
+        bm25_scopes_init_kernel<<<grid_for(std::max(sb.sum_v, sb.cap)), dim3(256), 0, s>>>(d_desc, d_v_off, S, sb.sum_v, d_first, keys.Current(),
+                                                                                          vals.Current(), sb.cap, tail_key, d_cursor);
+        MIR_HIP(hipGetLastError());
+        bm25_scopes_stats_kernel<<<grid_for(sb.sum_u), dim3(256), 0, s>>>(d_desc, reinterpret_cast<const int64_t *>(ws + sb.u_prefix),
+                                                                         reinterpret_cast<const int64_t *>(ws + sb.tok_prefix),
+                                                                         reinterpret_cast<const int32_t *>(ws + sb.blk_scope), S, (int32_t)sb.n_blk,
+                                                                         sb.sum_u, d_first);
+        MIR_HIP(hipGetLastError());
+        bm25_scopes_compact_kernel<<<grid_for(sb.sum_v), dim3(256), 0, s>>>(d_first, d_v_off, S, sb.sum_v, sb.pos_bits, keys.Current(), vals.Current(),
+                                                                           sb.cap, d_cursor);
+        MIR_HIP(hipGetLastError());
+        size_t bytes = h->sort_tmp.cap;
+        MIR_HIP(hipcub::DeviceRadixSort::SortPairs(h->sort_tmp.ptr, bytes, keys, vals, (int)sb.cap, 0, bits, s));
+        bm25_scopes_idf_kernel<<<dim3((unsigned)S), dim3(256), 0, s>>>(d_desc, keys.Current(), vals.Current(), sb.cap, sb.pos_bits, h->ln_half,
+                                                                      h->ln_half_n, h->epsilon, d_result + sb.result0);
+        MIR_HIP(hipGetLastError());
+    }
+    std::vector<Bm25ScopeResult> result((size_t)plan.n_device);
+    MIR_HIP(hipMemcpyAsync(result.data(), d_result, result.size() * sizeof(Bm25ScopeResult), hipMemcpyDeviceToHost, s));
+    MIR_HIP(hipStreamSynchronize(s));  // the call's one synchronisation
+    for (const Bm25ScopeSubBatch &sb : plan.sub)
+        for (size_t j = 0; j < sb.scopes.size(); ++j) {
+            mir_bm25_blocks_scope *sc = made[(size_t)sb.scopes[j]];
+            sc->n_terms = result[(size_t)sb.result0 + j].n_terms;
+            sc->average_idf = result[(size_t)sb.result0 + j].average_idf;
+        }
+    return MIR_OK;
+}
+
+int32_t mir_bm25_blocks_scopes_create(mir_bm25_blocks *h, const mir_bm25_doc *const *docs, const int32_t *scope_ptr_host, int32_t n_scopes,
+                                      mir_bm25_blocks_scope **out_scopes, int32_t *out_route) {
+    MIR_REQUIRE(h != nullptr, "searcher is NULL");
+    MIR_REQUIRE(n_scopes >= 0, "n_scopes=%d is negative", n_scopes);
+    if (n_scopes == 0) return MIR_OK;
+    MIR_REQUIRE(scope_ptr_host != nullptr && out_scopes != nullptr, "NULL buffer");
+    MIR_REQUIRE(scope_ptr_host[0] == 0, "scope_ptr does not start at 0");
+    for (int32_t i = 0; i < n_scopes; ++i) MIR_REQUIRE(scope_ptr_host[i + 1] >= scope_ptr_host[i], "scope_ptr decreases at %d", i);
+    // host checks of the whole batch first: nothing is allocated or launched for a batch with a malformed scope
+    std::vector<BlockListHost> lists((size_t)n_scopes);
+    std::vector<Bm25ScopeShape> shapes((size_t)n_scopes);
+    int32_t first_empty = -1;
+    for (int32_t i = 0; i < n_scopes; ++i) {
+        const int32_t n = scope_ptr_host[i + 1] - scope_ptr_host[i];
+        const int32_t rc = block_list_host(h, n ? docs + scope_ptr_host[i] : nullptr, n, &lists[(size_t)i]);
+        if (rc != MIR_OK) return rc;
+        const BlockListHost &l = lists[(size_t)i];
+        shapes[(size_t)i] = Bm25ScopeShape{n, l.upre[(size_t)n], l.tok[(size_t)n], l.pos[(size_t)n], (int64_t)l.max_term + 1};
+        if (l.tok[(size_t)n] == 0 && first_empty < 0) first_empty = i;
+    }
+    if (first_empty >= 0) {
+        set_error("Text index is empty. (scope %d of the batch)", first_empty);  // bm25_retriever.py:75-76 on that request's documents
+        return MIR_ERR_EMPTY;
+    }
+    int32_t rc = use_device(h->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::vector<mir_bm25_blocks_scope *> made((size_t)n_scopes, nullptr);
+    Bm25ScopeBatchPlan plan;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        plan = bm25_scope_batch_plan(shapes.data(), n_scopes, h->scope_workspace_bytes, h->scope_table_chunks);
+        if (plan.n_device) {
+            ScopesCallHold hold;
+            rc = scopes_build_device(h, lists, plan, made, &hold);
+            if (rc != MIR_OK) (void)hipStreamSynchronize(h->stream);
+            hold.release();
+        }
+    }
+    for (int32_t i = 0; i < n_scopes && rc == MIR_OK; ++i)  // (the host route takes the mutex itself)
+        if (!plan.route[(size_t)i])
+            rc = mir_bm25_blocks_scope_create(h, docs + scope_ptr_host[i], scope_ptr_host[i + 1] - scope_ptr_host[i], &made[(size_t)i]);
+    if (rc != MIR_OK) {
+        for (mir_bm25_blocks_scope *sc : made) free_blocks_scope(sc);
+        return rc;
+    }
+    for (int32_t i = 0; i < n_scopes; ++i) {
+        out_scopes[i] = made[(size_t)i];
+        if (out_route) out_route[i] = plan.route[(size_t)i];
+    }
     return MIR_OK;
 }
 

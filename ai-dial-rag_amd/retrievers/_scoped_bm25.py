@@ -98,8 +98,13 @@ class ScopedBM25Corpus:
         keys = [tuple(int(p) for p in s) for s in scopes]
         made = {key: self._cached_view(key) for key in dict.fromkeys(keys)}  # (holds evicted ones alive for this call)
         views = [made[key] for key in keys]
+        self._prepare_views(list(made.values()))
         _pos, doc, chunk, score, cnt = self._search_views([self._ids(q) for q in queries], views, int(k))
         return doc, chunk, score, cnt
+
+    def _prepare_views(self, views) -> None:
+        """A corpus that can make the missing scopes of a batch together does it here; otherwise each view makes its own
+        at first use."""
 
     def _cached_view(self, key: tuple):
         """Made and cached under one lock (``BlockBM25.remove`` evicts under it: no scope of a removed key is cached

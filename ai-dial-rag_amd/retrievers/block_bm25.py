@@ -40,10 +40,13 @@ class BlockBM25View(ScopedBM25View):
 class BlockBM25(ScopedBM25Corpus):
     """``add`` / ``remove`` / ``view`` / ``find_many`` may be called from any thread, also while searches run: a search
     works on the blocks its views took when they were made.  ``max_scopes``: how many document lists ``find_many`` keeps
-    the scope of (a scope holds 8 bytes of HBM per term id up to the largest of its blocks)."""
+    the scope of (a scope holds 8 bytes of HBM per term id up to the largest of its blocks).  ``device_scopes``: the
+    scopes a ``find_many`` lacks are made by ONE ``BM25BlockSearcher.scopes`` call, their statistics computed on the
+    device, and a single view's scope by the same entry with one list; the answers are the same bits."""
 
-    def __init__(self, device: int = 0, max_batch: int = 256, max_scopes: int = 256):
+    def __init__(self, device: int = 0, max_batch: int = 256, max_scopes: int = 256, device_scopes: bool = False):
         self.device = device
+        self.device_scopes = bool(device_scopes)
         self._docs: Dict[int, DeviceBM25Doc] = {}
         self._next_key = 0
         self._lock = threading.Lock()
@@ -63,7 +66,25 @@ class BlockBM25(ScopedBM25Corpus):
             return self._searcher
 
     def _make_scope(self, blocks: Sequence[DeviceBM25Doc]) -> BM25BlockScope:
+        if self.device_scopes:
+            return self._device_searcher().scopes([blocks])[0]
         return self._device_searcher().scope(blocks)
+
+    def _prepare_views(self, views: Sequence[BlockBM25View]) -> None:
+        """``find_many``'s views that have no scope yet get theirs from one native call.  A view that got its scope
+        meanwhile keeps its own."""
+        if not self.device_scopes:
+            return
+        lacking = [v for v in views if v._parent is None and v._scope is None]
+        if not lacking:
+            return
+        made = self._device_searcher().scopes([v.blocks for v in lacking])  # no token in a list: "Text index is empty."
+        for v, scope in zip(lacking, made):
+            with v._scope_lock:
+                if v._scope is None:
+                    v._scope = scope
+                else:
+                    scope.close()
 
     def _search_scopes(self, queries_ids: Sequence[Sequence[int]], views: Sequence[BlockBM25View], k: int):
         """The device search: (pos, ord, local, chunk, score, count).  The one place that touches the GPU."""
@@ -141,10 +162,10 @@ class BlockHybrid(CorpusHybrid):
     ``CorpusHybrid``'s, with ``scopes`` listing keys."""
 
     def __init__(self, device: int = 0, share_scopes: bool = False, share_pieces: bool = False, min_group: Optional[int] = None,
-                 share_paged: bool = False):
+                 share_paged: bool = False, device_scopes: bool = False):
         options = {} if min_group is None else {"min_group": min_group}
         super().__init__(BlockCorpus(device=device, share_scopes=share_scopes, share_pieces=share_pieces, share_paged=share_paged, **options),
-                         BlockBM25(device=device))
+                         BlockBM25(device=device, device_scopes=device_scopes))
         self._lock = threading.Lock()
 
     def add(self, doc_index, text_doc) -> int:

@@ -255,12 +255,13 @@ class DeviceBM25Doc(_HandleOwner):
 class BM25BlockScope(_HandleOwner):
     """Owner of one ``mir_bm25_blocks_scope``: an ordered list of document blocks with the statistics rank-bm25 would
     derive from their chunks alone.  Immutable; any number of searches may use it at once.  It keeps its blocks and its
-    searcher alive."""
+    searcher alive.  ``route``: 1 for a scope that ``BM25BlockSearcher.scopes`` built on the device, 0 for one built by
+    the host route."""
 
     _destroy = "mir_bm25_blocks_scope_destroy"
 
-    def __init__(self, handle, searcher: "BM25BlockSearcher", docs: Sequence[DeviceBM25Doc]):
-        self._h, self.searcher, self.docs = handle, searcher, list(docs)
+    def __init__(self, handle, searcher: "BM25BlockSearcher", docs: Sequence[DeviceBM25Doc], route: int = 0):
+        self._h, self.searcher, self.docs, self.route = handle, searcher, list(docs), int(route)
         i = self.info()
         self.n_chunks, self.vocab = i["n_chunks"], i["vocab"]
 
@@ -296,6 +297,26 @@ class BM25BlockSearcher(_HandleOwner):
         h = C.c_void_p()
         nat.check(nat.lib.mir_bm25_blocks_scope_create(self._h, handles, len(docs), C.byref(h)))
         return BM25BlockScope(h, self, docs)
+
+    def scopes(self, doc_lists: Sequence[Sequence[DeviceBM25Doc]]) -> List[BM25BlockScope]:
+        """One scope per document list, made by ONE native call that computes their statistics on the device
+        (csrc/bm25_scopes_build.h); each answers what ``scope`` of the same list answers, bit for bit.  A list without
+        any token fails the whole call ("Text index is empty."), and no scope is made."""
+        doc_lists = [list(docs) for docs in doc_lists]
+        n = len(doc_lists)
+        ptr = np.zeros(n + 1, np.int32)
+        ptr[1:] = np.cumsum([len(docs) for docs in doc_lists])
+        flat = [d.handle for docs in doc_lists for d in docs]
+        handles = (C.c_void_p * max(len(flat), 1))(*flat)
+        out = (C.c_void_p * max(n, 1))()
+        route = np.zeros(max(n, 1), np.int32)
+        nat.check(nat.lib.mir_bm25_blocks_scopes_create(self._h, handles, nat.ptr(ptr), n, out, nat.ptr(route)))
+        return [BM25BlockScope(C.c_void_p(out[i]), self, doc_lists[i], int(route[i])) for i in range(n)]
+
+    def scope_tune(self, workspace_bytes: int = 0, table_chunks: int = 0) -> None:
+        """The two caps of ``scopes`` (0: the default): the temporary HBM of a call, past which it runs as sub-batches,
+        and the chunks of the log table, past which a scope is built by the host route."""
+        nat.check(nat.lib.mir_bm25_blocks_scope_tune(self._h, int(workspace_bytes), int(table_chunks)))
 
     def get_scores(self, scope: BM25BlockScope, query_ids: Sequence[int]) -> np.ndarray:
         """``BM25Okapi(the scope's chunks).get_scores(query)`` -> float64[scope.n_chunks]."""

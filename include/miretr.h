@@ -41,6 +41,8 @@ extern "C" {
                             6: block BM25, ADDED without a new number (nothing of ABI 6 changed): mir_bm25_doc_create / _info / _destroy,
                                mir_bm25_blocks_create / _destroy / _scope_create / _scope_info / _scope_idf / _scope_destroy /
                                _scores / _search;
+                            6: block BM25 scopes built on the device, ADDED without a new number (nothing of ABI 6 changed):
+                               mir_bm25_blocks_scopes_create, mir_bm25_blocks_scope_tune;
                             6: block search, ADDED without a new number (no entry of ABI 6 changed its signature or meaning, a caller
                                built against the earlier header runs unchanged): mir_blocks_create / _destroy / _search /
                                _search_device, mir_rows_desc; a mir_rows block keeps its rows' float32 squared norms
@@ -672,6 +674,25 @@ int32_t mir_bm25_blocks_scope_info(const mir_bm25_blocks_scope *scope, int64_t *
                                    int64_t *hbm_bytes);
 int32_t mir_bm25_blocks_scope_idf(const mir_bm25_blocks_scope *scope, double *out_idf_host);
 int32_t mir_bm25_blocks_scope_destroy(mir_bm25_blocks_scope *scope);
+/* Many scopes in one call, built on the device (csrc/bm25_scopes_build.h): scope i lists docs[scope_ptr_host[i] ..
+ * scope_ptr_host[i + 1]) with mir_bm25_blocks_scope_create's semantics (an empty block keeps its ordinal, a block listed
+ * twice counts twice); equal lists give separate scopes.  Statistics, first-appearance order, idf, its average and the
+ * floor are computed on the device, the logarithms through a table of log(i + 0.5) that the host's libm fills, and the
+ * call synchronises once.  Every scope is an ordinary mir_bm25_blocks_scope that answers, bit for bit, what a scope of
+ * mir_bm25_blocks_scope_create over the same list answers; it holds ONE allocation of HBM, and its idf comes to the host
+ * at the first mir_bm25_blocks_scope_idf only.  out_scopes[n_scopes] receives the scopes; out_route[i] (may be NULL)
+ * is 1 for a scope built on the device and 0 for one this call built by the host route (mir_bm25_blocks_scope_tune).
+ * The whole batch is refused, out_scopes untouched, before anything is allocated or launched: MIR_ERR_INVALID for what
+ * mir_bm25_blocks_scope_create refuses, for scope_ptr_host not monotone from 0 and for n_scopes < 0; MIR_ERR_EMPTY
+ * ("Text index is empty.", naming the first such scope) if any scope has no token.  After a HIP error part-way every
+ * scope made so far is destroyed and none is returned.  n_scopes = 0 is MIR_OK. */
+int32_t mir_bm25_blocks_scopes_create(mir_bm25_blocks *s, const mir_bm25_doc *const *docs, const int32_t *scope_ptr_host,
+                                      int32_t n_scopes, mir_bm25_blocks_scope **out_scopes, int32_t *out_route);
+/* Two caps of mir_bm25_blocks_scopes_create; 0 or less = the default.  workspace_bytes (256 MiB): the call's temporary
+ * HBM (csrc/bm25_scope_batch_layout.h; the radix sort's own storage comes on top); a call that needs more runs as
+ * sub-batches one after the other, and a scope that alone needs more takes the host route.  table_chunks (2^22, a
+ * 32 MiB table): a scope with L > table_chunks takes the host route inside the same call. */
+int32_t mir_bm25_blocks_scope_tune(mir_bm25_blocks *s, int64_t workspace_bytes, int64_t table_chunks);
 /* get_scores for the scope: float64[L] over the scope's positions. */
 int32_t mir_bm25_blocks_scores(mir_bm25_blocks *s, const mir_bm25_blocks_scope *scope, const int32_t *q_terms_host,
                                int32_t nq, double *out_scores_host);

@@ -6,6 +6,9 @@ over all documents; the block route holds one `DeviceBM25Doc` per document and n
 one process, and the tool asserts that they return the same positions and scores.
 (a) one search call with the scopes already made;  (b) scope creation per scope;  (c) a document arrives: `BlockBM25.add`
 + the first `find_many` naming it, against a new `CorpusBM25` over all documents + its scope + the search;  (d) HBM held.
+Scopes built on the device, against row (b)'s host route in the same process:  (b2) all B scopes in one
+`BM25BlockSearcher.scopes` call;  (b3) one scope through that entry;  (c2) row (c) with `device_scopes=True`;  (d2) the HBM
+of B device-built scopes.
 
     python tools/block_bm25_timing.py [DOCS=256] [CHUNKS=1000] [B=256] [PER=10]
 """
@@ -70,7 +73,7 @@ def main():
     print(f"Corpus model: built in {t_model:.0f} ms.  Blocks: {sum(build_ms):.0f} ms for {docs}, {fmt(med(build_ms[3:]))} each.\n")
 
     # ---- (b) scope creation, alternating
-    model_ms, block_ms, m_scopes, b_scopes = [], [], [], []
+    model_ms, block_ms, one_ms, m_scopes, b_scopes = [], [], [], [], []
     for s in doc_lists:
         sb, se = scope_segments(lengths, s)
         t, sc = clock(lambda: corpus.scope(sb, se))
@@ -79,13 +82,33 @@ def main():
         t, sc = clock(lambda: searcher.scope([blocks[d] for d in s]))
         block_ms.append(t)
         b_scopes.append(sc)
-    model_ms, block_ms = model_ms[3:], block_ms[3:]  # (the first calls carry allocator warm-up)
+        t, made = clock(lambda: searcher.scopes([[blocks[d] for d in s]]))  # (b3) the same list through the batch entry
+        one_ms.append(t)
+        assert made[0].route == 1
+        made[0].close()
+    model_ms, block_ms, one_ms = model_ms[3:], block_ms[3:], one_ms[3:]  # (the first calls carry allocator warm-up)
+
+    # ---- (b2) all scopes in one call; the last set is kept for the comparison and (d2)
+    batch_ms, d_scopes = [], []
+    for _ in range(6):
+        for sc in d_scopes:
+            sc.close()
+        t, d_scopes = clock(lambda: searcher.scopes([[blocks[d] for d in s] for s in doc_lists]))
+        batch_ms.append(t)
+    batch_ms = batch_ms[1:]
+    assert all(sc.route == 1 for sc in d_scopes)
+    for host, dev in zip(b_scopes, d_scopes):
+        hi, di = host.info(), dev.info()
+        assert hi == di, (hi, di)
+    assert np.array_equal(b_scopes[0].idf(), d_scopes[0].idf())
 
     # ---- (a) one search call, scopes already made, alternating
     for _ in range(3):
         want = corpus.search_scoped(m_scopes, queries, K)
         got = searcher.search(b_scopes, queries, K)
     assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and np.array_equal(got[4], want[3]) and np.array_equal(got[5], want[4])
+    for g, w in zip(searcher.search(d_scopes, queries, K), got):  # the device-built scopes: the same positions and scores
+        assert np.array_equal(g, w)
     for i, s in enumerate(doc_lists):  # the model's document = the block's first chunk in the model + the chunk inside the block
         c = int(want[4][i])
         assert np.array_equal(want[2][i, :c], np.asarray(s)[got[1][i, :c]] * chunks + got[2][i, :c]), i
@@ -95,6 +118,7 @@ def main():
         t_block_s.append(clock(lambda: searcher.search(b_scopes, queries, K))[0])
     model_scope_hbm = sum(s.info()["hbm_bytes"] for s in m_scopes)
     block_scope_hbm = sum(s.info()["hbm_bytes"] for s in b_scopes)
+    device_scope_hbm = sum(s.info()["hbm_bytes"] for s in d_scopes)
     model_hbm = corpus.info()["hbm_bytes"]
     block_hbm = sum(blk.info()["hbm_bytes"] for blk in blocks)
 
@@ -102,11 +126,11 @@ def main():
     print("|---|---|---|")
     print(f"| (a) one search call, {b} scopes already made | {fmt(med(t_model_s))} | {fmt(med(t_block_s))} |")
     print(f"| (b) scope creation, per scope | {fmt(med(model_ms))} | {fmt(med(block_ms))} |")
-    for sc in m_scopes + b_scopes:
+    for sc in m_scopes + b_scopes + d_scopes:
         sc.close()
 
     # ---- (c) a document arrives
-    arrive_block, arrive_model = [], []
+    arrive_block, arrive_model, arrive_device = [], [], []
     listed = [int(d) for d in doc_lists[0][: per - 1]] + [docs]
     for rep in range(3):
         keyword = BlockBM25()
@@ -118,10 +142,27 @@ def main():
         t, res_m = clock(lambda: CorpusBM25(triples, vocab=BM25_VOCAB).find_many([queries[0]], [listed], K))
         arrive_model.append(t)
         assert all(np.array_equal(x, y) for x, y in zip(res_b, res_m)), rep
+    for rep in range(3):  # (c2) in a loop of its own, so that row (c) is taken as it always was
+        keyword = BlockBM25(device_scopes=True)
+        for blk in blocks:
+            keyword.add(blk)
+        t, res_d = clock(lambda: keyword.find_many([queries[0]], [listed[:-1] + [keyword.add(triples[docs])]], K))
+        arrive_device.append(t)
+        keyword._docs.clear()
+        assert all(np.array_equal(x, y) for x, y in zip(res_d, res_m)), rep
     print(f"| (c) a document arrives: add + first `find_many` naming it / a new `CorpusBM25` over {docs + 1} documents + scope + search | "
           f"{fmt(med(arrive_model))} | {fmt(med(arrive_block))} |")
     print(f"| (d) HBM held: documents + {b} scopes | {model_hbm / 2**20:.0f} MiB + {model_scope_hbm / 2**20:.1f} MiB | "
           f"{block_hbm / 2**20:.0f} MiB + {block_scope_hbm / 2**20:.1f} MiB |")
+    print()
+    b_med, total = statistics.median(block_ms), statistics.median(batch_ms)
+    print("| scopes built on the device | host route (row (b), this process) | device route |")
+    print("|---|---|---|")
+    print(f"| (b2) {b} scopes in one `scopes()` call: total | {b} x (b) = {b * b_med:.0f} ms | {fmt(med(batch_ms))} |")
+    print(f"| (b2) per scope | {fmt(med(block_ms))} | {total / b:.3f} ms |")
+    print(f"| (b3) one scope through the new entry | {fmt(med(block_ms))} | {fmt(med(one_ms))} |")
+    print(f"| (c2) a document arrives: add + first `find_many` naming it | {fmt(med(arrive_block))} | {fmt(med(arrive_device))} |")
+    print(f"| (d2) HBM of {b} scopes | {block_scope_hbm / 2**20:.1f} MiB | {device_scope_hbm / 2**20:.1f} MiB |")
     print()
     corpus.close()
     for blk in blocks:
