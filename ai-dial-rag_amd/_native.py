@@ -144,6 +144,8 @@ def _load():
         "mir_wordpiece_encode": ([vp, vp, vp, i32, i32, i32, vp, vp, vp], i32),
         "mir_rrf_fuse": ([vp, vp, vp, i32, i32, vp, vp, vp], i32),
         "mir_rrf_fuse_batch": ([vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp], i32),
+        "mir_rrf_fuse_device": ([vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp], i32),
+        "mir_block_hybrid_search": ([vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -168,6 +170,12 @@ class FanoutDesc(C.Structure):
     all null = the block has no fan-out."""
 
     _fields_ = [("rep_ptr", C.c_void_p), ("rep_chunk", C.c_void_p), ("rep_pos", C.c_void_p), ("n", C.c_int64)]
+
+
+class RrfList(C.Structure):
+    """mir_rrf_list: one result list of b queries as mir_rrf_fuse_device reads it (device pointers, and its k)."""
+
+    _fields_ = [("doc", C.c_void_p), ("chunk", C.c_void_p), ("count", C.c_void_p), ("k", C.c_int32)]
 
 
 def last_error() -> str:

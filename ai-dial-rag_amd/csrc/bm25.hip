@@ -1296,6 +1296,9 @@ __global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const doubl
 #include "bm25_scopes_build.h"
 #include "bm25_host.h"
 #include "bm25_scope_batch_layout.h"
+#include "fusion_host.h"
+#include "hybrid_layout.h"
+#include "vec_blocks_host.h"
 
 using namespace mir;
 
@@ -2031,6 +2034,9 @@ struct mir_bm25_blocks {
     DevScratch sort_tmp;
     double *ln_half = nullptr;
     int64_t ln_half_n = 0;
+    // mir_block_hybrid_search: pinned staging of its one upload and its one download; grows, never shrinks
+    char *pin = nullptr;
+    size_t pin_cap = 0;
 };
 
 // A scope of a searcher (mir_bm25_blocks_scope_create): immutable once built, shared by any number of searches.
@@ -2152,6 +2158,7 @@ int32_t mir_bm25_blocks_destroy(mir_bm25_blocks *h) {
     h->scratch.release();
     h->sort_tmp.release();
     (void)hipFree(h->ln_half);
+    if (h->pin) (void)hipHostFree(h->pin);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return MIR_OK;
@@ -2557,6 +2564,101 @@ int32_t mir_bm25_blocks_search(mir_bm25_blocks *h, const mir_bm25_blocks_scope *
     }
     OutColumn cols[5] = {{out_pos, 8}, {out_chunk, 8}, {out_score, 8}, {out_ord, 4}, {out_local, 4}};
     return scoped_search(BlockRoute{h}, h, scopes, q_terms_host, q_ptr_host, nt, b, k, cols, 5, out_count);
+}
+
+// A hybrid request batch in one call with one synchronisation: both legs' lists stay in the scratch and
+// rrf_fuse_kernel fuses them there.  Under the keyword searcher's mutex, on its stream; the vector leg rides that stream
+// through mir_blocks_search_device, whose workspace goes back to its pool pending on it (with_workspace, vec_index.hip).
+// Scratch: hybrid_layout.h, then the keyword leg's columns (bm25_host.h).  Every host array of the call - the plan's
+// descriptors, the pinned staging - outlives the one hipStreamSynchronize at the end, on every path.
+int32_t mir_block_hybrid_search(mir_blocks *vs, mir_bm25_blocks *h, const double *queries_host, int32_t b, int32_t k, int32_t metric,
+                                const int32_t *scope_ptr_host, const mir_rows *const *blocks_host,
+                                const mir_bm25_blocks_scope *const *text_scopes, const int32_t *q_terms_host, const int32_t *q_ptr_host,
+                                const double *weights2_host, int32_t c, int32_t *out_doc, int64_t *out_chunk, double *out_score,
+                                int32_t *out_count) {
+    // the fusion's refusals (they need no handle), then the vector leg's, then the keyword leg's: nothing of the device is
+    // touched before the last
+    const mir_rrf_list shape[2] = {{nullptr, nullptr, nullptr, 1}, {nullptr, nullptr, nullptr, 1}};  // (k itself: below)
+    int32_t rc = rrf_check(shape, 2, weights2_host, c, b, 2, true);
+    if (rc != MIR_OK) return rc;
+    if ((int64_t)2 * k > kRrfMaxItems) {
+        set_error("k=%d: the two lists hold %lld entries per query, this build fuses at most %d on the device", k, (long long)2 * k, kRrfMaxItems);
+        return MIR_ERR_UNSUPPORTED;
+    }
+    std::vector<mir_block_desc> table;
+    int32_t d = 0, vec_device = 0;
+    rc = blocks_check_host(vs, queries_host, b, k, metric, scope_ptr_host, blocks_host, out_count, &table, &d, &vec_device);
+    if (rc != MIR_OK) return rc;
+    MIR_REQUIRE(h != nullptr, "searcher is NULL");
+    MIR_REQUIRE(vec_device == h->device, "the vector searcher is on device %d, the keyword searcher on device %d", vec_device, h->device);
+    if (b == 0) return MIR_OK;
+    MIR_REQUIRE(out_doc && out_chunk && out_score, "an output is NULL");
+    MIR_REQUIRE(text_scopes && q_ptr_host, "NULL buffer");
+    int nt = 0;
+    rc = check_query_batch(q_terms_host, q_ptr_host, b, &nt);
+    if (rc != MIR_OK) return rc;
+    for (int i = 0; i < b; ++i) {
+        MIR_REQUIRE(text_scopes[i] != nullptr && text_scopes[i]->searcher == h, "scope %d is not one of this searcher", i);
+        MIR_REQUIRE(text_scopes[i]->n_pos < ((int64_t)1 << 31), "scope %d holds 2^31 chunks or more", i);
+    }
+    HybridLayout lay;
+    const HybridShape hs{b, k, d, (int64_t)table.size(), nt, sizeof(mir_block_desc), sizeof(BlockScopeDev)};
+    const HybridCarve carved = hybrid_carve(hs, &lay);
+    MIR_REQUIRE(carved == kHybridOk, "the call's arrays do not fit a scratch (b=%d k=%d d=%d, %zu blocks, %d terms)", b, k, d, table.size(), nt);
+    const BlockRoute route{h};
+    OutColumn cols[5] = {{nullptr, 8}, {nullptr, 8}, {nullptr, 8}, {nullptr, 4}, {nullptr, 4}};  // pos, chunk, score, ord, local
+    const ScopedInputs inputs{lay.terms, lay.q_ptr, lay.scopes};
+    ScopedPlan<BlockScopeDev> plan;
+    scoped_plan(route, text_scopes, nt, b, k, cols, 5, lay.keyword, &inputs, &plan);
+    rc = use_device(h->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    rc = h->take_scratch(plan.end);
+    if (rc != MIR_OK) return rc;
+    if (h->pin_cap < lay.in_bytes + lay.out_bytes) {
+        if (h->pin) (void)hipHostFree(h->pin);
+        h->pin = nullptr;
+        h->pin_cap = 0;
+        MIR_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin), lay.in_bytes + lay.out_bytes, hipHostMallocDefault));
+        h->pin_cap = lay.in_bytes + lay.out_bytes;
+    }
+    char *base = static_cast<char *>(h->scratch.ptr);
+    char *up = h->pin, *down = h->pin + lay.in_bytes;
+    hipStream_t s = h->stream;
+    const size_t bk2 = (size_t)b * 2 * k;
+    std::memcpy(up + lay.q, queries_host, (size_t)b * d * 8);
+    std::memcpy(up + lay.scope_ptr, scope_ptr_host, ((size_t)b + 1) * 4);
+    if (!table.empty()) std::memcpy(up + lay.table, table.data(), table.size() * sizeof(mir_block_desc));
+    if (nt) std::memcpy(up + lay.terms, q_terms_host, (size_t)nt * 4);
+    std::memcpy(up + lay.q_ptr, q_ptr_host, ((size_t)b + 1) * 4);
+    std::memcpy(up + lay.scopes, plan.sd.data(), (size_t)b * sizeof(BlockScopeDev));
+    int32_t *v_doc = reinterpret_cast<int32_t *>(base + lay.v_doc), *v_count = reinterpret_cast<int32_t *>(base + lay.v_count);
+    int64_t *v_chunk = reinterpret_cast<int64_t *>(base + lay.v_chunk);
+    auto enqueue = [&]() -> int32_t {
+        MIR_HIP(hipMemcpyAsync(base, up, lay.in_bytes, hipMemcpyHostToDevice, s));
+        int32_t r = mir_blocks_search_device(vs, reinterpret_cast<const double *>(base + lay.q), b, k, metric,
+                                             reinterpret_cast<const int32_t *>(base + lay.scope_ptr),
+                                             reinterpret_cast<const mir_block_desc *>(base + lay.table), v_doc, v_chunk, nullptr, nullptr, v_count,
+                                             nullptr, s);
+        if (r != MIR_OK) return r;
+        r = scoped_enqueue(route, plan, base, s, nullptr, nullptr, cols);
+        if (r != MIR_OK) return r;
+        const mir_rrf_list lists[2] = {{v_doc, v_chunk, v_count, k},
+                                       {cols[3].at<int32_t>(base), cols[1].at<int64_t>(base), reinterpret_cast<const int32_t *>(base + plan.o_cnt), k}};
+        r = rrf_launch(lists, 2, weights2_host, c, b, 2 * k, reinterpret_cast<int32_t *>(base + lay.f_doc), reinterpret_cast<int64_t *>(base + lay.f_chunk),
+                       reinterpret_cast<double *>(base + lay.f_score), reinterpret_cast<int32_t *>(base + lay.f_count), s);
+        if (r != MIR_OK) return r;
+        MIR_HIP(hipMemcpyAsync(down, base + lay.f_doc, lay.out_bytes, hipMemcpyDeviceToHost, s));
+        return MIR_OK;
+    };
+    rc = enqueue();
+    if (rc != MIR_OK) { (void)hipStreamSynchronize(s); return rc; }
+    MIR_HIP(hipStreamSynchronize(s));
+    std::memcpy(out_doc, down, bk2 * 4);
+    std::memcpy(out_chunk, down + (lay.f_chunk - lay.f_doc), bk2 * 8);
+    std::memcpy(out_score, down + (lay.f_score - lay.f_doc), bk2 * 8);
+    std::memcpy(out_count, down + (lay.f_count - lay.f_doc), (size_t)b * 4);
+    return MIR_OK;
 }
 
 }  // extern "C"

@@ -1,13 +1,15 @@
-// Weighted reciprocal-rank fusion of the retrievers' result lists (host code).
+// Weighted reciprocal-rank fusion of the retrievers' result lists: the host routines of the single request, and the
+// device form for batches whose lists are already in HBM (fusion_kernels.h).
 //
 // Replaces langchain 0.3.21 EnsembleRetriever.weighted_reciprocal_rank as wired
 // at aidial_rag/retrieval_chain.py:239-245 (weights all 1.0, c = 60): at most
-// 4 lists x 7 items, so this is host logic, not a kernel.
+// 4 lists x 7 items, so mir_rrf_fuse is host logic; rrf_fuse_kernel answers the same for b queries.
 // Restated in oracle/fusion.py: score[key] += w / (rank + c), rank from 1, over
 // every list in order (an item repeated inside a list is credited again);
 // unique keys in first-seen order over the chained lists; stable sort by score,
 // descending.
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <numeric>
@@ -15,6 +17,50 @@
 #include <vector>
 
 #include "common.h"
+#include "fusion_kernels.h"
+
+namespace mir {
+
+// Everything mir_rrf_fuse_device refuses, nothing of the device touched: MIR_ERR_INVALID / MIR_ERR_UNSUPPORTED with a message.
+// `k_only`: the lists' pointers are not there yet (mir_block_hybrid_search checks before it carves its scratch).
+int32_t rrf_check(const mir_rrf_list *lists, int32_t n_lists, const double *weights_host, int32_t c, int32_t b, int32_t cap,
+                  bool k_only) {
+    MIR_REQUIRE(n_lists >= 1 && n_lists <= kRrfMaxLists, "n_lists=%d outside [1, %d]", n_lists, kRrfMaxLists);
+    MIR_REQUIRE(lists != nullptr && weights_host != nullptr, "lists or weights is NULL");
+    MIR_REQUIRE(b >= 0, "b=%d is negative", b);
+    MIR_REQUIRE(c >= 0, "c=%d is negative", c);
+    int64_t total = 0;
+    for (int l = 0; l < n_lists; ++l) {
+        MIR_REQUIRE(k_only || (lists[l].doc && lists[l].chunk && lists[l].count), "list %d has a NULL pointer", l);
+        MIR_REQUIRE(lists[l].k >= 1, "list %d has k=%d, must be >= 1", l, lists[l].k);
+        MIR_REQUIRE(std::isfinite(weights_host[l]), "weight %d is not finite", l);
+        total += lists[l].k;
+    }
+    MIR_REQUIRE(cap >= total, "cap=%d is less than the lists' %lld entries", cap, (long long)total);
+    if (total > kRrfMaxItems) {
+        set_error("the lists hold %lld entries per query, this build fuses at most %d on the device", (long long)total, kRrfMaxItems);
+        return MIR_ERR_UNSUPPORTED;
+    }
+    return MIR_OK;
+}
+
+// The launch alone (arguments checked by rrf_check): asynchronous on `s`, no allocation, no synchronisation.
+int32_t rrf_launch(const mir_rrf_list *lists, int32_t n_lists, const double *weights_host, int32_t c, int32_t b, int32_t cap,
+                   int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_count, hipStream_t s) {
+    if (b == 0) return MIR_OK;
+    RrfArgs a{};
+    for (int l = 0; l < n_lists; ++l) {
+        a.list[l] = lists[l];
+        a.weight[l] = weights_host[l];
+    }
+    a.n_lists = n_lists; a.c = c; a.b = b; a.cap = cap;
+    a.out_doc = out_doc; a.out_chunk = out_chunk; a.out_score = out_score; a.out_count = out_count;
+    rrf_fuse_kernel<<<dim3((unsigned)b), dim3(64), 0, s>>>(a);
+    MIR_HIP(hipGetLastError());
+    return MIR_OK;
+}
+
+}  // namespace mir
 
 extern "C" int32_t mir_rrf_fuse(const int64_t *keys, const int32_t *list_ptr, const double *weights, int32_t n_lists,
                                 int32_t c, int64_t *out_keys, double *out_scores, int32_t *out_count) {
@@ -102,4 +148,13 @@ extern "C" int32_t mir_rrf_fuse_batch(const int64_t *keys, const int64_t *key_ba
         if (rc != MIR_OK) return rc;
     }
     return MIR_OK;
+}
+
+// The same fusion for b queries whose lists lie in HBM: rrf_fuse_kernel on `stream`, asynchronous.
+extern "C" int32_t mir_rrf_fuse_device(const mir_rrf_list *lists, int32_t n_lists, const double *weights_host, int32_t c, int32_t b, int32_t cap,
+                                       int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_count, void *stream) {
+    const int32_t rc = mir::rrf_check(lists, n_lists, weights_host, c, b, cap, false);
+    if (rc != MIR_OK) return rc;
+    MIR_REQUIRE(out_doc && out_chunk && out_score && out_count, "an output is NULL");
+    return mir::rrf_launch(lists, n_lists, weights_host, c, b, cap, out_doc, out_chunk, out_score, out_count, static_cast<hipStream_t>(stream));
 }

@@ -1,0 +1,18 @@
+// What vec_index.hip offers mir_block_hybrid_search (bm25.hip): the host checks of mir_blocks_search, so
+// that the fused entry refuses what the vector leg refuses, with its messages, before anything is uploaded.
+#pragma once
+
+#include <vector>
+
+#include "common.h"
+
+namespace mir {
+
+// Everything mir_blocks_search checks before it launches (handle, shape, metric, scope_ptr, every listed block against the
+// searcher).  MIR_OK: `table` holds one descriptor per listed block, the table mir_blocks_search_device reads once it is
+// in HBM; *d and *device are the searcher's.  With b == 0 nothing but the handle and the shape is looked at.
+int32_t blocks_check_host(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric, const int32_t *scope_ptr_host,
+                          const mir_rows *const *blocks_host, const int32_t *out_count, std::vector<mir_block_desc> *table, int32_t *d,
+                          int32_t *device);
+
+}  // namespace mir

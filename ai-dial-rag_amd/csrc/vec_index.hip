@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.h"
+#include "vec_blocks_host.h"
 #include "vec_kernels.h"
 #include "vec_kernels_f16.h"
 #include "vec_kernels_q16.h"
@@ -1689,6 +1690,21 @@ static int32_t check_blocks(const mir_index *ix, const int32_t *scope_ptr, int n
         *len = (uint64_t)r->n;
         return MIR_OK;
     }, rows);
+}
+
+// mir_blocks_search's checks for a caller in another translation unit (vec_blocks_host.h)
+int32_t blocks_check_host(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, const int32_t *scope_ptr_host,
+                          const mir_rows *const *blocks_host, const int32_t *out_count, std::vector<mir_block_desc> *table, int32_t *d,
+                          int32_t *device) {
+    MIR_REQUIRE(s_ != nullptr, "searcher is NULL");
+    const int32_t rc = check_scoped_args(s_->ix, queries_host, b, k, metric, scope_ptr_host, out_count);
+    if (rc != MIR_OK) return rc;
+    *d = s_->ix->d;
+    *device = s_->ix->device;
+    table->clear();
+    if (b == 0) return MIR_OK;
+    ScopeRows rows{0, 0};
+    return check_blocks(s_->ix, scope_ptr_host, b, "query", nullptr, blocks_host, *table, &rows);
 }
 
 // per-query norms (ngroups = 0: no fragments) + `counters` arrival counters zeroed

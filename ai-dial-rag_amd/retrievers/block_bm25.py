@@ -17,9 +17,12 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from ._scoped_bm25 import ScopedBM25Corpus, ScopedBM25View
+from .. import _native as nat
 from .block_corpus import BlockCorpus
 from .bm25_retriever import BM25BlockScope, BM25BlockSearcher, DeviceBM25Doc
 from .corpus_bm25 import CorpusHybrid, _document_arrays
+from .embeddings_index import BlockSearcher, DeviceRows
+from .embeddings_metrics import Metric
 
 __all__ = ["BlockBM25", "BlockBM25View", "BlockHybrid"]
 
@@ -159,14 +162,54 @@ class BlockBM25(ScopedBM25Corpus):
 class BlockHybrid(CorpusHybrid):
     """Vector + BM25 + weighted reciprocal-rank fusion over a ``BlockCorpus`` and a ``BlockBM25`` that hold the SAME
     documents under the same keys.  ``find_many(query_vectors, query_ids, scopes, metric, k, weights, c)`` is
-    ``CorpusHybrid``'s, with ``scopes`` listing keys."""
+    ``CorpusHybrid``'s, with ``scopes`` listing keys.
+
+    ``device_fusion=True``: ``find_many`` resolves the scopes as ever (a removed key is a ``KeyError``, a list without any
+    token "Text index is empty.") and then makes ONE native call, ``BM25BlockSearcher.hybrid_search``: both legs' lists
+    stay in HBM, are fused there, and the call synchronises once.  The arrays are the host route's, with
+    one difference: the device route packs no key, so it does not raise for chunk ids outside [0, 2^31).  A call the
+    native entry does not serve takes the inherited host route: 2k > 512, a paged document or a frozen run in the vector
+    corpus (they need the expanded and the indexed searches), a weight that is not finite, c < 0.  The sharing routes
+    of the vector leg (``share_scopes``, ``share_pieces``, ``share_paged``) do not go with it."""
 
     def __init__(self, device: int = 0, share_scopes: bool = False, share_pieces: bool = False, min_group: Optional[int] = None,
-                 share_paged: bool = False, device_scopes: bool = False):
+                 share_paged: bool = False, device_scopes: bool = False, device_fusion: bool = False):
+        if device_fusion and (share_scopes or share_pieces or share_paged):
+            raise ValueError("device_fusion goes through the per-query block search: it cannot be combined with share_scopes, share_pieces or share_paged")
         options = {} if min_group is None else {"min_group": min_group}
         super().__init__(BlockCorpus(device=device, share_scopes=share_scopes, share_pieces=share_pieces, share_paged=share_paged, **options),
                          BlockBM25(device=device, device_scopes=device_scopes))
+        self.device_fusion = bool(device_fusion)
         self._lock = threading.Lock()
+
+    def find_many(self, query_vectors, query_ids, scopes, metric, k: int, weights: Sequence[float] = (1.0, 1.0), c: int = 60):
+        """-> (doc_ids[b, 2k], chunk_ids[b, 2k], rrf score[b, 2k], count[b]), best first."""
+        if not self.device_fusion:
+            return super().find_many(query_vectors, query_ids, scopes, metric, k, weights, c)
+        vector, keywords = self.vector, self.keywords
+        w = np.asarray(weights, dtype=np.float64)
+        k = int(k)
+        q = np.atleast_2d(np.asarray(query_vectors, dtype=np.float64))
+        if w.shape != (2,) or not np.all(np.isfinite(w)) or int(c) < 0 or not 1 <= k <= 256 or len(scopes) != len(q) or len(query_ids) != len(q):
+            return super().find_many(query_vectors, query_ids, scopes, metric, k, weights, c)  # (the host route's answer, or its error)
+        Metric(metric)
+        lists = [vector._blocks_of(s) for s in scopes]  # KeyError for a removed key
+        with vector._lock:
+            d, dtype, frozen = vector.d, vector.dtype, bool(vector._frozen)
+            if d is not None and vector._searcher is None:
+                vector._searcher = BlockSearcher(d, dtype, vector.device)
+                vector._empty = DeviceRows.from_host(np.zeros((0, d), np.float16 if dtype == nat.DTYPE_F16 else np.float32), None, vector.device)
+            searcher, empty = vector._searcher, vector._empty
+        if searcher is None or frozen or any(getattr(blk, "fanout", None) is not None for s in lists for blk in s):
+            return super().find_many(query_vectors, query_ids, scopes, metric, k, weights, c)
+        keys = [tuple(int(p) for p in s) for s in scopes]  # ScopedBM25Corpus.find_many's resolution of the keyword scopes
+        made = {key: keywords._cached_view(key) for key in dict.fromkeys(keys)}
+        keywords._prepare_views(list(made.values()))
+        text_scopes = [made[key].scope() for key in keys]  # no token: "Text index is empty."
+        rows = [[empty if blk is None else blk for blk in s] for s in lists]
+        doc, chunk, score, cnt = keywords._device_searcher().hybrid_search(searcher, q, k, metric, rows, text_scopes,
+                                                                            [keywords._ids(t) for t in query_ids], w, int(c))
+        return doc.astype(np.int64), chunk, score, cnt
 
     def add(self, doc_index, text_doc) -> int:
         """``doc_index``: what ``BlockCorpus.add`` takes; ``text_doc``: what ``BlockBM25.add`` takes -> the common key.

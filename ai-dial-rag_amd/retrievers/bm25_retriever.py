@@ -343,6 +343,35 @@ class BM25BlockSearcher(_HandleOwner):
                                                  nat.ptr(order), nat.ptr(local), nat.ptr(chunk), nat.ptr(sc), nat.ptr(cnt)))
         return pos, order, local, chunk, sc, cnt
 
+    def hybrid_search(self, block_searcher, queries: np.ndarray, k: int, metric, row_scopes, text_scopes: Sequence[BM25BlockScope],
+                      queries_ids: Sequence[Sequence[int]], weights: Sequence[float] = (1.0, 1.0), c: int = 60):
+        """A hybrid request batch in ONE native call with one synchronisation (``mir_block_hybrid_search``, DESIGN.md
+        4.11): query i searches the ``DeviceRows`` blocks ``row_scopes[i]`` through ``block_searcher`` (a
+        ``BlockSearcher``) and ranks ``text_scopes[i]`` with ``queries_ids[i]``, both with ``k``, and the two lists are
+        fused on the device with ``weights`` (vector, keyword) and ``c`` -> (doc[b, 2k] i32 = the ordinal of the block in
+        the query's scope, chunk[b, 2k] i64, rrf score[b, 2k] f64, count[b] i32), best first, rows past the count zero.
+        The key is the pair (doc, chunk): any int64 chunk id.  ``NotImplementedError`` for 2k > 512."""
+        from .embeddings_index import Metric, _scope_table
+
+        q = nat.as_f64_queries(queries, block_searcher.d)
+        b = q.shape[0]
+        code = nat.METRIC_CODES[Metric(metric).value]
+        if len(row_scopes) != b or len(text_scopes) != b or len(queries_ids) != b:
+            raise ValueError(f"{len(row_scopes)} row scopes, {len(text_scopes)} text scopes and {len(queries_ids)} term lists for {b} queries")
+        _held, sp, table = _scope_table(row_scopes)  # (the blocks: alive across the call)
+        flat, ptr = _pack_queries(queries_ids)
+        handles = (C.c_void_p * max(b, 1))(*[s.handle for s in text_scopes])
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (2,):
+            raise ValueError(f"weights {tuple(w.shape)}: want one for the vector list and one for the keyword list")
+        cap = 2 * max(int(k), 0)
+        doc, chunk = np.zeros((b, cap), np.int32), np.zeros((b, cap), np.int64)
+        score, cnt = np.zeros((b, cap), np.float64), np.zeros(b, np.int32)
+        nat.check(nat.lib.mir_block_hybrid_search(block_searcher.handle, self._h, nat.ptr(q), b, int(k), code, nat.ptr(sp), table, handles,
+                                                  nat.ptr(flat) if len(flat) else None, nat.ptr(ptr), nat.ptr(w), int(c), nat.ptr(doc),
+                                                  nat.ptr(chunk), nat.ptr(score), nat.ptr(cnt)))
+        return doc, chunk, score, cnt
+
 
 class TextIndexItem:
     """index_record.py:9-15: one chunk's token list."""

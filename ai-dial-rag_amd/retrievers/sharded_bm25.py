@@ -221,6 +221,45 @@ def fuse_batch(lists: Sequence[Tuple[np.ndarray, np.ndarray]], weights: Sequence
     return out_keys[:, :, 0], out_scores, out_cnt
 
 
+def fuse_lists_device(lists, weights: Sequence[float], c: int = 60, cap: Optional[int] = None, stream=None):
+    """``fuse_batch`` for lists that are already on the device (``mir_rrf_fuse_device``, csrc/fusion_kernels.h): one kernel
+    launch on ``stream`` (default: torch's current stream), asynchronous, nothing copied or synchronised.
+
+    lists[l] = (doc[b, k_l] int32, chunk[b, k_l] int64, count[b] int32): contiguous torch tensors on one device, what a
+    block search writes; 1 to 4 lists, sum of k_l <= 512.  The key is the pair (doc, chunk).  Returns torch tensors on that
+    device: (doc[b, cap] int32, chunk[b, cap] int64, score[b, cap] float64, count[b] int32), cap = sum of k_l unless a
+    larger one is asked for; rows past a query's count are zero."""
+    import torch
+
+    nl = len(lists)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if len(w) != nl:
+        raise ValueError(f"{len(w)} weights for {nl} lists")
+    if not 1 <= nl <= 4:  # (the library's refusal, with its message)
+        nat.check(nat.lib.mir_rrf_fuse_device((nat.RrfList * 1)(), nl, nat.ptr(np.zeros(1)), int(c), 0, 0, None, None, None, None, None))
+    arr = (nat.RrfList * nl)()
+    b, dev = lists[0][0].shape[0], lists[0][0].device
+    for l, (doc, chunk, cnt) in enumerate(lists):
+        if doc.dtype != torch.int32 or chunk.dtype != torch.int64 or cnt.dtype != torch.int32:
+            raise ValueError(f"list {l}: want (int32 doc, int64 chunk, int32 count), got ({doc.dtype}, {chunk.dtype}, {cnt.dtype})")
+        if doc.dim() != 2 or chunk.shape != doc.shape or tuple(cnt.shape) != (b,) or doc.shape[0] != b:
+            raise ValueError(f"list {l}: shapes {tuple(doc.shape)}, {tuple(chunk.shape)}, {tuple(cnt.shape)} are not [{b}, k], [{b}, k], [{b}]")
+        if not (doc.is_contiguous() and chunk.is_contiguous() and cnt.is_contiguous()):
+            raise ValueError(f"list {l} is not contiguous")
+        if not doc.is_cuda or any(t.device != dev for t in (doc, chunk, cnt)):
+            raise ValueError(f"list {l} is not on the device of list 0, or not on a device at all")
+        arr[l] = nat.RrfList(doc.data_ptr() or 1, chunk.data_ptr() or 1, cnt.data_ptr() or 1, doc.shape[1])  # (b = 0: no storage, never read)
+    total = sum(int(doc.shape[1]) for doc, _, _ in lists)
+    cap = total if cap is None else int(cap)
+    rows = (b, max(cap, 0))
+    out = (torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int64, device=dev),
+           torch.empty(rows, dtype=torch.float64, device=dev), torch.empty(b, dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
+        nat.check(nat.lib.mir_rrf_fuse_device(arr, nl, nat.ptr(w), int(c), b, cap, *(t.data_ptr() or 1 for t in out), s or None))
+    return out
+
+
 class ShardedHybrid:
     """Semantic + BM25 + fusion over a sharded corpus: BASELINE config 4's step.  `vector` is a ``ShardedSearcher``,
     `keywords` a ``ShardedBM25`` over the same chunks in the same global order; both legs are enqueued on the current

@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: pieces search over paged blocks, ADDED without a new number (nothing of ABI 6 changed):
+#define MIR_ABI_VERSION 6 /* 6: block hybrid in one call and the fusion on the device, ADDED without a new number (nothing of ABI 6 changed):
+                               mir_rrf_fuse_device, mir_block_hybrid_search;
+                            6: pieces search over paged blocks, ADDED without a new number (nothing of ABI 6 changed):
                                mir_blocks_search_pieces_expanded;
                             6: expanded block search, ADDED without a new number (nothing of ABI 6 changed): mir_fanout_create / _info /
                                _get_desc / _destroy, mir_blocks_search_expanded, mir_blocks_search_expanded_device;
@@ -701,7 +703,9 @@ int32_t mir_bm25_blocks_scores(mir_bm25_blocks *s, const mir_bm25_blocks_scope *
  * out_pos = the scope position, out_ord = the ordinal of its block in the scope, out_local = the chunk inside its
  * block, out_chunk = that chunk's id.  Any k >= 1.  An output passed as NULL is not written.  MIR_ERR_INVALID, before
  * anything is launched and with the outputs untouched, for a NULL searcher or scope, a scope of another searcher,
- * q_ptr not monotone from 0 and k < 1.  There is no device form. */
+ * q_ptr not monotone from 0 and k < 1.  There is no exported device form: the per-query descriptor table comes from host
+ * memory, whose lifetime across an unsynchronised return an entry would have to guess at.  The library's own enqueue part
+ * (csrc/bm25_host.h) leaves the columns in HBM for mir_block_hybrid_search, which synchronises before its host arrays die. */
 int32_t mir_bm25_blocks_search(mir_bm25_blocks *s, const mir_bm25_blocks_scope *const *scopes,
                                const int32_t *q_terms_host, const int32_t *q_ptr_host, int32_t b, int32_t k,
                                int64_t *out_pos, int32_t *out_ord, int32_t *out_local, int64_t *out_chunk,
@@ -722,6 +726,46 @@ int32_t mir_rrf_fuse(const int64_t *keys, const int32_t *list_ptr, const double 
 int32_t mir_rrf_fuse_batch(const int64_t *keys, const int64_t *key_base, const int32_t *list_ptr, const double *weights,
                            int32_t n_lists, int32_t c, int32_t b, int32_t cap, int64_t *out_keys, double *out_scores,
                            int32_t *out_count);
+
+/* The fusion on the device (added within ABI 6; csrc/fusion_kernels.h, rrf_fuse_kernel): b queries, n_lists lists each,
+ * every buffer in HBM, asynchronous on `stream`; the call neither allocates nor synchronises.  List l is what a block
+ * search writes to out_doc, out_chunk and out_count with k = k_l: doc int32[b][k_l], chunk int64[b][k_l], count int32[b]
+ * (DEVICE pointers; the struct itself and `weights_host` are host memory, copied into the launch: nothing of the host is
+ * referenced after the call returns).  Query q's chained items are list 0's first count[q] entries, then list 1's, ...;
+ * a count outside [0, k_l] is clamped into it.  Semantics are mir_rrf_fuse's, bit for bit: the key is the PAIR
+ * (doc, chunk) compared as a pair (nothing is packed: any int64 chunk id), a key's score is the sum of
+ * weights[l] / (double)(rank + c) over its occurrences in chained order (rank from 1 inside its list; one float64 add
+ * per occurrence, an item repeated inside a list credited again), unique keys come out by score descending, equal
+ * scores (-0.0 == +0.0) in first-seen order.
+ *   out_doc int32[b][cap], out_chunk int64[b][cap], out_score double[b][cap], out_count int32[b]; cap >= sum of k_l.
+ *   Rows past out_count[q] are written as zeros by the kernel: the caller clears nothing.
+ * MIR_ERR_INVALID, before anything is launched, for n_lists outside [1, 4], a NULL list pointer or output, k_l < 1,
+ * cap < sum of k_l, b < 0, c < 0 and a weight that is not finite (with finite weights and c >= 0 every score is finite;
+ * mir_rrf_fuse's two host paths order NaN scores differently, so that case is shut out here, not defined).
+ * MIR_ERR_UNSUPPORTED for sum of k_l > 512.  b == 0 is MIR_OK.  The lists are trusted to hold b rows of k_l entries. */
+typedef struct { const int32_t *doc; const int64_t *chunk; const int32_t *count; int32_t k; } mir_rrf_list;
+int32_t mir_rrf_fuse_device(const mir_rrf_list *lists, int32_t n_lists, const double *weights_host, int32_t c, int32_t b,
+                            int32_t cap, int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_count,
+                            void *stream);
+
+/* A hybrid request batch in ONE call with ONE synchronisation (added within ABI 6): the vector leg as
+ * mir_blocks_search takes it (queries_host double[b][d], scope_ptr_host, blocks_host), the keyword leg as
+ * mir_bm25_blocks_search takes it (text_scopes[b], q_terms_host, q_ptr_host), both with the same k, and their two lists
+ * fused by rrf_fuse_kernel with weights2_host[0] for the vector list and weights2_host[1] for the keyword list.  The
+ * answer for query q is what mir_rrf_fuse returns for the two lists mir_blocks_search and mir_bm25_blocks_search return
+ * for it, bit for bit; a result's doc is the ordinal of its block in the query's scope, in both legs.
+ *   out_doc int32[b][2k], out_chunk int64[b][2k], out_score double[b][2k], out_count int32[b]  (host)
+ * The call works under the keyword searcher's mutex, on its stream and in its scratch (which grows, never shrinks): one
+ * upload, the vector leg through mir_blocks_search_device on that stream, the keyword leg, the fusion, one download,
+ * one hipStreamSynchronize.  The legs' own lists are not returned.
+ * Returns, before anything is uploaded or launched and with the outputs untouched: MIR_ERR_INVALID for everything
+ * mir_blocks_search or mir_bm25_blocks_search refuses (their messages), for searchers on different devices and for
+ * what mir_rrf_fuse_device refuses (c < 0, a weight that is not finite); MIR_ERR_UNSUPPORTED for 2k > 512. */
+int32_t mir_block_hybrid_search(mir_blocks *vs, mir_bm25_blocks *ts, const double *queries_host, int32_t b, int32_t k,
+                                int32_t metric, const int32_t *scope_ptr_host, const mir_rows *const *blocks_host,
+                                const mir_bm25_blocks_scope *const *text_scopes, const int32_t *q_terms_host,
+                                const int32_t *q_ptr_host, const double *weights2_host, int32_t c, int32_t *out_doc,
+                                int64_t *out_chunk, double *out_score, int32_t *out_count);
 
 /* ------------------------------------------------------------------------
  * WordPiece tokenisation (host code): the BertTokenizer step in front of the encoder
