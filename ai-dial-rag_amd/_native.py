@@ -146,6 +146,10 @@ def _load():
         "mir_rrf_fuse_batch": ([vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp], i32),
         "mir_rrf_fuse_device": ([vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp], i32),
         "mir_block_hybrid_search": ([vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp], i32),
+        "mir_rrf_fuse_device_origin": ([vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp], i32),
+        "mir_ensemble_create": ([i32, vp], i32),
+        "mir_ensemble_destroy": ([vp], i32),
+        "mir_block_ensemble_search": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -176,6 +180,18 @@ class RrfList(C.Structure):
     """mir_rrf_list: one result list of b queries as mir_rrf_fuse_device reads it (device pointers, and its k)."""
 
     _fields_ = [("doc", C.c_void_p), ("chunk", C.c_void_p), ("count", C.c_void_p), ("k", C.c_int32)]
+
+
+LEG_VECTOR, LEG_KEYWORD = 0, 1  # mir_ensemble_leg.kind
+
+
+class EnsembleLeg(C.Structure):
+    """mir_ensemble_leg: one leg of ``mir_block_ensemble_search`` (host pointers; the fields of the other kind stay null)."""
+
+    _fields_ = [("kind", C.c_int32), ("k", C.c_int32), ("weight", C.c_double),
+                ("searcher", C.c_void_p), ("queries_host", C.c_void_p), ("metric", C.c_int32),
+                ("scope_ptr_host", C.c_void_p), ("blocks_host", C.c_void_p), ("fanouts_host", C.c_void_p),
+                ("text_searcher", C.c_void_p), ("text_scopes", C.c_void_p), ("q_terms_host", C.c_void_p), ("q_ptr_host", C.c_void_p)]
 
 
 def last_error() -> str:

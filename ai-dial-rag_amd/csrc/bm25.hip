@@ -1298,6 +1298,7 @@ __global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const doubl
 #include "bm25_scope_batch_layout.h"
 #include "fusion_host.h"
 #include "hybrid_layout.h"
+#include "ensemble_layout.h"
 #include "vec_blocks_host.h"
 
 using namespace mir;
@@ -2646,7 +2647,7 @@ int32_t mir_block_hybrid_search(mir_blocks *vs, mir_bm25_blocks *h, const double
         const mir_rrf_list lists[2] = {{v_doc, v_chunk, v_count, k},
                                        {cols[3].at<int32_t>(base), cols[1].at<int64_t>(base), reinterpret_cast<const int32_t *>(base + plan.o_cnt), k}};
         r = rrf_launch(lists, 2, weights2_host, c, b, 2 * k, reinterpret_cast<int32_t *>(base + lay.f_doc), reinterpret_cast<int64_t *>(base + lay.f_chunk),
-                       reinterpret_cast<double *>(base + lay.f_score), reinterpret_cast<int32_t *>(base + lay.f_count), s);
+                       reinterpret_cast<double *>(base + lay.f_score), nullptr, reinterpret_cast<int32_t *>(base + lay.f_count), s);
         if (r != MIR_OK) return r;
         MIR_HIP(hipMemcpyAsync(down, base + lay.f_doc, lay.out_bytes, hipMemcpyDeviceToHost, s));
         return MIR_OK;
@@ -2657,6 +2658,217 @@ int32_t mir_block_hybrid_search(mir_blocks *vs, mir_bm25_blocks *h, const double
     std::memcpy(out_doc, down, bk2 * 4);
     std::memcpy(out_chunk, down + (lay.f_chunk - lay.f_doc), bk2 * 8);
     std::memcpy(out_score, down + (lay.f_score - lay.f_doc), bk2 * 8);
+    std::memcpy(out_count, down + (lay.f_count - lay.f_doc), (size_t)b * 4);
+    return MIR_OK;
+}
+
+// ---- block ensemble: up to four legs and their fusion in one call ---------------------------------------
+
+// The stream, the scratch, the pinned staging and the mutex of mir_block_ensemble_search; it owns no documents.
+struct mir_ensemble {
+    int device = 0;
+    std::mutex mu;  // serialises use of everything below
+    DevScratch scratch;
+    hipStream_t stream = nullptr;
+    char *pin = nullptr;  // the one upload and the one download; grows, never shrinks
+    size_t pin_cap = 0;
+};
+
+int32_t mir_ensemble_create(int32_t device, mir_ensemble **out) {
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    int32_t rc = use_device(device, nullptr);
+    if (rc != MIR_OK) return rc;
+    mir_ensemble *e = new (std::nothrow) mir_ensemble();
+    MIR_REQUIRE(e != nullptr, "out of host memory");
+    e->device = device;
+    hipError_t err = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
+    if (err != hipSuccess) {
+        set_error("hipStreamCreateWithFlags failed: %s", hipGetErrorString(err));
+        delete e;
+        return MIR_ERR_HIP;
+    }
+    *out = e;
+    return MIR_OK;
+}
+
+int32_t mir_ensemble_destroy(mir_ensemble *e) {
+    if (!e) return MIR_OK;
+    (void)hipSetDevice(e->device);
+    e->scratch.release();
+    if (e->pin) (void)hipHostFree(e->pin);
+    if (e->stream) (void)hipStreamDestroy(e->stream);
+    delete e;
+    return MIR_OK;
+}
+
+// What the host side of one leg leaves for the enqueue part.
+struct EnsembleLegHost {
+    std::vector<mir_block_desc> table;
+    std::vector<mir_fanout_desc> fan_table;
+    int32_t d = 0, device = 0;
+    int nt = 0;
+};
+
+// Everything mir_bm25_blocks_search refuses, with its messages, nothing of the device touched; *nt = the batch's terms.
+static int32_t ensemble_keyword_check(const mir_bm25_blocks *h, const mir_bm25_blocks_scope *const *scopes, const int32_t *q_terms_host,
+                                      const int32_t *q_ptr_host, int32_t b, int32_t k, int *nt) {
+    MIR_REQUIRE(h != nullptr, "searcher is NULL");
+    MIR_REQUIRE(b >= 0 && k >= 1, "bad shape b=%d k=%d", b, k);
+    *nt = 0;
+    if (b == 0) return MIR_OK;
+    MIR_REQUIRE(scopes && q_ptr_host, "NULL buffer");
+    const int32_t rc = check_query_batch(q_terms_host, q_ptr_host, b, nt);
+    if (rc != MIR_OK) return rc;
+    for (int i = 0; i < b; ++i) {
+        MIR_REQUIRE(scopes[i] != nullptr && scopes[i]->searcher == h, "scope %d is not one of this searcher", i);
+        MIR_REQUIRE(scopes[i]->n_pos < ((int64_t)1 << 31), "scope %d holds 2^31 chunks or more", i);
+    }
+    return MIR_OK;
+}
+
+// Under the ensemble's mutex, then the keyword searcher's; on the ensemble's stream and in its scratch: ensemble_layout.h,
+// then the keyword leg's columns (scoped_plan from lay.keyword on, with the ensemble's scratch as its base - so
+// mir_bm25_blocks_search and mir_block_hybrid_search, which work in the searcher's scratch, are as they were).  A vector leg
+// rides the stream through mir_blocks_search(_expanded)_device, whose workspace goes back to its pool pending on it.
+// Everything the stream reads from the host is in the pinned staging, which outlives the one hipStreamSynchronize.
+int32_t mir_block_ensemble_search(mir_ensemble *e, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c, int32_t cap,
+                                  int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_origin, int32_t *out_count) {
+    // refusals in a fixed order: the call's own shape, the fusion's, each leg's in the order of the legs, the ensemble and
+    // the devices; nothing of the device is touched before the last
+    MIR_REQUIRE(legs != nullptr, "legs is NULL");
+    MIR_REQUIRE(out_doc && out_chunk && out_score && out_origin && out_count, "an output is NULL");
+    MIR_REQUIRE(n_legs >= 1 && n_legs <= kRrfMaxLists, "n_legs=%d outside [1, %d]", n_legs, kRrfMaxLists);
+    int kw = -1;
+    mir_rrf_list lists[kRrfMaxLists] = {};
+    double weights[kRrfMaxLists] = {};
+    for (int l = 0; l < n_legs; ++l) {
+        MIR_REQUIRE(legs[l].kind == MIR_LEG_VECTOR || legs[l].kind == MIR_LEG_KEYWORD, "leg %d has unknown kind %d", l, legs[l].kind);
+        if (legs[l].kind == MIR_LEG_KEYWORD) {
+            MIR_REQUIRE(kw < 0, "legs %d and %d are both keyword legs: at most one", kw, l);
+            kw = l;
+        }
+        lists[l].k = legs[l].k;
+        weights[l] = legs[l].weight;
+    }
+    int32_t rc = rrf_check(lists, n_legs, weights, c, b, cap, true);
+    if (rc != MIR_OK) return rc;
+    EnsembleLegHost host[kRrfMaxLists];
+    for (int l = 0; l < n_legs; ++l) {
+        const mir_ensemble_leg &g = legs[l];
+        EnsembleLegHost &hl = host[l];
+        if (g.kind == MIR_LEG_KEYWORD) {
+            rc = ensemble_keyword_check(g.text_searcher, g.text_scopes, g.q_terms_host, g.q_ptr_host, b, g.k, &hl.nt);
+            if (rc == MIR_OK) hl.device = g.text_searcher->device;
+        } else if (g.fanouts_host) {
+            rc = blocks_expanded_check_host(g.searcher, g.queries_host, b, g.k, g.metric, g.scope_ptr_host, g.blocks_host, g.fanouts_host, out_count,
+                                            &hl.table, &hl.fan_table, &hl.d, &hl.device);
+        } else {
+            rc = blocks_check_host(g.searcher, g.queries_host, b, g.k, g.metric, g.scope_ptr_host, g.blocks_host, out_count, &hl.table, &hl.d,
+                                   &hl.device);
+        }
+        if (rc != MIR_OK) return rc;
+    }
+    MIR_REQUIRE(e != nullptr, "ensemble is NULL");
+    for (int l = 0; l < n_legs; ++l)
+        MIR_REQUIRE(host[l].device == e->device, "the searcher of leg %d is on device %d, the ensemble on device %d", l, host[l].device, e->device);
+    if (b == 0) return MIR_OK;
+    EnsembleShape es{};
+    es.b = b; es.cap = cap; es.n_legs = n_legs;
+    es.desc_bytes = sizeof(mir_block_desc); es.fan_bytes = sizeof(mir_fanout_desc); es.scope_bytes = sizeof(BlockScopeDev);
+    for (int l = 0; l < n_legs; ++l) {
+        const mir_ensemble_leg &g = legs[l];
+        EnsembleLegShape &ls = es.leg[l];
+        ls.kind = g.kind; ls.k = g.k; ls.d = host[l].d; ls.listed = (int64_t)host[l].table.size(); ls.terms = host[l].nt;
+        ls.fanouts = g.kind == MIR_LEG_VECTOR && g.fanouts_host != nullptr;
+        ls.q_of = -1;
+        for (int j = 0; j < l && g.kind == MIR_LEG_VECTOR && ls.q_of < 0; ++j)  // the same host queries at the same d: uploaded once
+            if (legs[j].kind == MIR_LEG_VECTOR && es.leg[j].q_of < 0 && legs[j].queries_host == g.queries_host && host[j].d == host[l].d) ls.q_of = j;
+    }
+    EnsembleLayout lay;
+    const EnsembleCarve carved = ensemble_carve(es, &lay);
+    MIR_REQUIRE(carved == kEnsembleOk, "the call's arrays do not fit a scratch (b=%d cap=%d, %d legs)", b, cap, n_legs);
+    mir_bm25_blocks *h = kw >= 0 ? legs[kw].text_searcher : nullptr;
+    const BlockRoute route{h};
+    OutColumn cols[5] = {{nullptr, 8}, {nullptr, 8}, {nullptr, 8}, {nullptr, 4}, {nullptr, 4}};  // pos, chunk, score, ord, local
+    ScopedPlan<BlockScopeDev> plan;
+    size_t need = lay.keyword;
+    if (kw >= 0) {
+        const ScopedInputs inputs{lay.leg[kw].terms, lay.leg[kw].q_ptr, lay.leg[kw].scopes};
+        scoped_plan(route, legs[kw].text_scopes, host[kw].nt, b, legs[kw].k, cols, 5, lay.keyword, &inputs, &plan);
+        need = plan.end;
+    }
+    rc = use_device(e->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    std::unique_lock<std::mutex> lk_text;
+    if (h) lk_text = std::unique_lock<std::mutex>(h->mu);
+    rc = e->scratch.ensure(need);
+    if (rc != MIR_OK) return rc;
+    if (e->pin_cap < lay.in_bytes + lay.out_bytes) {
+        if (e->pin) (void)hipHostFree(e->pin);
+        e->pin = nullptr;
+        e->pin_cap = 0;
+        MIR_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->pin), lay.in_bytes + lay.out_bytes, hipHostMallocDefault));
+        e->pin_cap = lay.in_bytes + lay.out_bytes;
+    }
+    char *base = static_cast<char *>(e->scratch.ptr);
+    char *up = e->pin, *down = e->pin + lay.in_bytes;
+    hipStream_t s = e->stream;
+    for (int l = 0; l < n_legs; ++l) {
+        const mir_ensemble_leg &g = legs[l];
+        const EnsembleLegLayout &at = lay.leg[l];
+        if (g.kind == MIR_LEG_KEYWORD) {
+            if (host[l].nt) std::memcpy(up + at.terms, g.q_terms_host, (size_t)host[l].nt * 4);
+            std::memcpy(up + at.q_ptr, g.q_ptr_host, ((size_t)b + 1) * 4);
+            std::memcpy(up + at.scopes, plan.sd.data(), (size_t)b * sizeof(BlockScopeDev));
+            continue;
+        }
+        if (es.leg[l].q_of < 0) std::memcpy(up + at.q, g.queries_host, (size_t)b * host[l].d * 8);
+        std::memcpy(up + at.scope_ptr, g.scope_ptr_host, ((size_t)b + 1) * 4);
+        if (!host[l].table.empty()) std::memcpy(up + at.table, host[l].table.data(), host[l].table.size() * sizeof(mir_block_desc));
+        if (es.leg[l].fanouts && !host[l].fan_table.empty())
+            std::memcpy(up + at.fan_table, host[l].fan_table.data(), host[l].fan_table.size() * sizeof(mir_fanout_desc));
+    }
+    auto enqueue = [&]() -> int32_t {
+        MIR_HIP(hipMemcpyAsync(base, up, lay.in_bytes, hipMemcpyHostToDevice, s));
+        for (int l = 0; l < n_legs; ++l) {
+            const mir_ensemble_leg &g = legs[l];
+            const EnsembleLegLayout &at = lay.leg[l];
+            int32_t r;
+            if (g.kind == MIR_LEG_KEYWORD) {
+                r = scoped_enqueue(route, plan, base, s, nullptr, nullptr, cols);
+                lists[l] = mir_rrf_list{cols[3].at<int32_t>(base), cols[1].at<int64_t>(base), reinterpret_cast<const int32_t *>(base + plan.o_cnt), g.k};
+            } else {
+                int32_t *l_doc = reinterpret_cast<int32_t *>(base + at.l_doc), *l_count = reinterpret_cast<int32_t *>(base + at.l_count);
+                int64_t *l_chunk = reinterpret_cast<int64_t *>(base + at.l_chunk);
+                const double *q = reinterpret_cast<const double *>(base + at.q);
+                const int32_t *sp = reinterpret_cast<const int32_t *>(base + at.scope_ptr);
+                const mir_block_desc *table = reinterpret_cast<const mir_block_desc *>(base + at.table);
+                if (es.leg[l].fanouts)
+                    r = mir_blocks_search_expanded_device(g.searcher, q, b, g.k, g.metric, sp, table, reinterpret_cast<const mir_fanout_desc *>(base + at.fan_table),
+                                                          l_doc, l_chunk, nullptr, nullptr, l_count, nullptr, s);
+                else
+                    r = mir_blocks_search_device(g.searcher, q, b, g.k, g.metric, sp, table, l_doc, l_chunk, nullptr, nullptr, l_count, nullptr, s);
+                lists[l] = mir_rrf_list{l_doc, l_chunk, l_count, g.k};
+            }
+            if (r != MIR_OK) return r;
+        }
+        const int32_t r = rrf_launch(lists, n_legs, weights, c, b, cap, reinterpret_cast<int32_t *>(base + lay.f_doc), reinterpret_cast<int64_t *>(base + lay.f_chunk),
+                                     reinterpret_cast<double *>(base + lay.f_score), reinterpret_cast<int32_t *>(base + lay.f_origin),
+                                     reinterpret_cast<int32_t *>(base + lay.f_count), s);
+        if (r != MIR_OK) return r;
+        MIR_HIP(hipMemcpyAsync(down, base + lay.f_doc, lay.out_bytes, hipMemcpyDeviceToHost, s));
+        return MIR_OK;
+    };
+    rc = enqueue();
+    if (rc != MIR_OK) { (void)hipStreamSynchronize(s); return rc; }
+    MIR_HIP(hipStreamSynchronize(s));
+    const size_t rows = (size_t)b * cap;
+    std::memcpy(out_doc, down, rows * 4);
+    std::memcpy(out_chunk, down + (lay.f_chunk - lay.f_doc), rows * 8);
+    std::memcpy(out_score, down + (lay.f_score - lay.f_doc), rows * 8);
+    std::memcpy(out_origin, down + (lay.f_origin - lay.f_doc), rows * 4);
     std::memcpy(out_count, down + (lay.f_count - lay.f_doc), (size_t)b * 4);
     return MIR_OK;
 }

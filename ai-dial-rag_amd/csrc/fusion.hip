@@ -45,17 +45,20 @@ int32_t rrf_check(const mir_rrf_list *lists, int32_t n_lists, const double *weig
 }
 
 // The launch alone (arguments checked by rrf_check): asynchronous on `s`, no allocation, no synchronisation.
+// out_origin NULL: the variant without the origin, the kernel mir_rrf_fuse_device always launched.
 int32_t rrf_launch(const mir_rrf_list *lists, int32_t n_lists, const double *weights_host, int32_t c, int32_t b, int32_t cap,
-                   int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_count, hipStream_t s) {
+                   int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_origin, int32_t *out_count, hipStream_t s) {
     if (b == 0) return MIR_OK;
-    RrfArgs a{};
+    RrfArgsOrigin a{};
     for (int l = 0; l < n_lists; ++l) {
         a.list[l] = lists[l];
         a.weight[l] = weights_host[l];
     }
     a.n_lists = n_lists; a.c = c; a.b = b; a.cap = cap;
     a.out_doc = out_doc; a.out_chunk = out_chunk; a.out_score = out_score; a.out_count = out_count;
-    rrf_fuse_kernel<<<dim3((unsigned)b), dim3(64), 0, s>>>(a);
+    a.out_origin = out_origin;
+    if (out_origin) rrf_fuse_kernel<true><<<dim3((unsigned)b), dim3(64), 0, s>>>(a);
+    else rrf_fuse_kernel<false><<<dim3((unsigned)b), dim3(64), 0, s>>>(static_cast<const RrfArgs &>(a));
     MIR_HIP(hipGetLastError());
     return MIR_OK;
 }
@@ -156,5 +159,18 @@ extern "C" int32_t mir_rrf_fuse_device(const mir_rrf_list *lists, int32_t n_list
     const int32_t rc = mir::rrf_check(lists, n_lists, weights_host, c, b, cap, false);
     if (rc != MIR_OK) return rc;
     MIR_REQUIRE(out_doc && out_chunk && out_score && out_count, "an output is NULL");
-    return mir::rrf_launch(lists, n_lists, weights_host, c, b, cap, out_doc, out_chunk, out_score, out_count, static_cast<hipStream_t>(stream));
+    return mir::rrf_launch(lists, n_lists, weights_host, c, b, cap, out_doc, out_chunk, out_score, nullptr, out_count, static_cast<hipStream_t>(stream));
+}
+
+// mir_rrf_fuse_device that also says where each key was first seen: out_origin[q][slot] = the list of the key's first
+// occurrence in chained order; rows past the count are zero like the other outputs.
+extern "C" int32_t mir_rrf_fuse_device_origin(const mir_rrf_list *lists, int32_t n_lists, const double *weights_host, int32_t c, int32_t b,
+                                              int32_t cap, int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_origin,
+                                              int32_t *out_count, void *stream) {
+    const int32_t rc = mir::rrf_check(lists, n_lists, weights_host, c, b, cap, false);
+    if (rc != MIR_OK) return rc;
+    MIR_REQUIRE(out_doc && out_chunk && out_score && out_count, "an output is NULL");
+    MIR_REQUIRE(out_origin != nullptr, "out_origin is NULL");
+    return mir::rrf_launch(lists, n_lists, weights_host, c, b, cap, out_doc, out_chunk, out_score, out_origin, out_count,
+                           static_cast<hipStream_t>(stream));
 }

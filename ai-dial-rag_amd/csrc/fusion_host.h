@@ -12,8 +12,9 @@ namespace mir {
 int32_t rrf_check(const mir_rrf_list *lists, int32_t n_lists, const double *weights_host, int32_t c, int32_t b, int32_t cap, bool k_only);
 
 // The launch alone, its arguments checked by rrf_check: asynchronous on `s`, no allocation, no synchronisation; lists
-// and weights travel in the kernel's arguments.
+// and weights travel in the kernel's arguments.  out_origin: int32[b][cap] for the list each key was first seen in (the
+// kernel's origin variant), or NULL for the variant without it.
 int32_t rrf_launch(const mir_rrf_list *lists, int32_t n_lists, const double *weights_host, int32_t c, int32_t b, int32_t cap,
-                   int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_count, hipStream_t s);
+                   int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_origin, int32_t *out_count, hipStream_t s);
 
 }  // namespace mir

@@ -15,7 +15,13 @@
 //                     Every lane reads the SAME item j in the same step (a broadcast: no bank conflict).  O(T^2 / 64)
 //                     steps per lane, T <= kRrfMaxItems.
 // The key is the pair (doc, chunk) compared as a pair: nothing is packed, any int64 chunk id is a key.
+//
+// rrf_fuse_kernel<true> is the same body with one more output: out_origin[q][slot] = the list that holds
+// the key's first occurrence in chained order - the list of item i itself, since only a first occurrence is written.
+// rrf_fuse_kernel<false> takes RrfArgs as it always did and compiles to the kernel it was.
 #pragma once
+
+#include <type_traits>
 
 #include "fusion_host.h"
 
@@ -31,9 +37,14 @@ struct RrfArgs {
     int32_t *out_count;
 };
 
+struct RrfArgsOrigin : RrfArgs {
+    int32_t *out_origin;  // int32[b][cap]
+};
+
 // Travels by value: the kernel references no host memory and no table in HBM.  Every index into a.list / a.weight is a
 // constant after unrolling, so the arguments stay in scalar registers.
-__global__ __launch_bounds__(64) void rrf_fuse_kernel(const RrfArgs a) {
+template <bool ORIGIN>
+__global__ __launch_bounds__(64) void rrf_fuse_kernel(const std::conditional_t<ORIGIN, RrfArgsOrigin, RrfArgs> a) {
     __shared__ int64_t s_chunk[kRrfMaxItems];
     __shared__ double s_score[kRrfMaxItems];  // of the unique keys, by first occurrence
     __shared__ int32_t s_doc[kRrfMaxItems];
@@ -104,12 +115,14 @@ __global__ __launch_bounds__(64) void rrf_fuse_kernel(const RrfArgs a) {
             a.out_doc[row + slot] = s_doc[i];
             a.out_chunk[row + slot] = s_chunk[i];
             a.out_score[row + slot] = mine;
+            if constexpr (ORIGIN) a.out_origin[row + slot] = (i >= off1) + (i >= off2) + (i >= off3);  // the list of item i
         }
     }
     for (int r = n_uniq + lane; r < a.cap; r += 64) {
         a.out_doc[row + r] = 0;
         a.out_chunk[row + r] = 0;
         a.out_score[row + r] = 0.0;
+        if constexpr (ORIGIN) a.out_origin[row + r] = 0;
     }
     if (lane == 0) a.out_count[q] = n_uniq;
 }

@@ -1707,6 +1707,39 @@ int32_t blocks_check_host(mir_blocks *s_, const double *queries_host, int32_t b,
     return check_blocks(s_->ix, scope_ptr_host, b, "query", nullptr, blocks_host, *table, &rows);
 }
 
+// mir_blocks_search_expanded's part past check_blocks: the fan-outs against their blocks, while they become the descriptor
+// table the expansion reads (all null = the block has none); the expanded scopes' rows
+static int32_t check_fanouts(const int32_t *scope_ptr_host, int32_t b, const mir_rows *const *blocks_host, const mir_fanout *const *fanouts_host,
+                             size_t listed, std::vector<mir_fanout_desc> *fan_table) {
+    fan_table->assign(listed, mir_fanout_desc{nullptr, nullptr, nullptr, 0});
+    for (int i = 0; i < b; ++i) {
+        uint64_t rows = 0;
+        for (int t = scope_ptr_host[i]; t < scope_ptr_host[i + 1]; ++t) {
+            const mir_fanout *f = fanouts_host ? fanouts_host[t] : nullptr;
+            const int ordinal = t - scope_ptr_host[i];
+            if (f) {
+                MIR_REQUIRE(f->n == blocks_host[t]->n && f->device == blocks_host[t]->device,
+                            "the fan-out of block %d of query %d is of %lld stored rows on device %d, the block holds %lld on device %d", ordinal, i,
+                            (long long)f->n, f->device, (long long)blocks_host[t]->n, blocks_host[t]->device);
+                (*fan_table)[(size_t)t] = mir_fanout_desc{f->d_ptr, f->d_chunk, f->d_pos, f->n};
+            }
+            rows += (uint64_t)(f ? f->R : blocks_host[t]->n);
+            MIR_REQUIRE(rows < (1ull << 32), "the expanded scope of query %d holds 2^32 rows or more", i);
+        }
+    }
+    return MIR_OK;
+}
+
+// mir_blocks_search_expanded's checks for a caller in another translation unit (vec_blocks_host.h)
+int32_t blocks_expanded_check_host(mir_blocks *s_, const double *queries_host, int32_t b, int32_t k, int32_t metric, const int32_t *scope_ptr_host,
+                                   const mir_rows *const *blocks_host, const mir_fanout *const *fanouts_host, const int32_t *out_count,
+                                   std::vector<mir_block_desc> *table, std::vector<mir_fanout_desc> *fan_table, int32_t *d, int32_t *device) {
+    const int32_t rc = blocks_check_host(s_, queries_host, b, k, metric, scope_ptr_host, blocks_host, out_count, table, d, device);
+    fan_table->clear();
+    if (rc != MIR_OK || b == 0) return rc;
+    return check_fanouts(scope_ptr_host, b, blocks_host, fanouts_host, table->size(), fan_table);
+}
+
 // per-query norms (ngroups = 0: no fragments) + `counters` arrival counters zeroed
 static void launch_scoped_prep(const ScopedCall &c, const ScopedBuffers &sb, int counters, hipStream_t stream) {
     const int arrive_words = (counters + 1) / 2;
@@ -1998,23 +2031,9 @@ int32_t mir_blocks_search_expanded(mir_blocks *s_, const double *queries_host, i
                  {out_doc, out_chunk, out_row, out_dist, out_count, out_flags}};
     rc = check_blocks(s_->ix, scope_ptr_host, b, "query", nullptr, blocks_host, table, &c.rows);
     if (rc != MIR_OK) return rc;
-    // the fan-outs against their blocks, while they become the descriptor table the expansion reads; the expanded scopes' rows
-    std::vector<mir_fanout_desc> fan_table(table.size(), mir_fanout_desc{nullptr, nullptr, nullptr, 0});
-    for (int i = 0; i < b; ++i) {
-        uint64_t rows = 0;
-        for (int t = scope_ptr_host[i]; t < scope_ptr_host[i + 1]; ++t) {
-            const mir_fanout *f = fanouts_host ? fanouts_host[t] : nullptr;
-            const int ordinal = t - scope_ptr_host[i];
-            if (f) {
-                MIR_REQUIRE(f->n == blocks_host[t]->n && f->device == blocks_host[t]->device,
-                            "the fan-out of block %d of query %d is of %lld stored rows on device %d, the block holds %lld on device %d", ordinal, i,
-                            (long long)f->n, f->device, (long long)blocks_host[t]->n, blocks_host[t]->device);
-                fan_table[(size_t)t] = mir_fanout_desc{f->d_ptr, f->d_chunk, f->d_pos, f->n};
-            }
-            rows += (uint64_t)(f ? f->R : blocks_host[t]->n);
-            MIR_REQUIRE(rows < (1ull << 32), "the expanded scope of query %d holds 2^32 rows or more", i);
-        }
-    }
+    std::vector<mir_fanout_desc> fan_table;
+    rc = mir::check_fanouts(scope_ptr_host, b, blocks_host, fanouts_host, table.size(), &fan_table);
+    if (rc != MIR_OK) return rc;
     c.host_api = true; c.table = table.data();
     c.expanded = true; c.fan_table = fan_table.data();
     return run_scoped(c);

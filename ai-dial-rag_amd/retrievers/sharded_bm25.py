@@ -221,14 +221,15 @@ def fuse_batch(lists: Sequence[Tuple[np.ndarray, np.ndarray]], weights: Sequence
     return out_keys[:, :, 0], out_scores, out_cnt
 
 
-def fuse_lists_device(lists, weights: Sequence[float], c: int = 60, cap: Optional[int] = None, stream=None):
+def fuse_lists_device(lists, weights: Sequence[float], c: int = 60, cap: Optional[int] = None, stream=None, with_origin: bool = False):
     """``fuse_batch`` for lists that are already on the device (``mir_rrf_fuse_device``, csrc/fusion_kernels.h): one kernel
     launch on ``stream`` (default: torch's current stream), asynchronous, nothing copied or synchronised.
 
     lists[l] = (doc[b, k_l] int32, chunk[b, k_l] int64, count[b] int32): contiguous torch tensors on one device, what a
     block search writes; 1 to 4 lists, sum of k_l <= 512.  The key is the pair (doc, chunk).  Returns torch tensors on that
     device: (doc[b, cap] int32, chunk[b, cap] int64, score[b, cap] float64, count[b] int32), cap = sum of k_l unless a
-    larger one is asked for; rows past a query's count are zero."""
+    larger one is asked for; rows past a query's count are zero.  ``with_origin=True`` (``mir_rrf_fuse_device_origin``):
+    (doc, chunk, score, origin[b, cap] int32, count), origin = the list a key was first seen in, in chained order."""
     import torch
 
     nl = len(lists)
@@ -254,9 +255,12 @@ def fuse_lists_device(lists, weights: Sequence[float], c: int = 60, cap: Optiona
     rows = (b, max(cap, 0))
     out = (torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int64, device=dev),
            torch.empty(rows, dtype=torch.float64, device=dev), torch.empty(b, dtype=torch.int32, device=dev))
+    if with_origin:
+        out = out[:3] + (torch.empty(rows, dtype=torch.int32, device=dev), out[3])
+    fuse = nat.lib.mir_rrf_fuse_device_origin if with_origin else nat.lib.mir_rrf_fuse_device
     with torch.cuda.device(dev):
         s = torch.cuda.current_stream(dev).cuda_stream if stream is None else int(stream)
-        nat.check(nat.lib.mir_rrf_fuse_device(arr, nl, nat.ptr(w), int(c), b, cap, *(t.data_ptr() or 1 for t in out), s or None))
+        nat.check(fuse(arr, nl, nat.ptr(w), int(c), b, cap, *(t.data_ptr() or 1 for t in out), s or None))
     return out
 
 

@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: block hybrid in one call and the fusion on the device, ADDED without a new number (nothing of ABI 6 changed):
+#define MIR_ABI_VERSION 6 /* 6: block ensemble in one call and the fusion's origin, ADDED without a new number (nothing of ABI 6 changed):
+                               mir_rrf_fuse_device_origin, mir_ensemble_create / _destroy, mir_block_ensemble_search;
+                            6: block hybrid in one call and the fusion on the device, ADDED without a new number (nothing of ABI 6 changed):
                                mir_rrf_fuse_device, mir_block_hybrid_search;
                             6: pieces search over paged blocks, ADDED without a new number (nothing of ABI 6 changed):
                                mir_blocks_search_pieces_expanded;
@@ -766,6 +768,59 @@ int32_t mir_block_hybrid_search(mir_blocks *vs, mir_bm25_blocks *ts, const doubl
                                 const mir_bm25_blocks_scope *const *text_scopes, const int32_t *q_terms_host,
                                 const int32_t *q_ptr_host, const double *weights2_host, int32_t c, int32_t *out_doc,
                                 int64_t *out_chunk, double *out_score, int32_t *out_count);
+
+/* mir_rrf_fuse_device that also reports where each key was FIRST SEEN (added within ABI 6; DESIGN.md 4.12, the origin
+ * variant of rrf_fuse_kernel): out_origin int32[b][cap], out_origin[q][s] = the index l of the list that holds the first
+ * occurrence, in chained order, of the key written to slot s; rows past out_count[q] are zeros.  Every other output, bit
+ * for bit, and every refusal are mir_rrf_fuse_device's; a NULL out_origin is MIR_ERR_INVALID as well. */
+int32_t mir_rrf_fuse_device_origin(const mir_rrf_list *lists, int32_t n_lists, const double *weights_host, int32_t c,
+                                   int32_t b, int32_t cap, int32_t *out_doc, int64_t *out_chunk, double *out_score,
+                                   int32_t *out_origin, int32_t *out_count, void *stream);
+
+/* An ensemble request batch in ONE call with ONE synchronisation (added within ABI 6): up to four legs -
+ * the reference's semantic, BM25, multimodal and description retrievers (retrieval_chain.py:193-252) - each searched for
+ * b queries, their lists left in HBM and fused there by rrf_fuse_kernel's origin variant.
+ *   A mir_ensemble owns a stream, a device scratch and pinned staging (both grow, never shrink) and a mutex: calls on one
+ *   handle are serialised, different handles run side by side.  mir_ensemble_destroy(NULL) is MIR_OK.
+ *   A leg: kind MIR_LEG_VECTOR takes what mir_blocks_search_expanded takes (searcher, queries_host double[b][d],
+ *   metric, scope_ptr_host, blocks_host, fanouts_host; fanouts_host NULL = no listed block is paged, the leg is
+ *   mir_blocks_search and launches no expansion), kind MIR_LEG_KEYWORD what mir_bm25_blocks_search takes
+ *   (text_searcher, text_scopes[b], q_terms_host, q_ptr_host).  Fields of the other kind are ignored.  Each leg has its
+ *   own k >= 1 and weight; 1 <= n_legs <= 4, at most one keyword leg, at any place.  Two legs may name the same searcher.
+ *   Two vector legs with the same queries_host pointer and the same d upload the queries once.
+ * The answer for query q is what mir_rrf_fuse returns for the n_legs lists chained in the order of `legs` under the legs'
+ * weights and c, bit for bit, where a vector leg's list is mir_blocks_search_expanded's (mir_blocks_search's without
+ * fan-outs) and a keyword leg's list mir_bm25_blocks_search's; out_origin = the index in `legs` of the list a key was
+ * first seen in.  A result's doc is the ordinal of its block in q's scope: the CALLER guarantees that every leg of a query
+ * lists the same documents in the same order.
+ *   out_doc int32[b][cap], out_chunk int64[b][cap], out_score double[b][cap], out_origin int32[b][cap],
+ *   out_count int32[b] (host); cap >= sum of k_l; rows past the count are zero.
+ * Route: one upload, the legs enqueued one after the other on the ensemble's stream and in its scratch (the keyword
+ * leg's columns too), the fusion, one download, one hipStreamSynchronize.  Locks: the ensemble's mutex, then the keyword
+ * searcher's.
+ * Refusals come before anything is uploaded or launched, outputs untouched, in this order: MIR_ERR_INVALID for NULL legs or
+ * output, n_legs outside [1, 4], an unknown kind, two keyword legs; what mir_rrf_fuse_device refuses (b < 0, c < 0,
+ * k_l < 1, a weight that is not finite, cap < sum of k_l; MIR_ERR_UNSUPPORTED for sum of k_l > 512); leg after leg
+ * everything mir_blocks_search_expanded / mir_blocks_search / mir_bm25_blocks_search refuses (their messages);
+ * MIR_ERR_INVALID for a NULL ensemble and for a searcher on another device than the ensemble's.  b == 0 is MIR_OK then. */
+typedef struct mir_ensemble mir_ensemble;
+int32_t mir_ensemble_create(int32_t device, mir_ensemble **out);
+int32_t mir_ensemble_destroy(mir_ensemble *e);
+#define MIR_LEG_VECTOR 0
+#define MIR_LEG_KEYWORD 1
+typedef struct {
+    int32_t kind;
+    int32_t k;
+    double weight;
+    mir_blocks *searcher; const double *queries_host; int32_t metric;
+    const int32_t *scope_ptr_host; const mir_rows *const *blocks_host;
+    const mir_fanout *const *fanouts_host;
+    mir_bm25_blocks *text_searcher; const mir_bm25_blocks_scope *const *text_scopes;
+    const int32_t *q_terms_host; const int32_t *q_ptr_host;
+} mir_ensemble_leg;
+int32_t mir_block_ensemble_search(mir_ensemble *e, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c,
+                                  int32_t cap, int32_t *out_doc, int64_t *out_chunk, double *out_score,
+                                  int32_t *out_origin, int32_t *out_count);
 
 /* ------------------------------------------------------------------------
  * WordPiece tokenisation (host code): the BertTokenizer step in front of the encoder
