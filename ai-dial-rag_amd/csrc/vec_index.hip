@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "vec_blocks_host.h"
+#include "vec_counted_copy.h"
 #include "vec_kernels.h"
 #include "vec_kernels_f16.h"
 #include "vec_kernels_q16.h"
@@ -581,15 +582,16 @@ static int32_t host_round_trip(Workspace *w, hipStream_t s, const HostPiece *pie
                         user.dist ? st.dist : nullptr, st.count, st.flags};
     const int32_t rc = enqueue(out);
     if (rc != MIR_OK) return bail(rc);
-    const size_t bk = (size_t)b * k;
     char *res = w->pin + in_pad;
     MIR_TRY(hipMemcpyAsync(res, span0, span, hipMemcpyDeviceToHost, s), bail(MIR_ERR_HIP));
     MIR_TRY(hipStreamSynchronize(s), bail(MIR_ERR_HIP));
     auto at = [&](const void *dev_ptr) { return res + (reinterpret_cast<const char *>(dev_ptr) - span0); };
-    if (user.doc) std::memcpy(user.doc, at(st.doc), bk * 4);
-    if (user.chunk) std::memcpy(user.chunk, at(st.chunk), bk * 8);
-    if (user.row) std::memcpy(user.row, at(st.row), bk * 8);
-    if (user.dist) std::memcpy(user.dist, at(st.dist), bk * 8);
+    // the kernels write a query's first count[q] entries alone: what the span holds past them is an earlier call's, and stays here
+    const int32_t *count = reinterpret_cast<const int32_t *>(at(st.count));
+    mir::counted_copy(user.doc, at(st.doc), count, b, k, 4);
+    mir::counted_copy(user.chunk, at(st.chunk), count, b, k, 8);
+    mir::counted_copy(user.row, at(st.row), count, b, k, 8);
+    mir::counted_copy(user.dist, at(st.dist), count, b, k, 8);
     std::memcpy(user.count, at(st.count), (size_t)b * 4);
     if (user.flags) std::memcpy(user.flags, at(st.flags), (size_t)b * 4);
     return MIR_OK;

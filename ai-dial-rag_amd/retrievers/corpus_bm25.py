@@ -137,8 +137,9 @@ class CorpusHybrid:
         """-> (doc_ids[b, 2k], chunk_ids[b, 2k], rrf score[b, 2k], count[b]), best first."""
         v_doc, v_chunk, _dist, v_cnt = self.vector.find_many(query_vectors, scopes, metric, k)
         t_doc, t_chunk, _score, t_cnt = self.keywords.find_many(query_ids, scopes, k)
-        for chunk in (v_chunk, t_chunk):
-            if np.any((np.asarray(chunk) < 0) | (np.asarray(chunk) >= 2**31)):
+        for chunk, cnt in ((v_chunk, v_cnt), (t_chunk, t_cnt)):
+            listed = np.arange(k)[None, :] < np.asarray(cnt)[:, None]  # (entries past a query's count are not results)
+            if np.any(((np.asarray(chunk) < 0) | (np.asarray(chunk) >= 2**31)) & listed):
                 raise ValueError("chunk id outside [0, 2^31): it does not fit the fused key")
         key = lambda doc, chunk: (np.asarray(doc, np.int64) << 32) | np.asarray(chunk, np.int64)  # one key per (doc, chunk)
         ids, scores, cnt = fuse_batch([(key(v_doc, v_chunk), v_cnt), (key(t_doc, t_chunk), t_cnt)], weights, c)

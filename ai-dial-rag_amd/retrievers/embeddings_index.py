@@ -158,7 +158,9 @@ class DeviceFanout:
 
 def _result_arrays(b: int, k: int) -> Tuple[np.ndarray, ...]:
     """The six arrays every search returns: (doc i32, chunk i64, row i64, dist f64)[b, k], (count, flags) i32[b].
-    A negative k gives empty arrays, so it reaches the C check and is a ValueError like any other bad argument."""
+    Made of zeros, and the host forms write a query's first count[q] entries alone (csrc/vec_counted_copy.h): past the
+    count every array is zero.  A negative k gives empty arrays, so it reaches the C check and is a ValueError like any
+    other bad argument."""
     bk = (b, max(k, 0))
     return (np.zeros(bk, np.int32), np.zeros(bk, np.int64), np.zeros(bk, np.int64), np.zeros(bk, np.float64),
             np.zeros(b, np.int32), np.zeros(b, np.int32))
@@ -189,7 +191,8 @@ class BlockSearcher:
     def search(self, queries: np.ndarray, k: int, metric, scopes: Sequence[Sequence["DeviceRows"]]) -> Tuple[np.ndarray, ...]:
         """Query q searches the rows of ``scopes[q]``'s blocks concatenated in that order.  Returns the six arrays of
         ``DeviceIndex.search_scoped``: doc = the ordinal of the block inside the scope, chunk = the block's chunk id,
-        row = the row INSIDE its block, count[q] = min(k, rows of the scope).  The blocks are held until the call returns."""
+        row = the row INSIDE its block, count[q] = min(k, rows of the scope); past the count: zero.  The blocks are held
+        until the call returns."""
         q = nat.as_f64_queries(queries, self.d)
         b = q.shape[0]
         code = nat.METRIC_CODES[Metric(metric).value]
@@ -220,7 +223,8 @@ class BlockSearcher:
         """``search`` over the EXPANDED blocks while only the stored rows are read (csrc/vec_kernels_expand.h).
         ``fanouts[q][j]``: the fan-out of ``scopes[q][j]``, or None where that block is its own expanded block; ``fanouts=None``:
         no block has one.  Returns the six arrays of ``search``: chunk = the replica's chunk id, row = its position inside the
-        expanded block, count[q] = min(k, expanded rows of the scope).  Blocks and fan-outs are held until the call returns."""
+        expanded block, count[q] = min(k, expanded rows of the scope); past the count: zero.  Blocks and fan-outs are held
+        until the call returns."""
         q = nat.as_f64_queries(queries, self.d)
         b = q.shape[0]
         code = nat.METRIC_CODES[Metric(metric).value]
@@ -257,7 +261,7 @@ class BlockSearcher:
                       group_sizes: Sequence[int]) -> Tuple[np.ndarray, ...]:
         """Queries that share a scope read its rows once (csrc/vec_kernels_shared.h).  Group g = the next
         ``group_sizes[g]`` queries (0 is allowed); all of them search ``scopes[g]``.  Returns the six arrays of ``search``,
-        indexed by query: the same answer, its dot products summed in the matrix unit's order."""
+        indexed by query (past the count: zero): the same answer, its dot products summed in the matrix unit's order."""
         q = nat.as_f64_queries(queries, self.d)
         b = q.shape[0]
         code = nat.METRIC_CODES[Metric(metric).value]
@@ -279,7 +283,7 @@ class BlockSearcher:
         blocks; query q's scope is the blocks of the pieces ``scopes[q]`` (indices into ``pieces``) concatenated in that
         order.  A piece named ``min_riders`` times or more in the call is read once per slab of its riders
         (``search_shared``'s arithmetic), the others per query (``search``'s).  Returns the six arrays of ``search`` over
-        the flattened scopes: doc = the ordinal of the block in the flattened scope."""
+        the flattened scopes: doc = the ordinal of the block in the flattened scope; past the count: zero."""
         return self.search_pieces_indexed(queries, k, metric, pieces, None, scopes, min_riders)
 
     def search_pieces_indexed(self, queries: np.ndarray, k: int, metric, pieces: Sequence[Sequence["DeviceRows"]],
@@ -323,7 +327,7 @@ class BlockSearcher:
         run's index is composed of its blocks' STORED rows - and one launch expands the hits (csrc/vec_kernels_expand.h,
         DESIGN.md 3.12).  Returns ``search_expanded``'s six arrays over the flattened scopes: doc = the ordinal of the
         block in the flattened scope, chunk = the replica's chunk id, row = its position inside the expanded block,
-        count[q] = min(k, expanded rows).  ``piece_fanouts=None``: ``search_pieces_indexed``'s call."""
+        count[q] = min(k, expanded rows); past the count: zero.  ``piece_fanouts=None``: ``search_pieces_indexed``'s call."""
         if piece_fanouts is None:
             return self.search_pieces_indexed(queries, k, metric, pieces, piece_indexes, scopes, min_riders)
         q = nat.as_f64_queries(queries, self.d)
@@ -428,7 +432,8 @@ class DeviceIndex:
         return int(b.value)
 
     def search(self, queries: np.ndarray, k: int, metric) -> Tuple[np.ndarray, ...]:
-        """-> (doc_ids[b,k] i32, chunk_ids[b,k] i64, rows[b,k] i64, dist[b,k] f64, count[b] i32, flags[b] i32)"""
+        """-> (doc_ids[b,k] i32, chunk_ids[b,k] i64, rows[b,k] i64, dist[b,k] f64, count[b] i32, flags[b] i32);
+        count[q] = min(k, rows of the index), past the count: zero."""
         q = nat.as_f64_queries(queries, self.d)
         b = q.shape[0]
         code = nat.METRIC_CODES[Metric(metric).value]
@@ -447,7 +452,7 @@ class DeviceIndex:
     def search_scoped(self, queries: np.ndarray, k: int, metric, scope_ptr, seg_begin, seg_end) -> Tuple[np.ndarray, ...]:
         """Every query searches its own rows: query q's scope is the concatenation of the LOCAL row ranges
         [seg_begin[s], seg_end[s]), s in [scope_ptr[q], scope_ptr[q + 1]).  Returns the tuple of `search`; doc_ids are
-        the ordinals of the segments inside each query's scope, count[q] = min(k, rows of the scope)."""
+        the ordinals of the segments inside each query's scope, count[q] = min(k, rows of the scope); past the count: zero."""
         q = nat.as_f64_queries(queries, self.d)
         b = q.shape[0]
         code = nat.METRIC_CODES[Metric(metric).value]

@@ -164,12 +164,14 @@ int32_t mir_index_info(const mir_index *idx, int64_t *n, int32_t *d, int32_t *dt
  *   out_dist            : the metric value in float64 (reference promotion)
  * out_count[q] = min(k, n).  Any k >= 1 (the reference takes any `limit`,
  * embeddings_index.py:58,81).  out_flags may be NULL.
- * Any of out_doc / out_chunk / out_row / out_dist may be NULL. */
+ * Any of out_doc / out_chunk / out_row / out_dist may be NULL.
+ * Entries past out_count[q] are not written: the caller's memory stays as it was. */
 int32_t mir_index_search(mir_index *idx, const double *queries_host, int32_t b, int32_t k, int32_t metric,
                          int32_t *out_doc, int64_t *out_chunk, int64_t *out_row, double *out_dist,
                          int32_t *out_count, int32_t *out_flags);
 
-/* The same with every buffer in HBM, asynchronous on `stream`. */
+/* The same with every buffer in HBM, asynchronous on `stream`.
+ * The kernels write only the first out_count[q] entries of a query: what the buffers hold past them is not touched. */
 int32_t mir_index_search_device(mir_index *idx, const double *queries_device, int32_t b, int32_t k,
                                 int32_t metric, int32_t *out_doc, int64_t *out_chunk, int64_t *out_row,
                                 double *out_dist, int32_t *out_count, int32_t *out_flags, void *stream);
@@ -188,7 +190,8 @@ int32_t mir_index_search_device(mir_index *idx, const double *queries_device, in
  * Any k >= 1; any of out_doc / out_chunk / out_row / out_dist / out_flags may be NULL.  scope_ptr: int32[b + 1],
  * scope_ptr[0] = 0, non-decreasing; seg_begin / seg_end: int64[scope_ptr[b]].
  * The host form returns MIR_ERR_INVALID, before anything is launched, for scope_ptr[0] != 0, a decreasing
- * scope_ptr, a segment outside 0 <= begin <= end <= n and a scope of 2^32 rows or more. */
+ * scope_ptr, a segment outside 0 <= begin <= end <= n and a scope of 2^32 rows or more.
+ * Entries past out_count[q] are not written: the caller's memory stays as it was. */
 int32_t mir_index_search_scoped(mir_index *idx, const double *queries_host, int32_t b, int32_t k, int32_t metric,
                                 const int32_t *scope_ptr_host, const int64_t *seg_begin_host,
                                 const int64_t *seg_end_host, int32_t *out_doc, int64_t *out_chunk,
@@ -197,7 +200,8 @@ int32_t mir_index_search_scoped(mir_index *idx, const double *queries_host, int3
 /* The same with every buffer in HBM, asynchronous on `stream` (no synchronisation).  This form cannot see the
  * arrays and validates nothing in them: the kernel clamps begin / end into [0, n], treats end < begin as empty
  * and cuts a scope off at 2^32 - 1 rows, so it never reads a row outside the index; what a malformed scope
- * returns is unspecified.  scope_ptr must still index inside the segment arrays. */
+ * returns is unspecified.  scope_ptr must still index inside the segment arrays.
+ * The kernels write only the first out_count[q] entries of a query: what the buffers hold past them is not touched. */
 int32_t mir_index_search_scoped_device(mir_index *idx, const double *queries_device, int32_t b, int32_t k,
                                        int32_t metric, const int32_t *scope_ptr_device,
                                        const int64_t *seg_begin_device, const int64_t *seg_end_device,
@@ -217,7 +221,8 @@ int32_t mir_index_search_scoped_device(mir_index *idx, const double *queries_dev
  * float16 blocks are read as float16 at any d.  Any of out_doc / out_chunk / out_row / out_dist / out_flags may be NULL.
  * The host form returns MIR_ERR_INVALID, before anything is launched, for a NULL handle, scope_ptr[0] != 0, a decreasing
  * scope_ptr, a NULL entry of `blocks`, a block whose d, dtype or device differs from the searcher's, a scope of 2^32 rows or
- * more, k < 1 and an unknown metric.  The caller keeps every listed block alive until the call returns. */
+ * more, k < 1 and an unknown metric.  The caller keeps every listed block alive until the call returns.
+ * Entries past out_count[q] are not written: the caller's memory stays as it was. */
 typedef struct mir_blocks mir_blocks;
 int32_t mir_blocks_create(int32_t d, int32_t dtype, int32_t device, mir_blocks **out);
 int32_t mir_blocks_destroy(mir_blocks *s);
@@ -231,7 +236,8 @@ int32_t mir_blocks_search(mir_blocks *s, const double *queries_host, int32_t b, 
  * that scope_ptr is non-decreasing from 0 and indexes inside the table, and that every descriptor names n rows of the
  * searcher's d and dtype with their n squared norms; the kernel only clamps n into [0, 2^32 - 1] and cuts a scope off at
  * 2^32 - 1 rows.  A descriptor that lies about its block makes the kernel read outside it.  The caller keeps every
- * listed block alive until `stream` has passed the call. */
+ * listed block alive until `stream` has passed the call.
+ * The kernels write only the first out_count[q] entries of a query: what the buffers hold past them is not touched. */
 typedef struct { const void *emb; const float *doc_sq; const int64_t *chunk; int64_t n; } mir_block_desc;
 int32_t mir_rows_desc(const mir_rows *rows, mir_block_desc *out);
 int32_t mir_blocks_search_device(mir_blocks *s, const double *queries_device, int32_t b, int32_t k, int32_t metric,
@@ -255,14 +261,16 @@ int32_t mir_blocks_search_device(mir_blocks *s, const double *queries_device, in
  * bit-identical rows tie exactly and go by position.
  * Any k >= 1, float32 and float16 blocks, any d.  The host form returns MIR_ERR_INVALID, before anything is launched and
  * with the outputs untouched, for everything mir_blocks_search refuses and for n_groups < 0, group_ptr[0] != 0, a decreasing
- * group_ptr and group_ptr[n_groups] != b. */
+ * group_ptr and group_ptr[n_groups] != b.
+ * Entries past out_count[q] are not written: the caller's memory stays as it was. */
 int32_t mir_blocks_search_shared(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric,
                                  int32_t n_groups, const int32_t *group_ptr_host, const int32_t *scope_ptr_host,
                                  const mir_rows *const *blocks_host, int32_t *out_doc, int64_t *out_chunk,
                                  int64_t *out_row, double *out_dist, int32_t *out_count, int32_t *out_flags);
 
 /* The same with every buffer in HBM, asynchronous on `stream`.  It trusts group_ptr, scope_ptr and the table as
- * mir_blocks_search_device trusts its arrays; it sees none of them and sizes its launch from b, n_groups and k alone. */
+ * mir_blocks_search_device trusts its arrays; it sees none of them and sizes its launch from b, n_groups and k alone.
+ * The kernels write only the first out_count[q] entries of a query: what the buffers hold past them is not touched. */
 int32_t mir_blocks_search_shared_device(mir_blocks *s, const double *queries_device, int32_t b, int32_t k, int32_t metric,
                                         int32_t n_groups, const int32_t *group_ptr_device, const int32_t *scope_ptr_device,
                                         const mir_block_desc *table_device, int32_t *out_doc, int64_t *out_chunk,
@@ -294,7 +302,8 @@ int32_t mir_blocks_search_shared_device(mir_blocks *s, const double *queries_dev
  * n_pieces < 0, a NULL piece_ptr with n_pieces > 0, piece_ptr[0] != 0, a decreasing piece_ptr, a NULL rider_ptr,
  * rider_ptr[0] != 0, a decreasing rider_ptr, a rider_piece outside [0, n_pieces), min_riders < 1, a query whose flattened
  * scope holds 2^32 rows or 2^31 blocks or more, and a call whose occurrences (one per ride of a shared piece, one per query
- * with unshared pieces) times k reach 2^31.  Host form only: there is no _device form. */
+ * with unshared pieces) times k reach 2^31.  Host form only: there is no _device form.
+ * Entries past out_count[q] are not written: the caller's memory stays as it was. */
 int32_t mir_blocks_search_pieces(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric,
                                  int32_t n_pieces, const int32_t *piece_ptr_host, const mir_rows *const *blocks_host,
                                  const int32_t *rider_ptr_host, const int32_t *rider_piece_host, int32_t min_riders,
@@ -325,7 +334,8 @@ int32_t mir_blocks_search_pieces(mir_blocks *s, const double *queries_host, int3
  * verify that the index was composed of these very blocks: that is TRUSTED, as the _device forms trust their tables
  * (an index of other rows of the same count gives wrong rows, never a read outside the blocks: every row it reports is
  * clamped into the piece).  The caller keeps the indexes and the blocks alive until the call returns; other searches of
- * the same index may run meanwhile.  Host form only. */
+ * the same index may run meanwhile.  Host form only.
+ * Entries past out_count[q] are not written: the caller's memory stays as it was. */
 int32_t mir_blocks_search_pieces_indexed(mir_blocks *s, const double *queries_host, int32_t b, int32_t k, int32_t metric,
                                          int32_t n_pieces, const int32_t *piece_ptr_host, const mir_rows *const *blocks_host,
                                          const mir_index *const *piece_index_host, const int32_t *rider_ptr_host,
@@ -362,8 +372,9 @@ int32_t mir_fanout_get_desc(const mir_fanout *f, mir_fanout_desc *out);
  *   out_count : min(k, sum of R_t over the scope)                                 mir_blocks_search's bits
  *   out_flags : 0
  * in the order (distance ascending with -0 = +0, NaN last, then ordinal, then expanded position): csrc/merge_order.h's key
- * on the distance.  Only the first out_count[q] entries of a query are written; any output but out_count may be NULL; any
- * k >= 1.  Route: mir_blocks_search's stream kernel, unchanged, selects min(k, stored rows) STORED rows per query into the
+ * on the distance.  Entries past out_count[q] are not written: the caller's memory stays as it was.  Any output but
+ * out_count may be NULL; any k >= 1.
+ * Route: mir_blocks_search's stream kernel, unchanged, selects min(k, stored rows) STORED rows per query into the
  * workspace; expand_topk_kernel writes the answer from them (the first k stored rows under (distance, stored position) hold
  * every row of the first k expanded ones: DESIGN.md 3.11).
  * Returns MIR_ERR_INVALID, before anything is launched and with the outputs untouched, for everything mir_blocks_search
@@ -377,7 +388,8 @@ int32_t mir_blocks_search_expanded(mir_blocks *s, const double *queries_host, in
 /* The same with every buffer in HBM, asynchronous on `stream`.  fanout_table_device: one mir_fanout_desc per listed block,
  * parallel to table_device (NULL: no block has a fan-out).  It trusts scope_ptr and both tables as mir_blocks_search_device
  * trusts its arrays.  The expansion kernel clamps what it takes from them - a stored row below n, a replica range inside
- * [0, rep_ptr[n]] - so a fan-out descriptor that lies gives wrong rows, never a read outside the arrays it names. */
+ * [0, rep_ptr[n]] - so a fan-out descriptor that lies gives wrong rows, never a read outside the arrays it names.
+ * The kernels write only the first out_count[q] entries of a query: what the buffers hold past them is not touched. */
 int32_t mir_blocks_search_expanded_device(mir_blocks *s, const double *queries_device, int32_t b, int32_t k, int32_t metric,
                                           const int32_t *scope_ptr_device, const mir_block_desc *table_device,
                                           const mir_fanout_desc *fanout_table_device, int32_t *out_doc, int64_t *out_chunk,
@@ -394,7 +406,7 @@ int32_t mir_blocks_search_expanded_device(mir_blocks *s, const double *queries_d
  * flattened scope, out_chunk = the replica's chunk id, out_row = the replica's position inside its expanded block, out_dist
  * = the stored row's distance with mir_blocks_search's bits, out_count[q] = min(k, expanded rows of the flattened scope),
  * out_flags 0, in the order (distance ascending with -0 = +0, NaN last, then ordinal, then expanded position); any k >= 1;
- * only the first out_count[q] entries of a query are written; any output but out_count may be NULL.
+ * entries past out_count[q] are not written: the caller's memory stays as it was; any output but out_count may be NULL.
  * Route: mir_blocks_search_pieces_indexed's, unchanged, over the STORED rows - pieces with min_riders rides or more are read
  * once per slab, index pieces go through one batched search of their index and the rescore, the rest goes per query, the
  * merge puts a query's occurrences into one list sorted by written distance - and then ONE launch of the expansion kernel

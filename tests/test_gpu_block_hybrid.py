@@ -378,12 +378,11 @@ def test_hybrid_search_of_no_query(amd, corpus):
 
 # ---- 3. BlockHybrid(device_fusion=True) -----------------------------------------------------------------------------------
 def test_block_hybrid_device_fusion_equals_the_host_route(amd, corpus):
-    """The host route tests EVERY entry of the legs' [b, k] chunk arrays for the packed key's range, and the vector leg
-    leaves the entries past a query's count unwritten; so the comparison uses scopes that hold k rows or more (a shorter
-    scope, where only the native entry is defined for certain, is case 2's)."""
+    """Both routes on the same scopes, array for array: the scopes of k rows or more and the two that hold 3 (a leg's
+    entries past its count are no results, and neither route reads them)."""
     c = corpus
     host, dev = amd.bb.BlockHybrid(), amd.bb.BlockHybrid(device_fusion=True)
-    pick = [0, 1, 2, 3, 4, 5, 8]  # test_block_hybrid_find_many's scopes and the one with an empty block inside: 5 rows or more each
+    pick = [0, 1, 2, 3, 4, 5, 6, 7, 8]  # test_block_hybrid_find_many's scopes, the two of 3 rows and chunks, and the one with an empty block inside
     lists, qt, qv0 = [DOC_LISTS[i] for i in pick], [c.qt[i] for i in pick], c.qv[pick]
     big = [list(range(12)) * 2, list(range(11, -1, -1)) * 2]  # 506 rows and chunks each: every entry of a k = 300 call is written
     try:

@@ -721,8 +721,8 @@ def test_float32_wide_dims_k_split_scan(amd, metric, d, n):
 def test_host_forms_share_a_workspace_pool(amd):
     """Host-form calls of different layouts on ONE handle - its workspace slab and pinned staging buffer are reused,
     regrown and carved anew from call to call - answer exactly as a freshly built index (empty pool) does, and leave
-    alone the outputs the caller did not ask for.  Arrays are compared bit for bit over what the C ABI defines: the
-    first count[q] entries of row q (miretr.h: the rest of a row is not written)."""
+    alone the outputs the caller did not ask for.  WHOLE arrays are compared bit for bit: the first count[q] entries of
+    row q are the answer, and the rest of a row is not written (miretr.h), so it is still the wrapper's zeros."""
     nat, ei = amd.nat, amd.ei
     rng = np.random.default_rng(20250)
     n, d = 2000, 48
@@ -750,12 +750,13 @@ def test_host_forms_share_a_workspace_pool(amd):
         ("search", (q(1), 10, "cosine_sim")),
     ]
 
-    def defined(res):  # bytes of the entries the ABI defines
+    def defined(res):  # bytes of every array, whole
         if isinstance(res, np.ndarray):
             return [res.tobytes()]
         cnt = res[4]
-        keep = np.arange(res[0].shape[1])[None, :] < cnt[:, None]
-        return [np.where(keep, a, a.dtype.type(0)).tobytes() for a in res[:4]] + [cnt.tobytes(), res[5].tobytes()]
+        past = np.arange(res[0].shape[1])[None, :] >= cnt[:, None]
+        assert all(not a[past].view(np.uint8).any() for a in res[:4])  # past the count: the zeros the wrapper allocated
+        return [a.tobytes() for a in res]
 
     used = build()
     got = []

@@ -5,6 +5,7 @@
     corpus index composed from the same blocks, in alternating runs of one job, answers compared; the HBM each route holds.
 (b) a document arrives: `BlockCorpus.add` of one new ROWS-row document + the first search that names it, against what the
     corpus index can do: a new `CorpusIndex` over all DOCS + 1 blocks + its first search.
+(c) B queries whose scopes hold 1 to 3 rows each, fewer than k: ONE `BlockSearcher.search` call, results copied per count.
 
     python tools/block_search_timing.py [DOCS=2560] [ROWS=1000] [B=256] [PER=10]
 """
@@ -98,6 +99,21 @@ def main():
     print(f"Block route median / index route median = {mb / mi:.3f} ({mr / mi:.3f} with the handle table made once); the block route's median lies inside "
           f"the index route's min - max spread: {inside} ({min(t_index) <= mr <= max(t_index)})\n")
     index.close()
+
+    # ---- (c) scopes shorter than k: the host form copies each query's first count entries alone (csrc/vec_counted_copy.h)
+    tiny = [DeviceRows.from_host(emb[i * 3:i * 3 + 1 + i % 3]) for i in range(b)]  # blocks of 1, 2 and 3 rows
+    short_scopes = [[blk] for blk in tiny]
+    by_short = lambda: searcher.search(qs, K, METRIC, short_scopes)
+    for _ in range(3):
+        short = by_short()
+    t_short = times(by_short, 10) + times(by_short, 10)
+    listed = np.arange(K)[None, :] < short[4][:, None]
+    print("## (c) scopes shorter than k\n")
+    print(f"| route | ms per batch of {b} |")
+    print("|---|---|")
+    print(f"| ONE `BlockSearcher.search` call, every scope one block of 1 to 3 rows (count < k = {K} for all {b} queries) | {fmt(t_short)} |")
+    print(f"\ncount = rows of the scope for all {b} queries: {bool((short[4] == np.array([1 + i % 3 for i in range(b)])).all())}; "
+          f"every entry past a count is the zero the wrapper allocated: {all(not a[~listed].view(np.uint8).any() for a in short[:4])}\n")
 
     # ---- (b) a document arrives
     corpus = BlockCorpus()
