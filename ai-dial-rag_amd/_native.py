@@ -150,6 +150,11 @@ def _load():
         "mir_ensemble_create": ([i32, vp], i32),
         "mir_ensemble_destroy": ([vp], i32),
         "mir_block_ensemble_search": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], i32),
+        "mir_ensemble_scope_create": ([i32, i32, vp, i32, vp, vp], i32),
+        "mir_ensemble_scope_info": ([vp, vp, vp, vp, vp], i32),
+        "mir_ensemble_scope_destroy": ([vp], i32),
+        "mir_block_ensemble_search_scopes": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp], i32),
+        "mir_ensemble_scopes_gather_ms": ([vp, vp, i32, i32, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -192,6 +197,12 @@ class EnsembleLeg(C.Structure):
                 ("searcher", C.c_void_p), ("queries_host", C.c_void_p), ("metric", C.c_int32),
                 ("scope_ptr_host", C.c_void_p), ("blocks_host", C.c_void_p), ("fanouts_host", C.c_void_p),
                 ("text_searcher", C.c_void_p), ("text_scopes", C.c_void_p), ("q_terms_host", C.c_void_p), ("q_ptr_host", C.c_void_p)]
+
+
+class ScopeSlot(C.Structure):
+    """mir_scope_slot: one vector leg's view of a document list for ``mir_ensemble_scope_create`` (host tables of handles)."""
+
+    _fields_ = [("searcher", C.c_void_p), ("blocks", C.c_void_p), ("fanouts", C.c_void_p)]
 
 
 def last_error() -> str:

@@ -1299,6 +1299,7 @@ __global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const doubl
 #include "fusion_host.h"
 #include "hybrid_layout.h"
 #include "ensemble_layout.h"
+#include "ensemble_scope_kernels.h"
 #include "vec_blocks_host.h"
 
 using namespace mir;
@@ -2727,6 +2728,88 @@ static int32_t ensemble_keyword_check(const mir_bm25_blocks *h, const mir_bm25_b
     return MIR_OK;
 }
 
+}  // extern "C"
+
+// Where a leg's arrays start in the ensemble's scratch, whichever header carved them (ensemble_layout.h, ensemble_scopes_layout.h)
+struct EnsembleLegAt {
+    size_t q = 0, scope_ptr = 0, table = 0, fan_table = 0, l_doc = 0, l_chunk = 0, l_count = 0;
+    bool expanded = false;  // the leg has a fan-out table: mir_blocks_search_expanded_device
+};
+struct EnsembleSpans { size_t in_bytes, f_doc, f_chunk, f_score, f_origin, f_count, out_bytes; };
+struct EnsembleOut { int32_t *doc; int64_t *chunk; double *score; int32_t *origin; int32_t *count; };
+
+// What both ensemble entries do once every host check has passed and the scratch is carved: the device, the locks, the
+// scratch and the staging; `fill(up)` writes the upload span into the pinned staging; one upload; `prepare(base, stream)`
+// enqueues what must run before the first leg; the legs through the public _device searches and scoped_enqueue; the fusion
+// with the origin; one download; one hipStreamSynchronize; the five arrays copied out.
+template <typename Fill, typename Prepare>
+static int32_t ensemble_run(mir_ensemble *e, mir_bm25_blocks *h, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c, int32_t cap,
+                            const BlockRoute &route, const ScopedPlan<BlockScopeDev> &plan, OutColumn *cols, size_t need, const EnsembleLegAt *at,
+                            const EnsembleSpans &sp, mir_rrf_list *lists, const double *weights, Fill fill, Prepare prepare, const EnsembleOut &out) {
+    int32_t rc = use_device(e->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    std::unique_lock<std::mutex> lk_text;
+    if (h) lk_text = std::unique_lock<std::mutex>(h->mu);
+    rc = e->scratch.ensure(need);
+    if (rc != MIR_OK) return rc;
+    if (e->pin_cap < sp.in_bytes + sp.out_bytes) {
+        if (e->pin) (void)hipHostFree(e->pin);
+        e->pin = nullptr;
+        e->pin_cap = 0;
+        MIR_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->pin), sp.in_bytes + sp.out_bytes, hipHostMallocDefault));
+        e->pin_cap = sp.in_bytes + sp.out_bytes;
+    }
+    char *base = static_cast<char *>(e->scratch.ptr);
+    char *up = e->pin, *down = e->pin + sp.in_bytes;
+    hipStream_t s = e->stream;
+    fill(up);
+    auto enqueue = [&]() -> int32_t {
+        MIR_HIP(hipMemcpyAsync(base, up, sp.in_bytes, hipMemcpyHostToDevice, s));
+        int32_t r = prepare(base, s);
+        if (r != MIR_OK) return r;
+        for (int l = 0; l < n_legs; ++l) {
+            const mir_ensemble_leg &g = legs[l];
+            if (g.kind == MIR_LEG_KEYWORD) {
+                r = scoped_enqueue(route, plan, base, s, nullptr, nullptr, cols);
+                lists[l] = mir_rrf_list{cols[3].at<int32_t>(base), cols[1].at<int64_t>(base), reinterpret_cast<const int32_t *>(base + plan.o_cnt), g.k};
+            } else {
+                int32_t *l_doc = reinterpret_cast<int32_t *>(base + at[l].l_doc), *l_count = reinterpret_cast<int32_t *>(base + at[l].l_count);
+                int64_t *l_chunk = reinterpret_cast<int64_t *>(base + at[l].l_chunk);
+                const double *q = reinterpret_cast<const double *>(base + at[l].q);
+                const int32_t *scope_ptr = reinterpret_cast<const int32_t *>(base + at[l].scope_ptr);
+                const mir_block_desc *table = reinterpret_cast<const mir_block_desc *>(base + at[l].table);
+                if (at[l].expanded)
+                    r = mir_blocks_search_expanded_device(g.searcher, q, b, g.k, g.metric, scope_ptr, table,
+                                                          reinterpret_cast<const mir_fanout_desc *>(base + at[l].fan_table), l_doc, l_chunk, nullptr, nullptr,
+                                                          l_count, nullptr, s);
+                else
+                    r = mir_blocks_search_device(g.searcher, q, b, g.k, g.metric, scope_ptr, table, l_doc, l_chunk, nullptr, nullptr, l_count, nullptr, s);
+                lists[l] = mir_rrf_list{l_doc, l_chunk, l_count, g.k};
+            }
+            if (r != MIR_OK) return r;
+        }
+        r = rrf_launch(lists, n_legs, weights, c, b, cap, reinterpret_cast<int32_t *>(base + sp.f_doc), reinterpret_cast<int64_t *>(base + sp.f_chunk),
+                       reinterpret_cast<double *>(base + sp.f_score), reinterpret_cast<int32_t *>(base + sp.f_origin),
+                       reinterpret_cast<int32_t *>(base + sp.f_count), s);
+        if (r != MIR_OK) return r;
+        MIR_HIP(hipMemcpyAsync(down, base + sp.f_doc, sp.out_bytes, hipMemcpyDeviceToHost, s));
+        return MIR_OK;
+    };
+    rc = enqueue();
+    if (rc != MIR_OK) { (void)hipStreamSynchronize(s); return rc; }
+    MIR_HIP(hipStreamSynchronize(s));
+    const size_t rows = (size_t)b * cap;
+    std::memcpy(out.doc, down, rows * 4);
+    std::memcpy(out.chunk, down + (sp.f_chunk - sp.f_doc), rows * 8);
+    std::memcpy(out.score, down + (sp.f_score - sp.f_doc), rows * 8);
+    std::memcpy(out.origin, down + (sp.f_origin - sp.f_doc), rows * 4);
+    std::memcpy(out.count, down + (sp.f_count - sp.f_doc), (size_t)b * 4);
+    return MIR_OK;
+}
+
+extern "C" {
+
 // Under the ensemble's mutex, then the keyword searcher's; on the ensemble's stream and in its scratch: ensemble_layout.h,
 // then the keyword leg's columns (scoped_plan from lay.keyword on, with the ensemble's scratch as its base - so
 // mir_bm25_blocks_search and mir_block_hybrid_search, which work in the searcher's scratch, are as they were).  A vector leg
@@ -2798,78 +2881,337 @@ int32_t mir_block_ensemble_search(mir_ensemble *e, const mir_ensemble_leg *legs,
         scoped_plan(route, legs[kw].text_scopes, host[kw].nt, b, legs[kw].k, cols, 5, lay.keyword, &inputs, &plan);
         need = plan.end;
     }
-    rc = use_device(e->device, nullptr);
-    if (rc != MIR_OK) return rc;
-    std::lock_guard<std::mutex> lk(e->mu);
-    std::unique_lock<std::mutex> lk_text;
-    if (h) lk_text = std::unique_lock<std::mutex>(h->mu);
-    rc = e->scratch.ensure(need);
-    if (rc != MIR_OK) return rc;
-    if (e->pin_cap < lay.in_bytes + lay.out_bytes) {
-        if (e->pin) (void)hipHostFree(e->pin);
-        e->pin = nullptr;
-        e->pin_cap = 0;
-        MIR_HIP(hipHostMalloc(reinterpret_cast<void **>(&e->pin), lay.in_bytes + lay.out_bytes, hipHostMallocDefault));
-        e->pin_cap = lay.in_bytes + lay.out_bytes;
-    }
-    char *base = static_cast<char *>(e->scratch.ptr);
-    char *up = e->pin, *down = e->pin + lay.in_bytes;
-    hipStream_t s = e->stream;
+    EnsembleLegAt at[kRrfMaxLists];
     for (int l = 0; l < n_legs; ++l) {
-        const mir_ensemble_leg &g = legs[l];
-        const EnsembleLegLayout &at = lay.leg[l];
-        if (g.kind == MIR_LEG_KEYWORD) {
-            if (host[l].nt) std::memcpy(up + at.terms, g.q_terms_host, (size_t)host[l].nt * 4);
-            std::memcpy(up + at.q_ptr, g.q_ptr_host, ((size_t)b + 1) * 4);
-            std::memcpy(up + at.scopes, plan.sd.data(), (size_t)b * sizeof(BlockScopeDev));
-            continue;
-        }
-        if (es.leg[l].q_of < 0) std::memcpy(up + at.q, g.queries_host, (size_t)b * host[l].d * 8);
-        std::memcpy(up + at.scope_ptr, g.scope_ptr_host, ((size_t)b + 1) * 4);
-        if (!host[l].table.empty()) std::memcpy(up + at.table, host[l].table.data(), host[l].table.size() * sizeof(mir_block_desc));
-        if (es.leg[l].fanouts && !host[l].fan_table.empty())
-            std::memcpy(up + at.fan_table, host[l].fan_table.data(), host[l].fan_table.size() * sizeof(mir_fanout_desc));
+        const EnsembleLegLayout &ll = lay.leg[l];
+        at[l] = EnsembleLegAt{ll.q, ll.scope_ptr, ll.table, ll.fan_table, ll.l_doc, ll.l_chunk, ll.l_count, es.leg[l].fanouts};
     }
-    auto enqueue = [&]() -> int32_t {
-        MIR_HIP(hipMemcpyAsync(base, up, lay.in_bytes, hipMemcpyHostToDevice, s));
+    const EnsembleSpans spans{lay.in_bytes, lay.f_doc, lay.f_chunk, lay.f_score, lay.f_origin, lay.f_count, lay.out_bytes};
+    auto fill = [&](char *up) {
         for (int l = 0; l < n_legs; ++l) {
             const mir_ensemble_leg &g = legs[l];
-            const EnsembleLegLayout &at = lay.leg[l];
-            int32_t r;
+            const EnsembleLegLayout &ll = lay.leg[l];
             if (g.kind == MIR_LEG_KEYWORD) {
-                r = scoped_enqueue(route, plan, base, s, nullptr, nullptr, cols);
-                lists[l] = mir_rrf_list{cols[3].at<int32_t>(base), cols[1].at<int64_t>(base), reinterpret_cast<const int32_t *>(base + plan.o_cnt), g.k};
-            } else {
-                int32_t *l_doc = reinterpret_cast<int32_t *>(base + at.l_doc), *l_count = reinterpret_cast<int32_t *>(base + at.l_count);
-                int64_t *l_chunk = reinterpret_cast<int64_t *>(base + at.l_chunk);
-                const double *q = reinterpret_cast<const double *>(base + at.q);
-                const int32_t *sp = reinterpret_cast<const int32_t *>(base + at.scope_ptr);
-                const mir_block_desc *table = reinterpret_cast<const mir_block_desc *>(base + at.table);
-                if (es.leg[l].fanouts)
-                    r = mir_blocks_search_expanded_device(g.searcher, q, b, g.k, g.metric, sp, table, reinterpret_cast<const mir_fanout_desc *>(base + at.fan_table),
-                                                          l_doc, l_chunk, nullptr, nullptr, l_count, nullptr, s);
-                else
-                    r = mir_blocks_search_device(g.searcher, q, b, g.k, g.metric, sp, table, l_doc, l_chunk, nullptr, nullptr, l_count, nullptr, s);
-                lists[l] = mir_rrf_list{l_doc, l_chunk, l_count, g.k};
+                if (host[l].nt) std::memcpy(up + ll.terms, g.q_terms_host, (size_t)host[l].nt * 4);
+                std::memcpy(up + ll.q_ptr, g.q_ptr_host, ((size_t)b + 1) * 4);
+                std::memcpy(up + ll.scopes, plan.sd.data(), (size_t)b * sizeof(BlockScopeDev));
+                continue;
             }
-            if (r != MIR_OK) return r;
+            if (es.leg[l].q_of < 0) std::memcpy(up + ll.q, g.queries_host, (size_t)b * host[l].d * 8);
+            std::memcpy(up + ll.scope_ptr, g.scope_ptr_host, ((size_t)b + 1) * 4);
+            if (!host[l].table.empty()) std::memcpy(up + ll.table, host[l].table.data(), host[l].table.size() * sizeof(mir_block_desc));
+            if (es.leg[l].fanouts && !host[l].fan_table.empty())
+                std::memcpy(up + ll.fan_table, host[l].fan_table.data(), host[l].fan_table.size() * sizeof(mir_fanout_desc));
         }
-        const int32_t r = rrf_launch(lists, n_legs, weights, c, b, cap, reinterpret_cast<int32_t *>(base + lay.f_doc), reinterpret_cast<int64_t *>(base + lay.f_chunk),
-                                     reinterpret_cast<double *>(base + lay.f_score), reinterpret_cast<int32_t *>(base + lay.f_origin),
-                                     reinterpret_cast<int32_t *>(base + lay.f_count), s);
-        if (r != MIR_OK) return r;
-        MIR_HIP(hipMemcpyAsync(down, base + lay.f_doc, lay.out_bytes, hipMemcpyDeviceToHost, s));
+    };
+    auto prepare = [](char *, hipStream_t) -> int32_t { return MIR_OK; };  // the tables came with the upload
+    return ensemble_run(e, h, legs, n_legs, b, c, cap, route, plan, cols, need, at, spans, lists, weights, fill, prepare,
+                        EnsembleOut{out_doc, out_chunk, out_score, out_origin, out_count});
+}
+
+// ---- resident ensemble scopes: a document list described once, named by one handle per query ----------
+
+// Immutable after creation: any number of threads and of mir_ensemble handles read it.  It owns `mem` alone.
+struct mir_ensemble_scope {
+    int device = 0;
+    int32_t n_docs = 0, n_slots = 0, paged_mask = 0;
+    const mir_blocks *searcher[kScopeMaxSlots] = {nullptr, nullptr, nullptr};  // compared, never dereferenced after creation
+    const mir_bm25_blocks_scope *text = nullptr;
+    const mir_bm25_blocks *text_searcher = nullptr;  // text's, read at creation
+    char *mem = nullptr;  // ScopeAllocLayout (ensemble_scopes_layout.h), in HBM
+    size_t bytes = 0;
+    const void *desc[kScopeMaxSlots] = {nullptr, nullptr, nullptr}, *fan[kScopeMaxSlots] = {nullptr, nullptr, nullptr};
+};
+
+// The O(b) host part of a scoped call: scope_ptr[b + 1] from the scopes' n_docs, one reference record per query.
+static void scopes_fill(const mir_ensemble_scope *const *scopes, int32_t b, int32_t *scope_ptr, EnsembleScopeRef *refs) {
+    scope_ptr[0] = 0;
+    for (int i = 0; i < b; ++i) {
+        const mir_ensemble_scope &sc = *scopes[i];
+        scope_ptr[i + 1] = scope_ptr[i] + sc.n_docs;
+        EnsembleScopeRef r{};
+        for (int j = 0; j < kScopeMaxSlots; ++j) { r.desc[j] = sc.desc[j]; r.fan[j] = sc.fan[j]; }
+        r.n_docs = sc.n_docs;
+        refs[i] = r;
+    }
+}
+
+int32_t mir_ensemble_scope_create(int32_t device, int32_t n_docs, const mir_scope_slot *slots, int32_t n_slots,
+                                  const mir_bm25_blocks_scope *text_scope, mir_ensemble_scope **out) {
+    MIR_REQUIRE(out != nullptr, "out is NULL");
+    *out = nullptr;
+    MIR_REQUIRE(device >= 0, "device=%d is negative", device);
+    MIR_REQUIRE(n_docs >= 0, "n_docs=%d is negative", n_docs);
+    MIR_REQUIRE(n_slots >= 0 && n_slots <= kScopeMaxSlots, "n_slots=%d outside [0, %d]", n_slots, kScopeMaxSlots);
+    MIR_REQUIRE(n_slots == 0 || slots != nullptr, "slots is NULL");
+    // the per-call walk of the list entries (blocks_check_host, blocks_expanded_check_host), once: nothing of the device is touched before it has passed
+    std::vector<mir_block_desc> desc[kScopeMaxSlots];
+    std::vector<mir_fanout_desc> fan[kScopeMaxSlots];
+    int32_t paged_mask = 0;
+    for (int32_t j = 0; j < n_slots; ++j) {
+        desc[j].resize((size_t)n_docs);
+        fan[j].resize((size_t)n_docs);
+        bool paged = false;
+        const int32_t rc = scope_slot_check_host(j, slots[j].searcher, slots[j].blocks, slots[j].fanouts, n_docs, device, desc[j].data(), fan[j].data(), &paged);
+        if (rc != MIR_OK) return rc;
+        if (paged) paged_mask |= 1 << j;
+    }
+    MIR_REQUIRE(text_scope == nullptr || text_scope->device == device, "the text scope is on device %d, the scope on device %d",
+                text_scope ? text_scope->device : 0, device);
+    ScopeAllocLayout lay;
+    const ScopeAllocCarve carved = scope_alloc_carve(n_docs, n_slots, paged_mask, sizeof(mir_block_desc), sizeof(mir_fanout_desc), &lay);
+    MIR_REQUIRE(carved == kScopeAllocOk, "the scope's arrays do not fit an allocation (n_docs=%d, %d slots)", n_docs, n_slots);
+    mir_ensemble_scope *sc = new (std::nothrow) mir_ensemble_scope();
+    MIR_REQUIRE(sc != nullptr, "out of host memory");
+    sc->device = device; sc->n_docs = n_docs; sc->n_slots = n_slots; sc->paged_mask = paged_mask;
+    sc->text = text_scope;
+    sc->text_searcher = text_scope ? text_scope->searcher : nullptr;
+    for (int32_t j = 0; j < n_slots; ++j) sc->searcher[j] = slots[j].searcher;
+    if (lay.bytes) {  // (a scope without a slot or without a document holds nothing in HBM and needs no device)
+        std::vector<char> host(lay.bytes, 0);
+        for (int32_t j = 0; j < n_slots; ++j) {
+            std::memcpy(host.data() + lay.desc[j], desc[j].data(), (size_t)n_docs * sizeof(mir_block_desc));
+            if (paged_mask >> j & 1) std::memcpy(host.data() + lay.fan[j], fan[j].data(), (size_t)n_docs * sizeof(mir_fanout_desc));
+        }
+        int32_t rc = use_device(device, nullptr);
+        hipError_t err = hipSuccess;
+        if (rc == MIR_OK && (err = hipMalloc(reinterpret_cast<void **>(&sc->mem), lay.bytes)) == hipSuccess)
+            err = hipMemcpy(sc->mem, host.data(), lay.bytes, hipMemcpyHostToDevice);  // the scope's one upload
+        if (rc == MIR_OK && err != hipSuccess) {
+            set_error("mir_ensemble_scope_create: %s", hipGetErrorString(err));
+            rc = MIR_ERR_HIP;
+        }
+        if (rc != MIR_OK) {
+            if (sc->mem) (void)hipFree(sc->mem);
+            delete sc;
+            return rc;
+        }
+        sc->bytes = lay.bytes;
+        for (int32_t j = 0; j < n_slots; ++j) {
+            sc->desc[j] = sc->mem + lay.desc[j];
+            if (paged_mask >> j & 1) sc->fan[j] = sc->mem + lay.fan[j];
+        }
+    }
+    *out = sc;
+    return MIR_OK;
+}
+
+int32_t mir_ensemble_scope_info(const mir_ensemble_scope *s, int32_t *n_docs, int32_t *n_slots, int32_t *paged_mask, int64_t *hbm_bytes) {
+    MIR_REQUIRE(s != nullptr, "scope is NULL");
+    if (n_docs) *n_docs = s->n_docs;
+    if (n_slots) *n_slots = s->n_slots;
+    if (paged_mask) *paged_mask = s->paged_mask;
+    if (hbm_bytes) *hbm_bytes = (int64_t)s->bytes;
+    return MIR_OK;
+}
+
+int32_t mir_ensemble_scope_destroy(mir_ensemble_scope *s) {
+    if (!s) return MIR_OK;
+    if (s->mem) {
+        (void)hipSetDevice(s->device);
+        (void)hipFree(s->mem);
+    }
+    delete s;
+    return MIR_OK;
+}
+
+// mir_block_ensemble_search with every leg's document lists named by scopes[q].  The host part is O(b):
+// scope_ptr from the scopes' n_docs, one reference record per query; scope_gather_kernel flattens the resident descriptor
+// arrays into the legs' tables on the ensemble's stream, and from there the call is ensemble_run, as the parent entry's.
+int32_t mir_block_ensemble_search_scopes(mir_ensemble *e, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c, int32_t cap,
+                                         const mir_ensemble_scope *const *scopes, int32_t *out_doc, int64_t *out_chunk, double *out_score,
+                                         int32_t *out_origin, int32_t *out_count) {
+    // the parent entry's refusals and order up to the legs' lists
+    MIR_REQUIRE(legs != nullptr, "legs is NULL");
+    MIR_REQUIRE(out_doc && out_chunk && out_score && out_origin && out_count, "an output is NULL");
+    MIR_REQUIRE(n_legs >= 1 && n_legs <= kRrfMaxLists, "n_legs=%d outside [1, %d]", n_legs, kRrfMaxLists);
+    int kw = -1, n_vec = 0;
+    int slot_of[kRrfMaxLists] = {};
+    mir_rrf_list lists[kRrfMaxLists] = {};
+    double weights[kRrfMaxLists] = {};
+    for (int l = 0; l < n_legs; ++l) {
+        MIR_REQUIRE(legs[l].kind == MIR_LEG_VECTOR || legs[l].kind == MIR_LEG_KEYWORD, "leg %d has unknown kind %d", l, legs[l].kind);
+        if (legs[l].kind == MIR_LEG_KEYWORD) {
+            MIR_REQUIRE(kw < 0, "legs %d and %d are both keyword legs: at most one", kw, l);
+            kw = l;
+        } else {
+            slot_of[l] = n_vec++;
+        }
+        lists[l].k = legs[l].k;
+        weights[l] = legs[l].weight;
+    }
+    int32_t rc = rrf_check(lists, n_legs, weights, c, b, cap, true);
+    if (rc != MIR_OK) return rc;
+    // the scopes, in place of the legs' lists: O(b)
+    int64_t listed = 0;
+    int32_t expanded_mask = 0;
+    if (b > 0) {
+        MIR_REQUIRE(scopes != nullptr, "scopes is NULL");
+        for (int i = 0; i < b; ++i) MIR_REQUIRE(scopes[i] != nullptr, "scope %d is NULL", i);
+        for (int i = 0; i < b; ++i)
+            MIR_REQUIRE(scopes[i]->n_slots == n_vec, "scope %d has %d slots, the call %d vector legs", i, scopes[i]->n_slots, n_vec);
+        for (int i = 0; i < b; ++i)
+            for (int l = 0; l < n_legs; ++l)
+                MIR_REQUIRE(legs[l].kind != MIR_LEG_VECTOR || scopes[i]->searcher[slot_of[l]] == legs[l].searcher,
+                            "slot %d of scope %d was made for another searcher than leg %d's", slot_of[l], i, l);
+        for (int i = 0; i < b && kw >= 0; ++i) {
+            MIR_REQUIRE(scopes[i]->text != nullptr, "scope %d has no text scope, leg %d is a keyword leg", i, kw);
+            MIR_REQUIRE(scopes[i]->text_searcher == legs[kw].text_searcher, "the text scope of scope %d is not one of the searcher of leg %d", i, kw);
+        }
+        for (int i = 0; i < b; ++i) {
+            MIR_REQUIRE(scopes[i]->device == scopes[0]->device, "scope %d is on device %d, scope 0 on device %d", i, scopes[i]->device, scopes[0]->device);
+            listed += scopes[i]->n_docs;
+            expanded_mask |= scopes[i]->paged_mask;
+        }
+        MIR_REQUIRE(listed < ((int64_t)1 << 31), "the scopes of the batch list 2^31 documents or more");
+    }
+    // what is left of each leg's own checks: the searcher, the metric, the queries; the keyword leg's query batch
+    int32_t d_of[kRrfMaxLists] = {}, device_of[kRrfMaxLists] = {};
+    int nt = 0;
+    std::vector<const mir_bm25_blocks_scope *> text_scopes;
+    for (int l = 0; l < n_legs; ++l) {
+        const mir_ensemble_leg &g = legs[l];
+        if (g.kind == MIR_LEG_VECTOR) {
+            std::vector<mir_block_desc> none;
+            rc = blocks_check_host(g.searcher, g.queries_host, 0, g.k, g.metric, nullptr, nullptr, out_count, &none, &d_of[l], &device_of[l]);
+            if (rc != MIR_OK) return rc;
+            MIR_REQUIRE(b == 0 || g.queries_host != nullptr, "queries is NULL");
+            continue;
+        }
+        if (b > 0) {
+            text_scopes.resize((size_t)b);
+            for (int i = 0; i < b; ++i) text_scopes[(size_t)i] = scopes[i]->text;
+        }
+        rc = ensemble_keyword_check(g.text_searcher, text_scopes.data(), g.q_terms_host, g.q_ptr_host, b, g.k, &nt);
+        if (rc != MIR_OK) return rc;
+        device_of[l] = g.text_searcher->device;
+    }
+    MIR_REQUIRE(e != nullptr, "ensemble is NULL");
+    for (int l = 0; l < n_legs; ++l)
+        MIR_REQUIRE(device_of[l] == e->device, "the searcher of leg %d is on device %d, the ensemble on device %d", l, device_of[l], e->device);
+    if (b == 0) return MIR_OK;
+    MIR_REQUIRE(scopes[0]->device == e->device, "the scopes are on device %d, the ensemble on device %d", scopes[0]->device, e->device);
+    EnsembleScopesShape es{};
+    es.b = b; es.cap = cap; es.listed = listed; es.n_legs = n_legs;
+    es.desc_bytes = sizeof(mir_block_desc); es.fan_bytes = sizeof(mir_fanout_desc); es.scope_bytes = sizeof(BlockScopeDev);
+    es.ref_bytes = sizeof(EnsembleScopeRef);
+    for (int l = 0; l < n_legs; ++l) {
+        const mir_ensemble_leg &g = legs[l];
+        EnsembleScopesLegShape &ls = es.leg[l];
+        ls.kind = g.kind; ls.k = g.k; ls.d = d_of[l]; ls.terms = nt;
+        ls.expanded = g.kind == MIR_LEG_VECTOR && (expanded_mask >> slot_of[l] & 1);
+        ls.q_of = -1;
+        for (int j = 0; j < l && g.kind == MIR_LEG_VECTOR && ls.q_of < 0; ++j)  // the same host queries at the same d: uploaded once
+            if (legs[j].kind == MIR_LEG_VECTOR && es.leg[j].q_of < 0 && legs[j].queries_host == g.queries_host && d_of[j] == d_of[l]) ls.q_of = j;
+    }
+    EnsembleScopesLayout lay;
+    const EnsembleScopesCarve carved = ensemble_scopes_carve(es, &lay);
+    MIR_REQUIRE(carved == kScopesOk, "the call's arrays do not fit a scratch (b=%d cap=%d, %d legs)", b, cap, n_legs);
+    mir_bm25_blocks *h = kw >= 0 ? legs[kw].text_searcher : nullptr;
+    const BlockRoute route{h};
+    OutColumn cols[5] = {{nullptr, 8}, {nullptr, 8}, {nullptr, 8}, {nullptr, 4}, {nullptr, 4}};  // pos, chunk, score, ord, local
+    ScopedPlan<BlockScopeDev> plan;
+    size_t need = lay.keyword;
+    if (kw >= 0) {
+        const ScopedInputs inputs{lay.leg[kw].terms, lay.leg[kw].q_ptr, lay.leg[kw].scopes};
+        scoped_plan(route, text_scopes.data(), nt, b, legs[kw].k, cols, 5, lay.keyword, &inputs, &plan);
+        need = plan.end;
+    }
+    EnsembleLegAt at[kRrfMaxLists];
+    for (int l = 0; l < n_legs; ++l) {
+        const EnsembleScopesLegLayout &ll = lay.leg[l];
+        at[l] = EnsembleLegAt{ll.q, lay.scope_ptr, ll.table, ll.fan_table, ll.l_doc, ll.l_chunk, ll.l_count, es.leg[l].expanded};
+    }
+    const EnsembleSpans spans{lay.in_bytes, lay.f_doc, lay.f_chunk, lay.f_score, lay.f_origin, lay.f_count, lay.out_bytes};
+    auto fill = [&](char *up) {
+        scopes_fill(scopes, b, reinterpret_cast<int32_t *>(up + lay.scope_ptr), reinterpret_cast<EnsembleScopeRef *>(up + lay.refs));
+        for (int l = 0; l < n_legs; ++l) {
+            const mir_ensemble_leg &g = legs[l];
+            const EnsembleScopesLegLayout &ll = lay.leg[l];
+            if (g.kind == MIR_LEG_KEYWORD) {
+                if (nt) std::memcpy(up + ll.terms, g.q_terms_host, (size_t)nt * 4);
+                std::memcpy(up + ll.q_ptr, g.q_ptr_host, ((size_t)b + 1) * 4);
+                std::memcpy(up + ll.scopes, plan.sd.data(), (size_t)b * sizeof(BlockScopeDev));
+            } else if (es.leg[l].q_of < 0) {
+                std::memcpy(up + ll.q, g.queries_host, (size_t)b * d_of[l] * 8);
+            }
+        }
+    };
+    auto prepare = [&](char *base, hipStream_t s) -> int32_t {  // after the upload, before the first leg: the legs' tables
+        if (n_vec == 0 || listed == 0) return MIR_OK;
+        ScopeGatherArgs ga{};
+        ga.refs = reinterpret_cast<const EnsembleScopeRef *>(base + lay.refs);
+        ga.scope_ptr = reinterpret_cast<const int32_t *>(base + lay.scope_ptr);
+        for (int l = 0; l < n_legs; ++l) {
+            if (legs[l].kind != MIR_LEG_VECTOR) continue;
+            ga.table[slot_of[l]] = reinterpret_cast<uint4 *>(base + lay.leg[l].table);
+            ga.fan_table[slot_of[l]] = es.leg[l].expanded ? reinterpret_cast<uint4 *>(base + lay.leg[l].fan_table) : nullptr;
+        }
+        scope_gather_kernel<<<dim3((unsigned)b, (unsigned)n_vec), dim3(kScopeGatherThreads), 0, s>>>(ga);  // one launch for all slots
+        MIR_HIP(hipGetLastError());
         return MIR_OK;
     };
-    rc = enqueue();
-    if (rc != MIR_OK) { (void)hipStreamSynchronize(s); return rc; }
-    MIR_HIP(hipStreamSynchronize(s));
-    const size_t rows = (size_t)b * cap;
-    std::memcpy(out_doc, down, rows * 4);
-    std::memcpy(out_chunk, down + (lay.f_chunk - lay.f_doc), rows * 8);
-    std::memcpy(out_score, down + (lay.f_score - lay.f_doc), rows * 8);
-    std::memcpy(out_origin, down + (lay.f_origin - lay.f_doc), rows * 4);
-    std::memcpy(out_count, down + (lay.f_count - lay.f_doc), (size_t)b * 4);
+    return ensemble_run(e, h, legs, n_legs, b, c, cap, route, plan, cols, need, at, spans, lists, weights, fill, prepare,
+                        EnsembleOut{out_doc, out_chunk, out_score, out_origin, out_count});
+}
+
+// A measurement hook (tools/block_ensemble_scopes_timing.py): scope_gather_kernel alone for the scopes of a batch, `reps`
+// launches on the ensemble's stream and in its scratch, each between two device events.  Every slot writes its table, and
+// its fan-out table where some scope of the batch is paged in it, as a search of these scopes would.
+int32_t mir_ensemble_scopes_gather_ms(mir_ensemble *e, const mir_ensemble_scope *const *scopes, int32_t b, int32_t reps, float *out_ms) {
+    MIR_REQUIRE(e != nullptr, "ensemble is NULL");
+    MIR_REQUIRE(b >= 1 && reps >= 1 && scopes != nullptr && out_ms != nullptr, "bad arguments b=%d reps=%d", b, reps);
+    int64_t listed = 0;
+    int32_t expanded_mask = 0;
+    for (int i = 0; i < b; ++i) {
+        MIR_REQUIRE(scopes[i] != nullptr && scopes[i]->device == e->device && scopes[i]->n_slots == scopes[0]->n_slots,
+                    "scope %d is NULL, on another device than the ensemble or of another slot count than scope 0", i);
+        listed += scopes[i]->n_docs;
+        expanded_mask |= scopes[i]->paged_mask;
+    }
+    const int n_slots = scopes[0]->n_slots;
+    MIR_REQUIRE(n_slots >= 1 && listed >= 1 && listed < ((int64_t)1 << 31), "nothing to gather (%d slots, %lld documents)", n_slots, (long long)listed);
+    EnsembleScopesShape es{};  // the carve of a search with one vector leg per slot (k = 1, d = 1): its scope_ptr, records and tables
+    es.b = b; es.cap = n_slots; es.listed = listed; es.n_legs = n_slots;
+    es.desc_bytes = sizeof(mir_block_desc); es.fan_bytes = sizeof(mir_fanout_desc); es.scope_bytes = sizeof(BlockScopeDev);
+    es.ref_bytes = sizeof(EnsembleScopeRef);
+    for (int j = 0; j < n_slots; ++j) es.leg[j] = EnsembleScopesLegShape{kScopesLegVector, 1, 1, 0, (expanded_mask >> j & 1) != 0, -1};
+    EnsembleScopesLayout lay;
+    MIR_REQUIRE(ensemble_scopes_carve(es, &lay) == kScopesOk, "the tables do not fit a scratch (b=%d)", b);
+    int32_t rc = use_device(e->device, nullptr);
+    if (rc != MIR_OK) return rc;
+    std::lock_guard<std::mutex> lk(e->mu);
+    rc = e->scratch.ensure(lay.keyword);
+    if (rc != MIR_OK) return rc;
+    std::vector<char> up(lay.in_bytes, 0);
+    scopes_fill(scopes, b, reinterpret_cast<int32_t *>(up.data() + lay.scope_ptr), reinterpret_cast<EnsembleScopeRef *>(up.data() + lay.refs));
+    char *base = static_cast<char *>(e->scratch.ptr);
+    MIR_HIP(hipMemcpy(base, up.data(), lay.in_bytes, hipMemcpyHostToDevice));
+    ScopeGatherArgs ga{};
+    ga.refs = reinterpret_cast<const EnsembleScopeRef *>(base + lay.refs);
+    ga.scope_ptr = reinterpret_cast<const int32_t *>(base + lay.scope_ptr);
+    for (int j = 0; j < n_slots; ++j) {
+        ga.table[j] = reinterpret_cast<uint4 *>(base + lay.leg[j].table);
+        ga.fan_table[j] = es.leg[j].expanded ? reinterpret_cast<uint4 *>(base + lay.leg[j].fan_table) : nullptr;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t err = hipEventCreate(&e0);
+    if (err == hipSuccess) err = hipEventCreate(&e1);
+    for (int r = 0; r < reps && err == hipSuccess; ++r) {
+        err = hipEventRecord(e0, e->stream);
+        scope_gather_kernel<<<dim3((unsigned)b, (unsigned)n_slots), dim3(kScopeGatherThreads), 0, e->stream>>>(ga);
+        if (err == hipSuccess) err = hipEventRecord(e1, e->stream);
+        if (err == hipSuccess) err = hipEventSynchronize(e1);
+        if (err == hipSuccess) err = hipEventElapsedTime(&out_ms[r], e0, e1);
+    }
+    if (err == hipSuccess) err = hipGetLastError();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (err != hipSuccess) {
+        (void)hipStreamSynchronize(e->stream);
+        set_error("mir_ensemble_scopes_gather_ms: %s", hipGetErrorString(err));
+        return MIR_ERR_HIP;
+    }
     return MIR_OK;
 }
 

@@ -23,4 +23,11 @@ int32_t blocks_expanded_check_host(mir_blocks *s, const double *queries_host, in
                                    const mir_rows *const *blocks_host, const mir_fanout *const *fanouts_host, const int32_t *out_count,
                                    std::vector<mir_block_desc> *table, std::vector<mir_fanout_desc> *fan_table, int32_t *d, int32_t *device);
 
+// One slot of mir_ensemble_scope_create: what the two walks above do per call, once per document list.
+// Every block against the searcher (d, dtype, device), every fan-out against its block, the slot's stored rows and its
+// expanded rows below 2^32, the searcher on `device`.  MIR_OK: desc[n_docs] and fan[n_docs] are the descriptors (an
+// un-paged entry of `fan` all null), *paged says whether any block has a fan-out.  `fanouts` may be null.
+int32_t scope_slot_check_host(int32_t slot, const mir_blocks *s, const mir_rows *const *blocks, const mir_fanout *const *fanouts, int32_t n_docs,
+                              int32_t device, mir_block_desc *desc, mir_fanout_desc *fan, bool *paged);
+
 }  // namespace mir

@@ -1742,6 +1742,39 @@ int32_t blocks_expanded_check_host(mir_blocks *s_, const double *queries_host, i
     return check_fanouts(scope_ptr_host, b, blocks_host, fanouts_host, table->size(), fan_table);
 }
 
+// mir_ensemble_scope_create's walk of one slot (vec_blocks_host.h): check_blocks and check_fanouts for ONE document list
+int32_t scope_slot_check_host(int32_t slot, const mir_blocks *s_, const mir_rows *const *blocks, const mir_fanout *const *fanouts, int32_t n_docs,
+                              int32_t device, mir_block_desc *desc, mir_fanout_desc *fan, bool *paged) {
+    MIR_REQUIRE(s_ != nullptr, "the searcher of slot %d is NULL", slot);
+    const mir_index *ix = s_->ix;
+    MIR_REQUIRE(ix->device == device, "the searcher of slot %d is on device %d, the scope on device %d", slot, ix->device, device);
+    MIR_REQUIRE(n_docs == 0 || blocks != nullptr, "the block table of slot %d is NULL", slot);
+    *paged = false;
+    uint64_t rows = 0, expanded = 0;
+    for (int32_t t = 0; t < n_docs; ++t) {
+        const mir_rows *r = blocks[t];
+        MIR_REQUIRE(r != nullptr, "block %d of slot %d is NULL", t, slot);
+        MIR_REQUIRE(r->d == ix->d && r->dtype == ix->dtype && r->device == ix->device,
+                    "block %d of slot %d is %d-dimensional dtype %d on device %d, the searcher %d-dimensional dtype %d on device %d", t, slot, r->d,
+                    r->dtype, r->device, ix->d, ix->dtype, ix->device);
+        desc[t] = mir_block_desc{r->d_emb, r->d_docsq, r->d_chunk, r->n};
+        rows += (uint64_t)r->n;
+        MIR_REQUIRE(rows < (1ull << 32), "the scope of slot %d holds 2^32 rows or more", slot);
+        const mir_fanout *f = fanouts ? fanouts[t] : nullptr;
+        fan[t] = mir_fanout_desc{nullptr, nullptr, nullptr, 0};
+        if (f) {
+            MIR_REQUIRE(f->n == r->n && f->device == r->device,
+                        "the fan-out of block %d of slot %d is of %lld stored rows on device %d, the block holds %lld on device %d", t, slot,
+                        (long long)f->n, f->device, (long long)r->n, r->device);
+            fan[t] = mir_fanout_desc{f->d_ptr, f->d_chunk, f->d_pos, f->n};
+            *paged = true;
+        }
+        expanded += (uint64_t)(f ? f->R : r->n);
+        MIR_REQUIRE(expanded < (1ull << 32), "the expanded scope of slot %d holds 2^32 rows or more", slot);
+    }
+    return MIR_OK;
+}
+
 // per-query norms (ngroups = 0: no fragments) + `counters` arrival counters zeroed
 static void launch_scoped_prep(const ScopedCall &c, const ScopedBuffers &sb, int counters, hipStream_t stream) {
     const int arrive_words = (counters + 1) / 2;

@@ -11,10 +11,15 @@ list it was FIRST SEEN in: the ensemble keeps the first ``Document`` it sees of 
 ``retrieval_type`` (``documents``).  ``device_fusion=True`` makes ONE native call per batch
 (``mir_block_ensemble_search``): every leg's list stays in HBM, is fused there by the origin variant of
 ``rrf_fuse_kernel``, and the call synchronises once.
+
+A chat's document list changes only when it gains or loses an attachment.  ``BlockEnsemble.scope(keys)`` describes the
+list ONCE - an ``EnsembleScope``, its descriptor tables resident in HBM - and ``find_scoped`` names it per query with one
+handle (``mir_block_ensemble_search_scopes``): the host work of a call no longer grows with the lists.
 """
 
 import ctypes as C
 import threading
+import weakref
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -28,7 +33,7 @@ from .embeddings_index import BlockSearcher, DeviceFanout, DeviceRows, DocIndex,
 from .embeddings_metrics import Metric
 from .sharded_bm25 import fuse_batch
 
-__all__ = ["BlockEnsemble", "EnsembleSearcher", "VectorLeg", "KeywordLeg", "LEG_NAMES", "first_seen_origin"]
+__all__ = ["BlockEnsemble", "EnsembleScope", "EnsembleSearcher", "VectorLeg", "KeywordLeg", "LEG_NAMES", "first_seen_origin"]
 
 LEG_NAMES = ("semantic", "keywords", "multimodal", "description")  # retrieval_chain.py:193-252, in its order
 # the type each leg's retriever class gives its documents (semantic_retriever.py, bm25_retriever.py: TEXT; page_retrievers.py: IMAGE)
@@ -59,6 +64,71 @@ class KeywordLeg(NamedTuple):
     queries_ids: Sequence[Sequence[int]]
     k: int
     weight: float = 1.0
+
+
+class EnsembleScope(_HandleOwner):
+    """Owner of one ``mir_ensemble_scope``: an ordered document list as every vector leg sees it, its descriptor tables
+    resident in HBM, plus the keyword leg's scope of the same list.  ``slots[j]`` = (``BlockSearcher``, the ``DeviceRows``
+    blocks, their ``DeviceFanout`` / None entries or None) for the j-th VECTOR leg; ``text_scope``: a ``BM25BlockScope`` or
+    None.  The scope is immutable and may be named by any number of queries, threads and ``EnsembleSearcher`` objects.  It
+    HOLDS every block, fan-out and the text scope it names (and whatever ``keep`` lists): nothing it points at can be freed
+    under it.  ``close`` while a search uses the scope is safe: the handle goes with the last search that holds it.
+    ``native=False`` makes a scope without a handle (``BlockEnsemble``: served by the host route)."""
+
+    _destroy = "mir_ensemble_scope_destroy"
+
+    def __init__(self, keys: Sequence[int], slots: Sequence[tuple] = (), text_scope: Optional[BM25BlockScope] = None, device: int = 0,
+                 n_docs: Optional[int] = None, keep=(), native: bool = True):
+        self.keys = tuple(int(key) for key in keys)
+        self.n_docs = len(self.keys) if n_docs is None else int(n_docs)
+        self.device, self.hbm_bytes, self.native = device, 0, bool(native)
+        self._mu = threading.Lock()
+        self._users, self._closed, self._stale = 0, False, False
+        self._held = (list(slots), text_scope, keep)
+        if not native:
+            return
+        arr = (nat.ScopeSlot * max(len(slots), 1))()
+        tables = []
+        for j, (searcher, blocks, fanouts) in enumerate(slots):
+            if len(blocks) != self.n_docs or (fanouts is not None and len(fanouts) != self.n_docs):
+                raise ValueError(f"slot {j}: {len(blocks)} blocks and {0 if fanouts is None else len(fanouts)} fan-out entries for {self.n_docs} documents")
+            table = (C.c_void_p * max(self.n_docs, 1))(*[blk.handle for blk in blocks])
+            arr[j].searcher, arr[j].blocks = searcher.handle, C.cast(table, C.c_void_p)
+            tables.append(table)
+            if fanouts is not None:
+                fan_table = (C.c_void_p * max(self.n_docs, 1))(*[None if f is None else f.handle for f in fanouts])
+                arr[j].fanouts = C.cast(fan_table, C.c_void_p)
+                tables.append(fan_table)
+        h = C.c_void_p()
+        nat.check(nat.lib.mir_ensemble_scope_create(device, self.n_docs, arr, len(slots), None if text_scope is None else text_scope.handle, C.byref(h)))
+        del tables  # (the library has copied what it needs: the handle tables are the call's)
+        self._h = h
+        nbytes = C.c_int64()
+        nat.check(nat.lib.mir_ensemble_scope_info(h, None, None, None, C.byref(nbytes)))
+        self.hbm_bytes = int(nbytes.value)
+
+    def _acquire(self):
+        """-> the handle, held against ``close`` until ``_release``."""
+        with self._mu:
+            if self._closed or not self._h:
+                raise ValueError("the scope is closed" if self._closed else "the scope has no native handle")
+            self._users += 1
+            return self._h
+
+    def _release(self):
+        with self._mu:
+            self._users -= 1
+            if self._closed and self._users == 0:
+                _HandleOwner.close(self)
+
+    def close(self):
+        mu = getattr(self, "_mu", None)
+        if mu is None:  # (a constructor that raised before the lock was made)
+            return
+        with mu:
+            self._closed = True
+            if self._users == 0:
+                _HandleOwner.close(self)
 
 
 class EnsembleSearcher(_HandleOwner):
@@ -92,32 +162,66 @@ class EnsembleSearcher(_HandleOwner):
         del held
         return doc, chunk, score, origin, cnt
 
+    def search_scopes(self, legs: Sequence, scopes: Sequence[EnsembleScope], b: int, c: int = 60, cap: Optional[int] = None):
+        """``search`` with the document lists named by ``scopes[q]`` (``mir_block_ensemble_search_scopes``): the legs'
+        ``scopes`` / ``fanouts`` are not looked at (None will do) - the l-th ``VectorLeg``, in order, reads slot l of
+        ``scopes[q]``, the ``KeywordLeg`` its text scope.  The five arrays are ``search``'s over the flattened lists of
+        the same scopes, bit for bit; the host work is O(b) whatever the length of the scopes."""
+        b = int(b)
+        if len(scopes) != b:
+            raise ValueError(f"{len(scopes)} scopes for {b} queries")
+        arr, held = self._marshal(legs, b, lists=False)
+        total = sum(max(int(leg.k), 0) for leg in legs)
+        cap = total if cap is None else int(cap)
+        rows = (b, max(cap, 0))
+        doc, chunk, score = np.zeros(rows, np.int32), np.zeros(rows, np.int64), np.zeros(rows, np.float64)
+        origin, cnt = np.zeros(rows, np.int32), np.zeros(b, np.int32)
+        taken = []
+        try:
+            handles = (C.c_void_p * max(b, 1))()
+            for i, s in enumerate(scopes):  # (a scope closed meanwhile: ValueError, nothing launched)
+                handles[i] = s._acquire()
+                taken.append(s)
+            nat.check(nat.lib.mir_block_ensemble_search_scopes(self._h, arr, len(legs), b, int(c), cap, handles, doc.ctypes.data, chunk.ctypes.data,
+                                                               score.ctypes.data, origin.ctypes.data, cnt.ctypes.data))
+        finally:
+            for s in taken:
+                s._release()
+        del held
+        return doc, chunk, score, origin, cnt
+
     @staticmethod
-    def _marshal(legs: Sequence, b: int):
-        """-> (the mir_ensemble_leg array, everything it points into: host arrays and handle tables, to be kept alive across the call)."""
+    def _marshal(legs: Sequence, b: int, lists: bool = True):
+        """-> (the mir_ensemble_leg array, everything it points into: host arrays and handle tables, to be kept alive across the
+        call).  ``lists=False``: the document lists come from resident scopes, the legs' own are left null."""
         arr = (nat.EnsembleLeg * max(len(legs), 1))()
         held = []
         for l, leg in enumerate(legs):
             a = arr[l]
             a.k, a.weight = int(leg.k), float(leg.weight)
             if isinstance(leg, KeywordLeg):
-                if len(leg.scopes) != b or len(leg.queries_ids) != b:
-                    raise ValueError(f"leg {l}: {len(leg.scopes)} text scopes and {len(leg.queries_ids)} term lists for {b} queries")
+                if (lists and len(leg.scopes) != b) or len(leg.queries_ids) != b:
+                    raise ValueError(f"leg {l}: {len(leg.scopes) if lists else b} text scopes and {len(leg.queries_ids)} term lists for {b} queries")
                 flat, ptr = _pack_queries(leg.queries_ids)
-                handles = (C.c_void_p * max(b, 1))(*[s.handle for s in leg.scopes])
-                held += [flat, ptr, handles, leg.scopes]
+                held += [flat, ptr]
                 a.kind, a.text_searcher = nat.LEG_KEYWORD, leg.searcher.handle
-                a.text_scopes = C.cast(handles, C.c_void_p)
+                if lists:
+                    handles = (C.c_void_p * max(b, 1))(*[s.handle for s in leg.scopes])
+                    held += [handles, leg.scopes]
+                    a.text_scopes = C.cast(handles, C.c_void_p)
                 a.q_terms_host = flat.ctypes.data if len(flat) else None
                 a.q_ptr_host = ptr.ctypes.data
                 continue
             q = nat.as_f64_queries(leg.queries, leg.searcher.d)
-            if q.shape[0] != b or len(leg.scopes) != b:
-                raise ValueError(f"leg {l}: {q.shape[0]} queries and {len(leg.scopes)} scopes for {b} queries")
-            blocks, sp, table = _scope_table(leg.scopes)
-            held += [q, blocks, sp, table]
+            if q.shape[0] != b or (lists and len(leg.scopes) != b):
+                raise ValueError(f"leg {l}: {q.shape[0]} queries and {len(leg.scopes) if lists else b} scopes for {b} queries")
+            held.append(q)
             a.kind, a.searcher, a.metric = nat.LEG_VECTOR, leg.searcher.handle, nat.METRIC_CODES[Metric(leg.metric).value]
             a.queries_host = q.ctypes.data
+            if not lists:
+                continue
+            blocks, sp, table = _scope_table(leg.scopes)
+            held += [blocks, sp, table]
             a.scope_ptr_host = sp.ctypes.data
             a.blocks_host = C.cast(table, C.c_void_p)
             if leg.fanouts is not None:
@@ -162,6 +266,8 @@ class BlockEnsemble:
         self.keywords: Optional[BlockBM25] = BlockBM25(device=device) if "keywords" in legs else None
         self._lock = threading.Lock()
         self._searcher: Optional[EnsembleSearcher] = None
+        self._scopes_of: Dict[int, "weakref.WeakSet[EnsembleScope]"] = {}  # key -> the live scopes that list it
+        self._removals = 0
 
     # ---- documents --------------------------------------------------------------------------------------------
     def _as_block(self, name: str, doc) -> Optional[DeviceRows]:
@@ -226,6 +332,9 @@ class BlockEnsemble:
                 raise KeyError(key)
             for corpus in self._corpora():
                 corpus.remove(key)
+            self._removals += 1
+            for scope in self._scopes_of.pop(int(key), ()):  # every scope that lists the key: find_scoped raises KeyError from now on
+                scope._stale = True
 
     def __len__(self) -> int:
         return len(self._corpora()[0])
@@ -309,12 +418,7 @@ class BlockEnsemble:
                 continue
             corpus = self.vectors[name]
             lists = [corpus._blocks_of(s) for s in scopes]  # KeyError for a removed key
-            with corpus._lock:
-                d, dtype = corpus.d, corpus.dtype
-                if d is not None and corpus._searcher is None:
-                    corpus._searcher = BlockSearcher(d, dtype, corpus.device)
-                    corpus._empty = DeviceRows.from_host(np.zeros((0, d), np.float16 if dtype == nat.DTYPE_F16 else np.float32), None, corpus.device)
-                searcher, empty, frozen = corpus._searcher, corpus._empty, bool(corpus._frozen)
+            searcher, empty, frozen = self._leg_searcher(corpus)
             if searcher is None or frozen:
                 return None
             rows = [[empty if blk is None else blk for blk in s] for s in lists]
@@ -322,6 +426,96 @@ class BlockEnsemble:
             paged = any(f is not None for fs in fanouts for f in fs)
             legs.append(VectorLeg(searcher, mm if name == "multimodal" else q, metrics[name], rows, fanouts if paged else None, k, float(weight)))
         return legs
+
+    @staticmethod
+    def _leg_searcher(corpus: BlockCorpus):
+        """-> (the corpus's searcher, made at first use; its block of no rows; whether it holds a frozen run).  The searcher
+        is None while the corpus holds no row: its d is not known yet."""
+        with corpus._lock:
+            d, dtype = corpus.d, corpus.dtype
+            if d is not None and corpus._searcher is None:
+                corpus._searcher = BlockSearcher(d, dtype, corpus.device)
+                corpus._empty = DeviceRows.from_host(np.zeros((0, d), np.float16 if dtype == nat.DTYPE_F16 else np.float32), None, corpus.device)
+            return corpus._searcher, corpus._empty, bool(corpus._frozen)
+
+    # ---- resident scopes (DESIGN.md 4.13) ------------------------------------------------------------------------------
+    def scope(self, keys: Sequence[int]) -> EnsembleScope:
+        """The document list ``keys`` (in this order, a key may come twice) described once for every leg -> the scope
+        ``find_scoped`` names.  ``KeyError`` for an unknown or removed key; "Text index is empty." where the keyword leg has
+        no token in the list.  A document that is None in a page leg is that corpus's block of no rows and keeps its
+        ordinal.  Where a vector corpus holds no row yet, or holds a frozen run, the scope has no native handle and
+        ``find_scoped`` serves it by the host route.  The scope stays valid across ``add`` and across ``remove`` of keys it
+        does not list; after ``remove`` of one it lists, ``find_scoped`` raises ``KeyError``.  ``close()`` it, or drop it."""
+        keys = tuple(int(key) for key in keys)
+        slots, native, view, text_scope = [], True, None, None
+        for corpus in self.vectors.values():
+            blocks = corpus._blocks_of(keys)  # KeyError for a removed key
+            searcher, empty, frozen = self._leg_searcher(corpus)
+            if searcher is None or frozen:
+                native = False
+                continue
+            rows = [empty if blk is None else blk for blk in blocks]
+            fanouts = [getattr(blk, "fanout", None) for blk in rows]
+            slots.append((searcher, rows, fanouts if any(f is not None for f in fanouts) else None))
+        if self.keywords is not None:
+            view = self.keywords._cached_view(keys)  # KeyError for a removed key
+            self.keywords._prepare_views([view])
+            text_scope = view.scope()  # no token: "Text index is empty."
+        scope = EnsembleScope(keys, slots if native else (), text_scope, self.device, keep=(view,), native=native)
+        scope._owner = weakref.ref(self)
+        with self._lock:  # (a key removed while the scope was made: no scope of it is registered after the removal)
+            gone = [key for key in keys if any(key not in corpus for corpus in self._corpora())]
+            if gone:
+                scope.close()
+                raise KeyError(gone[0])
+            for key in set(keys):
+                self._scopes_of.setdefault(key, weakref.WeakSet()).add(scope)
+        return scope
+
+    def find_scoped(self, query_vectors, query_ids, scopes: Sequence[EnsembleScope], multimodal_vectors=None, metric=Metric.SQEUCLIDEAN_DIST,
+                    multimodal_metric=Metric.SQEUCLIDEAN_DIST, k=7, weights: Optional[Sequence[float]] = None, c: int = 60):
+        """``find_many`` for ``[s.keys for s in scopes]``, exactly - its tuple, its errors - where ``scopes[i]`` was made by
+        ``scope``.  With ``device_fusion`` ONE ``EnsembleSearcher.search_scopes`` call: nothing of a document list is
+        resolved, tabled or uploaded again, the host work is O(b).  Without it, and wherever ``find_many`` takes the host
+        route (the sum of the legs' k > 512, a weight that is not finite, c < 0) or a scope has no native handle, this IS
+        that ``find_many`` call."""
+        for s in scopes:
+            if not isinstance(s, EnsembleScope) or getattr(s, "_owner", lambda: None)() is not self:
+                raise ValueError("find_scoped takes the scopes this ensemble's scope() made")
+        if self._removals:  # (a flag per scope, set by remove: nothing is looked up per key)
+            for s in scopes:
+                if s._stale:
+                    raise KeyError(next(key for key in s.keys if key not in self))
+        if any(s._closed for s in scopes):
+            raise ValueError("find_scoped was given a closed scope")
+
+        def host():
+            return self.find_many(query_vectors, query_ids, [s.keys for s in scopes], multimodal_vectors, metric, multimodal_metric, k, weights, c)
+
+        n = len(self.legs)
+        ks = [int(k)] * n if np.isscalar(k) else [int(x) for x in k]
+        w = np.ones(n) if weights is None else np.asarray(weights, dtype=np.float64)
+        if not self.device_fusion or len(ks) != n or w.shape != (n,) or not all(s.native for s in scopes):
+            return host()
+        if not (all(x >= 1 for x in ks) and sum(ks) <= MAX_FUSED and bool(np.all(np.isfinite(w))) and int(c) >= 0):
+            return host()
+        q, mm = self._leg_queries(query_vectors, multimodal_vectors)
+        if len(scopes) != len(q) or (self.keywords is not None and len(query_ids) != len(q)):
+            return host()  # (its ValueError)
+        legs = []
+        for name, kk, weight in zip(self.legs, ks, w):
+            if name == "keywords":
+                legs.append(KeywordLeg(self.keywords._device_searcher(), None, [self.keywords._ids(t) for t in query_ids], kk, float(weight)))
+            else:
+                m = multimodal_metric if name == "multimodal" else metric
+                Metric(m)
+                legs.append(VectorLeg(self.vectors[name]._searcher, mm if name == "multimodal" else q, m, None, None, kk, float(weight)))
+        with self._lock:
+            if self._searcher is None:
+                self._searcher = EnsembleSearcher(self.device)
+            searcher = self._searcher
+        doc, chunk, score, origin, cnt = searcher.search_scopes(legs, scopes, len(q), int(c))  # (a scope closed meanwhile: ValueError)
+        return doc.astype(np.int64), chunk, score, origin, cnt
 
     def documents(self, doc, chunk, origin, count, q: int) -> List[Document]:
         """Query ``q``'s fused items as the reference's ensemble returns them: the first ``Document`` seen of each key, so

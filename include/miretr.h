@@ -32,7 +32,10 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: block ensemble in one call and the fusion's origin, ADDED without a new number (nothing of ABI 6 changed):
+#define MIR_ABI_VERSION 6 /* 6: resident ensemble scopes, ADDED without a new number (nothing of ABI 6 changed):
+                               mir_ensemble_scope_create / _info / _destroy, mir_block_ensemble_search_scopes,
+                               mir_ensemble_scopes_gather_ms (a measurement hook);
+                            6: block ensemble in one call and the fusion's origin, ADDED without a new number (nothing of ABI 6 changed):
                                mir_rrf_fuse_device_origin, mir_ensemble_create / _destroy, mir_block_ensemble_search;
                             6: block hybrid in one call and the fusion on the device, ADDED without a new number (nothing of ABI 6 changed):
                                mir_rrf_fuse_device, mir_block_hybrid_search;
@@ -833,6 +836,66 @@ typedef struct {
 int32_t mir_block_ensemble_search(mir_ensemble *e, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c,
                                   int32_t cap, int32_t *out_doc, int64_t *out_chunk, double *out_score,
                                   int32_t *out_origin, int32_t *out_count);
+
+/* RESIDENT ENSEMBLE SCOPES (added within ABI 6): the ordered document list of a chat, described ONCE in
+ * every vector leg, and named per query by one handle.  mir_block_ensemble_search re-describes every list in every call
+ * (a handle table per leg as long as all scopes together, walked and uploaded again); with scopes a call costs O(b) on
+ * the host whatever the length of the scopes.
+ *   Slot j is the document list as the j-th VECTOR leg of a later search sees it: `searcher` fixes the slot's d, dtype and
+ *   device; blocks[n_docs] has no NULL entry (an empty document is a block of n = 0); fanouts[n_docs] may hold NULL
+ *   entries, or be NULL: no block of the slot is paged.  0 <= n_slots <= 3, n_docs >= 0; text_scope may be NULL, for an
+ *   ensemble without a keyword leg.
+ * mir_ensemble_scope_create does once what the per-call walk does: each block is checked against the slot's searcher (d,
+ * dtype, device), each fan-out against its block (stored rows, device), and per slot the stored rows and the expanded
+ * rows stay below 2^32.  Every refusal is MIR_ERR_INVALID, comes before the device is touched and leaves *out NULL.
+ * Then the mir_block_desc[n_docs] array of every slot, and the mir_fanout_desc[n_docs] array of a slot that has any
+ * fan-out (an un-paged entry all null), are written to HBM: one allocation per scope, one upload.  A scope without a slot
+ * or without a document allocates nothing.
+ *   The scope is immutable: any number of threads and of mir_ensemble handles on that device may use it.
+ *   The scope owns only its descriptor arrays.  The caller keeps every listed block, fan-out and the text scope alive
+ *   until the scope is destroyed: the same contract the _device searches have for their tables.
+ * mir_ensemble_scope_info: any output may be NULL; paged_mask bit j = slot j has a fan-out; hbm_bytes = the allocation.
+ * mir_ensemble_scope_destroy(NULL) is MIR_OK. */
+typedef struct mir_ensemble_scope mir_ensemble_scope;
+typedef struct {
+    mir_blocks *searcher;               /* fixes the slot's d, dtype, device */
+    const mir_rows *const *blocks;      /* [n_docs], no NULL entry; an empty document is a block of n = 0 */
+    const mir_fanout *const *fanouts;   /* [n_docs] with NULL entries allowed, or NULL: no block of the slot is paged */
+} mir_scope_slot;
+int32_t mir_ensemble_scope_create(int32_t device, int32_t n_docs, const mir_scope_slot *slots, int32_t n_slots,
+                                  const mir_bm25_blocks_scope *text_scope, mir_ensemble_scope **out);
+int32_t mir_ensemble_scope_info(const mir_ensemble_scope *s, int32_t *n_docs, int32_t *n_slots, int32_t *paged_mask,
+                                int64_t *hbm_bytes);
+int32_t mir_ensemble_scope_destroy(mir_ensemble_scope *s);
+
+/* mir_block_ensemble_search with the document lists named by scopes[b] (added within ABI 6).  The legs are
+ * mir_block_ensemble_search's; a vector leg's scope_ptr_host, blocks_host and fanouts_host and a keyword leg's text_scopes
+ * are IGNORED: the l-th vector leg, in order, reads slot l of scopes[q], the keyword leg scopes[q]'s text scope.
+ * The answer is what mir_block_ensemble_search returns when every leg is given the flattened lists of the same scopes:
+ * all five output arrays bit for bit, rows past the count zero.
+ * Route: the host computes scope_ptr[b + 1] from the scopes' n_docs (one copy for all vector legs) and writes one 64-byte
+ * reference record per query; one upload carries them with the queries and the keyword leg's inputs; scope_gather_kernel,
+ * on the ensemble's stream, flattens the resident descriptor arrays into each leg's table in the ensemble's scratch; from
+ * there the call is mir_block_ensemble_search's: the legs, the fusion, one download, one hipStreamSynchronize.  A vector
+ * leg takes the expanded search exactly when some scope of the batch is paged in its slot.
+ * Refusals come before anything is uploaded or launched, outputs untouched, in this order: mir_block_ensemble_search's
+ * for NULL legs or output, n_legs, the kinds and what mir_rrf_fuse_device refuses; then MIR_ERR_INVALID for NULL scopes or
+ * a NULL entry, a scope whose slot count differs from the number of vector legs, a slot whose searcher is not the leg's, a
+ * keyword leg with a scope that has no text scope or one of another keyword searcher, a scope on another device than
+ * scopes[0], a batch whose documents add up to 2^31 or more; then, leg after leg, what is left of a leg's own checks (an
+ * unknown metric, NULL queries, the keyword leg's query batch); then a NULL ensemble and an ensemble on another device.
+ * b == 0 is MIR_OK then, and scopes may be NULL. */
+int32_t mir_block_ensemble_search_scopes(mir_ensemble *e, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b,
+                                         int32_t c, int32_t cap, const mir_ensemble_scope *const *scopes,
+                                         int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_origin,
+                                         int32_t *out_count);
+
+/* A measurement hook (added within ABI 6; tools/block_ensemble_scopes_timing.py): scope_gather_kernel ALONE for the b
+ * scopes of a batch - all of one slot count >= 1, on the ensemble's device, listing at least one document - `reps`
+ * launches on the ensemble's stream and in its scratch, each between two device events: out_ms float[reps] (host).  A
+ * slot's fan-out table is written where some scope of the batch is paged in it, as a search of these scopes would. */
+int32_t mir_ensemble_scopes_gather_ms(mir_ensemble *e, const mir_ensemble_scope *const *scopes, int32_t b, int32_t reps,
+                                      float *out_ms);
 
 /* ------------------------------------------------------------------------
  * WordPiece tokenisation (host code): the BertTokenizer step in front of the encoder
