@@ -322,8 +322,10 @@ static int32_t encode_impl(mir_encoder *e, const int32_t *token_ids, const int32
     if (n_seq == 0) return MIR_OK;
     MIR_REQUIRE(token_ids && seq_lens && out, "NULL buffer");
     std::vector<int64_t> offs(n_seq + 1, 0);
+    // the position table holds min(max_pos, 512) rows of the checkpoint's (the rest is zero padding: never a position)
+    const int max_len = std::min(e->max_pos, 512);
     for (int s = 0; s < n_seq; ++s) {
-        MIR_REQUIRE(seq_lens[s] >= 1 && seq_lens[s] <= 512, "sequence %d has length %d (must be 1..512)", s, seq_lens[s]);
+        MIR_REQUIRE(seq_lens[s] >= 1 && seq_lens[s] <= max_len, "sequence %d has length %d (must be 1..%d)", s, seq_lens[s], max_len);
         offs[s + 1] = offs[s] + seq_lens[s];
     }
     for (int64_t i = 0; i < offs[n_seq]; ++i)
@@ -485,9 +487,10 @@ static int32_t encode_impl(mir_encoder *e, const int32_t *token_ids, const int32
         s0 = s1;
         ++pass;
     }
-    // drain: results reach the caller's buffers, the workspaces become reusable
-    rc = retire(0);
-    if (rc == MIR_OK) rc = retire(1);
+    // drain in pass order (the debug hidden states are the LAST pass's): results reach the caller's buffers, the workspaces
+    // become reusable
+    rc = retire(pass & 1);
+    if (rc == MIR_OK) rc = retire((pass & 1) ^ 1);
     if (rc != MIR_OK) return rc;
     MIR_HIP(hipStreamSynchronize(s));
     return MIR_OK;

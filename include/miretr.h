@@ -933,8 +933,12 @@ int32_t mir_wordpiece_encode(const mir_wordpiece *t, const char *texts, const in
  * This build is specialised for the bge-small-en shape and refuses others.
  *
  * mir_encoder_encode: token_ids = the sequences back to back (with [CLS] /
- * [SEP] already in place), seq_lens[n_seq] in 1..512; out float32
- * [n_seq][384].  normalize = 1 for the reference's behaviour.
+ * [SEP] already in place), seq_lens[n_seq] in 1..min(max_pos, 512), max_pos
+ * as given to mir_encoder_create (the rows of the checkpoint's position
+ * table); out float32 [n_seq][384].  normalize = 1 for the reference's
+ * behaviour.  A length outside that range, or a token id outside the
+ * vocabulary, is MIR_ERR_INVALID for the whole call: nothing is launched and
+ * `out` is not written.  The same holds for the two entries below.
  * ---------------------------------------------------------------------- */
 typedef struct mir_encoder mir_encoder;
 

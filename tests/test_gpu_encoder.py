@@ -63,6 +63,79 @@ def test_hidden_states_vs_transformers(setup, layers, note):
     note(f"[encoder parity] {layers} layers: max |hidden - float32 transformers| = {worst:.3e} (gate {tol:.1e})")
 
 
+@pytest.fixture(scope="module")
+def every_layer(setup):
+    """T, P64, P32 and their gates after 0 .. 12 layers for the fixture's sequences (oracle/encoder.py), computed once."""
+    model, enc, seqs, oe = setup
+    return oe.references_every_layer(model, seqs, 12)
+
+
+SMALL_TILES = 256  # kSmallTiles (encoder_kernels.h)
+
+
+@pytest.mark.parametrize("route", ["small", "single", "throughput"])
+def test_every_layer_against_the_oracles(setup, every_layer, route, note):
+    """The 12-layer model after every layer count n = 0 .. 12 against the rounding-aware references, on the latency kernels
+    (`small`: the fixture's 11 sequences, 45 tiles), the single-tile kernels (`single`: its five sequences of at most 32
+    tokens) and the throughput kernels (`throughput`: the 11 sequences repeated to more than 256 tiles; the copies must be
+    bit-equal).  Per n: the two maximum gates of `gates()` (max |kernel - P64| <= 4 max |P32 - P64| + h, max |kernel - T| <=
+    2 max |P64 - T| + h) and the RMS gates - R = rms(kernel - T) / rms(P64 - T) <= RMS_G x R(P32) over all real rows and per
+    sequence of at least 64 rows; the normalised embedding gets the pooled RMS gate.  The maxima are set by single flipped
+    float16 roundings and leave a 0.2 % error in every FFN output weight unseen at every depth; R sees it
+    (tests/test_oracle_encoder_points.py).  Measured on an MI355X (DESIGN.md 4b has the table): R over all rows 0.9957 .. 1.0015 on
+    `small` and `throughput` (bit-identical), 0.9713 .. 1.0207 on the 77 rows of `single`; largest per sequence 1.0276; pooled
+    0.9638 / 0.9265; the case models of tests/test_gpu_encoder_attention.py reach R_max = 1.0444, so
+    RMS_G = max(1.05, 1 + 2 (R_max - 1)) = 1.0888 (oracle/encoder.py)."""
+    model, enc, seqs, oe = setup
+    idx = [i for i, s in enumerate(seqs) if len(s) <= 32] if route == "single" else list(range(len(seqs)))
+    batch = [seqs[i] for i in idx]
+    tiles = sum((len(s) + 31) // 32 for s in batch)
+    copies = SMALL_TILES // tiles + 1 if route == "throughput" else 1
+    if route == "single":
+        assert tiles == len(batch) == 5
+    elif route == "small":
+        assert len(batch) < tiles <= SMALL_TILES
+    else:
+        assert tiles * copies > SMALL_TILES
+    failures = []
+
+    def check(what, res):
+        (_, r_all, lim_all), per_seq = res[0], res[1:]
+        line = f"[encoder rms] main / {route} / {what}: R {r_all:.4f} <= {lim_all:.4f} ({oe.RMS_G} x R(P32) {lim_all / oe.RMS_G:.4f})"
+        if per_seq:
+            w, r, lim = max(per_seq, key=lambda e: e[1] if e[1] == e[1] else np.inf)  # the largest, a NaN before any number
+            line += f";  largest per sequence {r:.4f} (length {len(batch[int(w.split()[1])])}) <= {lim:.4f}"
+        note(line)
+        failures.extend(f"{what}: R {w} {r:.4f} > {lim:.4f}" for w, r, lim in res if not r <= lim)
+
+    for n in range(13):
+        ref = every_layer[n]
+        _, hidden = enc.debug_hidden(batch * copies, n)
+        parts = [p.astype(np.float64) for p in split_hidden(hidden, batch * copies)]
+        for k in range(1, copies):  # a copy's rows do not depend on its place in the batch
+            for a, b in zip(parts[: len(batch)], parts[k * len(batch) : (k + 1) * len(batch)]):
+                np.testing.assert_array_equal(a, b)
+        got = parts[: len(batch)]
+        assert all(np.isfinite(g).all() for g in got), f"{n} layers: non-finite hidden state"
+        t, p64, p32 = ([ref[k][i] for i in idx] for k in ("T", "P64", "P32"))
+        e64 = float(np.max(np.concatenate([np.abs(a - b).ravel() for a, b in zip(got, p64)])))
+        et = float(np.max(np.concatenate([np.abs(a - b).ravel() for a, b in zip(got, t)])))
+        note(f"[encoder parity] main / {route} / {n} layers: |kernel - P64| {e64:.3e} <= {ref['gate_p64']:.3e};  |kernel - T| {et:.3e} "
+             f"<= {ref['gate_t']:.3e}")
+        if not e64 <= ref["gate_p64"]:
+            failures.append(f"{n} layers: |kernel - P64| {e64:.3e} > {ref['gate_p64']:.3e}")
+        if not et <= ref["gate_t"]:
+            failures.append(f"{n} layers: |kernel - T| {et:.3e} > {ref['gate_t']:.3e}")
+        check(f"{n} layers", oe.rms_gates(got, t, p64, p32))
+    pooled = enc.encode_ids(batch * copies)
+    for k in range(1, copies):
+        np.testing.assert_array_equal(pooled[: len(batch)], pooled[k * len(batch) : (k + 1) * len(batch)])
+    ref = every_layer[12]
+    t, p64, p32 = ([ref[k][i] for i in idx] for k in ("T", "P64", "P32"))
+    check("pooled", oe.rms_gates(None, t, p64, p32, pooled_x=pooled[: len(batch)]))
+    assert not failures, failures
+
+
 def test_embeddings_cls_normalised(setup, note):
     model, enc, seqs, oe = setup
     got = enc.encode_ids(seqs)
