@@ -155,6 +155,7 @@ def _load():
         "mir_ensemble_scope_destroy": ([vp], i32),
         "mir_block_ensemble_search_scopes": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp], i32),
         "mir_ensemble_scopes_gather_ms": ([vp, vp, i32, i32, vp], i32),
+        "mir_block_ensemble_search_scopes_encoded": ([vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp], i32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -203,6 +204,13 @@ class ScopeSlot(C.Structure):
     """mir_scope_slot: one vector leg's view of a document list for ``mir_ensemble_scope_create`` (host tables of handles)."""
 
     _fields_ = [("searcher", C.c_void_p), ("blocks", C.c_void_p), ("fanouts", C.c_void_p)]
+
+
+class EnsembleTextQueries(C.Structure):
+    """mir_ensemble_text_queries: the text queries of ``mir_block_ensemble_search_scopes_encoded`` (host pointers)."""
+
+    _fields_ = [("encoder", C.c_void_p), ("token_ids_host", C.c_void_p), ("seq_lens_host", C.c_void_p), ("normalize", C.c_int32),
+                ("leg_mask", C.c_uint32)]
 
 
 def last_error() -> str:

@@ -1300,6 +1300,8 @@ __global__ __launch_bounds__(kDkThreads) void bm25_dense_topk_kernel(const doubl
 #include "hybrid_layout.h"
 #include "ensemble_layout.h"
 #include "ensemble_scope_kernels.h"
+#include "ensemble_encode_kernels.h"
+#include "encoder_common.h"
 #include "vec_blocks_host.h"
 
 using namespace mir;
@@ -2741,11 +2743,14 @@ struct EnsembleOut { int32_t *doc; int64_t *chunk; double *score; int32_t *origi
 // What both ensemble entries do once every host check has passed and the scratch is carved: the device, the locks, the
 // scratch and the staging; `fill(up)` writes the upload span into the pinned staging; one upload; `prepare(base, stream)`
 // enqueues what must run before the first leg; the legs through the public _device searches and scoped_enqueue; the fusion
-// with the origin; one download; one hipStreamSynchronize; the five arrays copied out.
-template <typename Fill, typename Prepare>
+// with the origin; one download; one hipStreamSynchronize; the five arrays copied out; `after(down)`, still under the locks,
+// takes what else the call placed in the download span (the encoded entry's embeddings; nothing by default).
+struct EnsembleNoAfter { void operator()(const char *) const {} };
+template <typename Fill, typename Prepare, typename After = EnsembleNoAfter>
 static int32_t ensemble_run(mir_ensemble *e, mir_bm25_blocks *h, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c, int32_t cap,
                             const BlockRoute &route, const ScopedPlan<BlockScopeDev> &plan, OutColumn *cols, size_t need, const EnsembleLegAt *at,
-                            const EnsembleSpans &sp, mir_rrf_list *lists, const double *weights, Fill fill, Prepare prepare, const EnsembleOut &out) {
+                            const EnsembleSpans &sp, mir_rrf_list *lists, const double *weights, Fill fill, Prepare prepare, const EnsembleOut &out,
+                            After after = After{}) {
     int32_t rc = use_device(e->device, nullptr);
     if (rc != MIR_OK) return rc;
     std::lock_guard<std::mutex> lk(e->mu);
@@ -2805,6 +2810,7 @@ static int32_t ensemble_run(mir_ensemble *e, mir_bm25_blocks *h, const mir_ensem
     std::memcpy(out.score, down + (sp.f_score - sp.f_doc), rows * 8);
     std::memcpy(out.origin, down + (sp.f_origin - sp.f_doc), rows * 4);
     std::memcpy(out.count, down + (sp.f_count - sp.f_doc), (size_t)b * 4);
+    after(down);
     return MIR_OK;
 }
 
@@ -3015,20 +3021,26 @@ int32_t mir_ensemble_scope_destroy(mir_ensemble_scope *s) {
     return MIR_OK;
 }
 
-// mir_block_ensemble_search with every leg's document lists named by scopes[q] (DESIGN.md 4.13).  The host part is O(b):
-// scope_ptr from the scopes' n_docs, one reference record per query; scope_gather_kernel flattens the resident descriptor
-// arrays into the legs' tables on the ensemble's stream, and from there the call is ensemble_run, as the parent entry's.
-int32_t mir_block_ensemble_search_scopes(mir_ensemble *e, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c, int32_t cap,
-                                         const mir_ensemble_scope *const *scopes, int32_t *out_doc, int64_t *out_chunk, double *out_score,
-                                         int32_t *out_origin, int32_t *out_count) {
-    // the parent entry's refusals and order up to the legs' lists
-    MIR_REQUIRE(legs != nullptr, "legs is NULL");
-    MIR_REQUIRE(out_doc && out_chunk && out_score && out_origin && out_count, "an output is NULL");
-    MIR_REQUIRE(n_legs >= 1 && n_legs <= kRrfMaxLists, "n_legs=%d outside [1, %d]", n_legs, kRrfMaxLists);
+// What the scoped entries know of a call once its front checks have passed.
+struct ScopesFront {
     int kw = -1, n_vec = 0;
     int slot_of[kRrfMaxLists] = {};
     mir_rrf_list lists[kRrfMaxLists] = {};
     double weights[kRrfMaxLists] = {};
+    int64_t listed = 0;
+    int32_t expanded_mask = 0;
+};
+
+// The front of mir_block_ensemble_search_scopes and of its encoded form: the parent entry's refusals and order up to the
+// legs' lists, then the scopes in place of the lists, O(b).  Host only.
+static int32_t ensemble_scopes_front(const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c, int32_t cap, const mir_ensemble_scope *const *scopes,
+                                     const int32_t *out_doc, const int64_t *out_chunk, const double *out_score, const int32_t *out_origin,
+                                     const int32_t *out_count, ScopesFront *f) {
+    MIR_REQUIRE(legs != nullptr, "legs is NULL");
+    MIR_REQUIRE(out_doc && out_chunk && out_score && out_origin && out_count, "an output is NULL");
+    MIR_REQUIRE(n_legs >= 1 && n_legs <= kRrfMaxLists, "n_legs=%d outside [1, %d]", n_legs, kRrfMaxLists);
+    int &kw = f->kw, &n_vec = f->n_vec;
+    int *slot_of = f->slot_of;
     for (int l = 0; l < n_legs; ++l) {
         MIR_REQUIRE(legs[l].kind == MIR_LEG_VECTOR || legs[l].kind == MIR_LEG_KEYWORD, "leg %d has unknown kind %d", l, legs[l].kind);
         if (legs[l].kind == MIR_LEG_KEYWORD) {
@@ -3037,14 +3049,12 @@ int32_t mir_block_ensemble_search_scopes(mir_ensemble *e, const mir_ensemble_leg
         } else {
             slot_of[l] = n_vec++;
         }
-        lists[l].k = legs[l].k;
-        weights[l] = legs[l].weight;
+        f->lists[l].k = legs[l].k;
+        f->weights[l] = legs[l].weight;
     }
-    int32_t rc = rrf_check(lists, n_legs, weights, c, b, cap, true);
+    int32_t rc = rrf_check(f->lists, n_legs, f->weights, c, b, cap, true);
     if (rc != MIR_OK) return rc;
     // the scopes, in place of the legs' lists: O(b)
-    int64_t listed = 0;
-    int32_t expanded_mask = 0;
     if (b > 0) {
         MIR_REQUIRE(scopes != nullptr, "scopes is NULL");
         for (int i = 0; i < b; ++i) MIR_REQUIRE(scopes[i] != nullptr, "scope %d is NULL", i);
@@ -3060,11 +3070,29 @@ int32_t mir_block_ensemble_search_scopes(mir_ensemble *e, const mir_ensemble_leg
         }
         for (int i = 0; i < b; ++i) {
             MIR_REQUIRE(scopes[i]->device == scopes[0]->device, "scope %d is on device %d, scope 0 on device %d", i, scopes[i]->device, scopes[0]->device);
-            listed += scopes[i]->n_docs;
-            expanded_mask |= scopes[i]->paged_mask;
+            f->listed += scopes[i]->n_docs;
+            f->expanded_mask |= scopes[i]->paged_mask;
         }
-        MIR_REQUIRE(listed < ((int64_t)1 << 31), "the scopes of the batch list 2^31 documents or more");
+        MIR_REQUIRE(f->listed < ((int64_t)1 << 31), "the scopes of the batch list 2^31 documents or more");
     }
+    return MIR_OK;
+}
+
+// mir_block_ensemble_search with every leg's document lists named by scopes[q] (DESIGN.md 4.13).  The host part is O(b):
+// scope_ptr from the scopes' n_docs, one reference record per query; scope_gather_kernel flattens the resident descriptor
+// arrays into the legs' tables on the ensemble's stream, and from there the call is ensemble_run, as the parent entry's.
+int32_t mir_block_ensemble_search_scopes(mir_ensemble *e, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c, int32_t cap,
+                                         const mir_ensemble_scope *const *scopes, int32_t *out_doc, int64_t *out_chunk, double *out_score,
+                                         int32_t *out_origin, int32_t *out_count) {
+    ScopesFront front;
+    int32_t rc = ensemble_scopes_front(legs, n_legs, b, c, cap, scopes, out_doc, out_chunk, out_score, out_origin, out_count, &front);
+    if (rc != MIR_OK) return rc;
+    const int kw = front.kw, n_vec = front.n_vec;
+    const int *slot_of = front.slot_of;
+    mir_rrf_list *lists = front.lists;
+    const double *weights = front.weights;
+    const int64_t listed = front.listed;
+    const int32_t expanded_mask = front.expanded_mask;
     // what is left of each leg's own checks: the searcher, the metric, the queries; the keyword leg's query batch
     int32_t d_of[kRrfMaxLists] = {}, device_of[kRrfMaxLists] = {};
     int nt = 0;
@@ -3153,6 +3181,162 @@ int32_t mir_block_ensemble_search_scopes(mir_ensemble *e, const mir_ensemble_leg
     };
     return ensemble_run(e, h, legs, n_legs, b, c, cap, route, plan, cols, need, at, spans, lists, weights, fill, prepare,
                         EnsembleOut{out_doc, out_chunk, out_score, out_origin, out_count});
+}
+
+// mir_block_ensemble_search_scopes whose masked vector legs search with queries that enter as token ids.  On
+// the ensemble's stream, after the upload: scope_gather_kernel as in the parent, the encoder's pass into `emb`
+// (enc::encode_enqueue: its own staging copy, its kernels, no synchronise), queries_widen_kernel into the masked legs' one q
+// array; from there the call is ensemble_run.  Locks: the ensemble's, the keyword searcher's (both in ensemble_run), then
+// the encoder's, taken in `prepare` into a lock object of THIS function - held through ensemble_run's one
+// hipStreamSynchronize, dropped on every return path.
+int32_t mir_block_ensemble_search_scopes_encoded(mir_ensemble *e, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b, int32_t c, int32_t cap,
+                                                 const mir_ensemble_scope *const *scopes, const mir_ensemble_text_queries *tq, float *out_embeddings,
+                                                 int32_t *out_doc, int64_t *out_chunk, double *out_score, int32_t *out_origin, int32_t *out_count) {
+    // 1. the parent's refusals, its scope checks included
+    ScopesFront front;
+    int32_t rc = ensemble_scopes_front(legs, n_legs, b, c, cap, scopes, out_doc, out_chunk, out_score, out_origin, out_count, &front);
+    if (rc != MIR_OK) return rc;
+    const int kw = front.kw, n_vec = front.n_vec;
+    const int *slot_of = front.slot_of;
+    mir_rrf_list *lists = front.lists;
+    const double *weights = front.weights;
+    const int64_t listed = front.listed;
+    const int32_t expanded_mask = front.expanded_mask;
+    // 2. the text queries and the mask
+    MIR_REQUIRE(tq != nullptr, "text queries is NULL");
+    MIR_REQUIRE(tq->encoder != nullptr, "encoder is NULL");
+    MIR_REQUIRE(b == 0 || (tq->token_ids_host && tq->seq_lens_host), "NULL token ids or sequence lengths");
+    const uint32_t mask = tq->leg_mask;
+    MIR_REQUIRE(mask != 0, "leg_mask is empty: no leg searches with the encoded queries");
+    MIR_REQUIRE((mask >> n_legs) == 0, "leg_mask=0x%x names a leg at or beyond n_legs=%d", mask, n_legs);
+    MIR_REQUIRE(kw < 0 || !(mask >> kw & 1), "leg_mask=0x%x names leg %d, a keyword leg", mask, kw);
+    for (int l = 0; l < n_legs; ++l)
+        if ((mask >> l & 1) && legs[l].searcher)  // (a NULL searcher: the leg's own check below)
+            MIR_REQUIRE(blocks_dim(legs[l].searcher) == (int32_t)kEncodedDim, "leg %d searches %d-dimensional rows, the encoded queries are %d-dimensional", l,
+                        blocks_dim(legs[l].searcher), (int)kEncodedDim);
+    // 3. the encoder's own checks, with its messages; 4. one pass
+    int64_t tiles = 0;
+    rc = enc::encode_check_host(tq->encoder, tq->token_ids_host, tq->seq_lens_host, b, true, nullptr, &tiles);
+    if (rc != MIR_OK) return rc;
+    if (tiles > enc::encode_pass_tiles()) {
+        set_error("the %d sequences are %lld token tiles: more than one encoder pass (%lld tiles) in one call", b, (long long)tiles,
+                  (long long)enc::encode_pass_tiles());
+        return MIR_ERR_UNSUPPORTED;
+    }
+    // 5. what is left of each leg's own checks (a masked leg's queries_host is not looked at)
+    int32_t d_of[kRrfMaxLists] = {}, device_of[kRrfMaxLists] = {};
+    int nt = 0;
+    std::vector<const mir_bm25_blocks_scope *> text_scopes;
+    for (int l = 0; l < n_legs; ++l) {
+        const mir_ensemble_leg &g = legs[l];
+        if (g.kind == MIR_LEG_VECTOR) {
+            std::vector<mir_block_desc> none;
+            rc = blocks_check_host(g.searcher, g.queries_host, 0, g.k, g.metric, nullptr, nullptr, out_count, &none, &d_of[l], &device_of[l]);
+            if (rc != MIR_OK) return rc;
+            MIR_REQUIRE(b == 0 || (mask >> l & 1) || g.queries_host != nullptr, "queries is NULL");
+            continue;
+        }
+        if (b > 0) {
+            text_scopes.resize((size_t)b);
+            for (int i = 0; i < b; ++i) text_scopes[(size_t)i] = scopes[i]->text;
+        }
+        rc = ensemble_keyword_check(g.text_searcher, text_scopes.data(), g.q_terms_host, g.q_ptr_host, b, g.k, &nt);
+        if (rc != MIR_OK) return rc;
+        device_of[l] = g.text_searcher->device;
+    }
+    // 6. the ensemble; 7. the devices
+    MIR_REQUIRE(e != nullptr, "ensemble is NULL");
+    for (int l = 0; l < n_legs; ++l)
+        MIR_REQUIRE(device_of[l] == e->device, "the searcher of leg %d is on device %d, the ensemble on device %d", l, device_of[l], e->device);
+    MIR_REQUIRE(enc::encoder_device(tq->encoder) == e->device, "the encoder is on device %d, the ensemble on device %d", enc::encoder_device(tq->encoder),
+                e->device);
+    if (b == 0) return MIR_OK;
+    MIR_REQUIRE(scopes[0]->device == e->device, "the scopes are on device %d, the ensemble on device %d", scopes[0]->device, e->device);
+    EnsembleEncodedShape es{};
+    EnsembleScopesShape &eb = es.base;
+    es.leg_mask = mask;
+    es.want_emb = out_embeddings != nullptr;
+    eb.b = b; eb.cap = cap; eb.listed = listed; eb.n_legs = n_legs;
+    eb.desc_bytes = sizeof(mir_block_desc); eb.fan_bytes = sizeof(mir_fanout_desc); eb.scope_bytes = sizeof(BlockScopeDev);
+    eb.ref_bytes = sizeof(EnsembleScopeRef);
+    int first_masked = -1;
+    for (int l = 0; l < n_legs; ++l) {
+        const mir_ensemble_leg &g = legs[l];
+        EnsembleScopesLegShape &ls = eb.leg[l];
+        ls.kind = g.kind; ls.k = g.k; ls.d = d_of[l]; ls.terms = nt;
+        ls.expanded = g.kind == MIR_LEG_VECTOR && (expanded_mask >> slot_of[l] & 1);
+        ls.q_of = -1;
+        if (mask >> l & 1) {  // every masked leg reads the one array the device writes
+            ls.q_of = first_masked;
+            if (first_masked < 0) first_masked = l;
+            continue;
+        }
+        for (int j = 0; j < l && g.kind == MIR_LEG_VECTOR && ls.q_of < 0; ++j)  // the same host queries at the same d: uploaded once
+            if (legs[j].kind == MIR_LEG_VECTOR && !(mask >> j & 1) && eb.leg[j].q_of < 0 && legs[j].queries_host == g.queries_host && d_of[j] == d_of[l])
+                ls.q_of = j;
+    }
+    EnsembleEncodedLayout lay;
+    const EnsembleEncodedCarve carved = ensemble_encoded_carve(es, &lay);
+    MIR_REQUIRE(carved == kEncodedOk, "the call's arrays do not fit a scratch (b=%d cap=%d, %d legs)", b, cap, n_legs);
+    mir_bm25_blocks *h = kw >= 0 ? legs[kw].text_searcher : nullptr;
+    const BlockRoute route{h};
+    OutColumn cols[5] = {{nullptr, 8}, {nullptr, 8}, {nullptr, 8}, {nullptr, 4}, {nullptr, 4}};  // pos, chunk, score, ord, local
+    ScopedPlan<BlockScopeDev> plan;
+    size_t need = lay.keyword;
+    if (kw >= 0) {
+        const ScopedInputs inputs{lay.leg[kw].terms, lay.leg[kw].q_ptr, lay.leg[kw].scopes};
+        scoped_plan(route, text_scopes.data(), nt, b, legs[kw].k, cols, 5, lay.keyword, &inputs, &plan);
+        need = plan.end;
+    }
+    EnsembleLegAt at[kRrfMaxLists];
+    for (int l = 0; l < n_legs; ++l) {
+        const EnsembleScopesLegLayout &ll = lay.leg[l];
+        at[l] = EnsembleLegAt{ll.q, lay.scope_ptr, ll.table, ll.fan_table, ll.l_doc, ll.l_chunk, ll.l_count, eb.leg[l].expanded};
+    }
+    const EnsembleSpans spans{lay.in_bytes, lay.f_doc, lay.f_chunk, lay.f_score, lay.f_origin, lay.f_count, lay.out_bytes};
+    auto fill = [&](char *up) {
+        scopes_fill(scopes, b, reinterpret_cast<int32_t *>(up + lay.scope_ptr), reinterpret_cast<EnsembleScopeRef *>(up + lay.refs));
+        for (int l = 0; l < n_legs; ++l) {
+            const mir_ensemble_leg &g = legs[l];
+            const EnsembleScopesLegLayout &ll = lay.leg[l];
+            if (g.kind == MIR_LEG_KEYWORD) {
+                if (nt) std::memcpy(up + ll.terms, g.q_terms_host, (size_t)nt * 4);
+                std::memcpy(up + ll.q_ptr, g.q_ptr_host, ((size_t)b + 1) * 4);
+                std::memcpy(up + ll.scopes, plan.sd.data(), (size_t)b * sizeof(BlockScopeDev));
+            } else if (!(mask >> l & 1) && eb.leg[l].q_of < 0) {
+                std::memcpy(up + ll.q, g.queries_host, (size_t)b * d_of[l] * 8);
+            }
+        }
+    };
+    std::unique_lock<std::mutex> lk_encoder;  // this function's: taken in prepare, dropped when the function returns - after the synchronise
+    auto prepare = [&](char *base, hipStream_t s) -> int32_t {  // after the upload, before the first leg: the tables, the embeddings, the queries
+        if (n_vec > 0 && listed > 0) {
+            ScopeGatherArgs ga{};
+            ga.refs = reinterpret_cast<const EnsembleScopeRef *>(base + lay.refs);
+            ga.scope_ptr = reinterpret_cast<const int32_t *>(base + lay.scope_ptr);
+            for (int l = 0; l < n_legs; ++l) {
+                if (legs[l].kind != MIR_LEG_VECTOR) continue;
+                ga.table[slot_of[l]] = reinterpret_cast<uint4 *>(base + lay.leg[l].table);
+                ga.fan_table[slot_of[l]] = eb.leg[l].expanded ? reinterpret_cast<uint4 *>(base + lay.leg[l].fan_table) : nullptr;
+            }
+            scope_gather_kernel<<<dim3((unsigned)b, (unsigned)n_vec), dim3(kScopeGatherThreads), 0, s>>>(ga);  // one launch for all slots
+            MIR_HIP(hipGetLastError());
+        }
+        lk_encoder = std::unique_lock<std::mutex>(enc::encoder_mutex(tq->encoder));
+        float *emb = reinterpret_cast<float *>(base + lay.emb);
+        const int32_t r = enc::encode_enqueue(tq->encoder, tq->token_ids_host, tq->seq_lens_host, b, tq->normalize, emb, s);
+        if (r != MIR_OK) return r;
+        const int64_t n4 = (int64_t)b * (kEncodedDim / 4);
+        queries_widen_kernel<<<dim3((unsigned)((n4 + kWidenThreads - 1) / kWidenThreads)), dim3(kWidenThreads), 0, s>>>(
+            reinterpret_cast<const float4 *>(emb), reinterpret_cast<double2 *>(base + lay.q_enc), n4);
+        MIR_HIP(hipGetLastError());
+        return MIR_OK;
+    };
+    auto after = [&](const char *down) {
+        if (out_embeddings) std::memcpy(out_embeddings, down + (lay.emb - lay.f_doc), (size_t)b * kEncodedDim * 4);
+    };
+    return ensemble_run(e, h, legs, n_legs, b, c, cap, route, plan, cols, need, at, spans, lists, weights, fill, prepare,
+                        EnsembleOut{out_doc, out_chunk, out_score, out_origin, out_count}, after);
 }
 
 // A measurement hook (tools/block_ensemble_scopes_timing.py): scope_gather_kernel alone for the scopes of a batch, `reps`

@@ -33,6 +33,10 @@
 #include <stdint.h>
 #include <math.h>
 #include <type_traits>
+#include <mutex>
+#include <vector>
+
+struct mir_encoder;
 
 namespace mir {
 namespace enc {
@@ -492,6 +496,25 @@ __device__ __forceinline__ void ln4_tile(const float *__restrict__ Y, int tt, co
     const float rstd = rsqrtf(half_sum(xs[1][1][lane] + xs[1][3][lane]) * (1.0f / H) + LN_EPS);
     ln_part_store<QB, true>(y, QB * w, rstd, gamma, beta, out_tile, lane, true);
 }
+
+// ---- the host side's two halves (encoder.hip), for a caller inside the library that rides the encoder on a stream of its own
+// (the block ensemble's encoded entry, bm25.hip).  C++ functions, no C-ABI symbols.
+//
+// encode_check_host: everything mir_encoder_encode refuses, with its messages, and nothing of the device touched: the handle,
+// n_seq, the buffers (`out_given`: the caller has somewhere to put the result), every length in 1..min(max_pos, 512), every
+// token id inside the vocabulary.  offs_out (optional): the n_seq + 1 offsets of the sequences; tiles_out (optional): the
+// batch's 32-token tiles - more than encode_pass_tiles() of them take more than one pass.
+int32_t encode_check_host(const mir_encoder *e, const int32_t *token_ids, const int32_t *seq_lens, int32_t n_seq, bool out_given,
+                          std::vector<int64_t> *offs_out, int64_t *tiles_out);
+int64_t encode_pass_tiles();
+int encoder_device(const mir_encoder *e);
+// encode_enqueue: a CHECKED batch of at most one pass, enqueue only - the batch is built, staged through the encoder's own
+// pinned buffer and launched on `stream`; float32 [n_seq][384] go to `out_device`; nothing is synchronised.  The caller
+// holds encoder_mutex(e) from before this call until it has synchronised `stream` (the workspace and the staging are
+// reused by the next encode: see mir_encoder::ws_done), and has made the encoder's device current.
+std::mutex &encoder_mutex(mir_encoder *e);
+int32_t encode_enqueue(mir_encoder *e, const int32_t *token_ids, const int32_t *seq_lens, int32_t n_seq, int32_t normalize, float *out_device,
+                       hipStream_t stream);
 
 
 }  // namespace enc

@@ -16,6 +16,9 @@ int32_t blocks_check_host(mir_blocks *s, const double *queries_host, int32_t b, 
                           const mir_rows *const *blocks_host, const int32_t *out_count, std::vector<mir_block_desc> *table, int32_t *d,
                           int32_t *device);
 
+// The searcher's dimension alone (s is not NULL): for a caller that must refuse on it before the leg's other checks.
+int32_t blocks_dim(const mir_blocks *s);
+
 // The same for mir_blocks_search_expanded: blocks_check_host, then every fan-out against its block and the expanded scopes'
 // rows.  MIR_OK: `fan_table` holds one descriptor per listed block (all null: the block has no fan-out), the table
 // mir_blocks_search_expanded_device reads once it is in HBM.

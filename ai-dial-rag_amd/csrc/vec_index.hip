@@ -1709,6 +1709,8 @@ int32_t blocks_check_host(mir_blocks *s_, const double *queries_host, int32_t b,
     return check_blocks(s_->ix, scope_ptr_host, b, "query", nullptr, blocks_host, *table, &rows);
 }
 
+int32_t blocks_dim(const mir_blocks *s_) { return s_->ix->d; }
+
 // mir_blocks_search_expanded's part past check_blocks: the fan-outs against their blocks, while they become the descriptor
 // table the expansion reads (all null = the block has none); the expanded scopes' rows
 static int32_t check_fanouts(const int32_t *scope_ptr_host, int32_t b, const mir_rows *const *blocks_host, const mir_fanout *const *fanouts_host,

@@ -246,9 +246,13 @@ class BgeEncoder:
     def embed_query(self, text: str) -> List[float]:
         """One query (embeddings.py:93-96).  Encoding 1 or 16 short queries costs the same ~0.45 ms pass, and the
         reference calls this from concurrent requests: concurrent callers share passes (group commit)."""
-        text = text.replace("\n", " ")  # HuggingFaceBgeEmbeddings.embed_query
-        ids = self._tokenize([BGE_QUERY_INSTRUCTION_EN + text])[0]
-        return self._query_commit().submit(ids)[0].tolist()
+        return self._query_commit().submit(self.query_token_ids([text])[0])[0].tolist()
+
+    def query_token_ids(self, texts: Sequence[str]) -> List[List[int]]:
+        """The token ids ``embed_query`` encodes for each of ``texts``: newlines replaced by spaces
+        (HuggingFaceBgeEmbeddings.embed_query), the English BGE instruction in front, truncation at 512 tokens, [CLS] / [SEP]
+        in place - what ``BlockEnsemble.find_scoped_encoded`` takes."""
+        return self._tokenize([BGE_QUERY_INSTRUCTION_EN + t.replace("\n", " ") for t in texts])
 
     def _query_commit(self):
         gc = getattr(self, "_qc", None)

@@ -190,10 +190,53 @@ class EnsembleSearcher(_HandleOwner):
         del held
         return doc, chunk, score, origin, cnt
 
+    def search_scopes_encoded(self, legs: Sequence, scopes: Sequence[EnsembleScope], b: int, encoder, sequences: Sequence[Sequence[int]],
+                              encoded_legs: Sequence[int], normalize: bool = True, want_embeddings: bool = True, c: int = 60,
+                              cap: Optional[int] = None):
+        """``search_scopes`` whose legs ``encoded_legs`` (indices into ``legs``, vector legs at d = 384) search with the
+        embeddings of ``sequences`` - token ids, [CLS] / [SEP] in place - encoded by ``encoder`` (a ``BgeEncoder``) inside
+        the same native call (``mir_block_ensemble_search_scopes_encoded``): nothing is synchronised between
+        the encoder and the legs, and the embeddings never leave HBM on the way.  The ``queries`` of an encoded leg are not
+        looked at (None will do).  -> ``search_scopes``' tuple for ``encoder.encode_ids(sequences, normalize)`` widened to
+        float64, bit for bit, plus the embeddings float32[b, 384] (None unless ``want_embeddings``)."""
+        b = int(b)
+        if len(scopes) != b or len(sequences) != b:
+            raise ValueError(f"{len(scopes)} scopes and {len(sequences)} token sequences for {b} queries")
+        mask = 0
+        for l in encoded_legs:
+            if not 0 <= int(l) < 32:
+                raise ValueError(f"encoded leg {l}: a leg index is in [0, 32)")
+            mask |= 1 << int(l)
+        arr, held = self._marshal(legs, b, lists=False, encoded=mask)
+        lens = np.asarray([len(s) for s in sequences], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.int32) for s in sequences]) if b else np.zeros(0, np.int32))
+        tq = nat.EnsembleTextQueries(encoder._h, flat.ctypes.data if len(flat) else None, lens.ctypes.data if b else None, 1 if normalize else 0, mask)
+        total = sum(max(int(leg.k), 0) for leg in legs)
+        cap = total if cap is None else int(cap)
+        rows = (b, max(cap, 0))
+        doc, chunk, score = np.zeros(rows, np.int32), np.zeros(rows, np.int64), np.zeros(rows, np.float64)
+        origin, cnt = np.zeros(rows, np.int32), np.zeros(b, np.int32)
+        emb = np.zeros((b, 384), np.float32) if want_embeddings else None
+        taken = []
+        try:
+            handles = (C.c_void_p * max(b, 1))()
+            for i, s in enumerate(scopes):  # (a scope closed meanwhile: ValueError, nothing launched)
+                handles[i] = s._acquire()
+                taken.append(s)
+            nat.check(nat.lib.mir_block_ensemble_search_scopes_encoded(self._h, arr, len(legs), b, int(c), cap, handles, C.byref(tq), nat.ptr(emb),
+                                                                       doc.ctypes.data, chunk.ctypes.data, score.ctypes.data, origin.ctypes.data,
+                                                                       cnt.ctypes.data))
+        finally:
+            for s in taken:
+                s._release()
+        del held
+        return doc, chunk, score, origin, cnt, emb
+
     @staticmethod
-    def _marshal(legs: Sequence, b: int, lists: bool = True):
+    def _marshal(legs: Sequence, b: int, lists: bool = True, encoded: int = 0):
         """-> (the mir_ensemble_leg array, everything it points into: host arrays and handle tables, to be kept alive across the
-        call).  ``lists=False``: the document lists come from resident scopes, the legs' own are left null."""
+        call).  ``lists=False``: the document lists come from resident scopes, the legs' own are left null.  ``encoded``: a
+        mask of the vector legs whose queries the call encodes itself - their ``queries`` are left null."""
         arr = (nat.EnsembleLeg * max(len(legs), 1))()
         held = []
         for l, leg in enumerate(legs):
@@ -212,12 +255,13 @@ class EnsembleSearcher(_HandleOwner):
                 a.q_terms_host = flat.ctypes.data if len(flat) else None
                 a.q_ptr_host = ptr.ctypes.data
                 continue
-            q = nat.as_f64_queries(leg.queries, leg.searcher.d)
-            if q.shape[0] != b or (lists and len(leg.scopes) != b):
-                raise ValueError(f"leg {l}: {q.shape[0]} queries and {len(leg.scopes) if lists else b} scopes for {b} queries")
-            held.append(q)
             a.kind, a.searcher, a.metric = nat.LEG_VECTOR, leg.searcher.handle, nat.METRIC_CODES[Metric(leg.metric).value]
-            a.queries_host = q.ctypes.data
+            if not (encoded >> l & 1):
+                q = nat.as_f64_queries(leg.queries, leg.searcher.d)
+                if q.shape[0] != b or (lists and len(leg.scopes) != b):
+                    raise ValueError(f"leg {l}: {q.shape[0]} queries and {len(leg.scopes) if lists else b} scopes for {b} queries")
+                held.append(q)
+                a.queries_host = q.ctypes.data
             if not lists:
                 continue
             blocks, sp, table = _scope_table(leg.scopes)
@@ -516,6 +560,55 @@ class BlockEnsemble:
             searcher = self._searcher
         doc, chunk, score, origin, cnt = searcher.search_scopes(legs, scopes, len(q), int(c))  # (a scope closed meanwhile: ValueError)
         return doc.astype(np.int64), chunk, score, origin, cnt
+
+    def find_scoped_encoded(self, sequences: Sequence[Sequence[int]], query_ids, scopes: Sequence[EnsembleScope], encoder, multimodal_vectors=None,
+                            metric=Metric.SQEUCLIDEAN_DIST, multimodal_metric=Metric.SQEUCLIDEAN_DIST, k=7, weights: Optional[Sequence[float]] = None,
+                            c: int = 60, normalize: bool = True):
+        """``find_scoped`` for the text queries ``sequences`` (token ids, ``BgeEncoder.query_token_ids``): its tuple, exactly,
+        for ``encoder.encode_ids(sequences).astype(float64)``, plus the embeddings float32[b, 384].  The semantic and the
+        description legs search with the encoded queries, the multimodal leg with ``multimodal_vectors``.  With
+        ``device_fusion`` ONE ``EnsembleSearcher.search_scopes_encoded`` call: the encoder, the legs and the
+        fusion on one stream, one synchronisation.  Without it, and wherever ``find_scoped`` takes the host route, this IS
+        ``encode_ids`` followed by ``find_scoped``."""
+
+        def two_calls():
+            emb = encoder.encode_ids(sequences, normalize)
+            return (*self.find_scoped(emb.astype(np.float64), query_ids, scopes, multimodal_vectors, metric, multimodal_metric, k, weights, c), emb)
+
+        for s in scopes:
+            if not isinstance(s, EnsembleScope) or getattr(s, "_owner", lambda: None)() is not self:
+                raise ValueError("find_scoped takes the scopes this ensemble's scope() made")
+        n = len(self.legs)
+        ks = [int(k)] * n if np.isscalar(k) else [int(x) for x in k]
+        w = np.ones(n) if weights is None else np.asarray(weights, dtype=np.float64)
+        masked = [l for l, name in enumerate(self.legs) if name in ("semantic", "description")]
+        served = self.device_fusion and len(ks) == n and w.shape == (n,) and all(s.native and not s._stale and not s._closed for s in scopes)
+        served = served and all(x >= 1 for x in ks) and sum(ks) <= MAX_FUSED and bool(np.all(np.isfinite(w))) and int(c) >= 0
+        served = served and bool(masked) and len(sequences) == len(scopes) and len(sequences) > 0
+        served = served and all(self.vectors[self.legs[l]].d == 384 for l in masked)
+        served = served and (self.keywords is None or len(query_ids) == len(sequences))
+        mm = None
+        if served and "multimodal" in self.legs:
+            served = multimodal_vectors is not None
+            if served:
+                mm = np.atleast_2d(np.asarray(multimodal_vectors, dtype=np.float64))
+                served = len(mm) == len(sequences)
+        if not served:
+            return two_calls()  # (and find_scoped's errors)
+        legs = []
+        for name, kk, weight in zip(self.legs, ks, w):
+            if name == "keywords":
+                legs.append(KeywordLeg(self.keywords._device_searcher(), None, [self.keywords._ids(t) for t in query_ids], kk, float(weight)))
+            else:
+                m = multimodal_metric if name == "multimodal" else metric
+                Metric(m)
+                legs.append(VectorLeg(self.vectors[name]._searcher, mm if name == "multimodal" else None, m, None, None, kk, float(weight)))
+        with self._lock:
+            if self._searcher is None:
+                self._searcher = EnsembleSearcher(self.device)
+            searcher = self._searcher
+        doc, chunk, score, origin, cnt, emb = searcher.search_scopes_encoded(legs, scopes, len(sequences), encoder, sequences, masked, normalize, True, int(c))
+        return doc.astype(np.int64), chunk, score, origin, cnt, emb
 
     def documents(self, doc, chunk, origin, count, q: int) -> List[Document]:
         """Query ``q``'s fused items as the reference's ensemble returns them: the first ``Document`` seen of each key, so

@@ -32,7 +32,9 @@
 extern "C" {
 #endif
 
-#define MIR_ABI_VERSION 6 /* 6: resident ensemble scopes, ADDED without a new number (nothing of ABI 6 changed):
+#define MIR_ABI_VERSION 6 /* 6: ensemble queries as token ids, ADDED without a new number (nothing of ABI 6 changed):
+                               mir_ensemble_text_queries, mir_block_ensemble_search_scopes_encoded;
+                            6: resident ensemble scopes, ADDED without a new number (nothing of ABI 6 changed):
                                mir_ensemble_scope_create / _info / _destroy, mir_block_ensemble_search_scopes,
                                mir_ensemble_scopes_gather_ms (a measurement hook);
                             6: block ensemble in one call and the fusion's origin, ADDED without a new number (nothing of ABI 6 changed):
@@ -958,6 +960,45 @@ int32_t mir_encoder_encode_to_device(mir_encoder *e, const int32_t *token_ids_ho
 int32_t mir_encoder_debug_hidden(mir_encoder *e, const int32_t *token_ids_host, const int32_t *seq_lens_host,
                                  int32_t n_seq, int32_t run_layers, float *pooled_out_host,
                                  float *hidden_out_host, int64_t hidden_capacity_tokens);
+
+/* ------------------------------------------------------------------------
+ * mir_block_ensemble_search_scopes with queries that enter as TOKEN IDS (added within ABI 6): the encoder
+ * runs on the ensemble's stream, its embeddings never leave HBM, and the call still synchronises once.
+ *   tq describes the b text queries: the encoder, the b token sequences back to back with their lengths and `normalize` as
+ *   mir_encoder_encode takes them, and leg_mask - bit l set: vector leg l searches with the encoded queries (its searcher's
+ *   d is 384; its queries_host is IGNORED and may be NULL).  A leg outside the mask uses its own queries_host as before (a
+ *   leg whose vectors come from elsewhere: the multimodal one); the keyword leg is unchanged.
+ *   out_embeddings (host, float32 [b][384], may be NULL) receives mir_encoder_encode's bits for the same sequences.
+ * The answer is the two-call route's, exactly: the five arrays mir_block_ensemble_search_scopes returns when each masked
+ * leg's queries_host is (double) of what mir_encoder_encode returns for the same sequences and `normalize` - bit for bit,
+ * rows past the count zero.
+ * Route: the upload (no query bytes for a masked leg); scope_gather_kernel; the encoder's pass - its own staging copy and
+ * its kernels, enqueued without a synchronise - into an array of the ensemble's scratch; queries_widen_kernel (float32 ->
+ * float64) into the ONE query array all masked legs read; the legs, the fusion, one download (the embeddings ride in it
+ * when asked for), one hipStreamSynchronize.  Two host-to-device copies, one device-to-host copy.
+ * Locks, in this order: the ensemble's, the keyword searcher's, the encoder's - the last held until after the synchronise,
+ * so a concurrent mir_encoder_encode on the same encoder waits for the whole call.
+ * Refusals come before anything is uploaded or launched and leave every output, out_embeddings included, untouched, in
+ * this order: mir_block_ensemble_search_scopes' up to and including its scope checks; MIR_ERR_INVALID for a NULL tq or
+ * encoder, NULL token ids or lengths with b > 0, an empty leg_mask, a mask bit at or beyond n_legs or on the keyword leg,
+ * a masked leg whose searcher is not 384-dimensional; what mir_encoder_encode refuses, with its messages (a length
+ * outside 1..min(max_pos, 512), a token id outside the vocabulary); MIR_ERR_UNSUPPORTED for a batch of more than one
+ * encoder pass (12288 tiles of 32 tokens: more than 768 sequences of 512 tokens); what is left of each leg's own checks;
+ * a NULL ensemble; an ensemble or an encoder on another device.  b == 0 is MIR_OK then.
+ * ---------------------------------------------------------------------- */
+typedef struct {
+    mir_encoder *encoder;
+    const int32_t *token_ids_host;   /* the b sequences back to back, [CLS]/[SEP] in place */
+    const int32_t *seq_lens_host;    /* [b] */
+    int32_t normalize;               /* 1 = the reference's */
+    uint32_t leg_mask;               /* bit l: vector leg l searches with the encoded queries */
+} mir_ensemble_text_queries;
+
+int32_t mir_block_ensemble_search_scopes_encoded(mir_ensemble *e, const mir_ensemble_leg *legs, int32_t n_legs, int32_t b,
+                                                 int32_t c, int32_t cap, const mir_ensemble_scope *const *scopes,
+                                                 const mir_ensemble_text_queries *tq, float *out_embeddings,
+                                                 int32_t *out_doc, int64_t *out_chunk, double *out_score,
+                                                 int32_t *out_origin, int32_t *out_count);
 
 #ifdef __cplusplus
 }
